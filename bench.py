@@ -23,6 +23,9 @@ Prints ONE JSON line on rank 0 with the contract fields plus
 --config 3 measures BASELINE configs[2] instead (full HSF + IGF point-cloud path, batch 2, camera features precomputed)
 with the same contract and a stage table; the default (--config 2) is the headline.
 
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (inputs and weights are seeded: the same
+arguments give the same inputs, so two builds can be compared output for output).
+
 Diagnostics (never the headline; the line is labelled): --f16 (single-pass f16 kernels, reduced precision) and the
 --conv-diag knock-out kernels (garbage results, timing only; tools/conv_knockout.sh).
 """
@@ -68,6 +71,53 @@ def make_frames(rank, world, batch, num_points, frame_set=0):
             np.save(path, pts)
         frames.append(pts)
     return frames
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: everything written, in all
+DUMP_BEV_CELLS = 16384         # BEV cells (all channels) in the fixed sample: 32 MB for 512 channels
+
+
+def dump_arrays(out_dir, arrays):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy, float64 tensors as float64 and everything else as float32."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.cpu().numpy().astype(np.float64 if t.dtype == torch.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
+def bev_dump(bev, n_cells=DUMP_BEV_CELLS, seed=0):
+    """The BEV map [B, C, H, W] of the headline step is too large to write whole (265 MB at batch 4): a fixed, seeded
+    sample of min(n_cells, B*H*W) cells with all their channels (bev_cells [n, C], rows in the order of bev_cell_index,
+    flat b*H*W + y*W + x), plus the float64 sum of every (sample, channel) map of the whole tensor (bev_channel_sums
+    [B, C])."""
+    import numpy as np
+    import torch
+    B, C, H, W = bev.shape
+    cells = np.sort(np.random.default_rng(seed).choice(B * H * W, min(n_cells, B * H * W), replace=False))
+    idx = torch.from_numpy(cells).to(bev.device)
+    picked = bev.reshape(B, C, H * W)[idx // (H * W), :, idx % (H * W)]
+    return {"bev_cells": picked, "bev_cell_index": idx.double(),
+            "bev_channel_sums": bev.sum(dim=(2, 3), dtype=torch.float64)}
+
+
+def flat_outputs(obj, prefix):
+    """Nested tuples / lists / dicts of tensors -> {prefix_i_key: tensor} (non-tensor leaves are left out)."""
+    import torch
+    if torch.is_tensor(obj):
+        return {prefix: obj}
+    items = obj.items() if isinstance(obj, dict) else enumerate(obj) if isinstance(obj, (list, tuple)) else ()
+    out = {}
+    for k, v in items:
+        out.update(flat_outputs(v, f"{prefix}_{k}"))
+    return out
 
 
 def traffic_file():
@@ -281,7 +331,8 @@ def main_fusion(args):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world)
-    line = fusion_leg(args, rank, world, dev, args.batch, args.steps, args.warmup, not args.no_cpu_baseline)
+    line = fusion_leg(args, rank, world, dev, args.batch, args.steps, args.warmup, not args.no_cpu_baseline,
+                      args.dump_outputs)
     if rank == 0:
         line["launches_per_forward"] = line.pop("_count_launches")()
         print(json.dumps(line))
@@ -391,12 +442,13 @@ def count_launches(fn):
         return None
 
 
-def fusion_leg(args, rank, world, dev, B, steps, warmup, with_cpu_baseline):
+def fusion_leg(args, rank, world, dev, B, steps, warmup, with_cpu_baseline, dump_dir=""):
     """BASELINE configs[2]: full IS-Fusion HSF + IGF forward -- LiDAR branch, pillar voxelization, ISFusionEncoder
     (Point-to-Grid, conv_fusion, Grid-to-Region x2, instance mining / context / instance-to-scene), SECONDV2 stages,
     SECONDFPN neck, TransFusionHeadV2.forward -- on B x P-point sweeps + precomputed (random) 6-camera feature maps,
     fp32-class arithmetic.  Same JSON contract as the headline; stage table from HIP events in a separate pass.
-    Returns the line (rank 0) -- printed by --config 3, attached as "cfg3" to the headline line by the default run."""
+    Returns the line (rank 0) -- printed by --config 3, attached as "cfg3" to the headline line by the default run.
+    dump_dir: write the head outputs of the last timed step there (--config 3 --dump-outputs)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -449,6 +501,8 @@ def fusion_leg(args, rank, world, dev, B, steps, warmup, with_cpu_baseline):
         dt = float(t.item())
     heat = out[0][0]["heatmap"]
     assert torch.isfinite(heat).all()
+    if dump_dir and rank == 0:              # what the last timed step returned (outside the timed region)
+        dump_arrays(dump_dir, flat_outputs(out, "head"))
 
     if rank == 0:
         # ---- stage table (separate pass, HIP events on the launch stream; not part of the timed region)
@@ -812,7 +866,15 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL (the measurement); gloo = CPU REHEARSAL of the multi-rank launch / clock / JSON "
                          "line with a stub step (tests/test_host.py), never a measurement")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned on rank 0 as DIR/<name>.npy (float32 "
+                         "or float64, at most 64 MB): --config 2 a fixed sample of BEV cells + per-channel sums "
+                         "(bev_dump), --config 3 the head outputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.backend == "gloo":
+        ap.error("--dump-outputs needs the measured (nccl) path, not the gloo rehearsal")
     if args.batch <= 0:
         args.batch = BATCH_PER_GPU if args.config == 2 else 2
     # `python bench.py --gpus N` started plainly: become N ranks (one per GPU) under torch.distributed.run; fewer than N
@@ -905,6 +967,8 @@ def main():
     want_pipelined = world == 1 and not args.no_pipelined and not args.lib
     diag = (args.conv_diag & 15) != 0 or ((args.conv_diag >> 10) & 3) != 0   # timing diagnostics: results are garbage (16 = sharing off, 32 = uniform tiles: valid)
     assert diag or args.lib or torch.isfinite(out).all()
+    if args.dump_outputs and rank == 0:     # what the last timed step returned (outside the timed region)
+        dump_arrays(args.dump_outputs, bev_dump(out))
 
     if rank == 0:
         import numpy as np

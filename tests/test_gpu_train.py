@@ -343,6 +343,43 @@ def test_bench_under_torch_distributed_run_with_one_rccl_rank(dev):
     assert line["config"]["parallelism"] == "dp1" and "roofline" in line and len(json.dumps(line)) < 2048
 
 
+def test_bench_dump_outputs_hold_the_last_timed_step(dev, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the LAST timed step computed (steps 3, two frame sets: frame set 0) --
+    the same sample of BEV cells and per-channel sums as a forward of this process on the same seeded frames and
+    weights -- and --steps is the number of timed steps behind ms_per_step"""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    import torch
+    import isfusion_amd as m
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out_dir = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--points",
+           "40000", "--batch", "2", "--no-cfg3", "--no-cfg4", "--no-cfg5", "--no-pipelined", "--no-cpu-baseline",
+           "--dump-outputs", str(out_dir)]
+    p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert p.returncode == 0, p.stderr.decode()[-3000:]
+    line = json.loads([l for l in p.stdout.decode().splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    got = {f[:-4]: np.load(out_dir / f) for f in sorted(os.listdir(out_dir))}
+    assert sorted(got) == ["bev_cell_index", "bev_cells", "bev_channel_sums"]
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_LIMIT_BYTES
+    assert got["bev_cells"].dtype == np.float32 and got["bev_channel_sums"].dtype == np.float64
+    lb = m.LidarBranch().randomize_weights_(0).randomize_bn_(1).eval().to(dev).freeze()
+    frames = [torch.from_numpy(f).to(dev) for f in bench.make_frames(0, 1, 2, 40000, 0)]
+    with torch.no_grad():
+        want = {k: v.cpu().numpy() for k, v in bench.bev_dump(lb(frames)).items()}
+    assert got["bev_cells"].shape == want["bev_cells"].shape == (bench.DUMP_BEV_CELLS, 512)
+    assert np.array_equal(got["bev_cell_index"], want["bev_cell_index"])
+    assert np.count_nonzero(want["bev_cells"]) > 0
+    scale = max(1.0, float(np.abs(want["bev_cells"]).max()))
+    assert float(np.abs(got["bev_cells"] - want["bev_cells"]).max()) <= 1e-5 * scale
+    assert np.allclose(got["bev_channel_sums"], want["bev_channel_sums"], rtol=1e-6, atol=1e-6)
+
+
 def test_two_ranks_train_side_by_side_with_ddp_over_gloo(dev):
     """the DDP training step of tools/train_step.py with two ranks on ONE device (gloo all-reduce, NaiveSyncBatchNorm's
     statistics exchange with world size 2): the multi-rank training path runs end to end with the real kernels before an

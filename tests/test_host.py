@@ -195,6 +195,37 @@ def test_bench_gpus_2_starts_two_ranks_by_itself():
     assert sorted(fr[0] + fr[1]) == list(range(2 * len(fr[0]))) and not set(fr[0]) & set(fr[1])
 
 
+def test_bench_dump_outputs_sample_and_files(tmp_path):
+    """bench.py --dump-outputs helpers on CPU tensors: bev_dump picks a fixed set of whole BEV cells (the same on every
+    call) and sums every (sample, channel) map in float64; at the headline shape (batch 4, 512 x 180 x 180) the files stay
+    within the 64 MB limit; dump_arrays writes float32 / float64 .npy files; flat_outputs names the nested head outputs"""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    bev = torch.randn((3, 8, 20, 30), generator=g)
+    d = bench.bev_dump(bev, n_cells=100)
+    assert d["bev_cells"].shape == (100, 8) and d["bev_channel_sums"].shape == (3, 8)
+    idx = d["bev_cell_index"].numpy()
+    assert np.array_equal(idx, bench.bev_dump(bev, n_cells=100)["bev_cell_index"].numpy())
+    assert len(set(idx.tolist())) == 100 and idx.min() >= 0 and idx.max() < 3 * 20 * 30
+    for row, i in enumerate(idx.astype(np.int64)):
+        b, y, x = i // 600, (i % 600) // 30, i % 30
+        assert torch.equal(d["bev_cells"][row], bev[b, :, y, x])
+    assert torch.allclose(d["bev_channel_sums"], bev.double().sum((2, 3)))
+    assert bench.bev_dump(bev, n_cells=10 ** 6)["bev_cells"].shape == (3 * 20 * 30, 8)
+    cells = min(bench.DUMP_BEV_CELLS, 4 * 180 * 180)
+    assert cells * 512 * 4 + cells * 8 + 4 * 512 * 8 <= bench.DUMP_LIMIT_BYTES
+    total = bench.dump_arrays(str(tmp_path), d)
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["bev_cell_index.npy", "bev_cells.npy", "bev_channel_sums.npy"]
+    assert np.load(tmp_path / "bev_cells.npy").dtype == np.float32
+    assert np.load(tmp_path / "bev_channel_sums.npy").dtype == np.float64
+    assert total == sum(np.load(tmp_path / f).nbytes for f in files)
+    head = ([{"heatmap": torch.zeros(2, 10, 5), "center": torch.ones(2, 2, 5), "note": "text"}],)
+    assert sorted(bench.flat_outputs(head, "head")) == ["head_0_0_center", "head_0_0_heatmap"]
+    with pytest.raises(AssertionError):
+        bench.dump_arrays(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+
+
 def test_self_launch_refuses_fewer_devices_and_is_a_noop_under_a_launcher(monkeypatch):
     from isfusion_amd import launch
     monkeypatch.delenv("WORLD_SIZE", raising=False)
@@ -319,10 +350,11 @@ def test_parameter_changes_invalidate_packed_weight_caches():
     assert "linear0" not in ops._cache(sub, dev)
 
 
-def test_registry_surface_and_build_from_the_unmodified_reference_config():
+def test_registry_surface_and_build_from_the_unmodified_reference_config(tmp_path):
     """SURVEY 8b level 1: the reference's type names resolve to this build's classes; the point-cloud path builds from
-    configs/isfusion/isfusion_0075voxel.py as it stands (authoring container only: the file is not copied)"""
-    import os
+    the `model` dict of configs/isfusion/isfusion_0075voxel.py as it stands (tests/golden/isfusion_0075voxel_model.txt,
+    the evaluated dict written by tests/golden/make_golden_config.py), given as a dict and as an mmcv-style config file"""
+    import ast
     import pytest
     from isfusion_amd import registry
     from isfusion_amd.detector import ISFusionPtsPath
@@ -344,15 +376,19 @@ def test_registry_surface_and_build_from_the_unmodified_reference_config():
     assert type(vfe).__name__ == "HardSimpleVFE" and vfe.num_features == 5
     with pytest.raises(KeyError):
         registry.lookup("CenterHead")
-    cfg = "/root/reference/configs/isfusion/isfusion_0075voxel.py"
-    if not os.path.exists(cfg):
-        pytest.skip("reference tree not present (GPU box)")
-    net = registry.build_pts_path(cfg)
+    with open(os.path.join(ROOT, "tests", "golden", "isfusion_0075voxel_model.txt")) as f:
+        text = f.read()
+    model = ast.literal_eval(text)
+    cfg = tmp_path / "isfusion_0075voxel.py"
+    cfg.write_text("model = " + text)
     ref = ISFusionPtsPath()
-    a = {k: tuple(v.shape) for k, v in net.state_dict().items()}
-    assert a == {k: tuple(v.shape) for k, v in ref.state_dict().items()} and len(a) > 400
-    assert net.pts_bbox_head.test_cfg["nms_type"] is None and net.pts_bbox_head.bbox_coder["code_size"] == 10
-    assert net.fusion_encoder.num_points_in_pillar == 12 and net.pillar_size == [0.6, 0.6, 8]
+    want = {k: tuple(v.shape) for k, v in ref.state_dict().items()}
+    for config in ({"model": model}, str(cfg)):
+        net = registry.build_pts_path(config)
+        a = {k: tuple(v.shape) for k, v in net.state_dict().items()}
+        assert a == want and len(a) > 400
+        assert net.pts_bbox_head.test_cfg["nms_type"] is None and net.pts_bbox_head.bbox_coder["code_size"] == 10
+        assert net.fusion_encoder.num_points_in_pillar == 12 and net.pillar_size == [0.6, 0.6, 8]
 
 
 def test_neck_gemm_formulation_equals_the_conv_modules():

@@ -1,5 +1,5 @@
-import numpy as np, sys
-sys.path.insert(0,'/root/repo')
+import numpy as np, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from isfusion_amd import synthetic
 def down(c, shape, ks=(3,3,3), st=(2,2,2), pd=(1,1,1)):
     # c [n,4] (b,z,y,x); output o exists if any input i with o*st - pd <= i <= o*st - pd + ks - 1
