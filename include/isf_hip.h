@@ -897,6 +897,68 @@ int isf_nchw_to_split(const float* x, int batch_size, int x_channels, int x_chan
                       void* out_split, int out_channels, int channel_offset, isf_stream_t stream);
 int isf_split_to_nchw(const void* x_split, int batch_size, int channels, int hw, float* out, isf_stream_t stream);
 
+/* Detection-head training: targets, Hungarian assignment and losses (isf_head_loss.hip) ------------------------
+ * Boxes are [sum G, box_ld] fp32 rows in the LiDARInstance3DBoxes layout (x, y, z_bottom, dx, dy, dz, yaw, vx, vy), the
+ * samples' GT concatenated; gt_offsets is a HOST array of batch_size + 1 ints (sample b = rows [off[b], off[b+1])),
+ * batch_size <= ISF_HEAD_MAX_BATCH; gt_labels [sum G] int64.  Nothing here synchronises with the host.
+ * isf_head_heatmap_targets replaces the per-box loop of get_targets_single (dense_heads/transfusion_head_v2.py:1082-1128)
+ *   with gaussian_radius / draw_heatmap_gaussian (core/utils/gaussian.py:6-85): heatmap [B, classes, height, width]
+ *   (height = grid_size[1] / out_size_factor, rows indexed by the x cell as the reference's [[1, 0]] swap makes them).
+ *   params = 7 HOST floats: voxel_size (x, y), point_cloud_range (x, y), out_size_factor, gaussian_overlap, min_radius.
+ * isf_head_assign_cost replaces bbox_coder.decode (:980-994) and HungarianAssigner3D's cost (core/bbox/assigners/
+ *   hungarian_assigner.py:106-134): FocalLossCost + BBoxBEVL1Cost + IoU3DCost (BboxOverlaps3D, coordinate='lidar').
+ *   Head outputs [B, k, num_layers * num_proposals] (heatmap = logits, vel may be NULL); boxes [B, L*P, 9 | 7] decoded;
+ *   cost / iou [B, L, P, gt_stride] (gt_stride >= max G of a sample).  params = 15 HOST floats: out_size_factor *
+ *   voxel_size (x, y), pc_range (x, y), point_cloud_range (6), cls / reg / iou weights, focal alpha, gamma.
+ * isf_head_assign replaces linear_sum_assignment and the result assembly of :137-156: one workgroup per (sample, layer),
+ *   shortest augmenting paths in fp64; G or P above ISF_HEAD_MAX_ASSIGN -> ISF_ERR_UNSUPPORTED.  assigned_gt_inds
+ *   [B, L*P] int32 (0 background, k+1 = GT k of the sample), assigned_labels int64 (-1 background), max_overlaps fp32.
+ * isf_head_assemble_targets replaces :1036-1080 and the batch reductions of :932-948: labels [B, L*P] int64
+ *   (background = num_classes), label_weights fp32, bbox_targets / bbox_weights [B, L*P, code_size]
+ *   (TransFusionBBoxCoder.encode, core/bbox/coders/transfusion_bbox_coder.py:24-40), ious = clamp(max_overlaps, 0, 1),
+ *   num_pos [1] int32, stats [2] fp32 = (num_pos, matched_ious).  params = 5 HOST floats: out_size_factor * voxel_size
+ *   (x, y), pc_range (x, y), pos_weight.
+ * Losses (:1170-1276).  Each writes loss [1] (already divided by the avg factor and times loss_weight), scale [1] =
+ *   loss_weight / avg_factor and grad = the UNSCALED d loss_element / d input; isf_head_loss_grad_scale then writes
+ *   out = grad * scale * grad_output[0] (grad_output device scalar or NULL = 1) for the backward.  Reductions are fixed
+ *   order (no float atomics): bit-identical from run to run.
+ *   isf_gaussian_focal_loss: GaussianFocalLoss(alpha 2, gamma 4) of clip_sigmoid(logits) vs target, n elements,
+ *     avg = max(#(target == 1), 1); partials = 512 doubles of scratch.
+ *   isf_sigmoid_focal_loss: sigmoid focal loss of logits [B, classes, ld] columns [offset, offset + P) vs labels /
+ *     label_weights [B, ld], avg = max(num_pos[0], 1); grad has the logits' layout (columns outside the slice untouched).
+ *   isf_head_l1_loss: L1 of [center 2, height 1, dim 3, rot 2, vel 2] (each [B, k, ld]) vs bbox_targets [B, ld, code],
+ *     weight bbox_weights * code_weights (code_size HOST floats), avg = max(num_pos[0], 1); grad [B, code, ld]. */
+#define ISF_HEAD_MAX_BATCH 32
+#define ISF_HEAD_MAX_ASSIGN 1024
+int isf_head_heatmap_targets(const float* gt_boxes, int box_ld, const int64_t* gt_labels, const int* gt_offsets,
+                             int batch_size, int num_classes, int height, int width, const float* params,
+                             float* heatmap, isf_stream_t stream);
+int isf_head_assign_cost(const float* heatmap, const float* center, const float* height, const float* dim,
+                         const float* rot, const float* vel, int batch_size, int num_classes, int num_proposals,
+                         int num_layers, const float* gt_boxes, int box_ld, const int64_t* gt_labels,
+                         const int* gt_offsets, int gt_stride, const float* params, float* boxes, float* cost,
+                         float* iou, isf_stream_t stream);
+int isf_head_assign(const float* cost, const float* iou, int gt_stride, const int64_t* gt_labels,
+                    const int* gt_offsets, int batch_size, int num_proposals, int num_layers, int32_t* assigned_gt_inds,
+                    int64_t* assigned_labels, float* max_overlaps, isf_stream_t stream);
+int isf_head_assemble_targets(const int32_t* assigned_gt_inds, const float* max_overlaps, const float* gt_boxes,
+                              int box_ld, const int64_t* gt_labels, const int* gt_offsets, int batch_size,
+                              int num_proposals_total, int num_classes, int code_size, const float* params,
+                              int64_t* labels, float* label_weights, float* bbox_targets, float* bbox_weights,
+                              float* ious, int32_t* num_pos, float* stats, isf_stream_t stream);
+int isf_gaussian_focal_loss(const float* logits, const float* target, size_t n, float loss_weight, double* partials,
+                            float* grad, float* loss, float* scale, isf_stream_t stream);
+int isf_sigmoid_focal_loss(const float* logits, int batch_size, int num_classes, int num_proposals, int ld,
+                           int offset, const int64_t* labels, const float* label_weights, const int32_t* num_pos,
+                           float alpha, float gamma, float loss_weight, float* grad, float* loss, float* scale,
+                           isf_stream_t stream);
+int isf_head_l1_loss(const float* center, const float* height, const float* dim, const float* rot, const float* vel,
+                     int batch_size, int num_proposals, int ld, int offset, int code_size, const float* bbox_targets,
+                     const float* bbox_weights, const float* code_weights, const int32_t* num_pos, float loss_weight,
+                     float* grad, float* loss, float* scale, isf_stream_t stream);
+int isf_head_loss_grad_scale(const float* grad, size_t n, const float* scale, const float* grad_output, float* out,
+                             isf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -274,6 +274,21 @@ SIGNATURES = {
                                         c_int * 2, c_void_p]),
     "isf_nchw_to_split": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p]),
     "isf_split_to_nchw": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "isf_head_heatmap_targets": (c_int, [c_void_p, c_int, c_void_p, c_int_p, c_int, c_int, c_int, c_int, c_float_p,
+                                         c_void_p, c_void_p]),
+    "isf_head_assign_cost": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p, c_int, c_void_p, c_int_p, c_int,
+                                                                   c_float_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isf_head_assign": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                c_void_p, c_void_p]),
+    "isf_head_assemble_targets": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int_p, c_int, c_int, c_int,
+                                          c_int, c_float_p] + [c_void_p] * 8),
+    "isf_gaussian_focal_loss": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, ctypes.c_float] + [c_void_p] * 5),
+    "isf_sigmoid_focal_loss": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                       ctypes.c_float, ctypes.c_float, ctypes.c_float, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    "isf_head_l1_loss": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_void_p, c_float_p, c_void_p,
+                                                                ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isf_head_loss_grad_scale": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -7,6 +7,7 @@
 // (a device->host sync each).  Here: one wave per sample, one launch, no sync; lanes own proposals, the kept ones
 // are compacted in proposal order with ballot + popcount (the reference's mask indexing keeps that order).
 #include "isf_common.h"
+#include "isf_box.h"
 
 namespace isf {
 
@@ -43,20 +44,9 @@ __global__ __launch_bounds__(64) void decode_boxes_kernel(
         const float s = decode_sigmoid(hm[(size_t)c * ld + p]) * qs[(size_t)c * ld + p] * (c == lab ? 1.f : 0.f);
         if (c == 0 || s > best) { best = s; arg = c; }
       }
-      const float* ce = center + (size_t)b * 2 * ld;
-      const float* di = dim + (size_t)b * 3 * ld;
-      const float* ro = rot + (size_t)b * 2 * ld;
-      box[0] = ce[p] * prm.cell_x + prm.org_x;
-      box[1] = ce[ld + p] * prm.cell_y + prm.org_y;
-      box[3] = expf(di[p]);
-      box[4] = expf(di[ld + p]);
-      box[5] = expf(di[2 * ld + p]);
-      box[2] = height[(size_t)b * ld + p] - box[5] * 0.5f;   // gravity centre -> bottom centre
-      box[6] = atan2f(ro[p], ro[ld + p]);
-      if (vel) {
-        box[7] = vel[(size_t)b * 2 * ld + p];
-        box[8] = vel[(size_t)b * 2 * ld + ld + p];
-      }
+      decode_box(center + (size_t)b * 2 * ld, height + (size_t)b * ld, dim + (size_t)b * 3 * ld,
+                 rot + (size_t)b * 2 * ld, vel ? vel + (size_t)b * 2 * ld : nullptr, ld, p, prm.cell_x, prm.cell_y,
+                 prm.org_x, prm.org_y, box);
       keep = true;
 #pragma unroll
       for (int a = 0; a < 3; ++a) keep = keep && box[a] >= prm.lo[a] && box[a] <= prm.hi[a];

@@ -64,8 +64,8 @@ class ISFusionPtsPath(nn.Module):
         nk.pop("type", None)
         self.pts_neck = SECONDFPN(**nk)
         hd = dict(pts_bbox_head or ISFUSION_0075_FUSION["pts_bbox_head"])
-        for k in ("type", "loss_cls", "loss_bbox", "loss_heatmap", "loss_iou", "dropout", "bn_momentum", "activation"):
-            hd.pop(k, None)   # losses / training-only knobs: control plane
+        for k in ("type", "loss_iou", "bn_momentum", "activation"):
+            hd.pop(k, None)   # training-only knobs the head does not build (loss_iou is commented out in the config)
         self.pts_bbox_head = TransFusionHeadV2(**hd)
         osf = out_size_factor or ISFUSION_0075_FUSION["out_size_factor"]
         # isfusion.py:45-51
@@ -243,9 +243,8 @@ class ISFusionPtsPath(nn.Module):
 
     def forward_train_pts(self, pts, img_feats, img_metas, **kwargs):
         """training mode: extract_pts_feat + pts_neck WITH gradients (towards every parameter of the
-        LiDAR branch, the fusion encoder, the backbone stages and the neck, and towards the camera feature maps).  The
-        head's losses / target assignment are the reference's training control plane (out of scope): apply them to the
-        returned neck output."""
+        LiDAR branch, the fusion encoder, the backbone stages and the neck, and towards the camera feature maps).  forward_train
+        adds the detection head and its losses."""
         assert self.training, "call .train() first (eval mode runs the inference engine)"
         from .fusion_train import pack_stock_convs
         pack_stock_convs(self)
@@ -253,6 +252,15 @@ class ISFusionPtsPath(nn.Module):
         x = self._lidar(pts)
         feats, ins_heatmap = self.isfusion(pts, x, img_feats, img_metas, len(pts), **kwargs)
         return self.pts_neck(feats), ins_heatmap
+
+    def forward_train(self, points, img_feats, img_metas, gt_bboxes_3d, gt_labels_3d, **kwargs):
+        """ISFusionDetector.forward_train, points branch (isfusion.py:184-272): forward_train_pts (LiDAR branch, fusion
+        encoder, backbone, neck and the instance heat-map, with gradients), the head's forward_train on the neck output,
+        then TransFusionHeadV2.loss with the instance heat-map -> the reference's loss dict (loss_heatmap,
+        loss_heatmap_ins, layer_-1_loss_cls, layer_-1_loss_bbox, matched_ious).  The head needs train_cfg."""
+        feats, ins_heatmap = self.forward_train_pts(points, img_feats, img_metas, **kwargs)
+        preds = self.pts_bbox_head.forward_train(feats[0])
+        return self.pts_bbox_head.loss(gt_bboxes_3d, gt_labels_3d, preds, ins_heatmap=ins_heatmap)
 
     # ------------------------------------------------------------------------------------------- HIP graph
     def enable_graph(self, flag=True, pillar_side_stream=False, on_null_stream=False):

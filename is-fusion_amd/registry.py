@@ -81,7 +81,7 @@ def load_config(path):
 def build_pts_path(config):
     """config: path of configs/isfusion/isfusion_0075voxel.py (unmodified), its variable dict, or its `model` dict
     -> ISFusionPtsPath with every sub-module built from the config's own kwargs (isfusion.py:21-51 and
-    mvx_two_stage.py:36-75: the head receives test_cfg = model.test_cfg.pts)."""
+    mvx_two_stage.py:36-75: the head receives test_cfg = model.test_cfg.pts and train_cfg = model.train_cfg.pts)."""
     if isinstance(config, str):
         config = load_config(config)
     model = config["model"] if "model" in config else config
@@ -92,6 +92,9 @@ def build_pts_path(config):
     test_cfg = (model.get("test_cfg") or {}).get("pts")
     if test_cfg is not None:
         head["test_cfg"] = dict(test_cfg)
+    train_cfg = (model.get("train_cfg") or {}).get("pts")
+    if train_cfg is not None:      # mvx_two_stage.py:36-75 hands train_cfg.pts to the head the same way
+        head["train_cfg"] = dict(train_cfg)
     return ISFusionPtsPath(voxel_size=model["voxel_size"], pc_range=model["pc_range"],
                            out_size_factor=model.get("out_size_factor"),
                            pts_voxel_encoder=model["pts_voxel_encoder"], pts_middle_encoder=model["pts_middle_encoder"],

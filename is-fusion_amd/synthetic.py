@@ -4,7 +4,7 @@
 steps) ray-cast against a ground plane, 40 random axis-aligned boxes and 8 building facades, 10 sweeps with
 small ego motion, range-filtered to the point-cloud range, re-sampled to exactly ``num_points`` rows of
 (x, y, z, intensity, dt) and shuffled (PointShuffle).  ``uniform_cloud`` is BASELINE config-1's degenerate
-uniform-random cloud.
+uniform-random cloud.  ``scene_boxes(seed)`` returns the scene's object boxes as detection ground truth.
 """
 import numpy as np
 
@@ -75,6 +75,25 @@ def lidar_sweeps(seed, num_points, pc_range=PC_RANGE, num_sweeps=10):
     for j in range(3):
         pts[:, j] = np.clip(pts[:, j], r[j] + eps, r[3 + j] - eps)
     return np.ascontiguousarray(pts)
+
+
+def scene_boxes(seed):
+    """The 40 object boxes of the lidar_sweeps(seed, ...) scene (the same draws from the same generator, so the GT lies
+    where the points are) as detection ground truth: boxes [G, 9] float32 in the LiDARInstance3DBoxes layout (x, y,
+    z_bottom, dx, dy, dz, yaw 0, vx 0, vy 0), labels [G] int64 (0 'car' for boxes up to 6 m long, 1 'truck' above).
+    The boxes around the sensor that lidar_sweeps drops are dropped here too.  lidar_sweeps itself is untouched."""
+    rng = np.random.default_rng(seed)
+    nb = 40
+    ctr = np.stack([rng.uniform(-50, 50, nb), rng.uniform(-50, 50, nb)], 1)
+    size = np.stack([rng.uniform(1.5, 10, nb), rng.uniform(1.5, 3, nb), rng.uniform(1.0, 3.5, nb)], 1)
+    ground = -1.84
+    lo, hi = ctr - size[:, :2] / 2, ctr + size[:, :2] / 2
+    inside = (lo[:, 0] < 3) & (hi[:, 0] > -3) & (lo[:, 1] < 3) & (hi[:, 1] > -3)
+    keep = ~inside
+    n = int(keep.sum())
+    boxes = np.concatenate([ctr[keep], np.full((n, 1), ground), size[keep], np.zeros((n, 3))], 1).astype(np.float32)
+    labels = (size[keep, 0] > 6.0).astype(np.int64)
+    return np.ascontiguousarray(boxes), labels
 
 
 def uniform_cloud(seed, num_points, pc_range=PC_RANGE, num_features=5):

@@ -5,8 +5,9 @@ cross-attention over the BEV map with learned position embeddings, FFN) -> per-p
 
 Parameter / sub-module names equal the reference's (96 state-dict keys; checked with ``load_state_dict(strict=True)``
 into the reference class in tests/golden/make_golden_head.py).  Inference: ``forward`` / ``forward_split`` and the box
-decoding ``get_bboxes`` (isf_decode_boxes, below) are built and pinned by reference goldens; losses and target assignment
-(``loss``, ``get_targets``) are training control plane around this path and are not.
+decoding ``get_bboxes`` (isf_decode_boxes, below) are built and pinned by reference goldens.  Training:
+``forward_train`` (the same forward with gradients on the training autograd Functions), ``get_targets`` and ``loss``
+(head_loss.py / isf_head_loss.hip, pinned by tests/golden/head_loss_ref.npz).
 
 HIP path: the two 3x3 convs on the f16x3 sparse-conv kernel over the dense grid, top-k through ``isf_instance_topk``,
 all Linear layers through ``isf_linear_forward`` (the key / value projection of the 32400 x B BEV tokens folds the
@@ -15,11 +16,14 @@ learned key position embedding into a per-cell table), attention through ``isf_a
 proposals stay stock torch ops (tiny, channel counts below the MFMA tile).
 """
 import copy
+import warnings
 
 import torch
 from torch import nn
 
 from . import fusion_ops as ops
+from . import head_loss
+from ._lib import require_cuda as _lib_require_cuda
 from .dense_conv import PackedConvBN, SplitMap
 from .fusion_modules import PositionEmbeddingLearned, _SelfAttn
 from .spconv import from_split
@@ -79,12 +83,23 @@ class TransformerDecoderLayer(nn.Module):
 
 
 class TransFusionHeadV2(nn.Module):
+    _warned_cross_dropout = False
 
     def __init__(self, num_proposals=200, auxiliary=True, in_channels=512, hidden_channel=128, num_classes=10,
                  num_decoder_layers=1, num_heads=8, nms_kernel_size=3, ffn_channel=256, common_heads=None,
-                 num_heatmap_convs=2, test_cfg=None, bbox_coder=None, dense_conv="hip", **kwargs):
+                 num_heatmap_convs=2, test_cfg=None, bbox_coder=None, dense_conv="hip", train_cfg=None, loss_cls=None,
+                 loss_bbox=None, loss_heatmap=None, dropout=0.1, **kwargs):
         super().__init__()
         self.num_classes, self.num_proposals, self.auxiliary = num_classes, num_proposals, auxiliary
+        self.dropout = float(dropout)     # TransformerDecoderLayer dropouts (transfusion_head_v2.py:42-60), forward_train only
+        # training: the reference's names (transfusion_head_v2.py:642-646, 758-766); None = the shipped configuration
+        self.train_cfg = dict(train_cfg) if train_cfg is not None else None
+        self.loss_cls = dict(loss_cls or head_loss.SHIPPED_LOSS_CLS)
+        self.loss_bbox = dict(loss_bbox or head_loss.SHIPPED_LOSS_BBOX)
+        self.loss_heatmap = dict(loss_heatmap or head_loss.SHIPPED_LOSS_HEATMAP)
+        head_loss.check_loss_cfgs(self.loss_cls, self.loss_bbox, self.loss_heatmap)
+        if self.train_cfg is not None:
+            head_loss.check_train_cfg(self.train_cfg)
         self.num_heads, self.num_decoder_layers, self.nms_kernel_size = num_heads, num_decoder_layers, nms_kernel_size
         self.test_cfg = test_cfg or dict(dataset="nuScenes", grid_size=[1440, 1440, 40], out_size_factor=8)
         self.dense_conv = dense_conv
@@ -305,6 +320,106 @@ class TransFusionHeadV2(nn.Module):
             feats = [feats]
         # multi_apply transposes the per-level lists: a 1-tuple holding the list of per-level result dicts
         return ([self.forward_single(f, None, metas)[0] for f in feats],)
+
+    def forward_train(self, feats):
+        """forward_single (:771-892) in training mode WITH gradients, on the training autograd Functions: the 3x3 convs
+        through dense_train.conv_stack, top-k proposals through isf_instance_topk (no gradient), differentiable gathers
+        of the proposal features, the decoder layer's attention through fusion_train._mha (HIP linear + attention
+        kernels), FFN / layer norms, the prediction heads as HIP linears + bn1d_relu.  Dropout p = self.dropout where the
+        reference applies it (dropout1..3 and the FFN dropout; the attention-probability dropout of the 200 x 200
+        self-attention on the dropout kernels).  The 200 x 32400 cross-attention has no probability dropout (the kernels
+        take Lk <= 512): a warning says so once.  feats: [B, in_channels, X, Y] or a one-element list -> ([dict],) as
+        forward returns it."""
+        from . import dense_train, fusion_train
+        x = feats[0] if isinstance(feats, (list, tuple)) else feats
+        _lib_require_cuda(x)
+        B, _, X, Y = x.shape
+        HW, P, C = X * Y, self.num_proposals, self.num_classes
+        E = self.shared_conv.out_channels
+        p, tr = self.dropout, self.training
+        feat = dense_train.conv_stack(self.shared_conv, x)                                # NCHW view of [B*HW, E] rows
+        dense_heatmap = dense_train.conv_stack(self.heatmap_head[1], dense_train.conv_stack(self.heatmap_head[0], feat))
+        dense_heatmap = dense_heatmap.float().contiguous()
+        pool1 = (8, 9) if self.test_cfg["dataset"] == "nuScenes" else (1, 2)
+        top, raw, masked = ops.instance_topk(dense_heatmap.detach(), P, self.nms_kernel_size, pool1, return_masked=True)
+        cell, labels = top, torch.div(raw, HW, rounding_mode="floor")
+        self.query_labels = labels
+        self.last_top_index = cell
+        rows = dense_train.to_rows(feat)                                                   # [B*HW, E], row b*HW + cell
+        query = rows.view(B, HW, E).gather(1, cell[:, :, None].expand(-1, -1, E))          # [B, P, E]
+        one_hot = torch.nn.functional.one_hot(labels, C).float()                          # class_encoding (Conv1d, k=1)
+        query = (query + torch.nn.functional.linear(one_hot, self.class_encoding.weight[:, :, 0],
+                                                    self.class_encoding.bias)).reshape(B * P, E)
+        bev_pos = self._bev_pos(x.device)                                                  # [1, HW, 2]
+        query_pos = bev_pos[0][cell]                                                       # [B, P, 2]
+        drop = torch.nn.functional.dropout
+        ln = torch.nn.functional.layer_norm
+        if p > 0.0 and tr and not TransFusionHeadV2._warned_cross_dropout:
+            TransFusionHeadV2._warned_cross_dropout = True
+            warnings.warn("TransFusionHeadV2.forward_train: no dropout on the attention probabilities of the 200 x 32400 "
+                          "cross-attention (the dropout kernels take at most 512 keys); the output dropout is applied")
+        ret_dicts = []
+        for i, l in enumerate(self.decoder):
+            qpe = ops._pos_embed(l.self_posembed, query_pos).reshape(B * P, E)
+            kpe = ops._pos_embed(l.cross_posembed, bev_pos)[0]                             # [HW, E], the same per sample
+            xq = query + qpe                                                               # q = k = v (:98-101)
+            sa = fusion_train._mha(xq, xq, xq, l.self_attn, B, P, P, l.nhead, p if tr else 0.0)
+            query = ln(query + drop(sa, p, tr), (E,), l.norm1.weight, l.norm1.bias, l.norm1.eps)
+            kv = (rows.view(B, HW, E) + kpe[None]).reshape(B * HW, E)                      # key = value = feat + pos
+            ca = fusion_train._mha(query + qpe, kv, kv, l.multihead_attn, B, P, HW, l.nhead)
+            query = ln(query + drop(ca, p, tr), (E,), l.norm2.weight, l.norm2.bias, l.norm2.eps)
+            h = drop(torch.relu(fusion_train.linear(query, l.linear1)), p, tr)
+            query = ln(query + drop(fusion_train.linear(h, l.linear2), p, tr), (E,), l.norm3.weight, l.norm3.bias,
+                       l.norm3.eps)
+            res = {}
+            for name in self.prediction_heads[i].heads:
+                res[name] = self._train_pred_head(getattr(self.prediction_heads[i], name), query, B, P)
+            res["center"] = res["center"] + query_pos.permute(0, 2, 1)
+            query_pos = res["center"].detach().permute(0, 2, 1)
+            ret_dicts.append(res)
+        ret_dicts[0]["query_heatmap_score"] = masked.view(B, C, HW).gather(2, cell[:, None, :].expand(-1, C, -1))
+        ret_dicts[0]["dense_heatmap"] = dense_heatmap
+        if not self.auxiliary:
+            return ([ret_dicts[-1]],)
+        out = {}
+        for key in ret_dicts[0]:
+            if key in ("dense_heatmap", "query_heatmap_score"):
+                out[key] = ret_dicts[0][key]
+            else:
+                out[key] = torch.cat([r[key] for r in ret_dicts], -1) if len(ret_dicts) > 1 else ret_dicts[0][key]
+        return ([out],)
+
+    @staticmethod
+    def _train_pred_head(seq, query, B, P):
+        """one FFN output (:505-590; Conv1d k=1 = per-proposal linear) on [B*P, E] rows -> [B, n, P]: the HIP linear
+        (the last layer's rows zero-padded to 32, which both the forward's 16-column tiles and the backward's
+        32-deep K take) and bn1d_relu for the ConvModule1d layers"""
+        from .fusion_train import linear_w
+        from .norm import bn1d_relu
+        h = query
+        for m in seq:
+            if isinstance(m, _ConvModule1d):
+                h = bn1d_relu(m.bn, linear_w(h, m.conv.weight[:, :, 0]), relu=True)
+            else:
+                n = m.weight.shape[0]
+                pad = (-n) % 32            # 32: the backward's dX GEMM reads these rows as its K
+                w = torch.nn.functional.pad(m.weight[:, :, 0], (0, 0, 0, pad))
+                b = torch.nn.functional.pad(m.bias, (0, pad)) if m.bias is not None else None
+                h = linear_w(h, w, b)[:, :n]
+        return h.reshape(B, P, -1).permute(0, 2, 1)
+
+    def get_targets(self, gt_bboxes_3d, gt_labels_3d, preds_dict):
+        """:910-960 for the whole batch on the device (isf_head_loss.hip: heat-map targets, assignment cost, linear sum
+        assignment, target assembly).  gt_bboxes_3d: per sample a [G, 9] tensor in the LiDARInstance3DBoxes layout
+        (bottom centre) or an object with such a `.tensor`; preds_dict: the per-layer list of prediction dicts.
+        -> (labels, label_weights, bbox_targets, bbox_weights, ious, num_pos, matched_ious, heatmap); num_pos and
+        matched_ious are device scalars (no host sync)."""
+        return head_loss.get_targets(self, gt_bboxes_3d, gt_labels_3d, preds_dict[0])
+
+    def loss(self, gt_bboxes_3d, gt_labels_3d, preds_dicts, ins_heatmap=None, **kwargs):
+        """:1143-1276 -> dict(loss_heatmap, loss_heatmap_ins (when ins_heatmap is given), layer_-1_loss_cls,
+        layer_-1_loss_bbox, matched_ious); the losses are autograd Functions over the fused loss kernels."""
+        return head_loss.loss(self, gt_bboxes_3d, gt_labels_3d, preds_dicts, ins_heatmap)
 
     @torch.no_grad()
     def get_bboxes(self, preds_dicts, metas=None, img=None, rescale=False, for_roi=False):

@@ -12,8 +12,9 @@ than N visible GPUs is an error) -- the reference's tools/run-nus.sh:11-13; unde
 One process per GPU; every rank draws its own synthetic frames.  The module is wrapped in DistributedDataParallel
 (bucketed gradient all-reduce overlapped with the backward); the path's BatchNorm layers are the config's:
 isfusion_amd.norm.NaiveSyncBatchNorm where the reference uses naiveSyncBN (cross-rank statistics, one all_reduce of
-[2C] per layer, whenever the world size is > 1), plain BatchNorm (local-shard statistics) elsewhere.  The loss is a stand-in (feature energy + heat-map mean): the detection losses and
-target assignment are the reference's training control plane.  Prints one JSON line per rank 0 with ms per step.
+[2C] per layer, whenever the world size is > 1), plain BatchNorm (local-shard statistics) elsewhere.  The default loss is a stand-in (feature energy + heat-map mean); --loss detection trains
+on the detection head's real losses (ISFusionPtsPath.forward_train: targets, Hungarian assignment and losses on the HIP
+kernels) against the synthetic scenes' boxes (synthetic.scene_boxes).  Prints one JSON line per rank 0 with ms per step.
 Also runs on a single GPU without torchrun (world size 1)."""
 import argparse
 import json
@@ -45,6 +46,9 @@ def main():
                          "by side; with --backend gloo")
     ap.add_argument("--stock-dense", action="store_true",
                     help="the dense 3x3 conv + BatchNorm stacks on the stock modules (MIOpen) instead of dense_train.py (A/B)")
+    ap.add_argument("--loss", default="standin", choices=["standin", "detection"],
+                    help="standin: feature energy + heat-map mean (the neck output only); detection: the head's "
+                         "forward_train and TransFusionHeadV2.loss on the synthetic scenes' GT boxes")
     a = ap.parse_args()
     from isfusion_amd import launch, synthetic
     if a.stock_dense:
@@ -65,8 +69,14 @@ def main():
     net._lidar.randomize_weights_(0).randomize_bn_(1)
     for mod, seed in ((net.fusion_encoder, 100), (net.pts_backbone, 200), (net.pts_neck, 250)):
         mod.load_state_dict(seeded_state_dict(mod, seed))
-    for p in net.pts_bbox_head.parameters():
-        p.requires_grad_(False)                                      # head losses: control plane, not exercised here
+    detection = a.loss == "detection"
+    if detection:
+        from isfusion_amd import head_loss
+        if net.pts_bbox_head.train_cfg is None:
+            net.pts_bbox_head.train_cfg = dict(head_loss.SHIPPED_TRAIN_CFG)
+    else:
+        for p in net.pts_bbox_head.parameters():
+            p.requires_grad_(False)                                  # the stand-in loss does not reach the head
     net = net.to(dev)
 
     class Wrap(torch.nn.Module):                                     # DDP hooks forward(); the path's entry is a method
@@ -74,7 +84,9 @@ def main():
             super().__init__()
             self.m = m
 
-        def forward(self, pts, img, metas, kw):
+        def forward(self, pts, img, metas, kw, gt=None):
+            if gt is not None:
+                return self.m.forward_train(pts, img, metas, gt[0], gt[1], **kw)
             return self.m.forward_train_pts(pts, img, metas, **kw)
 
     # gradient_as_bucket_view: the gradients ARE views of the all-reduce buckets -- no per-parameter copy into a bucket
@@ -83,6 +95,10 @@ def main():
     ddp = torch.nn.parallel.DistributedDataParallel(Wrap(net), device_ids=[local], gradient_as_bucket_view=True)
     opt = torch.optim.SGD([p for p in net.parameters() if p.requires_grad], lr=1e-4, momentum=0.9)
     pts = [torch.from_numpy(synthetic.lidar_sweeps(9000 + 100 * rank + i, a.points)).to(dev) for i in range(a.batch)]
+    gt = None
+    if detection:
+        scenes = [synthetic.scene_boxes(9000 + 100 * rank + i) for i in range(a.batch)]
+        gt = ([torch.from_numpy(b).to(dev) for b, _ in scenes], [torch.from_numpy(l).to(dev) for _, l in scenes])
     inp = synthetic.fusion_inputs(7 + rank, a.batch)
     img = tuple(torch.from_numpy(x).to(dev).to(torch.bfloat16 if a.bf16 else torch.float32) for x in inp["img_feats"])
     kw = dict(lidar2img=torch.from_numpy(inp["lidar2img"]), img_aug_matrix=torch.from_numpy(inp["img_aug_matrix"]),
@@ -97,8 +113,12 @@ def main():
             dist.barrier()
             t0 = time.perf_counter()
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=a.autocast):
-            out, hm = ddp(pts, img, metas, kw)
-            loss = (out[0].float() ** 2).mean() + hm.float().sigmoid().mean()
+            if detection:
+                ld = ddp(pts, img, metas, kw, gt)
+                loss = sum(v.float() for k, v in ld.items() if k != "matched_ious")
+            else:
+                out, hm = ddp(pts, img, metas, kw)
+                loss = (out[0].float() ** 2).mean() + hm.float().sigmoid().mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()                                              # bucketed RCCL all-reduce inside
         opt.step()
@@ -109,7 +129,7 @@ def main():
     dt = (time.perf_counter() - t0) / max(a.steps, 1)
     per_step = [round(marks[i].elapsed_time(marks[i + 1]), 1) for i in range(a.steps + 1)]   # [0] = the warm-up step
     if rank == 0:
-        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast,
+        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss,
                           "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses]}))
     dist.destroy_process_group()
 
