@@ -959,6 +959,57 @@ int isf_head_l1_loss(const float* center, const float* height, const float* dim,
 int isf_head_loss_grad_scale(const float* grad, size_t n, const float* scale, const float* grad_output, float* out,
                              isf_stream_t stream);
 
+/* BEV NMS and test-time-augmentation merge (isf_nms.hip) ------------------------------------------------------
+ * isf_nms_segmented replaces the NMS branch of TransFusionHeadV2.get_bboxes (dense_heads/transfusion_head_v2.py:
+ *   1344-1403: circle_nms, core/post_processing/box3d_nms.py:183-218; nms_gpu, ops/iou3d/iou3d_utils.py:26-57) and the
+ *   per-class loop of merge_aug_bboxes_3d (core/post_processing/merge_augs.py:58-86: nms_gpu / nms_normal_gpu,
+ *   iou3d_utils.py:60-77, iou3d_kernel.cu nms_kernel / nms_normal_kernel) in ONE launch, one workgroup per segment.
+ *   Rows: boxes [num_groups * group_stride, box_ld] (box_format ISF_NMS_BOX_LIDAR: x, y, z_bottom, dx, dy, dz, yaw, ...
+ *   as isf_decode_boxes writes them, turned into xyxyr inside as xywhr2xyxyr does; ISF_NMS_BOX_XYXYR: x1, y1, x2, y2, r),
+ *   scores [rows], labels [rows] int32 or NULL (then every row is task 0).  Group g = rows [g * group_stride,
+ *   g * group_stride + counts[g]) (counts: DEVICE int32 [num_groups], or NULL = all rows); group_stride <=
+ *   ISF_NMS_MAX_SEGMENT, else ISF_ERR_UNSUPPORTED before any launch.  Segment (g, t) = the group's rows whose class maps
+ *   to task t through task_of_class (HOST, num_classes <= ISF_NMS_MAX_CLASSES entries, -1 = dropped).  Per task (HOST
+ *   arrays, num_tasks <= ISF_NMS_MAX_TASKS) a mode and a threshold:
+ *     ISF_NMS_KEEP    every row kept, in input order (a task with radius <= 0)
+ *     ISF_NMS_ROTATE  nms_gpu: suppressed when the rotated BEV IoU (fp64 overlap, isf_bev.h) > thr
+ *     ISF_NMS_NORMAL  nms_normal_gpu: suppressed when the float32 axis-aligned IoU of the xyxy corners > thr
+ *     ISF_NMS_CIRCLE  circle_nms on columns 0-1: suppressed when the SQUARED centre distance <= thr (the reference's
+ *                     own semantics; it passes the radius as thr)
+ *   Within a segment: score descending, equal scores by lower row (the reference's sorts are not stable), then the first
+ *   pre_maxsize (< 0: all), greedy suppression, the first post_max_size kept (< 0: all).  Outputs (device, no host
+ *   sync): keep [rows] uint8 (1 = kept; rows past a count or of no task 0), keep_index [num_groups * num_tasks,
+ *   group_stride] int32 = the kept rows (absolute row numbers) of each segment in kept order, keep_count
+ *   [num_groups * num_tasks] int32.  workspace = isf_nms_workspace_size(...) bytes of device scratch (the mask).
+ * isf_boxes_iou_bev replaces boxes_iou_bev (iou3d_utils.py:6-23, iou3d_kernel.cu boxes_iou_bev_kernel): boxes_a
+ *   [M, 5] / boxes_b [N, 5] xyxyr -> iou [M, N] = overlap / max(area_a + area_b - overlap, 1e-8), areas from the xyxy
+ *   corners.
+ * isf_bbox_mapping_back replaces bbox3d_mapping_back (core/bbox/transforms.py:5-24) for num_views <=
+ *   ISF_NMS_MAX_VIEWS views in place: rows [v * view_stride, v * view_stride + counts[v]) (counts DEVICE or NULL) of
+ *   boxes [*, box_ld >= 7]; LiDARInstance3DBoxes.flip (horizontal: columns 1::7 negated, yaw = pi - yaw; vertical:
+ *   columns 0::7 negated, yaw = -yaw) then scale(1 / scale_factor[v]) of every column but yaw.  horizontal / vertical
+ *   / scale_factor are HOST arrays of num_views. */
+#define ISF_NMS_MAX_SEGMENT 1024
+#define ISF_NMS_MAX_TASKS 16
+#define ISF_NMS_MAX_CLASSES 64
+#define ISF_NMS_MAX_VIEWS 16
+#define ISF_NMS_KEEP 0
+#define ISF_NMS_ROTATE 1
+#define ISF_NMS_NORMAL 2
+#define ISF_NMS_CIRCLE 3
+#define ISF_NMS_BOX_XYXYR 0
+#define ISF_NMS_BOX_LIDAR 1
+size_t isf_nms_workspace_size(int num_groups, int group_stride, int num_tasks, int pre_maxsize);
+int isf_nms_segmented(const float* boxes, int box_ld, int box_format, const float* scores, const int32_t* labels,
+                      const int32_t* counts, int num_groups, int group_stride, int num_classes,
+                      const int* task_of_class, int num_tasks, const int* task_mode, const float* task_thr,
+                      int pre_maxsize, int post_max_size, void* workspace, size_t workspace_bytes, uint8_t* keep,
+                      int32_t* keep_index, int32_t* keep_count, isf_stream_t stream);
+int isf_boxes_iou_bev(const float* boxes_a, int num_a, const float* boxes_b, int num_b, float* iou,
+                      isf_stream_t stream);
+int isf_bbox_mapping_back(float* boxes, int box_ld, int num_views, int view_stride, const int32_t* counts,
+                          const int* horizontal, const int* vertical, const float* scale_factor, isf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -289,6 +289,12 @@ SIGNATURES = {
     "isf_head_l1_loss": (c_int, [c_void_p] * 5 + [c_int] * 5 + [c_void_p, c_void_p, c_float_p, c_void_p,
                                                                 ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "isf_head_loss_grad_scale": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isf_nms_workspace_size": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "isf_nms_segmented": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int_p,
+                                  c_int, c_int_p, c_float_p, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
+    "isf_boxes_iou_bev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "isf_bbox_mapping_back": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int_p, c_int_p, c_float_p, c_void_p]),
 }
 
 _lib = None

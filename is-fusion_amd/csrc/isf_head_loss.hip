@@ -16,6 +16,7 @@
 //                      loss_weight / avg_factor; the backward multiplies by that scalar and the incoming gradient
 #include "isf_common.h"
 #include "isf_box.h"
+#include "isf_bev.h"
 
 // float arithmetic below restates torch float32 op sequences: keep every product and sum separately rounded
 #pragma clang fp contract(off)
@@ -126,65 +127,7 @@ __global__ __launch_bounds__(kThreads) void heatmap_targets_kernel(const float* 
 }
 
 // ------------------------------------------------------------------------------------------------ 3D IoU
-// BEV overlap of two rotated rectangles with the semantics of boxes_overlap_bev_gpu (mmdet3d/ops/iou3d/src/
-// iou3d_kernel.cu) on xywhr2xyxyr boxes: corner (x1,y1)..(x1,y2) of the axis-aligned box, each turned about the centre
-// by (dx cos a + dy sin a, -dx sin a + dy cos a).  Computed here as a convex clip (Sutherland-Hodgman) in fp64.
-struct Poly {
-  double x[16], y[16];
-  int n;
-};
-
-__device__ void bev_corners(const float* box, double* px, double* py) {
-  // xywhr2xyxyr (core/bbox/structures/utils.py:66-84) in float32, then the kernel's centre / rotation
-  const float hw = box[3] / 2.f, hl = box[4] / 2.f;
-  const float x1 = box[0] - hw, y1 = box[1] - hl, x2 = box[0] + hw, y2 = box[1] + hl;
-  const double cx = ((double)x1 + x2) / 2.0, cy = ((double)y1 + y2) / 2.0;
-  const double ca = cos((double)box[6]), sa = sin((double)box[6]);
-  const double xs[4] = {x1, x2, x2, x1}, ys[4] = {y1, y1, y2, y2};
-  for (int k = 0; k < 4; ++k) {
-    const double dx = xs[k] - cx, dy = ys[k] - cy;
-    px[k] = dx * ca + dy * sa + cx;
-    py[k] = -dx * sa + dy * ca + cy;
-  }
-}
-
-__device__ double bev_overlap(const float* a, const float* b) {
-  double ax[4], ay[4], bx[4], by[4];
-  bev_corners(a, ax, ay);
-  bev_corners(b, bx, by);
-  // orientation of the clipping polygon (a mirror image only flips the sign)
-  double sb = 0.0;
-  for (int k = 0; k < 4; ++k) sb += bx[k] * by[(k + 1) & 3] - bx[(k + 1) & 3] * by[k];
-  if (!(fabs(sb) > 0.0)) return 0.0;
-  const double orient = sb > 0.0 ? 1.0 : -1.0;
-  Poly cur, nxt;
-  cur.n = 4;
-  for (int k = 0; k < 4; ++k) { cur.x[k] = ax[k]; cur.y[k] = ay[k]; }
-  for (int e = 0; e < 4 && cur.n > 0; ++e) {
-    const double ex0 = bx[e], ey0 = by[e], ex1 = bx[(e + 1) & 3], ey1 = by[(e + 1) & 3];
-    const double ux = ex1 - ex0, uy = ey1 - ey0;
-    nxt.n = 0;
-    for (int k = 0; k < cur.n; ++k) {
-      const int k1 = (k + 1) % cur.n;
-      const double s0 = orient * (ux * (cur.y[k] - ey0) - uy * (cur.x[k] - ex0));
-      const double s1 = orient * (ux * (cur.y[k1] - ey0) - uy * (cur.x[k1] - ex0));
-      if (s0 >= 0.0 && nxt.n < 16) { nxt.x[nxt.n] = cur.x[k]; nxt.y[nxt.n] = cur.y[k]; ++nxt.n; }
-      if ((s0 >= 0.0) != (s1 >= 0.0) && nxt.n < 16) {
-        const double t = s0 / (s0 - s1);
-        nxt.x[nxt.n] = cur.x[k] + t * (cur.x[k1] - cur.x[k]);
-        nxt.y[nxt.n] = cur.y[k] + t * (cur.y[k1] - cur.y[k]);
-        ++nxt.n;
-      }
-    }
-    cur = nxt;
-  }
-  double area = 0.0;
-  for (int k = 0; k < cur.n; ++k) {
-    const int k1 = (k + 1) % cur.n;
-    area += cur.x[k] * cur.y[k1] - cur.x[k1] * cur.y[k];
-  }
-  return fabs(area) / 2.0;
-}
+// bev_overlap: isf_bev.h (shared with the rotated NMS)
 
 // BboxOverlaps3D(coordinate='lidar') = LiDARInstance3DBoxes.overlaps (core/bbox/structures/base_box3d.py:388-442):
 // BEV overlap x height overlap / union, bottom-centre boxes

@@ -358,3 +358,69 @@ class ISFusionPtsPath(nn.Module):
         backbone stays stock).  -> [dict(pts_bbox=...)] per sample."""
         x = self.pts_neck(self.extract_pts_feat(points, img_feats, img_metas, **kwargs))
         return [dict(pts_bbox=r) for r in self.simple_test_pts(x, img_feats, img_metas, rescale=rescale)]
+
+    @torch.no_grad()
+    def aug_test_pts(self, x, x_img, img_metas, rescale=False):
+        """mvx_two_stage.py:455-473 + merge_aug_bboxes_3d (core/post_processing/merge_augs.py:8-101) for the V views of
+        ONE frame run as one batch (x: the neck output [V, ...]; img_metas: one meta per view with pcd_scale_factor /
+        pcd_horizontal_flip / pcd_vertical_flip): head forward, the batched decode (+ the test_cfg NMS) of get_bboxes,
+        every view's boxes mapped back (isf_bbox_mapping_back, one launch), per-class NMS (nms_gpu when
+        test_cfg.use_rotate_nms else nms_normal_gpu, threshold nms_thr; one isf_nms_segmented launch), score order,
+        the first min(max_num, boxes) -- all on the device with one host read at the end.  At most
+        nms.MAX_SEGMENT // num_proposals views (5 at 200 proposals).  -> dict(boxes_3d, scores_3d, labels_3d), on the
+        device (the reference's bbox3d2result moves them to the CPU)."""
+        from . import nms
+        metas = [m[0] if isinstance(m, (list, tuple)) else m for m in img_metas]
+        head = self.pts_bbox_head
+        outs = head(x, x_img, metas)
+        boxes, scores, labels, counts, keep = head.decode_and_nms(outs)
+        V, P, D = boxes.shape
+        assert V == len(metas), (V, len(metas))
+        valid = keep if keep is not None else torch.arange(P, device=boxes.device)[None, :] < counts[:, None].long()
+        mapped = boxes.reshape(V * P, D).clone()
+        nms.mapping_back_(mapped, V, P, [m.get("pcd_scale_factor", 1.0) for m in metas],
+                          [m.get("pcd_horizontal_flip", False) for m in metas],
+                          [m.get("pcd_vertical_flip", False) for m in metas])
+        lab = torch.where(valid, labels, torch.full_like(labels, -1)).view(-1)
+        mb, ms, ml = nms.merge_rows(mapped, scores.reshape(-1), lab, head.test_cfg, head.num_classes)
+        box_type = metas[0].get("box_type_3d")
+        return dict(boxes_3d=box_type(mb, box_dim=mb.shape[-1]) if box_type is not None else mb, scores_3d=ms,
+                    labels_3d=ml)
+
+    @torch.no_grad()
+    def aug_test(self, points, img_metas, img_feats, rescale=False, **kwargs):
+        """mvx_two_stage.py:438-446 for the point-cloud branch, the views of one frame (input_pipeline.flip_tta_views)
+        run as ONE batched forward, views as samples.  points: V point tensors; img_metas: V metas (dicts, or
+        one-element lists of one); img_feats: the frame's camera neck outputs ([num_cams, C, H, W] per level), shared by
+        every view; lidar2img / img_aug_matrix: [1 or V, num_cams, 4, 4]; each view's lidar_aug_matrix comes from its
+        meta (or kwargs lidar_aug_matrix [V, 4, 4]) and is what makes Point-to-Grid / IGF sample the un-flipped pixels.
+        -> [dict(pts_bbox=dict(boxes_3d, scores_3d, labels_3d))]."""
+        metas = [m[0] if isinstance(m, (list, tuple)) else m for m in img_metas]
+        V = len(points)
+        assert V == len(metas) and V >= 1, (V, len(metas))
+        lam = kwargs.pop("lidar_aug_matrix", None)
+        if lam is None:
+            lam = torch.stack([torch.as_tensor(m["lidar_aug_matrix"]) for m in metas])
+        lam = torch.as_tensor(lam)
+        assert lam.shape[0] == V, lam.shape
+        l2i, iam = torch.as_tensor(kwargs.pop("lidar2img")), torch.as_tensor(kwargs.pop("img_aug_matrix"))
+        ncam = l2i.shape[1]
+        l2i = l2i.expand(V, *l2i.shape[1:]) if l2i.shape[0] == 1 else l2i
+        iam = iam.expand(V, *iam.shape[1:]) if iam.shape[0] == 1 else iam
+        feats = tuple(f.repeat(V, 1, 1, 1) if f.shape[0] == ncam else f for f in img_feats)
+        x = self.pts_neck(self.extract_pts_feat(list(points), feats, metas, lidar2img=l2i, img_aug_matrix=iam,
+                                                lidar_aug_matrix=lam, **kwargs))
+        return [dict(pts_bbox=self.aug_test_pts(x, feats, metas, rescale=rescale))]
+
+    def forward_test(self, points, img_metas, img_feats, **kwargs):
+        """Base3DDetector.forward_test (models/detectors/base.py:21-55): points / img_metas are lists over the
+        augmentations (each a list over samples); one augmentation -> simple_test, several -> aug_test (of one frame,
+        as the reference supports)."""
+        if not isinstance(points, (list, tuple)) or not isinstance(img_metas, (list, tuple)):
+            raise TypeError("points and img_metas must be lists (over augmentations)")
+        if len(points) != len(img_metas):
+            raise ValueError(f"num of augmentations ({len(points)}) != num of image meta ({len(img_metas)})")
+        if len(points) == 1:
+            return self.simple_test(points[0], img_metas[0], img_feats, **kwargs)
+        assert all(len(p) == 1 for p in points), "aug_test takes the views of one frame"
+        return self.aug_test([p[0] for p in points], [m[0] for m in img_metas], img_feats, **kwargs)

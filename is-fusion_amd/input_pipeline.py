@@ -38,6 +38,47 @@ def draw_train_aug(resize_lim=(0.9, 1.1), rot_lim=(-0.78539816, 0.78539816), tra
                 flip_horizontal=bool(fh), flip_vertical=bool(fv))
 
 
+def flip_tta_views(points, meta, flip=True, pcd_horizontal_flip=True, pcd_vertical_flip=True, pts_scale_ratio=(1.0,)):
+    """The views of MultiScaleFlipAug3D (datasets/pipelines/test_time_aug.py:66-111) through the test branch of
+    RandomFlip3DV2 (transforms_3d.py:1188-1204), for one frame.  points: [N, >= 3] tensor or array; meta: its dict
+    (lidar_aug_matrix 4 x 4, identity when absent).  Views in the reference's order: for each pts_scale_ratio, for
+    horizontal in ([False, True] if flip and pcd_horizontal_flip else [False]), for vertical in (likewise).  A
+    horizontal flip negates y, a vertical one x; lidar_aug_matrix[:3, :] = R @ lidar_aug_matrix[:3, :] with R = V @ H;
+    each view's meta gets pcd_horizontal_flip, pcd_vertical_flip, pcd_scale_factor and transformation_3d_flow.  As in
+    the shipped test pipeline (GlobalRotScaleTransV2 with is_train=False), the points are not scaled: pcd_scale_factor
+    only scales the boxes back in the merge.  -> (list of points, list of metas)."""
+    if not flip and (pcd_horizontal_flip or pcd_vertical_flip):
+        pcd_horizontal_flip = pcd_vertical_flip = False     # MultiScaleFlipAug3D: no flip views without `flip`
+    if isinstance(pts_scale_ratio, (int, float)):
+        pts_scale_ratio = [pts_scale_ratio]
+    hs = [False, True] if pcd_horizontal_flip else [False]
+    vs = [False, True] if pcd_vertical_flip else [False]
+    lam0 = np.asarray(meta.get("lidar_aug_matrix", np.eye(4, dtype=np.float32)))
+    out_pts, out_metas = [], []
+    for scale in pts_scale_ratio:
+        for h in hs:
+            for v in vs:
+                p = points.clone() if isinstance(points, torch.Tensor) else np.array(points, copy=True)
+                m = dict(meta)
+                flow = list(meta.get("transformation_3d_flow", []))
+                rotation = np.eye(3)
+                if h:
+                    rotation = np.array([[1, 0, 0], [0, -1, 0], [0, 0, 1]]) @ rotation
+                    p[:, 1] = -p[:, 1]
+                    flow.append("HF")
+                if v:
+                    rotation = np.array([[-1, 0, 0], [0, 1, 0], [0, 0, 1]]) @ rotation
+                    p[:, 0] = -p[:, 0]
+                    flow.append("VF")
+                lam = lam0.copy()
+                lam[:3, :] = rotation @ lam[:3, :]
+                m.update(lidar_aug_matrix=lam, pcd_horizontal_flip=h, pcd_vertical_flip=v, pcd_scale_factor=scale,
+                         transformation_3d_flow=flow, flip=bool(flip))
+                out_pts.append(p)
+                out_metas.append(m)
+    return out_pts, out_metas
+
+
 class MultiSweepPointLoader:
     """Batch replacement for the LoadPointsFromFile -> LoadPointsFromMultiSweeps -> [GlobalRotScaleTransV2 ->
     RandomFlip3DV2] -> PointsRangeFilter [-> PointShuffle] chain of configs/isfusion/isfusion_0075voxel.py:238-352.

@@ -421,15 +421,40 @@ class TransFusionHeadV2(nn.Module):
         layer_-1_loss_bbox, matched_ious); the losses are autograd Functions over the fused loss kernels."""
         return head_loss.loss(self, gt_bboxes_3d, gt_labels_3d, preds_dicts, ins_heatmap)
 
-    @torch.no_grad()
-    def get_bboxes(self, preds_dicts, metas=None, img=None, rescale=False, for_roi=False):
-        """:1278-1418 with test_cfg nms_type=None (the shipped nuScenes setting): proposal scores, box decoding and the
-        centre-range / score filter in one kernel (isf_decode_boxes).  -> one [boxes, scores, labels] per sample
-        (the reference asserts a single sample, :1407-1408); boxes are wrapped in metas[i]['box_type_3d'] when the meta
-        carries one."""
-        if self.test_cfg.get("nms_type") is not None:
-            raise NotImplementedError("get_bboxes: only nms_type=None (the shipped test_cfg) is built; circle / rotate "
-                                      "NMS is the TTA path (SURVEY.md section 8, out of scope)")
+    # the per-dataset task table of get_bboxes (:1314-1340): (class indices, radius); radius <= 0 = no NMS
+    NMS_TASKS = {
+        "nuScenes": [([0, 1, 2, 3, 4, 5, 6, 7], -1.0), ([8], 0.175), ([9], 0.175)],
+        "Waymo": [([0], 0.7), ([1], 0.7), ([2], 0.7)],
+    }
+
+    def _nms_plan(self):
+        """test_cfg -> None (nms_type None) or the segmented-NMS arguments of the task table"""
+        nms_type = self.test_cfg.get("nms_type")
+        if nms_type is None:
+            return None
+        if nms_type not in ("circle", "rotate"):
+            raise NotImplementedError(f"get_bboxes: nms_type={nms_type!r}; 'circle', 'rotate' or None are supported")
+        tasks = self.NMS_TASKS.get(self.test_cfg.get("dataset"))
+        if tasks is None:
+            raise NotImplementedError(f"get_bboxes: no NMS task table for dataset={self.test_cfg.get('dataset')!r} "
+                                      "(nuScenes, Waymo)")
+        task_of_class = [-1] * self.num_classes
+        for t, (classes, _) in enumerate(tasks):
+            for c in classes:
+                if c < self.num_classes:
+                    task_of_class[c] = t
+        modes = [nms_type if radius > 0 else "keep" for _, radius in tasks]
+        if nms_type == "circle":
+            pre, post = None, 83        # circle_nms's default post_max_size: the reference passes none
+        else:
+            pre, post = self.test_cfg.get("pre_maxsize"), self.test_cfg.get("post_maxsize")
+        return dict(modes=modes, thresholds=[float(r) for _, r in tasks], task_of_class=task_of_class,
+                    pre_maxsize=pre, post_max_size=post)
+
+    def decode_and_nms(self, preds_dicts):
+        """the device half of get_bboxes: isf_decode_boxes, then (nms_type circle / rotate) one isf_nms_segmented launch
+        for the whole batch.  -> boxes [B, P, 7|9], scores [B, P], labels [B, P] int32, counts [B] int32, keep [B, P]
+        bool (rows kept by the NMS; None without NMS, then rows [0, counts[b]) are the result).  No host sync."""
         assert len(preds_dicts) == 1, "one feature level"
         pd = preds_dicts[0][0]
         P, bc = self.num_proposals, self.bbox_coder
@@ -439,6 +464,40 @@ class TransFusionHeadV2(nn.Module):
         boxes, scores, labels, counts = ops.decode_boxes(
             last["heatmap"], pd["query_heatmap_score"], self.query_labels, last["center"], last["height"], last["dim"],
             last["rot"], vel, cell, bc["pc_range"], bc["post_center_range"], bc["score_threshold"])
+        plan = self._nms_plan()
+        if plan is None:
+            return boxes, scores, labels, counts, None
+        from . import nms
+        B = boxes.shape[0]
+        keep, _, _ = nms.segmented_nms(boxes.view(B * P, -1), scores.view(-1), group_stride=P, labels=labels.view(-1),
+                                       counts=counts, box_format=nms.BOX_LIDAR, **plan)
+        return boxes, scores, labels, counts, keep.view(B, P)
+
+    @torch.no_grad()
+    def get_bboxes(self, preds_dicts, metas=None, img=None, rescale=False, for_roi=False):
+        """:1278-1418: proposal scores, box decoding and the centre-range / score filter in one kernel
+        (isf_decode_boxes); with test_cfg nms_type 'circle' / 'rotate' the per-task NMS of :1314-1403 for the whole batch
+        in one more launch (isf_nms_segmented; circle_nms / nms_gpu semantics, the task table of NMS_TASKS), and the
+        kept boxes compacted on the device in their decode order, as the reference's keep mask leaves them.
+        -> one [boxes, scores, labels] per sample (the reference asserts a single sample, :1407-1408); boxes are wrapped
+        in metas[i]['box_type_3d'] when the meta carries one.
+        Deviation: the rotate branch reads test_cfg pre_maxsize / post_maxsize with .get (None when absent); the
+        reference indexes them and raises KeyError with the shipped test_cfg, which has neither.  Circle NMS keeps
+        circle_nms's default post_max_size=83, as the reference calls it without one."""
+        boxes, scores, labels, counts, keep = self.decode_and_nms(preds_dicts)
+        if keep is not None:
+            B, P = keep.shape
+            # stable compaction of the kept rows: row r goes to its rank among the sample's kept rows; the rest to a
+            # spare row past the end
+            dst = torch.cumsum(keep, 1, dtype=torch.int64) - 1
+            base = torch.arange(B, device=keep.device)[:, None] * P
+            dst = torch.where(keep, base + dst, torch.full_like(dst, B * P)).view(-1)
+            D = boxes.shape[-1]
+            cb = boxes.new_empty((B * P + 1, D)).index_copy_(0, dst, boxes.view(B * P, D))
+            cs = scores.new_empty(B * P + 1).index_copy_(0, dst, scores.view(-1))
+            cl = labels.new_empty(B * P + 1).index_copy_(0, dst, labels.view(-1))
+            boxes, scores, labels = cb[:B * P].view(B, P, D), cs[:B * P].view(B, P), cl[:B * P].view(B, P)
+            counts = keep.sum(1)
         res = []
         for i, n in enumerate(counts.tolist()):
             b = boxes[i, :n]
