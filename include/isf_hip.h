@@ -1010,6 +1010,55 @@ int isf_boxes_iou_bev(const float* boxes_a, int num_a, const float* boxes_b, int
 int isf_bbox_mapping_back(float* boxes, int box_ld, int num_views, int view_stride, const int32_t* counts,
                           const int* horizontal, const int* vertical, const float* scale_factor, isf_stream_t stream);
 
+/* Camera branch: Swin-T backbone and GeneralizedLSSFPN neck (isf_swin.hip) --------------------------------------
+ * isf_swin_gemm replaces every nn.Linear of SwinBlock (WindowMSA.qkv / proj, swin.py:96-103; FFN fc1 + GELU / fc2 +
+ *   identity, mmcv FFN), with norm1 / norm2 as a LayerNorm prologue (swin.py:341-356); PatchEmbed's Conv2d(k 4, s 4) +
+ *   AdaptivePadding 'corner' (utils/transformer.py:134-258); PatchMerging's nn.Unfold(2, 2) + LayerNorm(4C) + Linear
+ *   (utils/transformer.py:260-400); and the neck's F.interpolate(bilinear, align_corners) + torch.cat + 1x1 ConvModule
+ *   (generalized_lss.py:83-100).  y = act((A . W^T) * scale + shift) + residual, W packed by isf_pack_linear
+ *   ([out_features, k]), A rows generated by the loader (isf_swin_a):
+ *     ROWS  : x [num_rows, ldx]; k = channel.  With ln_stats ([num_rows, 2] mean, rstd from isf_swin_row_stats):
+ *             a = (x - mean) * rstd * ln_gamma[k] + ln_beta[k].
+ *     PATCH : x image [n, c, h, w]; row = (b, oy, ox) of the ceil(h/4) x ceil(w/4) grid; k = ci*16 + ky*4 + kx
+ *             (Conv2d weight order), zero past the image (corner padding) and for k >= 16 c (k padded to % 32).
+ *     MERGE : x token rows [n*h*w, c]; row = (b, oy, ox) of the ceil(h/2) x ceil(w/2) grid; k = (kh*2 + kw)*c + ci ->
+ *             x[b, 2 oy + kh, 2 ox + kw, ci], zero past the grid (corner padding).  nn.Unfold orders the same
+ *             elements ci*4 + kh*2 + kw: the caller packs W and gamma / beta in the loader's order.  k = 4 c.
+ *     UPCAT : x fine map [n, c, h, w], x2 coarse map [n, c2, h2, w2] (NCHW); row = (b, y, x) of the fine grid;
+ *             k < c -> x[b, k, y, x], else the bilinear (align_corners=True) sample of x2 channel k - c.  k = c + c2.
+ *   scale / shift: [out_features] or NULL (1 / 0); activation 0 none, 1 ReLU, 2 GELU (erf); residual [num_rows,
+ *   out_features] rows or NULL; y rows [num_rows, ldy], or [B, out_features, y_hw] when y_hw > 0.
+ * isf_swin_row_stats: mean and rstd = 1 / sqrt(var + eps) (biased variance) of each ROWS / MERGE loader row of k
+ *   elements -> stats [num_rows, 2].
+ * isf_swin_layernorm replaces nn.LayerNorm of token rows (PatchEmbed.norm; the out_indices norms + view/permute to
+ *   NCHW, swin.py:746-763): y rows [num_rows, channels], or [B, channels, y_hw] when y_hw > 0.  x != y.
+ * isf_swin_window_attention replaces ShiftWindowMSA + WindowMSA (swin.py:20-283) after the qkv Linear: qkv token rows
+ *   [batch*height*width, 3 channels] -> out token rows [batch*height*width, channels] (attention before proj).  Zero
+ *   padding to % window (padded cells' q / k / v = qkv_bias, NULL = no bias), torch.roll by -shift, window partition
+ *   and reverse are index arithmetic; rel_bias [heads, 49, 49] = relative_position_bias_table[index]; shifted blocks
+ *   add -100 between the 3 x 3 regions of the padded grid.  window 7, head dim 32. */
+typedef struct isf_swin_a {
+  const float* x;
+  const float* x2;
+  const float* ln_stats;
+  const float* ln_gamma;
+  const float* ln_beta;
+  int mode, ldx, n, c, h, w, c2, h2, w2;
+} isf_swin_a;
+#define ISF_SWIN_A_ROWS 0
+#define ISF_SWIN_A_PATCH 1
+#define ISF_SWIN_A_MERGE 2
+#define ISF_SWIN_A_UPCAT 3
+int isf_swin_gemm(const isf_swin_a* a, int num_rows, int k, const void* packed_weight, int out_features,
+                  const float* scale, const float* shift, int activation, const float* residual, float* y, int ldy,
+                  int y_hw, isf_stream_t stream);
+int isf_swin_row_stats(const isf_swin_a* a, int num_rows, int k, float eps, float* stats, isf_stream_t stream);
+int isf_swin_layernorm(const float* x, int num_rows, int channels, const float* gamma, const float* beta, float eps,
+                       float* y, int y_hw, isf_stream_t stream);
+int isf_swin_window_attention(const float* qkv, const float* qkv_bias, const float* rel_bias, int batch, int height,
+                              int width, int channels, int heads, int window, int shift, float scale, float* out,
+                              isf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

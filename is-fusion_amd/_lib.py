@@ -90,6 +90,16 @@ class PointAug(ctypes.Structure):
     ]
 
 
+class SwinA(ctypes.Structure):
+    """struct isf_swin_a: the A-operand loader of isf_swin_gemm / isf_swin_row_stats."""
+    _fields_ = [("x", c_void_p), ("x2", c_void_p), ("ln_stats", c_void_p), ("ln_gamma", c_void_p), ("ln_beta", c_void_p),
+                ("mode", c_int), ("ldx", c_int), ("n", c_int), ("c", c_int), ("h", c_int), ("w", c_int),
+                ("c2", c_int), ("h2", c_int), ("w2", c_int)]
+
+
+SWIN_A_ROWS, SWIN_A_PATCH, SWIN_A_MERGE, SWIN_A_UPCAT = 0, 1, 2, 3
+
+
 # name -> (restype, argtypes); every symbol include/isf_hip.h declares
 _F3 = ctypes.c_float * 3
 _F6 = ctypes.c_float * 6
@@ -295,6 +305,13 @@ SIGNATURES = {
                                   c_void_p, c_void_p]),
     "isf_boxes_iou_bev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "isf_bbox_mapping_back": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int_p, c_int_p, c_float_p, c_void_p]),
+    "isf_swin_gemm": (c_int, [ctypes.POINTER(SwinA), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                              c_void_p, c_int, c_int, c_void_p]),
+    "isf_swin_row_stats": (c_int, [ctypes.POINTER(SwinA), c_int, c_int, ctypes.c_float, c_void_p, c_void_p]),
+    "isf_swin_layernorm": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_int,
+                                   c_void_p]),
+    "isf_swin_window_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          ctypes.c_float, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -8,7 +8,8 @@ the detection neck / head consume.
 Same method names (``dynamic_voxelize`` is folded into the one-call LiDAR branch, ``voxelize(points, 'pillar')``,
 ``isfusion``, ``extract_pts_feat``), same sub-module attribute names (``pts_voxel_encoder``, ``pts_middle_encoder``,
 ``pts_pillar_layer``, ``fusion_encoder``, ``pts_backbone``) so a released checkpoint's ``pts_*`` / ``fusion_encoder.*``
-keys load unchanged.  The image backbone / necks and the bbox head stay stock (out of scope).
+keys load unchanged.  ``ISFusionDetector`` (end of this file) adds the camera branch, img_backbone (Swin-T) and
+img_neck (GeneralizedLSSFPN), and takes images instead of camera features.
 """
 import torch
 
@@ -424,3 +425,99 @@ class ISFusionPtsPath(nn.Module):
             return self.simple_test(points[0], img_metas[0], img_feats, **kwargs)
         assert all(len(p) == 1 for p in points), "aug_test takes the views of one frame"
         return self.aug_test([p[0] for p in points], [m[0] for m in img_metas], img_feats, **kwargs)
+
+
+class ISFusionDetector(ISFusionPtsPath):
+    """The whole model of isfusion.py: the camera branch (img_backbone = SwinTransformer, img_neck =
+    GeneralizedLSSFPN, swin.py / generalized_lss.py) in front of ISFusionPtsPath.  Images in, boxes out; the
+    ISFusionPtsPath methods keep their signatures (they take camera features).  Inference only."""
+
+    def __init__(self, img_backbone=None, img_neck=None, detach=False, **pts_kwargs):
+        super().__init__(**pts_kwargs)
+        from .generalized_lss import GeneralizedLSSFPN
+        from .swin import SwinTransformer
+        self.img_backbone = _build_camera(img_backbone, SwinTransformer)
+        self.img_neck = _build_camera(img_neck, GeneralizedLSSFPN)
+        self.detach = detach
+
+    @property
+    def with_img_backbone(self):
+        return self.img_backbone is not None
+
+    @property
+    def with_img_neck(self):
+        return self.img_neck is not None
+
+    def extract_img_feat(self, img, img_metas):
+        """isfusion.py:54-81: img [B, num_cams, 3, H, W] (normalised) -> the neck's tuple of [B*num_cams, C, h, w].
+        Cameras listed in a meta's img_mask_idx are zeroed in `img` (in place, as the reference does); every meta gets
+        input_shape = (H, W)."""
+        if "img_mask_idx" in img_metas[0].keys():
+            for i in range(len(img_metas)):
+                idx = img_metas[i]["img_mask_idx"]
+                if not idx[0] == -1:
+                    for j in (idx if isinstance(idx, (list, tuple)) else [int(v) for v in idx]):
+                        img[i, int(j)].zero_()
+        if not self.with_img_backbone or img is None:
+            return None
+        input_shape = img.shape[-2:]
+        for meta in img_metas:
+            meta.update(input_shape=input_shape)
+        assert img.dim() == 5
+        B, N, C, H, W = img.size()
+        img_feats = self.img_backbone(img.reshape(B * N, C, H, W).float())
+        if self.detach:
+            img_feats = [f.detach() for f in img_feats]
+        if self.with_img_neck:
+            img_feats = self.img_neck(img_feats)
+        return img_feats
+
+    def extract_feat(self, points, img, img_metas, **kwargs):
+        """isfusion.py:178-182 -> (img_feats, pts_feats)"""
+        img_feats = self.extract_img_feat(img, img_metas)
+        return img_feats, self.extract_pts_feat(points, img_feats, img_metas, **kwargs)
+
+    def forward_train(self, *args, **kwargs):
+        raise NotImplementedError("ISFusionDetector.forward_train: training the camera branch (neck backward, "
+                                  "DropPath in the backbone) is not implemented; train ISFusionPtsPath on features")
+
+    @torch.no_grad()
+    def simple_test(self, points, img_metas, img=None, rescale=False, **kwargs):
+        """isfusion.py:285-305 -> [dict(pts_bbox=...)] per sample"""
+        img_feats = self.extract_img_feat(img, img_metas)
+        return super().simple_test(points, img_metas, img_feats, rescale=rescale, **kwargs)
+
+    @torch.no_grad()
+    def aug_test(self, points, img_metas, imgs=None, rescale=False, **kwargs):
+        """ISFusionPtsPath.aug_test on the views of one frame; the views share the frame's images, so the camera
+        branch runs once.  imgs: [1, num_cams, 3, H, W] (or a list over views of those: the first is used)."""
+        metas = [m[0] if isinstance(m, (list, tuple)) else m for m in img_metas]
+        img = imgs[0] if isinstance(imgs, (list, tuple)) else imgs
+        if img is not None and img.dim() == 4:
+            img = img[None]
+        img_feats = self.extract_img_feat(img, metas[:1])
+        for m in metas[1:]:
+            m.update(input_shape=metas[0]["input_shape"])
+        return super().aug_test(points, metas, img_feats, rescale=rescale, **kwargs)
+
+    def forward_test(self, points, img_metas, img=None, **kwargs):
+        """Base3DDetector.forward_test (models/detectors/base.py:21-55) with images"""
+        if not isinstance(points, (list, tuple)) or not isinstance(img_metas, (list, tuple)):
+            raise TypeError("points and img_metas must be lists (over augmentations)")
+        if len(points) != len(img_metas):
+            raise ValueError(f"num of augmentations ({len(points)}) != num of image meta ({len(img_metas)})")
+        if len(points) == 1:
+            img = [img] if img is None else img
+            return self.simple_test(points[0], img_metas[0], img[0], **kwargs)
+        assert all(len(p) == 1 for p in points), "aug_test takes the views of one frame"
+        return self.aug_test([p[0] for p in points], [m[0] for m in img_metas], img, **kwargs)
+
+
+def _build_camera(cfg, cls):
+    if cfg is None or isinstance(cfg, nn.Module):
+        return cfg
+    cfg = dict(cfg)
+    t = cfg.pop("type", cls.__name__)
+    if t != cls.__name__:
+        raise NotImplementedError(f"camera module '{t}' is not built (only {cls.__name__})")
+    return cls(**cfg)

@@ -7,12 +7,14 @@ maintainer calls inside the reference tree: it regist
 names with `force=True`, after which `build_model(cfg.model)` constructs these modules from the unmodified config."""
 from torch import nn
 
-from .detector import ISFusionPtsPath
+from .detector import ISFusionDetector, ISFusionPtsPath
 from .fusion_encoder import ISFusionEncoder
 from .fusion_modules import SECONDFPN, SECONDV2, SSTInputLayerV2, SSTv2
+from .generalized_lss import GeneralizedLSSFPN
 from .norm import NaiveSyncBatchNorm1d, NaiveSyncBatchNorm2d
 from .sparse_encoder import SparseEncoder
 from .spconv import SparseConv3d, SubMConv3d
+from .swin import SwinTransformer
 from .transfusion_head import TransFusionHeadV2
 from .voxel_encoder import DynamicVFE, HardSimpleVFE
 from .voxelize import Voxelization
@@ -27,8 +29,10 @@ MODULES = {
         "SSTInputLayerV2": SSTInputLayerV2,      # sst/sst_input_layer_v2.py:18
         "TransFusionHeadV2": TransFusionHeadV2,  # dense_heads/transfusion_head_v2.py
     },
-    "BACKBONES": {"SSTv2": SSTv2, "SECONDV2": SECONDV2},          # backbones/sst_v2.py:11, second.py:98
-    "NECKS": {"SECONDFPN": SECONDFPN},                            # necks/second_fpn.py (stock conv stack)
+    "BACKBONES": {"SSTv2": SSTv2, "SECONDV2": SECONDV2,           # backbones/sst_v2.py:11, second.py:98
+                  "SwinTransformer": SwinTransformer},            # backbones/swin.py:458
+    "NECKS": {"SECONDFPN": SECONDFPN,                             # necks/second_fpn.py (stock conv stack)
+              "GeneralizedLSSFPN": GeneralizedLSSFPN},            # necks/generalized_lss.py:11
     "NORM_LAYERS": {"naiveSyncBN1d": NaiveSyncBatchNorm1d, "naiveSyncBN2d": NaiveSyncBatchNorm2d},  # ops/norm.py:136,205
     "CONV_LAYERS": {"SubMConv3d": SubMConv3d, "SparseConv3d": SparseConv3d},   # ops/spconv (write_spconv2.py:20-36)
 }
@@ -78,13 +82,13 @@ def load_config(path):
     return {k: v for k, v in ns.items() if not k.startswith("__")}
 
 
-def build_pts_path(config):
-    """config: path of configs/isfusion/isfusion_0075voxel.py (unmodified), its variable dict, or its `model` dict
-    -> ISFusionPtsPath with every sub-module built from the config's own kwargs (isfusion.py:21-51 and
-    mvx_two_stage.py:36-75: the head receives test_cfg = model.test_cfg.pts and train_cfg = model.train_cfg.pts)."""
+def _model_dict(config):
     if isinstance(config, str):
         config = load_config(config)
-    model = config["model"] if "model" in config else config
+    return config["model"] if "model" in config else config
+
+
+def _pts_kwargs(model):
     assert model.get("type", "ISFusionDetector") == "ISFusionDetector", model.get("type")
     layer = model.get("pts_voxel_layer", {})
     assert layer.get("max_num_points", -1) == -1, "isfusion.py:123-146 voxelizes the fine grid dynamically"
@@ -95,8 +99,23 @@ def build_pts_path(config):
     train_cfg = (model.get("train_cfg") or {}).get("pts")
     if train_cfg is not None:      # mvx_two_stage.py:36-75 hands train_cfg.pts to the head the same way
         head["train_cfg"] = dict(train_cfg)
-    return ISFusionPtsPath(voxel_size=model["voxel_size"], pc_range=model["pc_range"],
-                           out_size_factor=model.get("out_size_factor"),
-                           pts_voxel_encoder=model["pts_voxel_encoder"], pts_middle_encoder=model["pts_middle_encoder"],
-                           fusion_encoder=model["fusion_encoder"], pts_backbone=model["pts_backbone"],
-                           pts_neck=model["pts_neck"], pts_bbox_head=head)
+    return dict(voxel_size=model["voxel_size"], pc_range=model["pc_range"], out_size_factor=model.get("out_size_factor"),
+                pts_voxel_encoder=model["pts_voxel_encoder"], pts_middle_encoder=model["pts_middle_encoder"],
+                fusion_encoder=model["fusion_encoder"], pts_backbone=model["pts_backbone"], pts_neck=model["pts_neck"],
+                pts_bbox_head=head)
+
+
+def build_pts_path(config):
+    """config: path of configs/isfusion/isfusion_0075voxel.py (unmodified), its variable dict, or its `model` dict
+    -> ISFusionPtsPath with every sub-module built from the config's own kwargs (isfusion.py:21-51 and
+    mvx_two_stage.py:36-75: the head receives test_cfg = model.test_cfg.pts and train_cfg = model.train_cfg.pts)."""
+    return ISFusionPtsPath(**_pts_kwargs(_model_dict(config)))
+
+
+def build_detector(config):
+    """config: as build_pts_path -> ISFusionDetector: the point-cloud path of build_pts_path plus img_backbone
+    (SwinTransformer) and img_neck (GeneralizedLSSFPN) built from the config's own kwargs, and its `detach` flag
+    (isfusion.py:37)."""
+    model = _model_dict(config)
+    return ISFusionDetector(img_backbone=model.get("img_backbone"), img_neck=model.get("img_neck"),
+                            detach=model.get("detach", False), **_pts_kwargs(model))

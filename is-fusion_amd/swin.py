@@ -1,0 +1,357 @@
+"""Camera backbone: the reference's SwinTransformer (mmdet3d/models/backbones/swin.py, with PatchEmbed / PatchMerging of
+models/utils/transformer.py) on the HIP kernels of isf_swin.hip.  Inference only (eval mode).
+
+Same sub-module names, parameters and buffers as the reference, so an IS-Fusion checkpoint's ``img_backbone.*`` loads
+with ``strict=True`` (187 entries for configs/isfusion/isfusion_0075voxel.py, mmcv FFN naming ``ffn.layers.0.0`` /
+``ffn.layers.1``).  Per SwinBlock (token rows [N*H*W, C]):
+
+    row stats -> qkv GEMM (norm1 prologue) -> window attention -> proj GEMM (+ identity)
+    row stats -> fc1 GEMM (norm2 prologue, GELU) -> fc2 GEMM (+ identity)
+
+PatchEmbed is one GEMM whose loader gathers the 4 x 4 x 3 patches from the NCHW image (+ a LayerNorm pass), PatchMerging
+one GEMM whose loader gathers the 2 x 2 neighbourhood (+ its LayerNorm prologue), the out_indices norms one LayerNorm
+pass that stores NCHW.  Packed weights are derived once per parameter version (fusion_ops._cache).
+"""
+import ctypes
+
+import torch
+from torch import nn
+
+from . import _lib
+from .fusion_ops import ACT_GELU, ACT_NONE, PackedLinear, _cache
+
+WINDOW_TOKENS = 49
+
+
+def _a(mode, x, *, ldx=0, n=0, c=0, h=0, w=0, x2=None, c2=0, h2=0, w2=0, stats=None, ln=None):
+    """isf_swin_a for the loader `mode` (keeps the tensors it points to alive through the returned tuple)"""
+    g = b = None
+    if ln is not None:
+        g, b = ln
+    s = _lib.SwinA(_lib.ptr(x), _lib.ptr(x2), _lib.ptr(stats), _lib.ptr(g), _lib.ptr(b), mode, ldx, n, c, h, w, c2, h2,
+                   w2)
+    return s, (x, x2, stats, g, b)
+
+
+def gemm(a, rows, k, pl, *, scale=None, shift=None, act=ACT_NONE, residual=None, out_nchw=None):
+    """isf_swin_gemm: act((A W^T) * scale + shift) + residual -> [rows, N], or [B, N, H, W] for out_nchw=(B, H, W)"""
+    s, keep = a
+    N = pl.out_features
+    dev = keep[0].device
+    if out_nchw is not None:
+        B, H, W = out_nchw
+        y = torch.empty((B, N, H, W), dtype=torch.float32, device=dev)
+        ldy, y_hw = 0, H * W
+    else:
+        y = torch.empty((rows, N), dtype=torch.float32, device=dev)
+        ldy, y_hw = N, 0
+    if residual is not None:
+        assert residual.is_contiguous() and tuple(residual.shape) == (rows, N)
+    _lib.check(_lib.load().isf_swin_gemm(ctypes.byref(s), rows, k, _lib.ptr(pl.packed), N, _lib.ptr(scale),
+                                         _lib.ptr(shift), act, _lib.ptr(residual), _lib.ptr(y), ldy, y_hw,
+                                         _lib.stream()), "isf_swin_gemm")
+    return y
+
+
+def row_stats(a, rows, k, eps):
+    """isf_swin_row_stats -> [rows, 2] (mean, rstd)"""
+    s, keep = a
+    st = torch.empty((rows, 2), dtype=torch.float32, device=keep[0].device)
+    _lib.check(_lib.load().isf_swin_row_stats(ctypes.byref(s), rows, k, float(eps), _lib.ptr(st), _lib.stream()),
+               "isf_swin_row_stats")
+    return st
+
+
+def layernorm(x, norm, out_nchw=None):
+    """isf_swin_layernorm of token rows [M, C] -> rows, or [B, C, H, W] for out_nchw=(B, H, W)"""
+    M, C = x.shape
+    if out_nchw is not None:
+        B, H, W = out_nchw
+        y = torch.empty((B, C, H, W), dtype=torch.float32, device=x.device)
+        hw = H * W
+    else:
+        y = torch.empty_like(x)
+        hw = 0
+    _lib.check(_lib.load().isf_swin_layernorm(_lib.ptr(x), M, C, _lib.ptr(norm.weight), _lib.ptr(norm.bias),
+                                              float(norm.eps), _lib.ptr(y), hw, _lib.stream()), "isf_swin_layernorm")
+    return y
+
+
+def window_attention(qkv, qkv_bias, rel_bias, B, H, W, C, heads, window, shift, scale):
+    """isf_swin_window_attention: qkv rows [B*H*W, 3C] -> attention output rows [B*H*W, C] (before proj)"""
+    out = torch.empty((B * H * W, C), dtype=torch.float32, device=qkv.device)
+    _lib.check(_lib.load().isf_swin_window_attention(_lib.ptr(qkv), _lib.ptr(qkv_bias), _lib.ptr(rel_bias), B, H, W,
+                                                     C, heads, window, shift, float(scale), _lib.ptr(out),
+                                                     _lib.stream()), "isf_swin_window_attention")
+    return out
+
+
+def _ln_only(norm_cfg):
+    if (norm_cfg or {}).get("type", "LN") != "LN":
+        raise NotImplementedError(f"SwinTransformer: norm {norm_cfg} (only LN is built)")
+
+
+def _training_error(what):
+    return NotImplementedError(f"{what}: training-mode forward (DropPath, dropout, backward) is not implemented; "
+                               "the camera branch runs in eval() mode only")
+
+
+class WindowMSA(nn.Module):
+    """swin.py:20-113 (parameters and the relative_position_index buffer)"""
+
+    def __init__(self, embed_dims, num_heads, window_size, qkv_bias=True, qk_scale=None, attn_drop_rate=0.,
+                 proj_drop_rate=0.):
+        super().__init__()
+        self.embed_dims = embed_dims
+        self.window_size = window_size
+        self.num_heads = num_heads
+        self.scale = qk_scale or (embed_dims // num_heads) ** -0.5
+        self.relative_position_bias_table = nn.Parameter(
+            torch.zeros((2 * window_size[0] - 1) * (2 * window_size[1] - 1), num_heads))
+        Wh, Ww = window_size
+        seq = self.double_step_seq(2 * Ww - 1, Wh, 1, Ww)
+        self.register_buffer("relative_position_index", (seq + seq.T).flip(1).contiguous())
+        self.qkv = nn.Linear(embed_dims, embed_dims * 3, bias=qkv_bias)
+        self.attn_drop = nn.Dropout(attn_drop_rate)
+        self.proj = nn.Linear(embed_dims, embed_dims)
+        self.proj_drop = nn.Dropout(proj_drop_rate)
+
+    @staticmethod
+    def double_step_seq(step1, len1, step2, len2):
+        seq1 = torch.arange(0, step1 * len1, step1)
+        seq2 = torch.arange(0, step2 * len2, step2)
+        return (seq1[:, None] + seq2[None, :]).reshape(1, -1)
+
+    def relative_bias(self):
+        """[heads, 49, 49] = table[index] (swin.py:87-93), gathered on the device"""
+        n = self.window_size[0] * self.window_size[1]
+        t = self.relative_position_bias_table.detach().float()
+        return t[self.relative_position_index.view(-1)].view(n, n, -1).permute(2, 0, 1).contiguous()
+
+
+class ShiftWindowMSA(nn.Module):
+    """swin.py:116-283"""
+
+    def __init__(self, embed_dims, num_heads, window_size, shift_size=0, qkv_bias=True, qk_scale=None,
+                 attn_drop_rate=0, proj_drop_rate=0, drop_path_rate=0.):
+        super().__init__()
+        self.window_size = window_size
+        self.shift_size = shift_size
+        assert 0 <= shift_size < window_size
+        self.w_msa = WindowMSA(embed_dims, num_heads, (window_size, window_size), qkv_bias, qk_scale, attn_drop_rate,
+                               proj_drop_rate)
+        self.drop_path_rate = drop_path_rate
+
+
+class FFN(nn.Module):
+    """mmcv.cnn.bricks.transformer.FFN with num_fcs=2, add_identity=True: layers = [[Linear, GELU, Dropout], Linear,
+    Dropout] (state-dict names layers.0.0 / layers.1)"""
+
+    def __init__(self, embed_dims, feedforward_channels, ffn_drop=0., drop_path_rate=0.):
+        super().__init__()
+        self.embed_dims = embed_dims
+        self.feedforward_channels = feedforward_channels
+        self.layers = nn.Sequential(
+            nn.Sequential(nn.Linear(embed_dims, feedforward_channels), nn.GELU(), nn.Dropout(ffn_drop)),
+            nn.Linear(feedforward_channels, embed_dims), nn.Dropout(ffn_drop))
+        self.drop_path_rate = drop_path_rate
+
+
+class SwinBlock(nn.Module):
+    """swin.py:286-368"""
+
+    def __init__(self, embed_dims, num_heads, feedforward_channels, window_size=7, shift=False, qkv_bias=True,
+                 qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0., act_cfg=dict(type="GELU"),
+                 norm_cfg=dict(type="LN")):
+        super().__init__()
+        _ln_only(norm_cfg)
+        if (act_cfg or {}).get("type") != "GELU":
+            raise NotImplementedError(f"SwinBlock: activation {act_cfg} (only GELU is built)")
+        self.norm1 = nn.LayerNorm(embed_dims)
+        self.attn = ShiftWindowMSA(embed_dims, num_heads, window_size, window_size // 2 if shift else 0, qkv_bias,
+                                   qk_scale, attn_drop_rate, drop_rate, drop_path_rate)
+        self.norm2 = nn.LayerNorm(embed_dims)
+        self.ffn = FFN(embed_dims, feedforward_channels, drop_rate, drop_path_rate)
+
+    def pack(self):
+        m = self.attn.w_msa
+        l1, l2 = self.ffn.layers[0][0], self.ffn.layers[1]
+        return dict(qkv=PackedLinear(m.qkv.weight), qkv_b=None if m.qkv.bias is None else m.qkv.bias.detach(),
+                    proj=PackedLinear(m.proj.weight), proj_b=m.proj.bias.detach(), rel=m.relative_bias(),
+                    fc1=PackedLinear(l1.weight), fc1_b=l1.bias.detach(), fc2=PackedLinear(l2.weight),
+                    fc2_b=l2.bias.detach())
+
+    def run(self, p, x, B, H, W):
+        """x: token rows [B*H*W, C] -> the block's output rows"""
+        M, C = x.shape
+        m = self.attn.w_msa
+        ln1 = (self.norm1.weight.detach(), self.norm1.bias.detach())
+        st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm1.eps)
+        qkv = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln1), M, C, p["qkv"], shift=p["qkv_b"])
+        att = window_attention(qkv, p["qkv_b"], p["rel"], B, H, W, C, m.num_heads, self.attn.window_size,
+                               self.attn.shift_size, m.scale)
+        x = gemm(_a(_lib.SWIN_A_ROWS, att, ldx=C), M, C, p["proj"], shift=p["proj_b"], residual=x)
+        ln2 = (self.norm2.weight.detach(), self.norm2.bias.detach())
+        st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm2.eps)
+        F = self.ffn.feedforward_channels
+        h = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln2), M, C, p["fc1"], shift=p["fc1_b"], act=ACT_GELU)
+        return gemm(_a(_lib.SWIN_A_ROWS, h, ldx=F), M, F, p["fc2"], shift=p["fc2_b"], residual=x)
+
+
+class PatchEmbed(nn.Module):
+    """utils/transformer.py:134-258 with conv_type Conv2d, padding 'corner', kernel = stride"""
+
+    def __init__(self, in_channels=3, embed_dims=96, kernel_size=4, stride=4, norm_cfg=None):
+        super().__init__()
+        if kernel_size != 4 or stride != 4:
+            raise NotImplementedError(f"PatchEmbed: kernel {kernel_size} / stride {stride} (only 4 / 4 is built)")
+        self.embed_dims = embed_dims
+        self.projection = nn.Conv2d(in_channels, embed_dims, kernel_size, stride)
+        if norm_cfg is not None:
+            _ln_only(norm_cfg)
+            self.norm = nn.LayerNorm(embed_dims)
+        else:
+            self.norm = None
+
+    def pack(self):
+        w = self.projection.weight.detach().float().flatten(1)           # [C, cin*16], k = ci*16 + ky*4 + kx
+        k = (w.shape[1] + 31) // 32 * 32
+        wp = torch.cat([w, w.new_zeros(w.shape[0], k - w.shape[1])], 1)
+        return dict(w=PackedLinear(wp), b=self.projection.bias.detach().float().contiguous(), k=k)
+
+    def run(self, p, img):
+        N, C, H, W = img.shape
+        Ho, Wo = (H + 3) // 4, (W + 3) // 4
+        M = N * Ho * Wo
+        x = gemm(_a(_lib.SWIN_A_PATCH, img, n=N, c=C, h=H, w=W), M, p["k"], p["w"], shift=p["b"])
+        if self.norm is not None:
+            x = layernorm(x, self.norm)
+        return x, (Ho, Wo)
+
+
+class PatchMerging(nn.Module):
+    """utils/transformer.py:260-400: Unfold(2, stride 2, corner padding) -> LayerNorm(4C) -> Linear(4C, 2C, no bias)"""
+
+    def __init__(self, in_channels, out_channels, stride=2, norm_cfg=dict(type="LN")):
+        super().__init__()
+        if stride != 2:
+            raise NotImplementedError(f"PatchMerging: stride {stride} (only 2 is built)")
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        if norm_cfg is not None:
+            _ln_only(norm_cfg)
+            self.norm = nn.LayerNorm(4 * in_channels)
+        else:
+            self.norm = None
+        self.reduction = nn.Linear(4 * in_channels, out_channels, bias=False)
+
+    def pack(self):
+        # nn.Unfold orders the merged vector c*4 + q (q = kh*2 + kw); the loader reads q*C + c (contiguous channels)
+        C = self.in_channels
+        w = self.reduction.weight.detach().float()
+        wl = w.view(-1, C, 4).permute(0, 2, 1).reshape(w.shape[0], 4 * C)
+        p = dict(w=PackedLinear(wl))
+        if self.norm is not None:
+            p["g"] = self.norm.weight.detach().float().view(C, 4).t().contiguous().view(-1)
+            p["b"] = self.norm.bias.detach().float().view(C, 4).t().contiguous().view(-1)
+        return p
+
+    def run(self, p, x, B, H, W):
+        C = self.in_channels
+        Ho, Wo = (H + 1) // 2, (W + 1) // 2
+        M = B * Ho * Wo
+        geo = dict(n=B, c=C, h=H, w=W)
+        if self.norm is not None:
+            st = row_stats(_a(_lib.SWIN_A_MERGE, x, **geo), M, 4 * C, self.norm.eps)
+            a = _a(_lib.SWIN_A_MERGE, x, stats=st, ln=(p["g"], p["b"]), **geo)
+        else:
+            a = _a(_lib.SWIN_A_MERGE, x, **geo)
+        return gemm(a, M, 4 * C, p["w"]), (Ho, Wo)
+
+
+class SwinBlockSequence(nn.Module):
+    """swin.py:371-455"""
+
+    def __init__(self, embed_dims, num_heads, feedforward_channels, depth, window_size=7, qkv_bias=True,
+                 qk_scale=None, drop_rate=0., attn_drop_rate=0., drop_path_rate=0., downsample=None,
+                 act_cfg=dict(type="GELU"), norm_cfg=dict(type="LN")):
+        super().__init__()
+        rates = drop_path_rate if isinstance(drop_path_rate, list) else [drop_path_rate] * depth
+        assert len(rates) == depth
+        self.blocks = nn.ModuleList([
+            SwinBlock(embed_dims, num_heads, feedforward_channels, window_size, i % 2 == 1, qkv_bias, qk_scale,
+                      drop_rate, attn_drop_rate, rates[i], act_cfg, norm_cfg) for i in range(depth)])
+        self.downsample = downsample
+
+
+class SwinTransformer(nn.Module):
+    """swin.py:458-763 (BACKBONES 'SwinTransformer').  forward(x [N, 3, H, W]) -> [N, C_i, H_i, W_i] per out_index."""
+
+    def __init__(self, pretrain_img_size=224, in_channels=3, embed_dims=96, patch_size=4, window_size=7, mlp_ratio=4,
+                 depths=(2, 2, 6, 2), num_heads=(3, 6, 12, 24), strides=(4, 2, 2, 2), out_indices=(0, 1, 2, 3),
+                 qkv_bias=True, qk_scale=None, patch_norm=True, drop_rate=0., attn_drop_rate=0., drop_path_rate=0.1,
+                 use_abs_pos_embed=False, act_cfg=dict(type="GELU"), norm_cfg=dict(type="LN"), with_cp=False,
+                 pretrained=None, convert_weights=False, frozen_stages=-1, init_cfg=None):
+        super().__init__()
+        for flag, what in ((use_abs_pos_embed, "use_abs_pos_embed"), (with_cp, "with_cp"),
+                           (convert_weights, "convert_weights"), (frozen_stages >= 0, "frozen_stages >= 0"),
+                           (pretrained is not None, "pretrained"), (init_cfg is not None, "init_cfg")):
+            if flag:
+                raise NotImplementedError(f"SwinTransformer: {what} is not supported (load weights with "
+                                          "load_state_dict instead)")
+        _ln_only(norm_cfg)
+        if window_size != 7:
+            raise NotImplementedError(f"SwinTransformer: window_size {window_size} (only 7 is built)")
+        for C, h in zip([embed_dims * 2 ** i for i in range(len(depths))], num_heads):
+            if C != 32 * h:
+                raise NotImplementedError(f"SwinTransformer: head dim {C / h} (only 32 is built)")
+        assert strides[0] == patch_size, "Use non-overlapping patch embed."
+        self.out_indices = out_indices
+        self.use_abs_pos_embed = use_abs_pos_embed
+        self.patch_embed = PatchEmbed(in_channels, embed_dims, patch_size, strides[0],
+                                      norm_cfg if patch_norm else None)
+        self.drop_after_pos = nn.Dropout(p=drop_rate)
+        total = sum(depths)
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, total)]
+        self.stages = nn.ModuleList()
+        c = embed_dims
+        for i in range(len(depths)):
+            down = (PatchMerging(c, 2 * c, strides[i + 1], norm_cfg if patch_norm else None)
+                    if i < len(depths) - 1 else None)
+            self.stages.append(SwinBlockSequence(c, num_heads[i], mlp_ratio * c, depths[i], window_size, qkv_bias,
+                                                 qk_scale, drop_rate, attn_drop_rate,
+                                                 dpr[sum(depths[:i]):sum(depths[:i + 1])], down, act_cfg, norm_cfg))
+            if down is not None:
+                c = down.out_channels
+        self.num_features = [int(embed_dims * 2 ** i) for i in range(len(depths))]
+        for i in out_indices:
+            self.add_module(f"norm{i}", nn.LayerNorm(self.num_features[i]))
+
+    def _packed(self, dev):
+        c = _cache(self, dev)
+        if "patch" not in c:
+            with torch.no_grad():
+                c["patch"] = self.patch_embed.pack()
+                c["blocks"] = [[blk.pack() for blk in st.blocks] for st in self.stages]
+                c["merge"] = [st.downsample.pack() if st.downsample is not None else None for st in self.stages]
+        return c
+
+    @torch.no_grad()
+    def forward(self, x):
+        if self.training:
+            raise _training_error("SwinTransformer")
+        _lib.require_cuda(x)
+        assert x.dim() == 4, x.shape
+        x = x.float().contiguous()
+        N = x.shape[0]
+        p = self._packed(x.device)
+        t, (H, W) = self.patch_embed.run(p["patch"], x)
+        outs = []
+        for i, stage in enumerate(self.stages):
+            for blk, bp in zip(stage.blocks, p["blocks"][i]):
+                t = blk.run(bp, t, N, H, W)
+            if i in self.out_indices:
+                outs.append(layernorm(t, getattr(self, f"norm{i}"), out_nchw=(N, H, W)))
+            if stage.downsample is not None:
+                t, (H, W) = stage.downsample.run(p["merge"][i], t, N, H, W)
+        return outs

@@ -1,0 +1,96 @@
+"""Time the camera branch on one GPU (device events, after warm-up) at B = 2 samples x 6 cameras x 384 x 1056:
+  * SwinTransformer, GeneralizedLSSFPN and ISFusionDetector.extract_img_feat on the HIP kernels (isf_swin.hip,
+    dense_conv.py)
+  * the same backbone and neck as the float32 stock-torch composition (tests/camera_common.py: conv2d, layer_norm,
+    linear, roll / window copies, softmax, interpolate, conv2d + batch_norm) on the same GPU and weights
+  * ISFusionDetector.simple_test (images -> boxes) against ISFusionPtsPath.simple_test on precomputed camera features
+
+    python tools/camera_bench.py [--steps 10] [--warmup 3] [--points 300000]
+
+Prints one JSON line per measurement (ms per call, mean over --steps)."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import camera_common as CC  # noqa: E402
+from isfusion_amd import synthetic  # noqa: E402
+from isfusion_amd.detector import ISFusionDetector, ISFusionPtsPath  # noqa: E402
+from isfusion_amd.fusion_modules import seeded_state_dict  # noqa: E402
+
+
+def timed(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--points", type=int, default=300000)
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    det = ISFusionDetector(img_backbone=dict(type="SwinTransformer", **CC.BACKBONE),
+                           img_neck=dict(type="GeneralizedLSSFPN", **CC.NECK), detach=True).eval()
+    det._lidar.randomize_weights_(0).randomize_bn_(1)
+    for name, seed in (("fusion_encoder", 100), ("pts_backbone", 200), ("pts_neck", 250), ("pts_bbox_head", 300)):
+        getattr(det, name).load_state_dict(seeded_state_dict(getattr(det, name), seed))
+    det.img_backbone.load_state_dict(CC.seeded_module_state(det.img_backbone, 4101))
+    det.img_neck.load_state_dict(CC.seeded_module_state(det.img_neck, 4202))
+    det = det.to(dev)
+    det.freeze()
+    B, H, W = 2, 384, 1056
+    img = CC.images(3, B * 6, H, W).to(dev).view(B, 6, 3, H, W)
+    flat = img.view(B * 6, 3, H, W)
+    bb, nk = det.img_backbone, det.img_neck
+    with torch.no_grad():
+        feats = bb(flat)
+        necks = nk(feats)
+    ms = timed(lambda: bb(flat), a.steps, a.warmup)
+    print(json.dumps(dict(what="backbone", impl="hip", images=B * 6, hw=[H, W], ms=round(ms, 3))))
+    ms = timed(lambda: nk(feats), a.steps, a.warmup)
+    print(json.dumps(dict(what="neck", impl="hip", images=B * 6, ms=round(ms, 3))))
+    metas = [dict() for _ in range(B)]
+    ms = timed(lambda: det.extract_img_feat(img, metas), a.steps, a.warmup)
+    print(json.dumps(dict(what="extract_img_feat", impl="hip", images=B * 6, ms=round(ms, 3))))
+    sd = CC.cast(bb.state_dict(), torch.float32, dev)
+    nd = CC.cast(nk.state_dict(), torch.float32, dev)
+    with torch.no_grad():
+        ms_bb = timed(lambda: CC.swin_forward(sd, flat), a.steps, a.warmup)
+        ms_nk = timed(lambda: CC.neck_forward(nd, feats), a.steps, a.warmup)
+        ref = CC.swin_forward(sd, flat)
+        err = max(float((x - y).abs().max()) for x, y in zip(feats, ref))
+    print(json.dumps(dict(what="backbone", impl="torch_fp32", images=B * 6, ms=round(ms_bb, 3),
+                          max_abs_diff_vs_hip=err)))
+    print(json.dumps(dict(what="neck", impl="torch_fp32", images=B * 6, ms=round(ms_nk, 3))))
+    print(json.dumps(dict(what="extract_img_feat", impl="torch_fp32", images=B * 6, ms=round(ms_bb + ms_nk, 3),
+                          note="backbone + neck")))
+    # end to end: images -> boxes, against the point-cloud path on precomputed camera features
+    pts = [torch.from_numpy(p).to(dev) for p in synthetic.batch(2, B, a.points)]
+    inp = synthetic.fusion_inputs(5, B)
+    kw = dict(lidar2img=torch.from_numpy(inp["lidar2img"]), img_aug_matrix=torch.from_numpy(inp["img_aug_matrix"]),
+              lidar_aug_matrix=torch.from_numpy(inp["lidar_aug_matrix"]))
+    metas = [dict(input_shape=inp["input_shape"]) for _ in range(B)]
+    ms = timed(lambda: ISFusionPtsPath.simple_test(det, pts, metas, necks, **kw), a.steps, a.warmup)
+    print(json.dumps(dict(what="simple_test", input="camera_features", batch=B, ms=round(ms, 3))))
+    ms = timed(lambda: det.simple_test(pts, metas, img=img, **kw), a.steps, a.warmup)
+    n = sum(r["pts_bbox"]["scores_3d"].shape[0] for r in det.simple_test(pts, metas, img=img, **kw))
+    print(json.dumps(dict(what="simple_test", input="images", batch=B, ms=round(ms, 3), boxes=n)))
+
+
+if __name__ == "__main__":
+    main()
