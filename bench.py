@@ -13,15 +13,23 @@ isfusion_0075voxel architecture (no checkpoint / dataset access), eval-mode BN, 
 Multi-GPU: frames are independent units => every rank runs its own batch of 4 frames, no data-path
 collective (scaling "weak"); timing = barrier + synchronize on both sides, max over ranks.
 
-Prints ONE JSON line on rank 0 with the contract fields plus
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints ONE JSON line on rank 0 (the last
+line of its output) with the contract fields plus
   "roofline":     dominant kernel (sparse-conv template instantiation with the largest share of GPU time),
                   achieved = algorithmic flops (2*pairs*Cin*Cout) / mean hipEvent kernel time, vs what the matrix
                   pipe delivers per algorithmic flop (dense f16 peak / 3 passes of the split arithmetic, or the fp32
-                  MFMA peak with --fp32; MI355X_MICROARCH.md) -- plus the per-kernel table;
+                  MFMA peak with --fp32; MI355X_MICROARCH.md) -- plus the per-kernel table, all from the per-layer
+                  events of three of the timed steps.
+
+--full adds everything that takes runs of its own, after the timed steps (on one GPU; each has a --no-* switch):
+  "voxel_scatter" in the roofline (voxelize + DynamicVFE timed standalone), the legs "cfg3" (BASELINE configs[2]),
+  "cfg5_f16" (configs[4]), "cfg4_train" (configs[3]) and "pipelined" (two batches in flight), each on a line of its own
+  with scalar copies on the final line, and
   "cpu_baseline": the CPU oracle (C port of the reference algorithm, conv loop on all host threads) on one frame.
 
 --config 3 measures BASELINE configs[2] instead (full HSF + IGF point-cloud path, batch 2, camera features precomputed)
-with the same contract and a stage table; the default (--config 2) is the headline.
+with the same contract; with --full also its stage table, attention rooflines, CPU baseline and launch count.  The
+default (--config 2) is the headline.
 
 --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (inputs and weights are seeded: the same
 arguments give the same inputs, so two builds can be compared output for output).
@@ -52,25 +60,42 @@ def frames_for_rank(rank, world, batch):
     return [rank * batch + i for i in range(batch)]
 
 
-def make_frames(rank, world, batch, num_points, frame_set=0):
-    """Seeded synthetic sweeps of this rank.  ISF_BENCH_FRAME_CACHE=<dir> (tuning sweeps only: tools/conv_knockout.sh
-    runs bench.py two dozen times) keeps the generated frames on disk; the frames are the same either way."""
+def _frame(seed, num_points):
+    """One seeded synthetic sweep.  ISF_BENCH_FRAME_CACHE=<dir> (tuning sweeps only: tools/conv_knockout.sh runs
+    bench.py two dozen times) keeps the generated frames on disk; the frames are the same either way."""
     import numpy as np
     from isfusion_amd import synthetic
     cache = os.environ.get("ISF_BENCH_FRAME_CACHE", "")
-    frames = []
-    for f in frames_for_rank(rank, world, batch):
-        seed = 1234 + 1000 * CFG_ID + f + 100000 * frame_set
-        path = os.path.join(cache, f"frame_{seed}_{num_points}.npy") if cache else ""
-        if path and os.path.exists(path):
-            frames.append(np.load(path))
-            continue
-        pts = synthetic.lidar_sweeps(seed, num_points)
-        if path:
-            os.makedirs(cache, exist_ok=True)
-            np.save(path, pts)
-        frames.append(pts)
-    return frames
+    path = os.path.join(cache, f"frame_{seed}_{num_points}.npy") if cache else ""
+    if path and os.path.exists(path):
+        return np.load(path)
+    pts = synthetic.lidar_sweeps(seed, num_points)
+    if path:
+        os.makedirs(cache, exist_ok=True)
+        np.save(path, pts)
+    return pts
+
+
+def _frame_seed(f, frame_set):
+    return 1234 + 1000 * CFG_ID + f + 100000 * frame_set
+
+
+def make_frames(rank, world, batch, num_points, frame_set=0):
+    """Seeded synthetic sweeps of this rank (one frame set)."""
+    return [_frame(_frame_seed(f, frame_set), num_points) for f in frames_for_rank(rank, world, batch)]
+
+
+def make_frame_sets(rank, world, batch, num_points, frame_sets):
+    """[make_frames(rank, world, batch, num_points, fs) for fs in frame_sets], the frames generated on a thread pool: a
+    300 k-point sweep is about 2 s of numpy that releases the GIL, and the headline's eight of them would otherwise be
+    most of a plain run's set-up.  Same seeds, same arrays.  At most CPUs / world threads per rank."""
+    from concurrent.futures import ThreadPoolExecutor
+    jobs = [(_frame_seed(f, fs), num_points) for fs in frame_sets for f in frames_for_rank(rank, world, batch)]
+    cpus = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or os.cpu_count() or 1
+    workers = max(1, min(len(jobs), cpus // world))
+    with ThreadPoolExecutor(workers) as ex:
+        frames = list(ex.map(lambda job: _frame(*job), jobs))
+    return [frames[i * batch:(i + 1) * batch] for i in range(len(frame_sets))]
 
 
 DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: everything written, in all
@@ -185,7 +210,7 @@ def cpu_baseline(num_points, seed_frame):
 # ------------------------------------------------------------------------------------------- --config 3
 def cpu_baseline_fusion(seed):
     """Oracle ("port": C for the LiDAR branch, torch-CPU restatement for HSF / IGF + backbone stages) on ONE frame of
-    30 k points with the full-size 180 x 180 fusion grid; bounded so that the default run stays within minutes."""
+    30 k points with the full-size 180 x 180 fusion grid; bounded so that a --full run stays within minutes."""
     import numpy as np
     import torch
     import oracle
@@ -331,10 +356,11 @@ def main_fusion(args):
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         dist.init_process_group("nccl", rank=rank, world_size=world)
-    line = fusion_leg(args, rank, world, dev, args.batch, args.steps, args.warmup, not args.no_cpu_baseline,
-                      args.dump_outputs)
+    line = fusion_leg(args, rank, world, dev, args.batch, args.steps, args.warmup, args.full and not args.no_cpu_baseline,
+                      args.dump_outputs, details=args.full)
     if rank == 0:
-        line["launches_per_forward"] = line.pop("_count_launches")()
+        if args.full:
+            line["launches_per_forward"] = line.pop("_count_launches")()
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()
@@ -442,12 +468,85 @@ def count_launches(fn):
         return None
 
 
-def fusion_leg(args, rank, world, dev, B, steps, warmup, with_cpu_baseline, dump_dir=""):
+def fusion_stage_roofline(net, dev, B, pts, img_feats, metas, kw):
+    """--config 3 / the "cfg3" leg with --full: the stage table (HIP events, 10 calls per stage after one warm-up
+    call, on the first frame set) and the roofline of the dominant kernel, plus the attention kernels' rooflines."""
+    import torch
+
+    # ---- stage table (separate pass, HIP events on the launch stream; not part of the timed region)
+    def timed(fn, n=10):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            r = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n, r
+    enc, bb = net.fusion_encoder, net.pts_backbone
+    stages = {}
+    with torch.no_grad():
+        stages["lidar_branch"], x = timed(lambda: net._lidar(pts, want_stats=True, time_layers=True))
+        st, tab = net._lidar.last_stats, net._lidar.conv_layer_table()
+        stages["pillar_voxelize"], (pil, npts, pco) = timed(lambda: net.voxelize(pts, "pillar"))
+        ekw = dict(kw, pts_metas=dict(pillars=pil, pillars_num_points=npts, pillar_coors=pco), img_metas=metas,
+                   pts_backbone=bb)
+        stages["p2g"], img_bev = timed(lambda: enc.img_fv_to_bev([img_feats[1]], B, **ekw))
+        stages["conv_fusion"], bev = timed(lambda: enc.fuse(img_bev, x))
+        stages["grid2region_0"], g0 = timed(lambda: enc.grid2region(0, bev))
+        stages["instance_fusion"], (ret, _) = timed(lambda: enc.instance_fusion(bev, g0, B))
+        stages["second_stage1"], (nxt, _, f0) = timed(lambda: bb([ret], "stage1"))
+        stages["grid2region_1"], g1 = timed(lambda: enc.grid2region(1, nxt))
+        stages["second_stage2"], (_, _, f1) = timed(lambda: bb([g1], "stage2"))
+        if net.pts_neck.dense_conv == "hip" and net.pts_bbox_head.dense_conv == "hip":   # as forward_pts runs them
+            stages["neck"], nk = timed(lambda: net.pts_neck.forward_split([f0, f1]))
+            stages["head"], _ = timed(lambda: net.pts_bbox_head.forward_split(nk))
+        else:
+            stages["neck"], nk = timed(lambda: net.pts_neck([f0, f1]))
+            stages["head"], _ = timed(lambda: net.pts_bbox_head(nk, img_feats, metas))
+    stages = {k: round(v, 3) for k, v in stages.items()}
+    # ---- roofline of the dominant kernel: the sparse-conv kernel family (LiDAR branch layers by template
+    # instantiation; the 3x3 dense convs of conv_fusion / IGF / SECONDV2 run on the same kernels over a dense rulebook)
+    groups = {}
+    for i, (kind, cin, cout, K) in enumerate(tab):
+        by, fl = conv_layer_bytes_flops(kind, cin, cout, K, st.num_in[i], st.num_out[i], st.pairs[i])
+        g = groups.setdefault(f"spconv_mfma<cin={cin},cout={cout}>", dict(ms=0.0, flops=0.0, bytes=0.0, launches=0))
+        g["ms"] += float(st.ms[i]); g["flops"] += fl; g["bytes"] += by; g["launches"] += 1
+    # dense 3x3 convs: flops = 2 * 9 * Cin * Cout per output cell (every tap present except at the border)
+    dense = dict(ms=stages["second_stage1"] + stages["second_stage2"], launches=12,
+                 flops=2.0 * 9 * B * (180 * 180 * 128 * 128 * 6 + 90 * 90 * (128 * 256 + 5 * 256 * 256)))
+    name, dom = max(groups.items(), key=lambda kv: kv[1]["ms"])
+    t_s = dom["ms"] * 1e-3
+    tfl = dom["flops"] / t_s / 1e12 if t_s > 0 else 0.0
+    roof = dict(bound="mfma", achieved=round(tfl, 3), peak=round(MFMA_F16_PEAK_TFLOPS / 3, 1), unit="TFLOP/s",
+                frac=round(3 * tfl / MFMA_F16_PEAK_TFLOPS, 4), traffic=None,
+                arithmetic="f16x3 split MFMA: 3 f16 passes per fp32 product, fp32 accumulate; peak = 2500 / 3",
+                kernel=name + " (LiDAR branch, the largest single-kernel share of the step)",
+                launches_per_step=dom["launches"], avg_launch_ms=round(dom["ms"] / dom["launches"], 4),
+                algorithmic_bytes_per_launch=round(dom["bytes"] / dom["launches"]),
+                per_kernel={k: dict(ms=round(v["ms"], 4), tflops=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 3)
+                                    if v["ms"] > 0 else 0, launches=v["launches"]) for k, v in groups.items()},
+                dense_conv_stages=dict(ms=round(dense["ms"], 3), launches=dense["launches"],
+                                       tflops=round(dense["flops"] / (dense["ms"] * 1e-3) / 1e12, 2),
+                                       frac=round(3 * dense["flops"] / (dense["ms"] * 1e-3) / 1e12 / MFMA_F16_PEAK_TFLOPS, 4),
+                                       note="SECONDV2 stage 1 + 2: twelve 3x3 convs on the sparse-conv kernel over "
+                                            "the dense-grid rulebook (includes their layout conversions)"),
+                stages_ms=stages, stages_sum_ms=round(sum(stages.values()), 3))
+    try:
+        roof["attention_kernels"] = attention_rooflines(net, dev, B, timed, stages.get("p2g"), pil)
+    except Exception as e:                              # the line stands without the extra entries
+        roof["attention_kernels"] = {"error": str(e)[:200]}
+    return roof
+
+
+def fusion_leg(args, rank, world, dev, B, steps, warmup, with_cpu_baseline, dump_dir="", details=True):
     """BASELINE configs[2]: full IS-Fusion HSF + IGF forward -- LiDAR branch, pillar voxelization, ISFusionEncoder
     (Point-to-Grid, conv_fusion, Grid-to-Region x2, instance mining / context / instance-to-scene), SECONDV2 stages,
     SECONDFPN neck, TransFusionHeadV2.forward -- on B x P-point sweeps + precomputed (random) 6-camera feature maps,
-    fp32-class arithmetic.  Same JSON contract as the headline; stage table from HIP events in a separate pass.
-    Returns the line (rank 0) -- printed by --config 3, attached as "cfg3" to the headline line by the default run.
+    fp32-class arithmetic.  Same JSON contract as the headline; with `details`, the stage table from HIP events in a
+    separate pass, the roofline and a launch counter ("_count_launches").
+    Returns the line (rank 0) -- printed by --config 3, attached as "cfg3" to the headline line by --full.
     dump_dir: write the head outputs of the last timed step there (--config 3 --dump-outputs)."""
     import numpy as np
     import torch
@@ -466,8 +565,9 @@ def fusion_leg(args, rank, world, dev, B, steps, warmup, with_cpu_baseline, dump
         net.enable_graph()    # everything behind Point-to-Grid replays as one HIP graph per batch size (measured: no
                               # gain -- 7.95 vs 7.89 ms, profiles/r03_call10_graph.txt -- so off by default)
     sets = []
-    for fs in range(max(1, args.frame_sets)):
-        pts = [torch.from_numpy(p).to(dev) for p in make_frames(rank, world, B, args.points, 10 + fs)]
+    host_sets = make_frame_sets(rank, world, B, args.points, [10 + fs for fs in range(max(1, args.frame_sets))])
+    for fs, host in enumerate(host_sets):
+        pts = [torch.from_numpy(p).to(dev) for p in host]
         inp = synthetic.fusion_inputs(5 + fs + 100 * rank, B)
         img_feats = tuple(torch.from_numpy(x).to(dev) for x in inp["img_feats"])
         kw = dict(lidar2img=torch.from_numpy(inp["lidar2img"]), img_aug_matrix=torch.from_numpy(inp["img_aug_matrix"]),
@@ -504,107 +604,44 @@ def fusion_leg(args, rank, world, dev, B, steps, warmup, with_cpu_baseline, dump
     if dump_dir and rank == 0:              # what the last timed step returned (outside the timed region)
         dump_arrays(dump_dir, flat_outputs(out, "head"))
 
-    if rank == 0:
-        # ---- stage table (separate pass, HIP events on the launch stream; not part of the timed region)
-        def timed(fn, n=10):
-            fn()
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(n):
-                r = fn()
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1) / n, r
-        pts, img_feats, metas, kw = sets[0]
-        enc, bb = net.fusion_encoder, net.pts_backbone
-        stages = {}
-        with torch.no_grad():
-            stages["lidar_branch"], x = timed(lambda: net._lidar(pts, want_stats=True, time_layers=True))
-            st, tab = net._lidar.last_stats, net._lidar.conv_layer_table()
-            stages["pillar_voxelize"], (pil, npts, pco) = timed(lambda: net.voxelize(pts, "pillar"))
-            ekw = dict(kw, pts_metas=dict(pillars=pil, pillars_num_points=npts, pillar_coors=pco), img_metas=metas,
-                       pts_backbone=bb)
-            stages["p2g"], img_bev = timed(lambda: enc.img_fv_to_bev([img_feats[1]], B, **ekw))
-            stages["conv_fusion"], bev = timed(lambda: enc.fuse(img_bev, x))
-            stages["grid2region_0"], g0 = timed(lambda: enc.grid2region(0, bev))
-            stages["instance_fusion"], (ret, _) = timed(lambda: enc.instance_fusion(bev, g0, B))
-            stages["second_stage1"], (nxt, _, f0) = timed(lambda: bb([ret], "stage1"))
-            stages["grid2region_1"], g1 = timed(lambda: enc.grid2region(1, nxt))
-            stages["second_stage2"], (_, _, f1) = timed(lambda: bb([g1], "stage2"))
-            if net.pts_neck.dense_conv == "hip" and net.pts_bbox_head.dense_conv == "hip":   # as forward_pts runs them
-                stages["neck"], nk = timed(lambda: net.pts_neck.forward_split([f0, f1]))
-                stages["head"], _ = timed(lambda: net.pts_bbox_head.forward_split(nk))
-            else:
-                stages["neck"], nk = timed(lambda: net.pts_neck([f0, f1]))
-                stages["head"], _ = timed(lambda: net.pts_bbox_head(nk, img_feats, metas))
-        stages = {k: round(v, 3) for k, v in stages.items()}
-        # ---- roofline of the dominant kernel: the sparse-conv kernel family (LiDAR branch layers by template
-        # instantiation; the 3x3 dense convs of conv_fusion / IGF / SECONDV2 run on the same kernels over a dense rulebook)
-        groups = {}
-        for i, (kind, cin, cout, K) in enumerate(tab):
-            by, fl = conv_layer_bytes_flops(kind, cin, cout, K, st.num_in[i], st.num_out[i], st.pairs[i])
-            g = groups.setdefault(f"spconv_mfma<cin={cin},cout={cout}>", dict(ms=0.0, flops=0.0, bytes=0.0, launches=0))
-            g["ms"] += float(st.ms[i]); g["flops"] += fl; g["bytes"] += by; g["launches"] += 1
-        # dense 3x3 convs: flops = 2 * 9 * Cin * Cout per output cell (every tap present except at the border)
-        dense = dict(ms=stages["second_stage1"] + stages["second_stage2"], launches=12,
-                     flops=2.0 * 9 * B * (180 * 180 * 128 * 128 * 6 + 90 * 90 * (128 * 256 + 5 * 256 * 256)))
-        name, dom = max(groups.items(), key=lambda kv: kv[1]["ms"])
-        t_s = dom["ms"] * 1e-3
-        tfl = dom["flops"] / t_s / 1e12 if t_s > 0 else 0.0
-        roof = dict(bound="mfma", achieved=round(tfl, 3), peak=round(MFMA_F16_PEAK_TFLOPS / 3, 1), unit="TFLOP/s",
-                    frac=round(3 * tfl / MFMA_F16_PEAK_TFLOPS, 4), traffic=None,
-                    arithmetic="f16x3 split MFMA: 3 f16 passes per fp32 product, fp32 accumulate; peak = 2500 / 3",
-                    kernel=name + " (LiDAR branch, the largest single-kernel share of the step)",
-                    launches_per_step=dom["launches"], avg_launch_ms=round(dom["ms"] / dom["launches"], 4),
-                    algorithmic_bytes_per_launch=round(dom["bytes"] / dom["launches"]),
-                    per_kernel={k: dict(ms=round(v["ms"], 4), tflops=round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 3)
-                                        if v["ms"] > 0 else 0, launches=v["launches"]) for k, v in groups.items()},
-                    dense_conv_stages=dict(ms=round(dense["ms"], 3), launches=dense["launches"],
-                                           tflops=round(dense["flops"] / (dense["ms"] * 1e-3) / 1e12, 2),
-                                           frac=round(3 * dense["flops"] / (dense["ms"] * 1e-3) / 1e12 / MFMA_F16_PEAK_TFLOPS, 4),
-                                           note="SECONDV2 stage 1 + 2: twelve 3x3 convs on the sparse-conv kernel over "
-                                                "the dense-grid rulebook (includes their layout conversions)"),
-                    stages_ms=stages, stages_sum_ms=round(sum(stages.values()), 3))
-        try:
-            roof["attention_kernels"] = attention_rooflines(net, dev, B, timed, stages.get("p2g"), pil)
-        except Exception as e:                              # the line stands without the extra entries
-            roof["attention_kernels"] = {"error": str(e)[:200]}
-        line = {
-            "metric": "nuScenes frames/sec forward (0.075 voxel), full HSF+IGF point-cloud path incl. neck + head forward",
-            "value": round(B * world * steps / dt, 2), "unit": "frames/s", "n_gpus": world, "steps": steps,
-            "warmup": warmup, "ms_per_step": round(dt / steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32 (f16x3 split-precision MFMA, fp32 accumulate)",
-            "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]: full IS-Fusion HSF+IGF forward (LiDAR branch + pillar voxelize + "
-                                   "ISFusionEncoder + SECONDV2 stages + SECONDFPN + TransFusionHeadV2.forward), 6-camera "
-                                   f"feature maps precomputed (random), synthetic {args.points}-pt sweeps, batch={B}/GPU, "
-                                   "random-init weights, eval BN, fp32",
-                       "points_per_frame": args.points, "batch_per_gpu": B, "parallelism": f"dp{world}",
-                       "frame_sets_rotated": len(sets)},
-            "roofline": roof,
-        }
-        if world == 1 and with_cpu_baseline:
-            cdt, cp = cpu_baseline_fusion(1234 + 1000 * 3)
-            import oracle
-            line["cpu_baseline"] = {
-                "value": round(1.0 / cdt, 4), "unit": f"frames/s ({cp}-pt frame)", "cores": oracle.num_threads(),
-                "kind": "port",
-                "sample": f"oracle composition (C LiDAR branch with the conv loop on {oracle.num_threads()} host "
-                          f"threads + torch-CPU restatement of HSF / IGF / SECONDV2 stages, full 180 x 180 grid, no neck / "
-                          f"head) on 1 frame of {cp} points took {cdt:.2f} s",
-                "sample_seconds": round(cdt, 2)}
-        # the launch count comes from torch.profiler, and an initialised profiler slows every later launch of the process
-        # (measured: the training leg behind it 48 -> 134 ms per step): the caller runs `count` after ALL timed legs
-        line["launches_per_forward"] = None
-        line["_count_launches"] = lambda: count_launches(lambda: step(0))
-        line["config"]["hip_graph"] = ("off" if not args.graph else
-                                       "ISFusionPtsPath.enable_graph(): conv_fusion .. head (shape-static per batch size) "
-                                       "captured once and replayed; LiDAR branch, pillar voxelization and Point-to-Grid eager")
-        line["config"]["frozen_caches"] = ("net.freeze(): inference deployment, the packed-weight caches skip their "
-                                           "per-call parameter-change scan (about 0.4 ms of host time per forward)")
+    if rank != 0:
+        return None
+    line = {
+        "metric": "nuScenes frames/sec forward (0.075 voxel), full HSF+IGF point-cloud path incl. neck + head forward",
+        "value": round(B * world * steps / dt, 2), "unit": "frames/s", "n_gpus": world, "steps": steps,
+        "warmup": warmup, "ms_per_step": round(dt / steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32 (f16x3 split-precision MFMA, fp32 accumulate)",
+        "data": "synthetic",
+        "config": {"workload": "BASELINE configs[2]: full IS-Fusion HSF+IGF forward (LiDAR branch + pillar voxelize + "
+                               "ISFusionEncoder + SECONDV2 stages + SECONDFPN + TransFusionHeadV2.forward), 6-camera "
+                               f"feature maps precomputed (random), synthetic {args.points}-pt sweeps, batch={B}/GPU, "
+                               "random-init weights, eval BN, fp32",
+                   "points_per_frame": args.points, "batch_per_gpu": B, "parallelism": f"dp{world}",
+                   "frame_sets_rotated": len(sets),
+                   "hip_graph": ("off" if not args.graph else
+                                 "ISFusionPtsPath.enable_graph(): conv_fusion .. head (shape-static per batch size) "
+                                 "captured once and replayed; LiDAR branch, pillar voxelization and Point-to-Grid eager"),
+                   "frozen_caches": ("net.freeze(): inference deployment, the packed-weight caches skip their "
+                                     "per-call parameter-change scan (about 0.4 ms of host time per forward)")},
+    }
+    if not details:
         return line
-    return None
+    line["roofline"] = fusion_stage_roofline(net, dev, B, *sets[0])
+    if world == 1 and with_cpu_baseline:
+        cdt, cp = cpu_baseline_fusion(1234 + 1000 * 3)
+        import oracle
+        line["cpu_baseline"] = {
+            "value": round(1.0 / cdt, 4), "unit": f"frames/s ({cp}-pt frame)", "cores": oracle.num_threads(),
+            "kind": "port",
+            "sample": f"oracle composition (C LiDAR branch with the conv loop on {oracle.num_threads()} host "
+                      f"threads + torch-CPU restatement of HSF / IGF / SECONDV2 stages, full 180 x 180 grid, no neck / "
+                      f"head) on 1 frame of {cp} points took {cdt:.2f} s",
+            "sample_seconds": round(cdt, 2)}
+    # the launch count comes from torch.profiler, and an initialised profiler slows every later launch of the process
+    # (measured: the training leg behind it 48 -> 134 ms per step): the caller runs `count` after ALL timed legs
+    line["launches_per_forward"] = None
+    line["_count_launches"] = lambda: count_launches(lambda: step(0))
+    return line
 
 
 # ------------------------------------------------------------------------------ BASELINE configs[4] / configs[3] legs
@@ -660,7 +697,7 @@ def f16_stress_leg(args, rank, world, dev, steps=16, warmup=4, B=4, points=50000
     me["sparse_shape"] = [41, side, side]
     lb = m.LidarBranch(voxel_size=[voxel, voxel, 0.2], pts_middle_encoder=me)
     lb = lb.randomize_weights_(0).randomize_bn_(1).eval().to(dev).freeze()
-    sets = [[torch.from_numpy(q).to(dev) for q in make_frames(rank, world, B, points, 20 + fs)] for fs in range(2)]
+    sets = [[torch.from_numpy(q).to(dev) for q in host] for host in make_frame_sets(rank, world, B, points, [20, 21])]
     for i in range(warmup):
         out = lb(sets[i % 2], precision=2)
     torch.cuda.synchronize()
@@ -826,14 +863,20 @@ def main():
     ap.add_argument("--cpu-points", type=int, default=300000,
                     help="points of the CPU-baseline sample frame (one full 300 k-point frame: about 30 s on one "
                          "core, about 10 s on 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the secondary legs, the "
+                         "standalone voxel-scatter roofline and the CPU baseline (--config 3: the stage table, attention "
+                         "rooflines, CPU baseline and launch count); a plain run prints only the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-cfg3", action="store_true",
-                    help="skip the BASELINE configs[2] leg the default run appends to the headline line as \"cfg3\"")
+                    help="with --full: skip the BASELINE configs[2] leg appended to the headline line as \"cfg3\"")
     ap.add_argument("--cfg3-steps", type=int, default=30)
     ap.add_argument("--no-cfg4", action="store_true",
-                    help="skip the BASELINE configs[3] leg (1-GPU bf16-autocast training step) appended as \"cfg4_train\"")
+                    help="with --full: skip the BASELINE configs[3] leg (1-GPU bf16-autocast training step) appended as "
+                         "\"cfg4_train\"")
     ap.add_argument("--no-cfg5", action="store_true",
-                    help="skip the BASELINE configs[4] leg (0.05 m voxels, 500 k points, f16 storage) appended as \"cfg5_f16\"")
+                    help="with --full: skip the BASELINE configs[4] leg (0.05 m voxels, 500 k points, f16 storage) appended "
+                         "as \"cfg5_f16\"")
     ap.add_argument("--graph", action="store_true",
                     help="config 3: replay the shape-static tail (conv_fusion .. head) as one HIP graph instead of ~330 "
                          "eager launches")
@@ -844,7 +887,7 @@ def main():
     ap.add_argument("--launch-stream", action="store_true",
                     help="run every leg on a private (non-NULL) HIP stream instead of torch's default stream")
     ap.add_argument("--no-pipelined", action="store_true",
-                    help="skip the two-batches-in-flight leg appended as \"pipelined\"")
+                    help="with --full: skip the two-batches-in-flight leg appended as \"pipelined\"")
     ap.add_argument("--conv-diag", type=int, default=0, choices=[0, 2, 4, 6, 8, 16, 32, 48, 64, 96, 128, 192, 256, 512, 704] + [1024 * v for v in range(1, 8)] + [16384, 32768, 49152, 65536, 131072, 262144, 524288, 262144 + 32, 262144 + 64, 1048576, 2097152, 4194304, 8388608, 16777216, 33554432, 67108864, 134217728, 268435456, 536870912] + [512 + 1024 * v for v in range(1, 16)],
                     help="DIAGNOSTIC ONLY: knock-out timing modes of the sparse-conv kernel (isf_encoder_options.diagnostic; "
                          "results are garbage, the line is labelled)")
@@ -920,8 +963,8 @@ def main():
     else:
         lb = m.LidarBranch()
     lb = lb.randomize_weights_(0).randomize_bn_(1).eval().to(dev).freeze()
-    frame_sets = [[torch.from_numpy(p).to(dev) for p in make_frames(rank, world, args.batch, args.points, fs)]
-                  for fs in range(max(1, args.frame_sets))]
+    frame_sets = [[torch.from_numpy(p).to(dev) for p in host]
+                  for host in make_frame_sets(rank, world, args.batch, args.points, range(max(1, args.frame_sets)))]
     frames = frame_sets[0]
     torch.cuda.synchronize()
 
@@ -964,7 +1007,7 @@ def main():
     # streams + the library's geometry side streams -- make every later launch on torch's default stream slower; measured on
     # the configs[2] leg, same box, alternating: 6.71 / 6.75 ms on its own or without this leg before it, 6.92 / 6.92 with it:
     # gpurun_out/r06_cfg3_ctx)
-    want_pipelined = world == 1 and not args.no_pipelined and not args.lib
+    want_pipelined = args.full and world == 1 and not args.no_pipelined and not args.lib
     diag = (args.conv_diag & 15) != 0 or ((args.conv_diag >> 10) & 3) != 0   # timing diagnostics: results are garbage (16 = sharing off, 32 = uniform tiles: valid)
     assert diag or args.lib or torch.isfinite(out).all()
     if args.dump_outputs and rank == 0:     # what the last timed step returned (outside the timed region)
@@ -1024,10 +1067,11 @@ def main():
                                         if v["ms"] > 0 else 0, gbs=round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1)
                                         if v["ms"] > 0 else 0, launches=v["launches"]) for k, v in groups.items()},
                     voxels_per_level=[int(samples[-1][1][0])] + [int(samples[-1][2][i]) for i, t in enumerate(tab) if t[0] == "spconv"])
-        try:
-            roof["voxel_scatter"] = voxel_scatter_roofline(lb, frame_sets[0])
-        except Exception as e:                              # the line stands without the extra entry
-            roof["voxel_scatter"] = {"error": str(e)[:200]}
+        if args.full:                                       # standalone runs of their own
+            try:
+                roof["voxel_scatter"] = voxel_scatter_roofline(lb, frame_sets[0])
+            except Exception as e:                          # the line stands without the extra entry
+                roof["voxel_scatter"] = {"error": str(e)[:200]}
         frames_total = args.batch * world * args.steps
         line = {
             "metric": "nuScenes frames/sec forward (0.075 voxel), LiDAR branch voxelize+spconv->BEV",
@@ -1053,12 +1097,12 @@ def main():
                                         "parameter-change scan"},
             "roofline": roof,
         }
-        # ---- secondary legs.  Each is printed on ITS OWN earlier line ({"leg": name, ...}); the final line carries short
+        # ---- secondary legs (--full).  Each is printed on ITS OWN earlier line ({"leg": name, ...}); the final line carries short
         # scalar copies of their headline numbers in front of the nested objects and stays under 2 KB, so that a reader who
         # keeps only the top-level keys / the tail of the output still sees every configuration.
         legs = {}
         cfg3_count = None
-        if world == 1 and not args.no_cfg3:
+        if args.full and world == 1 and not args.no_cfg3:
             # BASELINE configs[2] (full HSF + IGF forward, batch 2) measured by the same process, after the headline's
             # timed region: a driver-observed number for the second configuration
             if not want_pipelined:
@@ -1070,12 +1114,12 @@ def main():
             legs["cfg3"]["stages_ms"] = c3["roofline"].pop("stages_ms")
             legs["cfg3"]["roofline"] = c3["roofline"]
             cfg3_count = c3.pop("_count_launches")
-        if world == 1 and not args.no_cfg5:
+        if args.full and world == 1 and not args.no_cfg5:
             # BASELINE configs[4] (0.05 m voxels, 500 k points, f16 storage) and configs[3] (bf16-autocast training step)
             # on this GPU, same process, after the headline: driver-observed numbers for the two remaining configurations
             torch.cuda.empty_cache()
             legs["cfg5_f16"] = f16_stress_leg(args, rank, world, dev)
-        if world == 1 and not args.no_cfg4:
+        if args.full and world == 1 and not args.no_cfg4:
             torch.cuda.empty_cache()
             legs["cfg4_train"] = train_leg(args, rank, world, dev)
         if want_pipelined:
@@ -1083,7 +1127,7 @@ def main():
             legs["pipelined"] = pipelined_leg(lb, frame_sets, args.steps, max(2, args.warmup // 2), 2, precision=precision,
                                               conv_diag=args.conv_diag, **stage_kw)
         # the CPU baseline after every GPU leg (128 OpenMP threads on the host the launch thread runs on)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cdt, n0 = cpu_baseline(args.cpu_points, 1234 + 1000 * CFG_ID)
             import oracle
             cores = oracle.num_threads()

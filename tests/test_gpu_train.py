@@ -380,6 +380,39 @@ def test_bench_dump_outputs_hold_the_last_timed_step(dev, tmp_path):
     assert np.allclose(got["bev_channel_sums"], want["bev_channel_sums"], rtol=1e-6, atol=1e-6)
 
 
+def test_plain_bench_run_is_the_headline_alone_and_full_adds_the_rest(dev):
+    """`bench.py --gpus 1 --steps K --warmup W` runs the headline alone: the roofline from the timed steps' own events,
+    no secondary leg, no standalone voxel-scatter roofline, no CPU baseline.  With --full (configs[2] leg, two batches in
+    flight, CPU baseline on a small frame) those come back on the lines as before."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--points",
+            "40000", "--batch", "2"]
+
+    def run(extra):
+        p = subprocess.run(base + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        return [json.loads(l) for l in p.stdout.decode().splitlines() if l.startswith("{")]
+
+    lines = run([])
+    assert [l.get("leg") for l in lines] == ["headline_detail", None]
+    detail, line = lines
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["detail_lines"] == ["headline_detail"]
+    assert not [k for k in line if k.startswith(("cfg", "train_", "pipelined", "cpu_baseline"))], sorted(line)
+    assert detail["roofline"]["per_kernel"] and "voxel_scatter" not in detail["roofline"]
+    assert detail["cpu_baseline"] is None
+
+    lines = run(["--full", "--no-cfg4", "--no-cfg5", "--cfg3-steps", "3", "--cpu-points", "20000"])
+    assert [l.get("leg") for l in lines] == ["headline_detail", "cfg3", "pipelined", None]
+    detail, line = lines[0], lines[-1]
+    assert line["cfg3_fps"] > 0 and line["cfg3_launches"] > 0 and line["pipelined_fps"] > 0
+    assert line["cpu_baseline"]["value"] > 0 and detail["roofline"]["voxel_scatter"]["ms"] > 0
+    assert lines[1]["stages_ms"] and lines[2]["bit_identical_to_serial"]
+
+
 def test_two_ranks_train_side_by_side_with_ddp_over_gloo(dev):
     """the DDP training step of tools/train_step.py with two ranks on ONE device (gloo all-reduce, NaiveSyncBatchNorm's
     statistics exchange with world size 2): the multi-rank training path runs end to end with the real kernels before an

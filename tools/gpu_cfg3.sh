@@ -1,5 +1,5 @@
 #!/bin/bash
-# cfg3 (full HSF + IGF forward, B = 2) check: parity tests named by $2, then bench.py --config 3 $3 times.
+# cfg3 (full HSF + IGF forward, B = 2) check: parity tests named by $2, then bench.py --config 3 --full $3 times.
 # Usage (GPU box): bash tools/gpu_cfg3.sh <tag> [pytest -k expression | NONE] [reps]
 set -u
 TAG=${1:-r06_cfg3}
@@ -13,7 +13,7 @@ if [ "$KEXPR" != "NONE" ]; then
   tail -5 $OUT/pytest.txt
 fi
 for rep in $(seq 1 $REPS); do
-  timeout 600 python bench.py --config 3 --steps 30 --warmup 6 --no-cpu-baseline > $OUT/cfg3_$rep.json 2> $OUT/cfg3_$rep.err
+  timeout 600 python bench.py --config 3 --full --steps 30 --warmup 6 --no-cpu-baseline > $OUT/cfg3_$rep.json 2> $OUT/cfg3_$rep.err
   python - <<PY
 import json
 try:
