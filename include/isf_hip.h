@@ -1059,6 +1059,38 @@ int isf_swin_window_attention(const float* qkv, const float* qkv_bias, const flo
                               int width, int channels, int heads, int window, int shift, float scale, float* out,
                               isf_stream_t stream);
 
+/* Fused AdamW with global-norm gradient clipping (isf_optim.hip) ---------------------------------------------
+ * isf_optim_grad_sumsq + isf_optim_adamw replace, together, mmcv OptimizerHook.clip_grads (mmcv/runner/hooks/
+ *   optimizer.py: torch.nn.utils.clip_grad_norm_ over every gradient, max_norm, norm_type 2) followed by the step of
+ *   torch.optim.AdamW as built by build_optimizer (mmdet3d/apis/train.py:92; torch 2.x _single_tensor_adam with decoupled
+ *   weight decay): 2 launches for any number of tensors and param groups, no host sync, no copy.
+ * isf_optim_grad_sumsq + isf_optim_adamw(mode ISF_OPTIM_SCALE_GRADS) replace torch.nn.utils.clip_grad_norm_ alone: the
+ *   gradients are scaled in place (not written when the coefficient is 1).
+ *   tensors: DEVICE int64 [T, 6] = p, g, exp_avg, exp_avg_sq (addresses of contiguous fp32 storage; p / m / v unused in
+ *   ISF_OPTIM_SCALE_GRADS), numel, hyperparameter tuple index.  chunks: DEVICE int32 [num_chunks, 2] = tensor, chunk k =
+ *   elements [k * ISF_OPTIM_CHUNK, min((k + 1) * ISF_OPTIM_CHUNK, numel)).  Any 4-byte alignment is accepted.
+ *   partials: fp64 [num_chunks], one sum of squares per chunk (fixed-order reduction: bit-identical run to run).
+ *   isf_optim_adamw: every workgroup reduces the partials in one fixed order, norm = sqrt(sum),
+ *   coef = min(1, max_norm / (norm + 1e-6)) (ISF_OPTIM_NO_CLIP: coef = 1, partials / norm_out unused), norm_out[0] =
+ *   norm (fp32 device scalar); then per element g' = g * coef and p *= decay; m = lerp(m, g', w1);
+ *   v = v * b2 + w2 * g' * g'; p += neg_step_size * m / (sqrt(v) / bc2_sqrt + eps).  .grad is not written (except in
+ *   ISF_OPTIM_SCALE_GRADS).  hp: num_hp HOST tuples, passed as kernel arguments while num_hp <= ISF_OPTIM_MAX_HP_ARGS;
+ *   above that hp_device (DEVICE, num_hp tuples) is read instead.  Every field is computed on the host in double:
+ *   decay = 1 - lr * wd, w1 = 1 - b1, w2 = 1 - b2, neg_step_size = -lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t). */
+#define ISF_OPTIM_CHUNK 32768
+#define ISF_OPTIM_MAX_HP_ARGS 16
+#define ISF_OPTIM_NO_CLIP 0
+#define ISF_OPTIM_CLIP 1
+#define ISF_OPTIM_SCALE_GRADS 2
+typedef struct isf_adamw_hp {
+  float decay, w1, b2, w2, eps, neg_step_size, bc2_sqrt, pad;
+} isf_adamw_hp;
+int isf_optim_grad_sumsq(const int64_t* tensors, const int32_t* chunks, int num_chunks, double* partials,
+                         isf_stream_t stream);
+int isf_optim_adamw(const int64_t* tensors, const int32_t* chunks, int num_chunks, const isf_adamw_hp* hp, int num_hp,
+                    const isf_adamw_hp* hp_device, const double* partials, float max_norm, float* norm_out, int mode,
+                    isf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -100,6 +100,17 @@ class SwinA(ctypes.Structure):
 SWIN_A_ROWS, SWIN_A_PATCH, SWIN_A_MERGE, SWIN_A_UPCAT = 0, 1, 2, 3
 
 
+class AdamWHp(ctypes.Structure):
+    """struct isf_adamw_hp: one AdamW hyperparameter tuple of isf_optim_adamw (every field computed in double on the host)."""
+    _fields_ = [("decay", ctypes.c_float), ("w1", ctypes.c_float), ("b2", ctypes.c_float), ("w2", ctypes.c_float),
+                ("eps", ctypes.c_float), ("neg_step_size", ctypes.c_float), ("bc2_sqrt", ctypes.c_float),
+                ("pad", ctypes.c_float)]
+
+
+OPTIM_CHUNK, OPTIM_MAX_HP_ARGS = 32768, 16
+OPTIM_NO_CLIP, OPTIM_CLIP, OPTIM_SCALE_GRADS = 0, 1, 2
+
+
 # name -> (restype, argtypes); every symbol include/isf_hip.h declares
 _F3 = ctypes.c_float * 3
 _F6 = ctypes.c_float * 6
@@ -312,6 +323,9 @@ SIGNATURES = {
                                    c_void_p]),
     "isf_swin_window_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                           ctypes.c_float, c_void_p, c_void_p]),
+    "isf_optim_grad_sumsq": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "isf_optim_adamw": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(AdamWHp), c_int, c_void_p, c_void_p,
+                                ctypes.c_float, c_void_p, c_int, c_void_p]),
 }
 
 _lib = None

@@ -2,6 +2,7 @@
 all-reduce over xGMI on the GRADIENTS only -- the forward has no collective):
 
     python tools/train_step.py --gpus N [--batch 2] [--points 60000] [--steps 3] [--bf16] [--autocast]
+                               [--optimizer sgd|config] [--max-iters M]
 
 starts N ranks by itself (isfusion_amd.launch.self_launch: a re-exec under torch.distributed.run on 127.0.0.1; fewer
 than N visible GPUs is an error) -- the reference's tools/run-nus.sh:11-13; under a launcher it runs as the rank it is:
@@ -27,6 +28,14 @@ import torch.distributed as dist
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+# the training recipe of configs/isfusion/isfusion_0075voxel.py:398-413 (tests/golden/isfusion_0075voxel_train.txt)
+RECIPE = dict(optimizer=dict(type="AdamW", lr=0.0001, weight_decay=0.01,
+                             paramwise_cfg=dict(custom_keys={"img_backbone": dict(lr_mult=0.1)})),
+              optimizer_config=dict(grad_clip=dict(max_norm=0.01, norm_type=2)),
+              lr_config=dict(policy="cyclic", target_ratio=(10, 0.0001), cyclic_times=1, step_ratio_up=0.4),
+              momentum_config=dict(policy="cyclic", target_ratio=(0.8947368421052632, 1), cyclic_times=1,
+                                   step_ratio_up=0.4))
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -49,6 +58,11 @@ def main():
     ap.add_argument("--loss", default="standin", choices=["standin", "detection"],
                     help="standin: feature energy + heat-map mean (the neck output only); detection: the head's "
                          "forward_train and TransFusionHeadV2.loss on the synthetic scenes' GT boxes")
+    ap.add_argument("--optimizer", default="sgd", choices=["sgd", "config"],
+                    help="sgd: SGD(lr 1e-4, momentum 0.9) as before; config: the reference's recipe (isfusion_amd.optim."
+                         "TrainingRecipe: mmcv per-parameter groups, fused AdamW + grad clip 0.01, cyclic lr / momentum)")
+    ap.add_argument("--max-iters", type=int, default=0,
+                    help="iterations the cyclic schedules span with --optimizer config (0 = --steps + 1)")
     a = ap.parse_args()
     from isfusion_amd import launch, synthetic
     if a.stock_dense:
@@ -93,7 +107,13 @@ def main():
     # after the backward pass (~300 copy launches per step); every parameter that requires a gradient gets one in the
     # step, so no unused-parameter search either
     ddp = torch.nn.parallel.DistributedDataParallel(Wrap(net), device_ids=[local], gradient_as_bucket_view=True)
-    opt = torch.optim.SGD([p for p in net.parameters() if p.requires_grad], lr=1e-4, momentum=0.9)
+    recipe = None
+    if a.optimizer == "config":
+        from isfusion_amd.optim import TrainingRecipe
+        recipe = TrainingRecipe.from_config(RECIPE, net, a.max_iters or a.steps + 1)
+        opt = recipe.optimizer
+    else:
+        opt = torch.optim.SGD([p for p in net.parameters() if p.requires_grad], lr=1e-4, momentum=0.9)
     pts = [torch.from_numpy(synthetic.lidar_sweeps(9000 + 100 * rank + i, a.points)).to(dev) for i in range(a.batch)]
     gt = None
     if detection:
@@ -104,7 +124,7 @@ def main():
     kw = dict(lidar2img=torch.from_numpy(inp["lidar2img"]), img_aug_matrix=torch.from_numpy(inp["img_aug_matrix"]),
               lidar_aug_matrix=torch.from_numpy(inp["lidar_aug_matrix"]))
     metas = [dict(input_shape=inp["input_shape"]) for _ in range(a.batch)]
-    losses, t0 = [], None
+    losses, norms, t0 = [], [], None
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 2)]   # per-step GPU time stamps (no extra sync)
     for step in range(a.steps + 1):
         marks[step].record()
@@ -121,7 +141,10 @@ def main():
                 loss = (out[0].float() ** 2).mean() + hm.float().sigmoid().mean()
         opt.zero_grad(set_to_none=True)
         loss.backward()                                              # bucketed RCCL all-reduce inside
-        opt.step()
+        if recipe is not None:
+            norms.append(float(recipe.step(step)))                  # the device scalar is rewritten by the next step
+        else:
+            opt.step()
         losses.append(float(loss))
     marks[a.steps + 1].record()
     torch.cuda.synchronize()
@@ -130,7 +153,8 @@ def main():
     per_step = [round(marks[i].elapsed_time(marks[i + 1]), 1) for i in range(a.steps + 1)]   # [0] = the warm-up step
     if rank == 0:
         print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss,
-                          "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses]}))
+                          "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses],
+                          "optimizer": a.optimizer, **({"grad_norm": [round(n, 6) for n in norms]} if recipe else {})}))
     dist.destroy_process_group()
 
 
