@@ -217,26 +217,53 @@ int isf_sparse_conv_forward_packed(const float* features, int num_in, int c_in, 
  * (same 4 bytes/element as fp32; the 16-byte pieces the four k-group lanes of an MFMA row fetch together are
  * contiguous); isf_f32_to_split / isf_split_to_f32 convert ([N, C] row-major fp32, N*C a multiple of 32).
  * |activation| must be < 65504.  Cin, Cout in {32,64,128,256}.
- * `mode` of isf_sparse_conv_forward_f16x3 (per call; there is no process-wide switch): 0 = split precision (default);
- * 1 = single-pass f16 (opt-in): the same kernels fetch and multiply only the hi halves -- f16 operands, fp32
+ * `mode` of isf_sparse_conv_forward_f16x3 (per call; there is no process-wide switch) is a set of ISF_CONV_MODE_* bits
+ * (below): 0 = split precision (default);
+ * ISF_CONV_MODE_F16 = single-pass f16 (opt-in): the same kernels fetch and multiply only the hi halves -- f16 operands, fp32
  * accumulate, the accuracy of the reference's indice_conv_half under fp16 autocast (BASELINE configs[4]); results are
- * still exchanged in the split format.  TIMING DIAGNOSTICS (tools/conv_knockout.sh; never in production): 2 = no
- * activation gathers, 4 = no weight streaming, 6 = neither, 8 = no main loop -- the RESULTS ARE GARBAGE, only kernel
- * times are meaningful; 16 = gather every row (no neighbour sharing): results valid and
- * bit-identical to mode 0, the reference the sharing is tested against; +32 (combinable) = uniform row tiles instead
+ * still exchanged in the split format.  TIMING DIAGNOSTICS (tools/conv_knockout.sh; never in production):
+ * ISF_CONV_MODE_NO_GATHER = no activation gathers, ISF_CONV_MODE_NO_WEIGHTS = no weight streaming, both = neither,
+ * ISF_CONV_MODE_NO_LOOP = no main loop -- the RESULTS ARE GARBAGE, only kernel
+ * times are meaningful; ISF_CONV_MODE_NO_SHARING = gather every row (no neighbour sharing): results
+ * valid and bit-identical to mode 0, the reference the sharing is tested against; | ISF_CONV_MODE_UNIFORM_TILES (combinable)
+ * = uniform row tiles instead
  * of the full / half-tile mix that evens out the row groups per SIMD on launches of a single round of workgroups
  * (results bit-identical: a row's products and their order do not depend on the tile it falls into).
- * Round 5, mode 0 only, results valid and bit-identical, deep (128 / 256-column) shapes: +4096 / +8192 = one column block
- * for the 256-column layers (4 x 32-row / 8 x 16-row waves), +65536 = staggered issue phases, +131072 = round 4's issue
- * phase (index reads inside the step, separate weight-DMA pieces), +262144 = gathered rows two steps ahead -- experiments
+ * Round 5, mode 0 only, results valid and bit-identical, deep (128 / 256-column) shapes: | ISF_CONV_MODE_ONE_BLOCK_4W /
+ * _8W = one column block for the 256-column layers (4 x 32-row / 8 x 16-row waves), | ISF_CONV_MODE_STAGGER = staggered
+ * issue phases, | ISF_CONV_MODE_R4_ISSUE = round 4's issue phase (index reads inside the step, separate weight-DMA pieces),
+ * | ISF_CONV_MODE_TWO_AHEAD = gathered rows two steps ahead -- experiments
  * measured slower than the default, kept as tested opt-ins.
- * Round 6, mode 0 / +32, c_out = 256 (other shapes ignore it): +524288 = CHUNK SPLIT -- a tile is computed by two workgroups,
+ * Round 6, mode 0 / | ISF_CONV_MODE_UNIFORM_TILES, c_out = 256 (other shapes ignore it): | ISF_CONV_MODE_CHUNK_SPLIT = CHUNK
+ * SPLIT -- a tile is computed by two workgroups,
  * each over half of the 32-channel chunks; the second to arrive adds the other's accumulator tile and runs the epilogue.
  * Deterministic, NOT the bits of mode 0 (the sum over chunks becomes (lower half) + (upper half)); measured slower; opt-in.
- * Workgroup shape (mode 0 / +32; chosen per launch from c_out and num_out, never changes a result): 4 waves x 32 rows and two
+ * | ISF_CONV_MODE_DEEP (mode 0 / | ISF_CONV_MODE_UNIFORM_TILES): the deep layers' 4-wave launches on isf_spconv_deep.hip
+ * (LDS-DMA gathers + one instruction stream per step) -- bit-identical, measured 8 % slower (profiles/r06_deep.txt); opt-in.
+ * Workgroup shape (mode 0 / | ISF_CONV_MODE_UNIFORM_TILES; chosen per launch from c_out and num_out, never changes a
+ * result): 4 waves x 32 rows and two
  * 128-column blocks for c_out = 256, 8 waves x 32 rows for c_out = 128 from 2048 rows up; launches the tile plan would cut
  * into half tiles only (c_out = 256: num_out <= 96 x CUs; c_out = 128: 2048 <= num_out <= 256 x CUs) run with 16 rows per
- * wave instead.  Mode 16 keeps the 32-row shapes: the bit-equality reference of that rule too. */
+ * wave instead.  ISF_CONV_MODE_NO_SHARING keeps the 32-row shapes: the bit-equality reference of
+ * that rule too.
+ * Bits 64 and 1024 of the same int are hand-overs between the library's own translation units, named in
+ * csrc/isf_spconv16.h; callers do not set them. */
+#define ISF_CONV_MODE_F16 1               /* single-pass f16: hi halves only, fp32 accumulation */
+#define ISF_CONV_MODE_NO_GATHER 2         /* timing knock-out: no activation gathers (results garbage) */
+#define ISF_CONV_MODE_NO_WEIGHTS 4        /* timing knock-out: no weight streaming (results garbage; 6 = 2 | 4 = neither) */
+#define ISF_CONV_MODE_NO_LOOP 8           /* timing knock-out: no main loop (results garbage) */
+#define ISF_CONV_MODE_NO_SHARING 16       /* gather every row, no neighbour sharing (bit-identical) */
+#define ISF_CONV_MODE_UNIFORM_TILES 32    /* uniform row tiles, no full / half-tile mix (bit-identical; combinable) */
+#define ISF_CONV_MODE_F16_ROWS 256        /* rows are plain f16; accepted only as ISF_CONV_MODE_F16_STORAGE */
+#define ISF_CONV_MODE_F16_STORAGE 257     /* ISF_CONV_MODE_F16_ROWS | ISF_CONV_MODE_F16: f16 storage, see below */
+#define ISF_CONV_MODE_DMA_PLAN 2048       /* isf_sparse_conv_tile_order: the table is for isf_sparse_conv_forward_dma's plan */
+#define ISF_CONV_MODE_ONE_BLOCK_4W 4096   /* 256-column layers as one column block, 4 waves x 32 rows (slower; opt-in) */
+#define ISF_CONV_MODE_ONE_BLOCK_8W 8192   /* 256-column layers as one column block, 8 waves x 16 rows (slower; opt-in) */
+#define ISF_CONV_MODE_DEEP 32768          /* deep layers' 4-wave launches on isf_spconv_deep.hip (8 % slower; opt-in) */
+#define ISF_CONV_MODE_STAGGER 65536       /* staggered issue phases in the deep layers' workgroups (slower; opt-in) */
+#define ISF_CONV_MODE_R4_ISSUE 131072     /* round 4's issue phase: the A/B partner of the default (slower; opt-in) */
+#define ISF_CONV_MODE_TWO_AHEAD 262144    /* gathered rows two steps ahead (slower; opt-in) */
+#define ISF_CONV_MODE_CHUNK_SPLIT 524288  /* two workgroups per tile, half the chunks each (not mode 0's bits; slower; opt-in) */
 size_t isf_packed_filter16_bytes(int num_taps, int c_in, int c_out);
 int isf_pack_filters_f16x3(const float* filters, int num_taps, int c_in, int c_out, void* packed16,
                            isf_stream_t stream);
@@ -246,7 +273,7 @@ int isf_pack_filters_f16x3_transposed(const float* filters_t, int num_taps, int 
                                       isf_stream_t stream);
 int isf_f32_to_split(const float* x, size_t num_elems, void* xs, isf_stream_t stream);
 int isf_split_to_f32(const void* xs, size_t num_elems, float* x, isf_stream_t stream);
-/* f16 STORAGE (mode 257 = 256 | 1 of isf_sparse_conv_forward_f16x3; isf_encoder_options.precision = 2): features,
+/* f16 STORAGE (mode ISF_CONV_MODE_F16_STORAGE of isf_sparse_conv_forward_f16x3; isf_encoder_options.precision = 2): features,
  * residual and output rows are plain f16, [N, C] row-major, 2 bytes per element -- the data type of the reference's
  * indice_conv_half / indice_conv_backward_half end to end (mmdet3d/ops/bevfusion-ops/spconv/src/all.cc:35-37; BASELINE
  * configs[4] "fp16, HBM-bound") -- with f16 operands and fp32 accumulation; every layer moves half the activation
@@ -263,7 +290,7 @@ int isf_sparse_conv_forward_f16x3(const void* features_split, int num_in, int c_
  * that work per tile of the launch isf_sparse_conv_forward_f16x3 would make for (c_in, c_out, mode, num_out) and hands
  * the tiles out longest-first to the least-loaded CU with a free slot; `order` (and the scratch `work`) hold at most
  * 8 * 255 ints, *num_entries = how many were written (0: the launch is not a single round -- pass order = NULL).  A
- * table belongs to ONE kernel's launch plan: mode + 2048 builds it for isf_sparse_conv_forward_dma (whose workgroups per
+ * table belongs to ONE kernel's launch plan: mode | ISF_CONV_MODE_DMA_PLAN builds it for isf_sparse_conv_forward_dma (whose workgroups per
  * CU, and with them the tiles, differ from isf_sparse_conv_forward_f16x3's on the same shape).
  * One table serves every layer of that channel shape on the rulebook (isf_sparse_encoder_forward builds it per level
  * behind the neighbour table).  isf_sparse_conv_forward_f16x3_ordered = the same convolution with workgroup slot j
@@ -291,7 +318,7 @@ int isf_sparse_conv_forward_f16x3_ordered(const void* features_split, int num_in
  * order do not depend on the tile it falls into); the table belongs to one (c_in, c_out, mode): the workgroup shape depends
  * on all three.  MEASURED SLOWER than uniform tiles + isf_sparse_conv_tile_order on the MI355X (256 -> 256: 1.32 vs 1.265 ms
  * per step; profiles/r04_tile_tables.txt, profiles/EXPERIMENTS.md section 5.4: a tile's time follows its STEP count, not its matrix
- * work), so it is an OPT-IN: isf_sparse_encoder_forward builds the tables with diagnostic +32768.
+ * work), so it is an OPT-IN: isf_sparse_encoder_forward builds the tables with ISF_ENC_DIAG_TILE_TABLES.
  * isf_sparse_conv_tile_table_host: the same arithmetic on the host (tests). */
 int isf_sparse_conv_tile_table(const int32_t* nbr, int nbr_stride, int num_taps, int num_out, int c_in, int c_out,
                                int mode, int32_t* scratch, int32_t* table, int* num_ints, isf_stream_t stream);
@@ -333,13 +360,13 @@ int isf_sparse_conv_dma_trace(const void* features_split, int num_in, int c_in, 
                               void* out_split, long long* trace, int trace_capacity_blocks, int* grid_blocks,
                               isf_stream_t stream);
 /* The same convolution for the NARROW layers (c_in, c_out in {32, 64}) with the gathered rows brought in by LDS-DMA
- * (isf_spconv_dma.hip; mode 0 | 1 | 257, +32; order: NULL or isf_sparse_conv_tile_order's table).  A gather instruction of
+ * (isf_spconv_dma.hip; mode 0 | ISF_CONV_MODE_F16 | ISF_CONV_MODE_F16_STORAGE, | ISF_CONV_MODE_UNIFORM_TILES; order: NULL or isf_sparse_conv_tile_order's table).  A gather instruction of
  * isf_sparse_conv_forward_f16x3 loads straight into the MFMA operand layout -- four different rows = four cache lines per
  * lane quad: 64 address-unit cycles -- and on the narrow layers (few MFMAs per gathered row) the address unit sets the
  * step time.  Here a quad fetches the 64 contiguous bytes of ONE row (16 cycles) into a wave-private LDS transit buffer
  * and the MFMA layout is produced by the LDS read; no neighbour table in LDS, 5-6 workgroups per CU.  Results are
  * BIT-IDENTICAL to isf_sparse_conv_forward_f16x3 (same products in the same order per accumulator);
- * isf_sparse_encoder_forward / isf_lidar_branch_forward run their narrow layers on it (diagnostic +128: gather kernel).
+ * isf_sparse_encoder_forward / isf_lidar_branch_forward run their narrow layers on it (ISF_ENC_DIAG_NARROW_GATHER: gather kernel).
  * Replaces the reference's gather stage (bevfusion-ops/spconv/include/spconv/reordering.cu.h:21-97) for those layers. */
 int isf_sparse_conv_forward_dma(const void* features_split, int num_in, int c_in, const void* packed16, int num_taps,
                                 int c_out, const int32_t* nbr, int nbr_stride, int num_out, const float* scale,
@@ -356,7 +383,7 @@ int isf_sparse_conv_forward_dma(const void* features_split, int num_in, int c_in
  * NULL) to 1 for any other table).  isf_rulebook_to_lines / isf_lines_to_rulebook convert; isf_sparse_conv_forward_dma_lines
  * = isf_sparse_conv_forward_dma reading the compressed table (a lane keeps its rows' masks in registers and loads one
  * index per LINE): results BIT-IDENTICAL.  isf_sparse_encoder_forward / isf_lidar_branch_forward build the tables of their
- * narrow levels directly in this form (diagnostic +16384: dense tables).  taps_per_line = kernel width (1 or 3).
+ * narrow levels directly in this form (ISF_ENC_DIAG_DENSE_TABLES: dense tables).  taps_per_line = kernel width (1 or 3).
  * Replaces nothing in the reference (its rulebook is pair lists, indice.cu.h:22-203); measured in DESIGN.md section 5.3. */
 int isf_rulebook_to_lines(const int32_t* nbr, int nbr_stride, int num_taps, int taps_per_line, int num_out,
                           int32_t* lines, uint32_t* mask, int* not_consecutive_flag, isf_stream_t stream);
@@ -380,7 +407,7 @@ int isf_sparse_conv_forward_dma_lines(const void* features_split, int num_in, in
  * through a ring of prefetch depth + 1 stages.  Results are
  * BIT-IDENTICAL to isf_sparse_conv_forward_f16x3 (mode 0).  MEASURED SLOWER than the tile kernel on the MI355X (256 -> 256:
  * 1.39 .. 1.50 ms per step against 1.26; profiles/r04_cu_kernel_ab.txt, profiles/EXPERIMENTS.md section 5.2), so it is an OPT-IN:
- * isf_sparse_encoder_forward / isf_lidar_branch_forward run their 256-column layers on it with diagnostic +512.  isf_sparse_conv_cu_plan_host / _max_units: the plan
+ * isf_sparse_encoder_forward / isf_lidar_branch_forward run their 256-column layers on it with ISF_ENC_DIAG_CU_KERNEL.  isf_sparse_conv_cu_plan_host / _max_units: the plan
  * arithmetic on the host (tests, tools; no device work): work [num_groups] -> units [max_units][2] = (first group, groups).
  * Replaces the reference's per-tap gather -> GEMM -> scatter-add (spconv_ops.h:260-361) for those layers. */
 typedef struct isf_conv_cu_plan {
@@ -416,7 +443,7 @@ int isf_sparse_conv_cu_max_units(int num_groups, int cus);
  * copies the listed rows global -> LDS once per tile and 32-channel chunk (row-coalesced LDS-DMA) and reads the A
  * operands of all taps from LDS; `stage_rows` = LDS rows per 128-row tile (clamped to what 160 KiB hold; list entries
  * beyond a unit's share are gathered from memory, so every value is correct).  Results are bit-identical to
- * isf_sparse_conv_forward_f16x3 (same products, same order).  mode: 0 | 1 (single-pass f16), +32 uniform tiles. */
+ * isf_sparse_conv_forward_f16x3 (same products, same order).  mode: 0 | ISF_CONV_MODE_F16, | ISF_CONV_MODE_UNIFORM_TILES. */
 int isf_stage_unit_rows(void);
 int isf_stage_unit_cap(void);
 int isf_rulebook_stage_tables(const int32_t* nbr, int nbr_stride, int num_taps, uint16_t* slots, int32_t* ulist,
@@ -459,29 +486,79 @@ typedef struct isf_encoder_stats { /* filled on the host after the call (for roo
 /* per-call options of the two engine entry points (NULL = all defaults; no process-wide state):
  * precision  0 = f16x3 split MFMA when every layer carries packed16, else fp32 MFMA (default); 1 = force the fp32 MFMA
  *            kernels; 2 = f16 storage + single-pass f16 arithmetic (opt-in, the reference's fp16 mode: activations are
- *            f16 rows between the layers, mode 257 of isf_sparse_conv_forward_f16x3);
- * diagnostic timing diagnostics of the conv kernels (0 = off; 2 / 4 / 6 / 8 / 16, +32: see isf_sparse_conv_forward_f16x3;
- *            +64 = tiles in launch order, no isf_sparse_conv_tile_order tables; +128 = narrow layers on the gather
- *            kernel instead of isf_sparse_conv_forward_dma; +256 (isf_lidar_branch_forward) = the voxel encoder writes
- *            fp32 rows and a conversion pass makes the split rows, instead of writing them directly; +512 = the
- *            256-column layers on isf_sparse_conv_forward_cu (one workgroup per CU; opt-in: measured slower than
- *            the tile kernel) -- results bit-identical either way; +1024 * v = isf_conv_cu_plan.variant v of those layers (timing diagnostics, v < 16);
- *            +16384 = dense neighbour tables for the narrow layers instead of the line-compressed ones -- bit-identical;
- *            +131072 = the encoder's per-level row counts reach the host through hipMemcpyAsync + synchronise instead of
- *            the pinned-memory mailbox (post_int / wait_int) -- bit-identical;
- *            +65536 (isf_lidar_branch_forward) = one dynamic-voxelize launch per frame + a separate byte-map marking pass
- *            instead of the fused voxelize + mark launch -- bit-identical;
- *            +32768 = equal-work tile tables for the deep levels instead of uniform tiles + tile order (opt-in:
+ *            f16 rows between the layers, mode ISF_CONV_MODE_F16_STORAGE of isf_sparse_conv_forward_f16x3);
+ * diagnostic timing diagnostics of the conv kernels: 0 = off, else a set of ISF_ENC_DIAG_* bits (below).
+ *            _NO_GATHER / _NO_WEIGHTS / both / _NO_LOOP / _NO_SHARING, | _UNIFORM_TILES: the conv mode bits of the same
+ *            value, see isf_sparse_conv_forward_f16x3;
+ *            _LAUNCH_ORDER = tiles in launch order, no isf_sparse_conv_tile_order tables; _NARROW_GATHER = narrow layers on
+ *            the gather kernel instead of isf_sparse_conv_forward_dma; _VFE_FP32_ROWS (isf_lidar_branch_forward) = the voxel
+ *            encoder writes fp32 rows and a conversion pass makes the split rows, instead of writing them directly;
+ *            _CU_KERNEL = the 256-column layers on isf_sparse_conv_forward_cu (one workgroup per CU; opt-in: measured
+ *            slower than the tile kernel) -- results bit-identical either way;
+ *            | v << ISF_ENC_DIAG_CU_VARIANT_SHIFT = isf_conv_cu_plan.variant v of those layers (timing diagnostics, v < 16);
+ *            _DENSE_TABLES = dense neighbour tables for the narrow layers instead of the line-compressed ones -- bit-identical;
+ *            _COUNTS_MEMCPY = the encoder's per-level row counts reach the host through hipMemcpyAsync + synchronise
+ *            instead of the pinned-memory mailbox (post_int / wait_int) -- bit-identical;
+ *            _VOXELIZE_PER_FRAME (isf_lidar_branch_forward) = one dynamic-voxelize launch per frame + a separate byte-map
+ *            marking pass instead of the fused voxelize + mark launch -- bit-identical;
+ *            _TILE_TABLES = equal-work tile tables for the deep levels instead of uniform tiles + tile order (opt-in:
  *            measured slower) -- bit-identical;
- *            layers run on the gather kernel whenever a diagnostic other than 32 is set.
+ *            layers run on the gather kernel whenever a diagnostic other than _UNIFORM_TILES is set.
  *            Round 5 (all bit-identical to the default, all measured SLOWER, kept as tested opt-ins):
- *            +262144 / +524288 = the 256-column layers as ONE column block, 4 x 32-row / 8 x 16-row waves (conv mode 4096 /
- *            8192); +1048576 = staggered issue phases inside the deep layers' workgroups (conv mode 65536); +4194304 = the
- *            gathered rows two steps ahead (conv mode 262144); +2097152 = round 4's issue phase (row-index reads inside the
- *            step, four separate weight-DMA pieces; conv mode 131072) -- the A/B partner of the default, which reads the
+ *            _ONE_BLOCK_4W / _ONE_BLOCK_8W = the 256-column layers as ONE column block, 4 x 32-row / 8 x 16-row waves
+ *            (ISF_CONV_MODE_ONE_BLOCK_4W / _8W); _STAGGER = staggered issue phases inside the deep layers' workgroups
+ *            (ISF_CONV_MODE_STAGGER); _TWO_AHEAD = the gathered rows two steps ahead (ISF_CONV_MODE_TWO_AHEAD); _R4_ISSUE =
+ *            round 4's issue phase (row-index reads inside the step, four separate weight-DMA pieces;
+ *            ISF_CONV_MODE_R4_ISSUE) -- the A/B partner of the default, which reads the
  *            indices one step ahead and stages a wave's weight share as one run.
- *            Round 6: +536870912 = the 256-column layers with the chunk split (conv mode 524288): valid, deterministic, not
- *            the default's bits, measured slower (opt-in). */
+ *            Round 6: _CHUNK_SPLIT = the 256-column layers with the chunk split (ISF_CONV_MODE_CHUNK_SPLIT): valid,
+ *            deterministic, not the default's bits, measured slower (opt-in): 256 -> 256 0.223 -> 0.256 ms per launch,
+ *            1 030 -> 980 frames/s (profiles/EXPERIMENTS.md) -- the launch is bound by what its workgroups move through the
+ *            CUs' vector-memory paths in total, not by its longest chain (216 steps against an average of 136); a second
+ *            prologue per tile and the exchange add to that.
+ *            _DEEP = the deep layers on isf_spconv_deep.hip (ISF_CONV_MODE_DEEP; LDS-DMA gathers + one instruction stream
+ *            per step): bit-identical, 8 % slower, opt-in.
+ *            _BAND_ORDER = the launches of several rounds take their tiles band by band in y (opt-in; bit-identical):
+ *            measured slower on the benchmark's scenes (one dominant ground plane per frame: 64 -> 32 0.135 -> 0.154,
+ *            32 -> 32 0.27 -> 0.29, 64 -> 64 0.694 -> 0.709 ms per step, profiles/r06_band_order.txt) -- row order already
+ *            keeps a plane's y-neighbours together.
+ *            _NO_ROW_SORT = the row sort of the deep SubM launches (rows of a tile / a 16-row group with the same tap mask)
+ *            off (A/B; bit-identical either way).  _NARROW_ROW_SORT = the row sort for the NARROW layers too (LDS-DMA
+ *            kernel, line-compressed tables; opt-in): 33 % fewer tile-taps at level 0 on paper, no gain measured (64 -> 64
+ *            0.703 -> 0.719, 32 -> 32 0.272 -> 0.276 ms per step: those layers are bound by their gathers, and like rows are
+ *            further apart), profiles/r06_row_sort.txt.  _SORT_KEY_AB = sort key 2 (coarse | in-plane taps) instead of
+ *            key 1 (six coarse bits, one radix pass) (A/B).  (Sixteen taps of the planes above / below as the key, two
+ *            passes, made the 256-column launches 0.8 % faster, 1.131 vs 1.140 ms per step, and their fabric traffic 37 %
+ *            larger, FETCH_SIZE 226 -> 311 MB per launch: finer key groups scatter a tile's rows over the grid -- not kept.)
+ *            _NARROW_TILES = the 128-column layers of the large levels on the 4-wave 128-row tile instead of the 8-wave
+ *            256-row one (A/B; bit-identical). */
+#define ISF_ENC_DIAG_NO_GATHER 2               /* -> ISF_CONV_MODE_NO_GATHER */
+#define ISF_ENC_DIAG_NO_WEIGHTS 4              /* -> ISF_CONV_MODE_NO_WEIGHTS */
+#define ISF_ENC_DIAG_NO_LOOP 8                 /* -> ISF_CONV_MODE_NO_LOOP */
+#define ISF_ENC_DIAG_NO_SHARING 16             /* -> ISF_CONV_MODE_NO_SHARING */
+#define ISF_ENC_DIAG_UNIFORM_TILES 32          /* -> ISF_CONV_MODE_UNIFORM_TILES; combines with all others */
+#define ISF_ENC_DIAG_LAUNCH_ORDER 64           /* tiles in launch order, no tile-order tables */
+#define ISF_ENC_DIAG_NARROW_GATHER 128         /* narrow layers on the gather kernel, not the LDS-DMA kernel */
+#define ISF_ENC_DIAG_VFE_FP32_ROWS 256         /* isf_lidar_branch_forward: fp32 voxel rows + a conversion pass */
+#define ISF_ENC_DIAG_CU_KERNEL 512             /* 256-column layers on the one-workgroup-per-CU kernel (slower; opt-in) */
+#define ISF_ENC_DIAG_CU_VARIANT_SHIFT 10       /* bits 10-13: isf_conv_cu_plan.variant of the CU kernel */
+#define ISF_ENC_DIAG_CU_VARIANT_MASK 15360     /* 15 << ISF_ENC_DIAG_CU_VARIANT_SHIFT */
+#define ISF_ENC_DIAG_DENSE_TABLES 16384        /* dense neighbour tables for the narrow layers */
+#define ISF_ENC_DIAG_TILE_TABLES 32768         /* equal-work tile tables for the deep levels (slower; opt-in) */
+#define ISF_ENC_DIAG_VOXELIZE_PER_FRAME 65536  /* isf_lidar_branch_forward: one voxelize launch per frame */
+#define ISF_ENC_DIAG_COUNTS_MEMCPY 131072      /* row counts by hipMemcpyAsync + synchronise, not the mailbox */
+#define ISF_ENC_DIAG_ONE_BLOCK_4W 262144       /* -> ISF_CONV_MODE_ONE_BLOCK_4W (256-column layers) */
+#define ISF_ENC_DIAG_ONE_BLOCK_8W 524288       /* -> ISF_CONV_MODE_ONE_BLOCK_8W (256-column layers) */
+#define ISF_ENC_DIAG_STAGGER 1048576           /* -> ISF_CONV_MODE_STAGGER (deep layers) */
+#define ISF_ENC_DIAG_R4_ISSUE 2097152          /* -> ISF_CONV_MODE_R4_ISSUE (deep layers) */
+#define ISF_ENC_DIAG_TWO_AHEAD 4194304         /* -> ISF_CONV_MODE_TWO_AHEAD (deep layers) */
+#define ISF_ENC_DIAG_DEEP 8388608              /* -> ISF_CONV_MODE_DEEP (deep layers) */
+#define ISF_ENC_DIAG_BAND_ORDER 16777216       /* band order for the launches of several rounds (slower; opt-in) */
+#define ISF_ENC_DIAG_NO_ROW_SORT 33554432      /* row sort of the deep launches off (A/B) */
+#define ISF_ENC_DIAG_NARROW_ROW_SORT 67108864  /* row sort for the narrow layers too (no gain; opt-in) */
+#define ISF_ENC_DIAG_SORT_KEY_AB 134217728     /* row sort key 2 instead of key 1 (A/B) */
+#define ISF_ENC_DIAG_NARROW_TILES 268435456    /* 128-column layers of the large levels on 4-wave tiles (A/B) */
+#define ISF_ENC_DIAG_CHUNK_SPLIT 536870912     /* -> ISF_CONV_MODE_CHUNK_SPLIT (256-column layers; opt-in) */
 typedef struct isf_encoder_options {
   int precision;
   int diagnostic;
@@ -752,12 +829,14 @@ int isf_sparse_conv_backward_filter(const float* features, int num_in, int c_in,
  * isf_sparse_conv_backward_filter_f16x3: grad_filters [K, Cin, Cout] = (*grad_inv_scale) * sum over the pairs of tap k of
  *   x[in]^T dY[out], x and dY in the split format (x: what the forward pass stored; dY: isf_grad_to_split), products as
  *   x_lo*g_hi + x_hi*g_lo + x_hi*g_hi on v_mfma_f32_16x16x32_f16 with fp32 accumulation; Cin, Cout in {32, 64, 128, 256};
- *   pair chunks -> partial blocks -> ordered second pass: deterministic.  mode 0 = that (fp32-class); mode 1 = SINGLE-PASS
+ *   pair chunks -> partial blocks -> ordered second pass: deterministic.  mode 0 = that (fp32-class); ISF_WGRAD_F16 = SINGLE-PASS
  *   f16: only the hi halves are read and multiplied -- fp16 operands, fp32 accumulation: the arithmetic of the reference's
  *   indice_conv_backward<at::Half>, which is what its sparse convolutions run under autocast (functional.py:24
- *   custom_fwd(cast_inputs=torch.half)); the forward / dX counterpart is mode 1 of isf_sparse_conv_forward_f16x3 / _dma.
- *   mode + 2: every tap's pair list is full (the rulebook of a dense grid, dense_train.py) -- larger reduction chunks (same
+ *   custom_fwd(cast_inputs=torch.half)); the forward / dX counterpart is ISF_CONV_MODE_F16 of isf_sparse_conv_forward_f16x3 / _dma.
+ *   | ISF_WGRAD_FULL_TAPS: every tap's pair list is full (the rulebook of a dense grid, dense_train.py) -- larger reduction chunks (same
  *   sums, chunk boundaries move; still deterministic).  All asynchronous. */
+#define ISF_WGRAD_F16 1       /* single-pass f16: hi halves only */
+#define ISF_WGRAD_FULL_TAPS 2 /* every tap's pair list is full (dense grid): larger reduction chunks */
 int isf_pair_list_capacity(int num_in, int num_out);
 int isf_rulebook_pair_lists(const int32_t* nbr, int nbr_stride, int num_out, int num_taps, int capacity,
                             int32_t* indice_pairs, int32_t* indice_num, isf_stream_t stream);

@@ -110,6 +110,22 @@ class AdamWHp(ctypes.Structure):
 OPTIM_CHUNK, OPTIM_MAX_HP_ARGS = 32768, 16
 OPTIM_NO_CLIP, OPTIM_CLIP, OPTIM_SCALE_GRADS = 0, 1, 2
 
+# ISF_CONV_MODE_*: bits of the sparse convolutions' `mode` (include/isf_hip.h, isf_sparse_conv_forward_f16x3)
+CONV_MODE_F16, CONV_MODE_NO_GATHER, CONV_MODE_NO_WEIGHTS, CONV_MODE_NO_LOOP, CONV_MODE_NO_SHARING = 1, 2, 4, 8, 16
+CONV_MODE_UNIFORM_TILES, CONV_MODE_F16_ROWS, CONV_MODE_F16_STORAGE, CONV_MODE_DMA_PLAN = 32, 256, 257, 2048
+CONV_MODE_ONE_BLOCK_4W, CONV_MODE_ONE_BLOCK_8W, CONV_MODE_DEEP, CONV_MODE_STAGGER = 4096, 8192, 32768, 65536
+CONV_MODE_R4_ISSUE, CONV_MODE_TWO_AHEAD, CONV_MODE_CHUNK_SPLIT = 131072, 262144, 524288
+# ISF_ENC_DIAG_*: bits of isf_encoder_options.diagnostic (`conv_diag` of SparseEncoder / LidarBranch, bench.py --conv-diag)
+ENC_DIAG_NO_GATHER, ENC_DIAG_NO_WEIGHTS, ENC_DIAG_NO_LOOP, ENC_DIAG_NO_SHARING, ENC_DIAG_UNIFORM_TILES = 2, 4, 8, 16, 32
+ENC_DIAG_LAUNCH_ORDER, ENC_DIAG_NARROW_GATHER, ENC_DIAG_VFE_FP32_ROWS, ENC_DIAG_CU_KERNEL = 64, 128, 256, 512
+ENC_DIAG_CU_VARIANT_SHIFT, ENC_DIAG_CU_VARIANT_MASK = 10, 15 << 10
+ENC_DIAG_DENSE_TABLES, ENC_DIAG_TILE_TABLES, ENC_DIAG_VOXELIZE_PER_FRAME, ENC_DIAG_COUNTS_MEMCPY = 16384, 32768, 65536, 131072
+ENC_DIAG_ONE_BLOCK_4W, ENC_DIAG_ONE_BLOCK_8W, ENC_DIAG_STAGGER, ENC_DIAG_R4_ISSUE = 262144, 524288, 1048576, 2097152
+ENC_DIAG_TWO_AHEAD, ENC_DIAG_DEEP, ENC_DIAG_BAND_ORDER, ENC_DIAG_NO_ROW_SORT = 4194304, 8388608, 16777216, 33554432
+ENC_DIAG_NARROW_ROW_SORT, ENC_DIAG_SORT_KEY_AB, ENC_DIAG_NARROW_TILES, ENC_DIAG_CHUNK_SPLIT = 67108864, 134217728, 268435456, 536870912
+# ISF_WGRAD_*: bits of isf_sparse_conv_backward_filter_f16x3's `mode`
+WGRAD_F16, WGRAD_FULL_TAPS = 1, 2
+
 
 # name -> (restype, argtypes); every symbol include/isf_hip.h declares
 _F3 = ctypes.c_float * 3

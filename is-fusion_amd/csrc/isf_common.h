@@ -74,7 +74,7 @@ class Arena {
   // kZeroInts ints that are ZERO between top-level calls: a kernel chain that counts into them puts the zeros back itself
   // (its last reader), which saves the memset in front of the chain (zero_ints())
   int* zero_pool = nullptr;
-  // CHUNK-SPLIT convolutions (isf_spconv16.hip, conv mode bit 524288): the partial accumulator tiles the two workgroups of
+  // CHUNK-SPLIT convolutions (isf_spconv16.hip, ISF_CONV_MODE_CHUNK_SPLIT): the partial accumulator tiles the two workgroups of
   // a tile exchange, and one arrival counter per tile (zero between launches: the second arriver puts the zero back)
   float* ks_scratch = nullptr;
   size_t ks_scratch_bytes = 0;
@@ -271,7 +271,7 @@ bool sparse_conv_f16x3_supported(int c_in, int c_out);
 int sparse_conv_forward_f16x3_impl(const void* xs, int c_in, const void* packed16, int K, int c_out,
                                    const int32_t* nbr, int nbr_stride, int n_out, const float* scale,
                                    const float* shift, const void* residual, int relu, void* ys,
-                                   int mode /* 0 | 1 single-pass f16 | timing diagnostics */, hipStream_t st,
+                                   int mode /* ISF_CONV_MODE_* bits (+ isf_spconv16.h's internal ones) */, hipStream_t st,
                                    const int32_t* order = nullptr, struct Conv16LaunchInfo* query = nullptr,
                                    const int32_t* rowmap = nullptr /* sorted launch: position -> output row (conv_row_sort_impl) */);
 // How a launch of that kernel is cut into tiles (query != nullptr: filled instead of launching), and the per-part tile
@@ -308,7 +308,7 @@ int sparse_conv_forward_dma_impl(const void* xs, int c_in, const void* packed16,
                                  const int32_t* order = nullptr, Conv16LaunchInfo* query = nullptr,
                                  const uint32_t* lmask = nullptr /* line-compressed table: nbr = lines */, int nx = 0,
                                  const int32_t* rowmap = nullptr /* sorted launch: position -> output row */,
-                                 long long* trace = nullptr /* mode 512: per-workgroup trace (isf_sparse_conv_dma_trace) */);
+                                 long long* trace = nullptr /* mode kKernTrace: per-workgroup trace (isf_sparse_conv_dma_trace) */);
 int conv16_tile_order_impl(const int32_t* nbr, int nbr_stride, int K, int n_out, const Conv16LaunchInfo& info,
                            int32_t* work /* [parts * tiles] scratch */, int32_t* order /* [parts * tiles] */,
                            hipStream_t st, const uint32_t* lmask = nullptr /* line-compressed table's masks instead of nbr */);

@@ -1,5 +1,6 @@
 // isf_encoder.hip -- A7: dense BEV write-out, SparseEncoder.forward and the fused LiDAR branch.
 #include "isf_common.h"
+#include "isf_spconv16.h"   // the conv mode bits that stay inside the library
 
 #include <algorithm>
 
@@ -243,7 +244,7 @@ static int build_cu_plan(Arena& a, const int32_t* nbr, int stride, int K, int n_
 
 // tile order / tile table of one conv launch over a neighbour table, built behind the table on the geometry stream.  A
 // launch of the tile kernel that is resident in one round gets a TILE TABLE (conv16_table_part: the groups dealt to the
-// compute units by equal work; *is_table = true, run the conv with mode | 1024); the LDS-DMA kernel's launches keep the
+// compute units by equal work; *is_table = true, run the conv with mode | kConvModeTileTable); the LDS-DMA kernel's launches keep the
 // permutation of uniform tiles (conv16_tile_order_impl); *order stays nullptr when neither applies.
 static int build_tile_order(Arena& a, const isf_conv_layer& ly, int K, const int32_t* nbr, int stride, int n_out,
                             int mode, bool dma, const int32_t** order, hipStream_t sg, const uint32_t* lmask = nullptr,
@@ -315,6 +316,26 @@ static int ensure_occ(Arena& a, LevelState& L, int B, hipStream_t st) {
   return ISF_OK;
 }
 
+// isf_encoder_options.diagnostic: what each bit selects, and what was measured with it, is recorded beside its ISF_ENC_DIAG_*
+// name in include/isf_hip.h.  sparse_encoder_forward_impl decodes it once, at its top.
+static constexpr int kKnockoutBits = ISF_ENC_DIAG_NO_GATHER | ISF_ENC_DIAG_NO_WEIGHTS | ISF_ENC_DIAG_NO_LOOP | ISF_ENC_DIAG_NO_SHARING;
+static constexpr int kDeepOptBits = ISF_CONV_MODE_STAGGER | ISF_CONV_MODE_R4_ISSUE | ISF_CONV_MODE_TWO_AHEAD | ISF_CONV_MODE_DEEP | kConvModeNarrowTiles;
+static constexpr struct { int diag, mode; } kDiagToConvMode[] = {
+    {ISF_ENC_DIAG_NO_GATHER, ISF_CONV_MODE_NO_GATHER},       {ISF_ENC_DIAG_NO_WEIGHTS, ISF_CONV_MODE_NO_WEIGHTS},
+    {ISF_ENC_DIAG_NO_LOOP, ISF_CONV_MODE_NO_LOOP},           {ISF_ENC_DIAG_NO_SHARING, ISF_CONV_MODE_NO_SHARING},
+    {ISF_ENC_DIAG_UNIFORM_TILES, ISF_CONV_MODE_UNIFORM_TILES}, {ISF_ENC_DIAG_CHUNK_SPLIT, ISF_CONV_MODE_CHUNK_SPLIT},
+    {ISF_ENC_DIAG_ONE_BLOCK_4W, ISF_CONV_MODE_ONE_BLOCK_4W}, {ISF_ENC_DIAG_ONE_BLOCK_8W, ISF_CONV_MODE_ONE_BLOCK_8W},
+    {ISF_ENC_DIAG_STAGGER, ISF_CONV_MODE_STAGGER},           {ISF_ENC_DIAG_R4_ISSUE, ISF_CONV_MODE_R4_ISSUE},
+    {ISF_ENC_DIAG_TWO_AHEAD, ISF_CONV_MODE_TWO_AHEAD},       {ISF_ENC_DIAG_DEEP, ISF_CONV_MODE_DEEP},
+    {ISF_ENC_DIAG_NARROW_TILES, kConvModeNarrowTiles}};
+// every bit the engine entry points know: the table's, the encoder's own, isf_lidar_branch_forward's two
+static constexpr int kEncDiagKnown =
+    kKnockoutBits | ISF_ENC_DIAG_UNIFORM_TILES | ISF_ENC_DIAG_CHUNK_SPLIT | ISF_ENC_DIAG_ONE_BLOCK_4W | ISF_ENC_DIAG_ONE_BLOCK_8W |
+    ISF_ENC_DIAG_STAGGER | ISF_ENC_DIAG_R4_ISSUE | ISF_ENC_DIAG_TWO_AHEAD | ISF_ENC_DIAG_DEEP | ISF_ENC_DIAG_NARROW_TILES |
+    ISF_ENC_DIAG_LAUNCH_ORDER | ISF_ENC_DIAG_NARROW_GATHER | ISF_ENC_DIAG_CU_KERNEL | ISF_ENC_DIAG_CU_VARIANT_MASK |
+    ISF_ENC_DIAG_DENSE_TABLES | ISF_ENC_DIAG_TILE_TABLES | ISF_ENC_DIAG_COUNTS_MEMCPY | ISF_ENC_DIAG_BAND_ORDER | ISF_ENC_DIAG_NO_ROW_SORT |
+    ISF_ENC_DIAG_NARROW_ROW_SORT | ISF_ENC_DIAG_SORT_KEY_AB | ISF_ENC_DIAG_VFE_FP32_ROWS | ISF_ENC_DIAG_VOXELIZE_PER_FRAME;
+
 int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0, int n0, int B,
                                 const int shape0[3], const OccIndex* occ0, const isf_conv_layer* layers,
                                 int num_layers, float* spatial_features, int out_shape[4],
@@ -322,53 +343,30 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
                                 hipStream_t st, hipEvent_t geometry_ready = nullptr,
                                 const void* x0_split = nullptr /* x0 already in the split format (DynamicVFE wrote it) */) {
   const int precision = opt ? opt->precision : 0, diagnostic = opt ? opt->diagnostic : 0;
-  const int dg = diagnostic & ~(32 | 64 | 128 | 256 | 512 | (15 << 10) | 16384 | 32768 | 65536 | 131072 | 262144 | 524288 | 1048576 | 2097152 | 4194304 | 8388608 | 16777216 | 33554432 | 67108864 | 134217728 | 268435456 | 536870912);   // 256: isf_lidar_branch_forward's VFE hand-over, not the encoder's   // bits 32 (uniform conv tiles) and 64 (tiles in launch order) combine with the others
-  const bool tile_order = (diagnostic & 64) == 0;
-  const bool dma_gather = (diagnostic & 128) == 0;   // bit 128: the narrow layers on the gather kernel as well
-  const bool tile_tables = (diagnostic & 32768) != 0;      // bit 32768 (opt-in; measured slower): equal-work
-                                                           // tile tables instead of uniform tiles + LPT order
-  const bool line_tables = (diagnostic & 256 * 64) == 0;   // bit 16384: full neighbour tables for the narrow layers too
-  const bool mailbox = (diagnostic & 131072) == 0;         // bit 131072: data-dependent counts through hipMemcpyAsync + sync
-  // band order of the launches of several rounds (conv16_band_order_kernel): OPT-IN with bit 16777216 -- measured slower on
-  // the benchmark's scenes (one dominant ground plane per frame: 64 -> 32 0.135 -> 0.154, 32 -> 32 0.27 -> 0.29, 64 -> 64
-  // 0.694 -> 0.709 ms per step, profiles/r06_band_order.txt): row order already keeps a plane's y-neighbours together
-  const bool band_order = (diagnostic & 16777216) != 0;
-  auto band_of = [&](const int shape[3]) -> int { return band_order ? std::max(8, shape[1] / 45) : 0; };
-  // row sort of the deep SubM launches (conv_row_sort_impl): rows of a tile / a 16-row group with the same tap mask;
-  // bit 33554432 switches it off (A/B; results are bit-identical either way)
-  const bool row_sort = (diagnostic & 33554432) == 0;
-  // ... of the NARROW layers too (LDS-DMA kernel, line-compressed tables): opt-in with bit 67108864 -- 33 % fewer tile-taps at
-  // level 0 on paper, no gain measured (64 -> 64 0.703 -> 0.719, 32 -> 32 0.272 -> 0.276 ms per step: those layers are bound
-  // by their gathers, and like rows are further apart), profiles/r06_row_sort.txt
-  const bool narrow_sort = (diagnostic & 67108864) != 0;
-  // CHUNK SPLIT of the 256-column layers (conv mode 524288, isf_spconv16.hip: two workgroups per tile, each over half of
-  // the 32-channel chunks, the second to arrive adds the other's accumulators and runs the epilogue): OPT-IN with bit
-  // 536870912.  Built on the reading that the small deep levels are ONE round of workgroups that ends with its longest tile
-  // (216 steps against an average of 136) -- and measured slower: 256 -> 256 0.223 -> 0.256 ms per launch, 1 030 -> 980
-  // frames/s (gpurun_out / profiles/EXPERIMENTS.md): the launch is bound by what its workgroups move through the CUs'
-  // vector-memory paths in total, not by its longest chain; a second prologue per tile and the exchange add to that.
-  // Deterministic (a + b == b + a), not the bits of the unsplit kernel (the sum over chunks is (lower half) + (upper half)).
-  const bool ksplit_on = (diagnostic & 536870912) != 0;
-  constexpr int sort_min_rows = 4096;   // (configs[2] at B = 2: 7.05 ms sorted from 4 096 rows up, 7.10 from 32 768, 7.10 unsorted)
-  // key of the sort: 1 = six coarse bits (one radix pass) everywhere.  Sixteen taps of the planes above / below (key 3,
-  // two passes) made the 256-column launches 0.8 % faster (1.131 vs 1.140 ms per step) and their fabric traffic 37 % larger
-  // (FETCH_SIZE 226 -> 311 MB per launch: finer key groups scatter a tile's rows over the grid) -- not kept;
-  // bit 134217728: coarse | in-plane taps (key 2; A/B)
-  const bool sort_key_ab = (diagnostic & 134217728) != 0;
-  const bool cu_units = (diagnostic & 512) != 0;     // bit 512 (opt-in; measured slower): the 256-column
-                                                     // layers on the one-workgroup-per-CU kernel
-  const int cu_cap = conv_cu_variant_cap((diagnostic >> 10) & 15);   // unit shape of the requested kernel variant
-  ISF_REQUIRE(precision >= 0 && precision <= 2 && diagnostic >= 0 &&
-                  (dg == 0 || dg == 2 || dg == 4 || dg == 6 || dg == 8 || dg == 16) && !(precision == 2 && dg != 0),
+  const int dg = diagnostic & kKnockoutBits;   // timing diagnostic of the conv kernels (they exist on the gather kernel only)
+  ISF_REQUIRE(precision >= 0 && precision <= 2 && diagnostic >= 0 && (diagnostic & ~kEncDiagKnown) == 0 &&
+                  (dg == 0 || conv_mode_is_knockout(dg) || dg == ISF_ENC_DIAG_NO_SHARING) && !(precision == 2 && dg != 0),
               ISF_ERR_ARG, "sparse_encoder: options (precision %d, diagnostic %d)", precision, diagnostic);
-  // precision 2: f16 storage + single-pass f16 arithmetic (mode 257 of the conv kernel)
-  const int conv_mode = precision == 2 ? (257 | (diagnostic & 32)) : (diagnostic & ~(64 | 128 | 256 | 512 | (15 << 10) | 16384 | 32768 | 65536 | 131072 | 262144 | 524288 | 1048576 | 2097152 | 4194304 | 8388608 | 16777216 | 33554432 | 67108864 | 134217728 | 268435456 | 536870912));
-  // bits 262144 / 524288: the 256-column layers as one column block (conv mode 4096 / 8192; isf_spconv16.hip)
-  const int wide_cols = (diagnostic & 262144 ? 4096 : 0) | (diagnostic & 524288 ? 8192 : 0);
-  const int stagger = ((diagnostic & 1048576) ? 65536 : 0) | ((diagnostic & 2097152) ? 131072 : 0) | ((diagnostic & 4194304) ? 262144 : 0) |
-                      ((diagnostic & 8388608) ? 32768 : 0) | ((diagnostic & 268435456) ? 64 : 0);   // bit 8388608: the deep layers on isf_spconv_deep.hip (opt-in: LDS-DMA gathers + one instruction stream per step; bit-identical, 8 % slower)   // bit 4194304: gathered rows two steps ahead (A2 loop); bit 2097152: round 4's issue phase in the deep layers (A/B)
-    // bit 1048576: staggered issue phases in the deep layers' workgroups
-  const bool f16io = precision == 2;
+  int translated = 0;
+  for (const auto& t : kDiagToConvMode)
+    if (diagnostic & t.diag) translated |= t.mode;
+  const bool f16io = precision == 2;             // f16 rows between the layers
+  const bool fp32_class = dg == 0 && !f16io;     // the split-precision kernels proper: the only ones the variants below apply to
+  // what every layer's launch starts from: a knock-out or f16 storage, | uniform tiles
+  const int conv_mode = (f16io ? ISF_CONV_MODE_F16_STORAGE : dg) | (translated & ISF_CONV_MODE_UNIFORM_TILES);
+  const int one_block = translated & (ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W);   // for the 256-column layers
+  const int deep_opts = translated & kDeepOptBits;                                                // for 128 columns and more
+  const bool chunk_split = (translated & ISF_CONV_MODE_CHUNK_SPLIT) && fp32_class && one_block == 0 && deep_opts == 0;
+  auto on = [&](int bit) { return (diagnostic & bit) != 0; };
+  const bool tile_order = !on(ISF_ENC_DIAG_LAUNCH_ORDER), dma_gather = !on(ISF_ENC_DIAG_NARROW_GATHER);
+  const bool line_tables = !on(ISF_ENC_DIAG_DENSE_TABLES), mailbox = !on(ISF_ENC_DIAG_COUNTS_MEMCPY), row_sort = !on(ISF_ENC_DIAG_NO_ROW_SORT);
+  const bool tile_tables = on(ISF_ENC_DIAG_TILE_TABLES), band_order = on(ISF_ENC_DIAG_BAND_ORDER);            // opt-ins
+  const bool narrow_sort = on(ISF_ENC_DIAG_NARROW_ROW_SORT), cu_units = on(ISF_ENC_DIAG_CU_KERNEL);
+  const int sort_key = on(ISF_ENC_DIAG_SORT_KEY_AB) ? 2 : 1;   // conv_row_sort_impl: 1 = six coarse bits (one radix pass), 2 = coarse | in-plane taps
+  const int cu_variant = (diagnostic & ISF_ENC_DIAG_CU_VARIANT_MASK) >> ISF_ENC_DIAG_CU_VARIANT_SHIFT;   // isf_conv_cu_plan.variant
+  auto band_of = [&](const int shape[3]) -> int { return band_order ? std::max(8, shape[1] / 45) : 0; };
+  constexpr int sort_min_rows = 4096;   // (configs[2] at B = 2: 7.05 ms sorted from 4 096 rows up, 7.10 from 32 768, 7.10 unsorted)
+  const int cu_cap = conv_cu_variant_cap(cu_variant);   // unit shape of the requested kernel variant
   const int stage_opt = opt ? opt->stage_rows : 0;
   const unsigned stage_mask = opt ? (unsigned)opt->stage_mask : 0u;
   ISF_REQUIRE(stage_opt >= -1, ISF_ERR_ARG, "sparse_encoder: stage_rows %d", stage_opt);
@@ -448,9 +446,10 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
     const bool cu = use16 && cu_units && srows == 0 && conv_mode == 0 && sparse_conv_cu_supported(ly.c_in, ly.c_out);
     ConvCuPlan cu_plan;
     const bool want_order = use16 && tile_order && srows == 0 && !cu;
-    const int ksbit = (ksplit_on && use16 && !f16io && !cu && srows == 0 && dg == 0 && ly.c_out == 256 && ly.c_in >= 128 &&
-                       conv_mode == (conv_mode & 32) && wide_cols == 0 && stagger == 0) ? 524288 : 0;
-    // narrow layers: LDS-DMA gathers (isf_spconv_dma.hip); the timing diagnostics and mode 16 exist on the gather kernel
+    // this layer's conv mode on the tile kernel, as the launch and everything planned for the launch (row sort, tile order) see it
+    const int layer_mode = conv_mode | (fp32_class && ly.c_out >= 128 ? deep_opts : 0) |
+                           (chunk_split && use16 && !cu && srows == 0 && ly.c_out == 256 && ly.c_in >= 128 ? ISF_CONV_MODE_CHUNK_SPLIT : 0);
+    // narrow layers: LDS-DMA gathers (isf_spconv_dma.hip); the timing diagnostics and ISF_CONV_MODE_NO_SHARING exist on the gather kernel
     const bool dma = use16 && dma_gather && srows == 0 && dg == 0 && sparse_conv_dma_supported(ly.c_in, ly.c_out);
     const uint32_t* lmask = nullptr;   // non-null: `nbr` is the line-compressed table of this layer
     const int nx = ly.ksize[2];
@@ -471,17 +470,16 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
     // ROW SORT (round 6): a SubM layer computes its rows in the order of their tap masks (deep layers on the tile kernel,
     // narrow layers on the LDS-DMA kernel, full or line-compressed table)
     // (the f16-storage mode too, round 6: the sort only renames positions; its epilogue reads / writes through the row map)
-    const bool sort_mode_ok = conv_mode == (conv_mode & 32) || conv_mode == (257 | (conv_mode & 32));
+    const bool sort_mode_ok = dg == 0 && one_block == 0 && (deep_opts & ~kConvModeNarrowTiles) == 0;
     const bool sort_ok = row_sort && use16 && !cu && srows == 0 && ly.conv_type == ISF_CONV_SUBM && K == 27 &&
-                         sort_mode_ok && wide_cols == 0 && (stagger & ~64) == 0 && L.n >= sort_min_rows &&
-                         (dma ? narrow_sort : ly.c_out >= 128);
+                         sort_mode_ok && L.n >= sort_min_rows && (dma ? narrow_sort : ly.c_out >= 128);
     const int32_t* rowmap = nullptr;
     auto launch_info = [&](const int32_t* table, int tstride, int rows, Conv16LaunchInfo* info) -> int {
       if (dma)
         return sparse_conv_forward_dma_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, table, tstride, rows, nullptr, nullptr,
                                             nullptr, 0, nullptr, conv_mode, sg, nullptr, info);
       return sparse_conv_forward_f16x3_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, table, tstride, rows, nullptr, nullptr,
-                                            nullptr, 0, nullptr, conv_mode | ksbit | (ly.c_out >= 128 ? stagger : 0), sg, nullptr, info);
+                                            nullptr, 0, nullptr, layer_mode, sg, nullptr, info);
     };
     auto ensure_row_sort = [&](const int32_t* table, int tstride, int rows, bool* built) -> int {
       *built = false;
@@ -501,7 +499,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
         L.cache_lmask_sorted = lms;
       } else {
         ISF_TRY(a.alloc_n(&ns, (size_t)K * tstride));
-        ISF_TRY(conv_row_sort_impl(a, table, tstride, K, rows, info.part_rows, rm, ns, sg, sort_key_ab ? 2 : 1));
+        ISF_TRY(conv_row_sort_impl(a, table, tstride, K, rows, info.part_rows, rm, ns, sg, sort_key));
       }
       L.cache_rowmap = rm;
       L.cache_nbr_sorted = ns;
@@ -554,7 +552,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
         }
         if (want_order) {
           ISF_TRY(build_tile_order(a, ly, K, sort_applies(nbr, stride, n_out) ? L.cache_nbr_sorted : nbr, stride, n_out,
-                                   conv_mode | ksbit | (ly.c_out >= 128 && conv_mode == (conv_mode & 32) ? stagger : 0), dma, &L.cache_order, sg,
+                                   layer_mode, dma, &L.cache_order, sg,
                                    (L.cache_lmask && sort_applies(nbr, stride, n_out)) ? L.cache_lmask_sorted : L.cache_lmask,
                                    &L.cache_order_is_table, tile_tables, L.coors, band_of(L.shape)));
           L.cache_order_cin = ly.c_in;
@@ -576,7 +574,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
         }
         if (want_order && (L.cache_order_cin != ly.c_in || L.cache_order_cout != ly.c_out)) {   // another launch shape
           ISF_TRY(build_tile_order(a, ly, K, sort_applies(nbr, stride, n_out) ? L.cache_nbr_sorted : nbr, stride, n_out,
-                                   conv_mode | ksbit | (ly.c_out >= 128 && conv_mode == (conv_mode & 32) ? stagger : 0), dma, &L.cache_order, sg,
+                                   layer_mode, dma, &L.cache_order, sg,
                                    (L.cache_lmask && sort_applies(nbr, stride, n_out)) ? L.cache_lmask_sorted : L.cache_lmask,
                                    &L.cache_order_is_table, tile_tables, L.coors, band_of(L.shape)));
           L.cache_order_cin = ly.c_in;
@@ -639,11 +637,11 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
       if (srows > 0) ISF_TRY(build_stage_tables(a, nbr, stride, K, &stg, sg));
       // ROW SORT of a deep strided convolution's own table (its rows want 10 of 27 taps, in many patterns: -12 % tile-taps,
       // -26 % MFMA blocks at level 3 on the benchmark geometry, profiles/r06_row_sort.txt)
-      if (row_sort && use16 && !dma && !cu && srows == 0 && !lmask && ly.c_out >= 128 && K == 27 &&
-          sort_mode_ok && wide_cols == 0 && (stagger & ~64) == 0 && Nx.n >= sort_min_rows) {
+      if (row_sort && use16 && !dma && !cu && srows == 0 && !lmask && ly.c_out >= 128 && K == 27 && sort_mode_ok &&
+          Nx.n >= sort_min_rows) {
         Conv16LaunchInfo info;
         ISF_TRY(sparse_conv_forward_f16x3_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, Nx.n, nullptr, nullptr,
-                                               nullptr, 0, nullptr, conv_mode | ksbit | stagger, sg, nullptr, &info));
+                                               nullptr, 0, nullptr, layer_mode, sg, nullptr, &info));
         int32_t *rm = nullptr, *ns = nullptr;
         ISF_TRY(a.alloc_n(&rm, (size_t)stride));
         ISF_TRY(a.alloc_n(&ns, (size_t)K * stride));
@@ -652,7 +650,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
         rowmap = rm;
       }
       if (want_order)
-        ISF_TRY(build_tile_order(a, ly, K, nbr, stride, Nx.n, conv_mode | ksbit | (ly.c_out >= 128 && conv_mode == (conv_mode & 32) ? stagger : 0), dma, &order, sg, lmask, &order_is_table, tile_tables,
+        ISF_TRY(build_tile_order(a, ly, K, nbr, stride, Nx.n, layer_mode, dma, &order, sg, lmask, &order_is_table, tile_tables,
                                  Nx.coors, band_of(Nx.shape)));
       if (cu && Nx.n > 0) ISF_TRY(build_cu_plan(a, nbr, stride, K, Nx.n, &cu_plan, sg, cu_cap));
       if (stats) stats->pairs[i] = -(long long)i - 1;
@@ -683,7 +681,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
       ISF_TRY(sparse_conv_forward_staged_impl(x, ly.c_in, ly.packed16, K, ly.c_out, stg.slots, stride, stg.ulist,
                                               stg.ucount, n_out, ly.scale, ly.shift, res, ly.relu, y, srows, conv_mode,
                                               st));
-    else if (cu && n_out > 0 && ((cu_plan.variant = (diagnostic >> 10) & 15), true))
+    else if (cu && n_out > 0 && ((cu_plan.variant = cu_variant), true))
       ISF_TRY(sparse_conv_forward_cu_impl(x, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, ly.scale, ly.shift, res,
                                           ly.relu, y, cu_plan, st));
     else if (dma)
@@ -692,8 +690,8 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
     else if (use16)
       ISF_TRY(sparse_conv_forward_f16x3_impl(x, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, ly.scale,
                                              ly.shift, res, ly.relu, y,
-                                             conv_mode | ksbit | (order_is_table ? 1024 : 0) | (ly.c_out == 256 && conv_mode == (conv_mode & 32) ? wide_cols : 0) |
-                                                 (ly.c_out >= 128 && conv_mode == (conv_mode & 32) ? stagger : 0),
+                                             layer_mode | (order_is_table ? kConvModeTileTable : 0) |
+                                                 (ly.c_out == 256 && fp32_class ? one_block : 0),
                                              st, order, nullptr, rowmap));
     else if (sparse_conv_mfma_supported(ly.c_in, ly.c_out))
       ISF_TRY(sparse_conv_forward_packed_impl(reinterpret_cast<const float*>(x), n_in, ly.c_in, ly.packed, K,
@@ -835,10 +833,10 @@ int isf_lidar_branch_forward(const float* points, const int64_t* point_offsets_h
   int32_t* coors4 = nullptr;
   ISF_TRY(a.alloc_n(&coors4, (size_t)P * 4));
   // batches of up to 8 frames: voxelized inside the byte-map marking launch of the VFE (one launch instead of B + 1 and
-  // one pass over the coordinates less); diagnostic 65536 and larger batches: one dynamic_voxelize launch per frame
+  // one pass over the coordinates less); ISF_ENC_DIAG_VOXELIZE_PER_FRAME and larger batches: one dynamic_voxelize launch per frame
   VoxBatch vb;
   vb.B = batch_size;
-  const bool fused_vox = batch_size <= kVoxMaxBatch && !(options && (options->diagnostic & 65536));
+  const bool fused_vox = batch_size <= kVoxMaxBatch && !(options && (options->diagnostic & ISF_ENC_DIAG_VOXELIZE_PER_FRAME));
   for (int b = 0; b < batch_size; ++b) {
     const int64_t lo = point_offsets_host[b], hi = point_offsets_host[b + 1];
     ISF_REQUIRE(hi >= lo, ISF_ERR_ARG, "lidar_branch_forward: bad offsets");
@@ -861,7 +859,7 @@ int isf_lidar_branch_forward(const float* points, const int64_t* point_offsets_h
   // max, the rows cut by a wave boundary from a fix-up pass): no [N, 64] fp32 -> split conversion pass in between
   void* vf_split = nullptr;
   if (encoder_takes_split_input(layers_host, num_layers, options) && vfe_host->c2 == layers_host[0].c_in &&
-      !(options && (options->diagnostic & 256)))   // diagnostic 256: fp32 rows + the conversion pass (same bits)
+      !(options && (options->diagnostic & ISF_ENC_DIAG_VFE_FP32_ROWS)))   // fp32 rows + the conversion pass (same bits)
     ISF_TRY(a.alloc(&vf_split, (size_t)P * vfe_host->c2 * 4));
   ISF_TRY(dynamic_vfe_impl(a, points, coors4, P, Cin, batch_size, vfe_host->voxel_size, vfe_host->coors_range,
                            vfe_host->w1, vfe_host->scale1, vfe_host->shift1, vfe_host->c1, vfe_host->w2,

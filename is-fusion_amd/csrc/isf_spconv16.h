@@ -11,6 +11,41 @@ typedef float f32x8 __attribute__((ext_vector_type(8)));
 
 static constexpr int kMaxTaps = 27;
 
+// CONV MODE bits that are hand-overs between the library's translation units.  They occupy the same int as the public
+// ISF_CONV_MODE_* bits (include/isf_hip.h), which therefore never take these values.
+static constexpr int kConvModeNarrowTiles = 64;   // the 128-column layers of the large levels on the 4-wave 128-row tile
+                                                  // instead of the 8-wave 256-row one (A/B; the encoder's ISF_ENC_DIAG_NARROW_TILES)
+static constexpr int kConvModeTileTable = 1024;   // `order` is a tile table (isf_sparse_conv_tile_table), not a tile order
+// what launch16_rows ignores when it compares `mode` with one of the launch variants
+static constexpr int kConvModeTileBits = ISF_CONV_MODE_UNIFORM_TILES | kConvModeTileTable;
+
+// Modes the exported entry points accept: a BASE mode (one of the values below) | any of the entry point's option bits.
+static constexpr bool conv_mode_is_production(int m) {   // valid results on the production workgroup shapes
+  return m == 0 || m == ISF_CONV_MODE_F16 || m == ISF_CONV_MODE_NO_SHARING || m == ISF_CONV_MODE_F16_STORAGE;
+}
+static constexpr bool conv_mode_is_knockout(int m) {     // timing diagnostics: results are garbage
+  return m == ISF_CONV_MODE_NO_GATHER || m == ISF_CONV_MODE_NO_WEIGHTS || m == (ISF_CONV_MODE_NO_GATHER | ISF_CONV_MODE_NO_WEIGHTS) ||
+         m == ISF_CONV_MODE_NO_LOOP;
+}
+static constexpr int kConvIssueOpts = ISF_CONV_MODE_STAGGER | ISF_CONV_MODE_R4_ISSUE | ISF_CONV_MODE_TWO_AHEAD | ISF_CONV_MODE_CHUNK_SPLIT;
+static constexpr int kConvOptsForward = ISF_CONV_MODE_UNIFORM_TILES | kConvIssueOpts | kConvModeNarrowTiles | ISF_CONV_MODE_ONE_BLOCK_4W |
+                                        ISF_CONV_MODE_ONE_BLOCK_8W | ISF_CONV_MODE_DEEP;   // isf_sparse_conv_forward_f16x3 (+ knock-outs)
+static constexpr int kConvOptsOrdered = ISF_CONV_MODE_UNIFORM_TILES | kConvIssueOpts;      // isf_sparse_conv_forward_f16x3_ordered
+static constexpr int kConvOptsTiled = 0;                                // isf_sparse_conv_tile_table / _forward_f16x3_tiled
+static constexpr int kConvOptsDma = ISF_CONV_MODE_UNIFORM_TILES;        // isf_sparse_conv_forward_dma / _lines: base 0 | F16 | F16_STORAGE
+static constexpr int kConvOptsStaged = ISF_CONV_MODE_UNIFORM_TILES;     // isf_sparse_conv_forward_staged: base 0 | F16
+
+// The kernels' template parameter MODE is a THIRD number space (after the runtime `mode` and the encoder's `diagnostic`).
+// These bits mean what the runtime bit of the same value means: launch16_rows hands them over unchanged ...
+static constexpr int kKernF16 = ISF_CONV_MODE_F16, kKernNoGather = ISF_CONV_MODE_NO_GATHER, kKernNoWeights = ISF_CONV_MODE_NO_WEIGHTS,
+                     kKernNoLoop = ISF_CONV_MODE_NO_LOOP, kKernNoSharing = ISF_CONV_MODE_NO_SHARING, kKernF16Rows = ISF_CONV_MODE_F16_ROWS,
+                     kKernStagger = ISF_CONV_MODE_STAGGER, kKernR4Issue = ISF_CONV_MODE_R4_ISSUE, kKernTwoAhead = ISF_CONV_MODE_TWO_AHEAD,
+                     kKernChunkSplit = ISF_CONV_MODE_CHUNK_SPLIT;
+// ... and these two do NOT: as runtime bits 2048 is ISF_CONV_MODE_DMA_PLAN, and 512 is the encoder's ISF_ENC_DIAG_CU_KERNEL.
+// Every other runtime bit (tiles, workgroup shape, kernel choice) is resolved on the host and never reaches a kernel.
+static constexpr int kKernTrace = 512;         // per-workgroup trace (isf_sparse_conv_trace, isf_sparse_conv_dma_trace)
+static constexpr int kKernPhaseTrace = 2048;   // with kKernTrace: per-wave phase trace (isf_sparse_conv_phase_trace)
+
 // narrow layers (CIN <= 64, <= 64 output columns) run all their 32-channel chunks in one step: half / the same
 // number of barriers for twice the MFMAs per barrier
 template <int CIN, int NT>

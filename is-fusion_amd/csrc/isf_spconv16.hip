@@ -33,7 +33,7 @@ namespace isf {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-// phase trace (MODE bit 2048): dwords per wave record = kPhaseHdr + kPhaseStep * kPhaseMaxSteps
+// phase trace (MODE bit kKernPhaseTrace): dwords per wave record = kPhaseHdr + kPhaseStep * kPhaseMaxSteps
 constexpr int kPhaseHdr = 8, kPhaseMaxSteps = kMaxTaps * 8, kPhaseStep = 8;
 
 __device__ __forceinline__ unsigned long long shader_clock64() {
@@ -60,13 +60,13 @@ struct Conv16Smem {
 
 // NW waves per workgroup (4, 8 or 16): all of them share one weight stage per step, so the weight bytes a CU pulls
 // through its vector memory path per MFMA fall with NW.
-// MODE bit 1 = single-pass mode (precision 2 of isf_encoder_options, mode 1 of isf_sparse_conv_forward_f16x3): only the hi halves of activations and weights are fetched
+// MODE (bit names: isf_spconv16.h) kKernF16 = single-pass mode (precision 2 of isf_encoder_options, ISF_CONV_MODE_F16 of isf_sparse_conv_forward_f16x3): only the hi halves of activations and weights are fetched
 // and multiplied -- plain f16 operands with fp32 accumulation, the accuracy of the reference under fp16 autocast
 // (indice_conv_half), one MFMA per product instead of three.  Same buffers, same layouts; outputs are still written
 // split.  Never the default: the headline configuration is fp32-class.
-// MODE bits 2 / 4 / 8 are TIMING DIAGNOSTICS (the `diagnostic` option / `mode` argument; results are garbage): 2 = no activation gathers
-// (A = 0), 4 = no weight DMA, 8 = no main loop (prologue + epilogue only) -- the knock-out decomposition of DESIGN.md
-// section 5 as a permanent tool (tools/conv_knockout.sh).  MODE bit 16 (valid results) switches the neighbour sharing of
+// kKernNoGather / kKernNoWeights / kKernNoLoop are TIMING DIAGNOSTICS (the `diagnostic` option / `mode` argument; results are garbage): no activation gathers
+// (A = 0), no weight DMA, no main loop (prologue + epilogue only) -- the knock-out decomposition of DESIGN.md
+// section 5 as a permanent tool (tools/conv_knockout.sh).  kKernNoSharing (valid results) switches the neighbour sharing of
 // the gathers off: the reference the sharing is checked against bit for bit.
 template <int CIN, int NT, int RG, int NW, int MODE = 0>
 __global__ __launch_bounds__(64 * NW, (NW >= 16 ? 1 : (NT * RG >= 16 ? 2 : 3))) void spconv_f16x3_kernel(
@@ -75,48 +75,49 @@ __global__ __launch_bounds__(64 * NW, (NW >= 16 ? 1 : (NT * RG >= 16 ? 2 : 3))) 
     const float* __restrict__ scale, const float* __restrict__ shift, const uint4* __restrict__ residual,
     uint4* __restrict__ ys, int n_out, int relu, Conv16Plan plan, const int32_t* __restrict__ order,
     long long* __restrict__ trace, const int32_t* __restrict__ rowmap /* nullptr | position -> output row (sorted launch) */,
-    float* __restrict__ ks_scratch, unsigned* __restrict__ ks_count /* chunk-split launches (MODE bit 524288) */) {
-  // MODE bit 524288: CHUNK SPLIT.  A tile is computed by TWO workgroups -- blocks b and b + gridDim.x / 2 (ids 8 apart
+    float* __restrict__ ks_scratch, unsigned* __restrict__ ks_count /* chunk-split launches (kKernChunkSplit) */) {
+  // kKernChunkSplit: CHUNK SPLIT.  A tile is computed by TWO workgroups -- blocks b and b + gridDim.x / 2 (ids 8 apart
   // share an XCD, so these do too) -- each over half of the 32-channel chunks; both store their accumulator tile, the
   // SECOND to arrive at the tile's counter adds the other's and runs the epilogue (a + b == b + a: the result does not
   // depend on who arrives first; per output element: (chunks of the lower half, taps ascending) + (chunks of the upper
   // half, taps ascending)).  Why: the 256-column layers live on the small deep levels -- 40 k rows at B = 4 x 300 k
   // points = 636 workgroups on 768 slots, ONE round, whose duration is its longest tile's (27 taps x 8 chunks = 216
   // steps of ~1.2 us) while the average tile has 136: 1 272 half-length workgroups refill the slots as they drain.
-  constexpr bool KSPLIT = (MODE & 524288) != 0;
-  // MODE bit 512: per-workgroup trace (isf_sparse_conv_trace): 8 x int64 per workgroup -- constant-clock time stamps at
+  constexpr bool KSPLIT = (MODE & kKernChunkSplit) != 0;
+  // kKernTrace: per-workgroup trace (isf_sparse_conv_trace): 8 x int64 per workgroup -- constant-clock time stamps at
   // entry / after the prologue / after the multiply loop / at exit, steps, HW_ID, XCC_ID, first row | half << 32
-  constexpr bool TRACE = (MODE & 512) != 0;
-  // MODE bit 2048 (with 512): PHASE TRACE (isf_sparse_conv_phase_trace; the image has no thread-trace decoder, so this is
+  constexpr bool TRACE = (MODE & kKernTrace) != 0;
+  // kKernPhaseTrace (with kKernTrace): PHASE TRACE (isf_sparse_conv_phase_trace; the image has no thread-trace decoder, so this is
   // the kernel's own instruction-level account): every wave stamps the shader clock (s_memtime, 1 tick = 1 shader cycle)
   // at the top of each step / after its s_waitcnt vmcnt(0) / after the barrier / after issuing the next step's loads;
   // the multiply section is what is left until the next top.  Per wave, behind the per-workgroup records:
   // kPhaseHdr dwords {clock at loop entry lo, hi, HW_ID, steps, rgm[0], rgm[1], wg_mask, clock at loop exit lo} +
   // 8 dwords per step {top, after wait, after barrier, after issue, after the index reads, after the gathers, 0, 0}.  The
   // stamps cost ~6 scalar-memory round trips per step (measured against the untraced launch by tools/conv_phase_trace.py).
-  constexpr bool PHASE = (MODE & 2048) != 0;
+  constexpr bool PHASE = (MODE & kKernPhaseTrace) != 0;
   long long t_entry = 0, t_pro = 0, t_loop = 0;
   if (TRACE) t_entry = wall_clock64();
-  constexpr bool HALF = (MODE & 1) != 0, NOGATHER = (MODE & 2) != 0, NODMA = (MODE & 4) != 0, NOLOOP = (MODE & 8) != 0;
-  // MODE bit 256 (with bit 1): F16 STORAGE -- input, residual and output rows are plain f16 (2 bytes per element, the
+  constexpr bool HALF = (MODE & kKernF16) != 0, NOGATHER = (MODE & kKernNoGather) != 0, NODMA = (MODE & kKernNoWeights) != 0,
+                 NOLOOP = (MODE & kKernNoLoop) != 0;
+  // kKernF16Rows (with kKernF16): F16 STORAGE -- input, residual and output rows are plain f16 (2 bytes per element, the
   // reference's indice_conv_half data type end to end: src/all.cc:35-37) instead of 4-byte split rows; half the
   // activation bytes of every layer (BASELINE configs[4], the HBM-bound run).  isf_encoder_options.precision = 2.
-  constexpr bool F16IO = (MODE & 256) != 0;
-  constexpr bool STAG = (MODE & 65536) != 0;   // staggered issue phases, see the main loop
-  // MODE bit 262144: the gathered rows TWO steps ahead (three register sets in rotation, loop unrolled by three, counted
+  constexpr bool F16IO = (MODE & kKernF16Rows) != 0;
+  constexpr bool STAG = (MODE & kKernStagger) != 0;   // staggered issue phases, see the main loop
+  // kKernTwoAhead: the gathered rows TWO steps ahead (three register sets in rotation, loop unrolled by three, counted
   // vmcnt waits) -- the A2 loop below; 4-wave deep shapes only
-  constexpr bool A2 = (MODE & 262144) != 0;
+  constexpr bool A2 = (MODE & kKernTwoAhead) != 0;
   static_assert(!F16IO || HALF, "f16 storage implies single-pass f16 arithmetic");
   // neighbour sharing of the gathers (load_A below) where it was measured to pay -- the layers whose gathers saturate
   // the vector-memory path: 64 -> 64 0.91 -> 0.76 ms, 64 -> 32 0.138 -> 0.128, 32 -> 32 0.312 -> 0.301 per step; the
   // layers with >= 128 output columns (and 32 -> 64) lose 3-5 % to its DPP / select / index work and keep plain gathers
-  // (profiles/r02_call3_sharing.txt).  MODE bit 16 switches it off everywhere (bit-equality reference).
-  constexpr bool SHARE = (MODE & 16) == 0 && NT <= 4 && (CIN >= 64 || NT == 2);
+  // (profiles/r02_call3_sharing.txt).  kKernNoSharing switches it off everywhere (bit-equality reference).
+  constexpr bool SHARE = (MODE & kKernNoSharing) == 0 && NT <= 4 && (CIN >= 64 || NT == 2);
   constexpr int KCH = Conv16Step<CIN, NT>::KCH;
-  // the multiply section in hand-scheduled assembly (isf_spconv16_mult.h) for the deep layers' 4-wave shape; MODE bit 16
+  // the multiply section in hand-scheduled assembly (isf_spconv16_mult.h) for the deep layers' 4-wave shape; kKernNoSharing
   // ("no neighbour sharing": the deep layers do not share anyway) keeps hipcc's section -- the bit-equality reference
-  constexpr bool ASMM = (MODE & (16 | 65536 | 262144)) == 0 && (RG == 2 || RG == 1) && NT == 8 && KCH == 1 &&
-                        (NW == 4 || NW == 8) && (MODE & 1) == 0;
+  constexpr bool ASMM = (MODE & (kKernNoSharing | kKernStagger | kKernTwoAhead)) == 0 && (RG == 2 || RG == 1) && NT == 8 && KCH == 1 &&
+                        (NW == 4 || NW == 8) && (MODE & kKernF16) == 0;
   using S = Conv16Smem<NT, RG, KCH, NW>;
   constexpr int NTHR = 64 * NW;
   constexpr int TM = S::TM;
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 16 ? 1 : (NT * RG >= 16 ? 2 : 3))) 
   for (int w = 0; w < NW; ++w) wg_mask |= (unsigned)misc[w];
   wg_mask = __builtin_amdgcn_readfirstlane(wg_mask);
   const int ntaps = __popc(wg_mask);
-  static_assert(!KSPLIT || (NCG % 2 == 0 && (MODE & (512 | 262144)) == 0), "chunk split: even chunk-group count, no trace / A2 loop");
+  static_assert(!KSPLIT || (NCG % 2 == 0 && (MODE & (kKernTrace | kKernTwoAhead)) == 0), "chunk split: even chunk-group count, no trace / A2 loop");
   const int nsteps = NOLOOP ? 0 : ntaps * (KSPLIT ? NCG / 2 : NCG);
   if (TRACE) t_pro = wall_clock64();
 
@@ -278,7 +279,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 16 ? 1 : (NT * RG >= 16 ? 2 : 3))) 
   };
   const unsigned bbuf_addr = __builtin_amdgcn_readfirstlane(lds_addr(bbuf));
   constexpr int PW = NT * 128 / NW;                       // 16-byte weight pieces per wave and step (KCH = 1)
-  constexpr bool RUNS = (MODE & 131072) == 0 && KCH == 1 && !NODMA && (HALF ? (PW == 128 || PW == 256)
+  constexpr bool RUNS = (MODE & kKernR4Issue) == 0 && KCH == 1 && !NODMA && (HALF ? (PW == 128 || PW == 256)
                                                                                  : (PW == 64 || PW == 128 || PW == 256));
   auto stage_B = [&](int tap, int cg, int buf) {
     if constexpr (RUNS) {   // this wave's share as ONE contiguous run: one M0 set-up, PW / 64 loads (glds16_run)
@@ -516,7 +517,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 16 ? 1 : (NT * RG >= 16 ? 2 : 3))) 
       }
     };
     if (STAG) {
-      // STAGGERED issue phases (MODE bit 65536, round 5): the barrier releases all waves into their issue phase at once
+      // STAGGERED issue phases (kKernStagger, round 5): the barrier releases all waves into their issue phase at once
       // and a gather costs the CU's address path 64 cycles -- the burst, not the average load, is what a wave waits out
       // (profiles/r05_att_256.txt: 31 % of the loop).  Every wave queues its weight pieces first (the others need them
       // at the next barrier); the first half of the workgroup's waves then gathers and multiplies as before, the second
@@ -533,7 +534,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 16 ? 1 : (NT * RG >= 16 ? 2 : 3))) 
       if (more && late) load_A(cur.tap, cur.ch, cur.ch == ch ? tap : -1);
       if (PHASE) ph_issue = (unsigned)shader_clock64();
       multiply(KCH * NT / 2, KCH * NT);
-    } else if (PHASE && !SHARE && (NW != 4 || (MODE & 131072) != 0)) {
+    } else if (PHASE && !SHARE && (NW != 4 || (MODE & kKernR4Issue) != 0)) {
       // the same issue phase in three stamped pieces: index reads from LDS (+ their wait) | the gathers | the weight DMA
       if (s + 1 < nsteps) {
         advance(cur);
@@ -565,7 +566,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 16 ? 1 : (NT * RG >= 16 ? 2 : 3))) 
       }
       ph_issue = (unsigned)shader_clock64();
       multiply(0, KCH * NT);
-    } else if (!SHARE && (MODE & 131072) == 0 && NW == 4) {   // (8-wave workgroups: the two extra registers cost a wave)
+    } else if (!SHARE && (MODE & kKernR4Issue) == 0 && NW == 4) {   // (8-wave workgroups: the two extra registers cost a wave)
       // deep layers (no neighbour sharing): the row indices of the NEXT step's gathers were read from the LDS table one
       // step ago (idx_pre) -- the phase trace put the index ds_reads + their wait at 230 exposed cycles per step
       // (profiles/r05_att_256_v2.txt) -- and this step ends by reading the ones of the step after next
@@ -800,7 +801,7 @@ static int launch16(bool balance, bool table /* `order` is a tile table (conv16_
   float* ks_scratch = nullptr;
   unsigned* ks_count = nullptr;
   int grid = conv16_grid_blocks(plan);
-  if constexpr ((MODE & 524288) != 0) {   // chunk split: two workgroups per tile, their exchange buffers from the workspace
+  if constexpr ((MODE & kKernChunkSplit) != 0) {   // chunk split: two workgroups per tile, their exchange buffers from the workspace
     ISF_TRY(ksplit_buffers(arena_for_stream(st), (size_t)grid * 2 * NW * RG * NT * 1024, grid, &ks_scratch, &ks_count, st));
     grid *= 2;
   }
@@ -842,70 +843,71 @@ static int launch16_rows(int mode, const uint4* xs, const uint4* wpk, const floa
                          const int32_t* nbr, int nbr_stride, int n_out, const float* scale, const float* shift,
                          const uint4* residual, int relu, uint4* ys, hipStream_t st, const int32_t* order,
                          Conv16LaunchInfo* query, const int32_t* rowmap = nullptr) {
-  // mode bit 64 (A/B): the 128-column layers of the large levels on the 4-wave 128-row tile instead of the 8-wave 256-row one
-  const bool narrow_tiles = (mode & 64) != 0;
-  mode &= ~64;
-  // mode bit 32768 (opt-in, bit-identical, measured 8 % slower: profiles/r06_deep.txt): the deep layers' 4-wave launches on
+  // kConvModeNarrowTiles (A/B): the 128-column layers of the large levels on the 4-wave 128-row tile instead of the 8-wave 256-row one
+  const bool narrow_tiles = (mode & kConvModeNarrowTiles) != 0;
+  mode &= ~kConvModeNarrowTiles;
+  // ISF_CONV_MODE_DEEP (opt-in, bit-identical, measured 8 % slower: profiles/r06_deep.txt): the deep layers' 4-wave launches on
   // isf_spconv_deep.hip (LDS-DMA gathers + one instruction stream per step)
-  const bool use_deep = (mode & 32768) != 0;
-  mode &= ~32768;
-#define ISF_ARGS16 (mode & 32) == 0, (mode & 1024) != 0 && order != nullptr, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, nullptr, rowmap
-  // mode bits 4096 / 8192 (round 5 experiment, valid results, bit-identical): the 256-COLUMN layers as ONE column block
+  const bool use_deep = (mode & ISF_CONV_MODE_DEEP) != 0;
+  mode &= ~ISF_CONV_MODE_DEEP;
+#define ISF_ARGS16 (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, (mode & kConvModeTileTable) != 0 && order != nullptr, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, nullptr, rowmap
+  // ISF_CONV_MODE_ONE_BLOCK_4W / _8W (round 5 experiment, valid results, bit-identical): the 256-COLUMN layers as ONE column block
   // -- a workgroup owns all 256 output columns of its rows, so a row is gathered ONCE per tap and chunk instead of once per
   // column block.  The phase trace (profiles/r05_att_256.txt) shows the step bound by the vector-memory issue path (a
   // gather in the MFMA operand layout costs 64 address cycles, 12 resident waves x (3 gathers + 4 weight DMA pieces) =
-  // the step time): per MFMA this halves the gather instructions.  4096: 4 waves x 32 rows (two workgroups per CU:
-  // 64 KiB weight stage); 8192: 8 waves x 16 rows.  Tile-order tables belong to the two-block launch plan: ignored.
-  // mode bit 524288: CHUNK SPLIT for the 256-column layers (see the kernel); the workgroup shape follows the small-launch
+  // the step time): per MFMA this halves the gather instructions.  _4W: 4 waves x 32 rows (two workgroups per CU:
+  // 64 KiB weight stage); _8W: 8 waves x 16 rows.  Tile-order tables belong to the two-block launch plan: ignored.
+  // ISF_CONV_MODE_CHUNK_SPLIT: CHUNK SPLIT for the 256-column layers (see the kernel); the workgroup shape follows the small-launch
   // rule below (the choice does not change the arithmetic); other shapes / modes ignore the bit
   if constexpr (NT == 8 && CIN >= 128) {
-    if ((mode & 524288) && cout == 256 && (mode & ~(32 | 1024 | 524288)) == 0) {
-      if (n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4, 524288>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, 524288>(ISF_ARGS16);
+    if ((mode & ISF_CONV_MODE_CHUNK_SPLIT) && cout == 256 && (mode & ~(kConvModeTileBits | ISF_CONV_MODE_CHUNK_SPLIT)) == 0) {
+      if (n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4, kKernChunkSplit>(ISF_ARGS16);
+      return launch16<CIN, NT, 2, 4, kKernChunkSplit>(ISF_ARGS16);
     }
   }
-  mode &= ~524288;
+  mode &= ~ISF_CONV_MODE_CHUNK_SPLIT;
   if constexpr (NT == 8 && CIN >= 128) {
-    if ((mode & (4096 | 8192)) && cout == 256 && (mode & ~(32 | 1024 | 4096 | 8192)) == 0 && !rowmap) {
-      if (mode & 8192)
+    constexpr int one_block = ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W;
+    if ((mode & one_block) && cout == 256 && (mode & ~(kConvModeTileBits | one_block)) == 0 && !rowmap) {
+      if (mode & ISF_CONV_MODE_ONE_BLOCK_8W)
         return launch16<CIN, 16, 1, 8>(false, false, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual,
                                        relu, ys, st, nullptr, query);
-      return launch16<CIN, 16, 2, 4>((mode & 32) == 0, false, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift,
+      return launch16<CIN, 16, 2, 4>((mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, false, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift,
                                      residual, relu, ys, st, nullptr, query);
     }
   }
-  mode &= ~(4096 | 8192);
-  if constexpr (NT == 8 && CIN >= 128) {   // mode bit 262144: gathered rows two steps ahead (A2 loop; 4-wave shapes)
-    if ((mode & ~(32 | 1024)) == 262144 && !(cout == 128 && n_out >= 8 * 256)) return launch16<CIN, NT, 2, 4, 262144>(ISF_ARGS16);
+  mode &= ~(ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W);
+  if constexpr (NT == 8 && CIN >= 128) {   // ISF_CONV_MODE_TWO_AHEAD: gathered rows two steps ahead (A2 loop; 4-wave shapes)
+    if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_TWO_AHEAD && !(cout == 128 && n_out >= 8 * 256)) return launch16<CIN, NT, 2, 4, kKernTwoAhead>(ISF_ARGS16);
   }
-  mode &= ~262144;
-  if constexpr (NT == 8) {   // mode bit 131072: round 4's issue phase (index reads in the step, four separate DMA pieces): A/B
-    if ((mode & ~(32 | 1024)) == 131072) {
-      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, 131072>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, 131072>(ISF_ARGS16);
+  mode &= ~ISF_CONV_MODE_TWO_AHEAD;
+  if constexpr (NT == 8) {   // ISF_CONV_MODE_R4_ISSUE: round 4's issue phase (index reads in the step, four separate DMA pieces): A/B
+    if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_R4_ISSUE) {
+      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, kKernR4Issue>(ISF_ARGS16);
+      return launch16<CIN, NT, 2, 4, kKernR4Issue>(ISF_ARGS16);
     }
   }
-  mode &= ~131072;
-  if constexpr (NT == 8) {   // mode bit 65536: staggered issue phases (deep layers; valid results, bit-identical)
-    if ((mode & ~(32 | 1024)) == 65536) {
-      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, 65536>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, 65536>(ISF_ARGS16);
+  mode &= ~ISF_CONV_MODE_R4_ISSUE;
+  if constexpr (NT == 8) {   // ISF_CONV_MODE_STAGGER: staggered issue phases (deep layers; valid results, bit-identical)
+    if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_STAGGER) {
+      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, kKernStagger>(ISF_ARGS16);
+      return launch16<CIN, NT, 2, 4, kKernStagger>(ISF_ARGS16);
     }
   }
-  mode &= ~65536;
-  switch (mode & ~(32 | 1024)) {   // single-pass f16 (opt-in) and the timing diagnostics run on the 4-wave shape
+  mode &= ~ISF_CONV_MODE_STAGGER;
+  switch (mode & ~kConvModeTileBits) {   // single-pass f16 (opt-in) and the timing diagnostics run on the 4-wave shape
     case 0: break;
-    case 1: return launch16<CIN, NT, 2, 4, 1>(ISF_ARGS16);
-    case 2: return launch16<CIN, NT, 2, 4, 2>(ISF_ARGS16);
-    case 4: return launch16<CIN, NT, 2, 4, 4>(ISF_ARGS16);
-    case 6: return launch16<CIN, NT, 2, 4, 6>(ISF_ARGS16);
-    case 8: return launch16<CIN, NT, 2, 4, 8>(ISF_ARGS16);
-    case 257:   // f16 storage (+ single-pass f16 arithmetic), production workgroup shapes
-      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, 257>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, 257>(ISF_ARGS16);
-    case 16:   // no neighbour sharing, production workgroup shapes
-      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, 16>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, 16>(ISF_ARGS16);
+    case ISF_CONV_MODE_F16: return launch16<CIN, NT, 2, 4, kKernF16>(ISF_ARGS16);
+    case ISF_CONV_MODE_NO_GATHER: return launch16<CIN, NT, 2, 4, kKernNoGather>(ISF_ARGS16);
+    case ISF_CONV_MODE_NO_WEIGHTS: return launch16<CIN, NT, 2, 4, kKernNoWeights>(ISF_ARGS16);
+    case ISF_CONV_MODE_NO_GATHER | ISF_CONV_MODE_NO_WEIGHTS: return launch16<CIN, NT, 2, 4, kKernNoGather | kKernNoWeights>(ISF_ARGS16);
+    case ISF_CONV_MODE_NO_LOOP: return launch16<CIN, NT, 2, 4, kKernNoLoop>(ISF_ARGS16);
+    case ISF_CONV_MODE_F16_STORAGE:   // f16 storage (+ single-pass f16 arithmetic), production workgroup shapes
+      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, kKernF16Rows | kKernF16>(ISF_ARGS16);
+      return launch16<CIN, NT, 2, 4, kKernF16Rows | kKernF16>(ISF_ARGS16);
+    case ISF_CONV_MODE_NO_SHARING:   // no neighbour sharing, production workgroup shapes
+      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, kKernNoSharing>(ISF_ARGS16);
+      return launch16<CIN, NT, 2, 4, kKernNoSharing>(ISF_ARGS16);
     default:
       ISF_REQUIRE(false, ISF_ERR_ARG, "sparse_conv16: mode %d (single-pass precision and the diagnostics {2,4,6,8} "
                   "are not combinable)", mode);
@@ -919,8 +921,8 @@ static int launch16_rows(int mode, const uint4* xs, const uint4* wpk, const floa
     if (cout == 256 && n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4>(ISF_ARGS16);
   }
   if constexpr (NT == 8 && CIN >= 128) {
-    if (use_deep && !rowmap && (mode & ~(32 | 1024)) == 0 && sparse_conv_deep_supported(CIN, cout))
-      return sparse_conv_forward_deep_impl((mode & 32) == 0, (mode & 1024) != 0 && order != nullptr, xs, CIN, wpk, winv, K, cout,
+    if (use_deep && !rowmap && (mode & ~kConvModeTileBits) == 0 && sparse_conv_deep_supported(CIN, cout))
+      return sparse_conv_forward_deep_impl((mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, (mode & kConvModeTileTable) != 0 && order != nullptr, xs, CIN, wpk, winv, K, cout,
                                            nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query);
   }
   return launch16<CIN, NT, 2, 4>(ISF_ARGS16);
@@ -1000,12 +1002,12 @@ int sparse_conv_trace_impl(const void* xs, int c_in, const void* packed16, int K
       if (pass == 1)
         ISF_REQUIRE((size_t)8 * (info.full + info.half) * (64 + (size_t)nw * (kPhaseHdr + kPhaseStep * kPhaseMaxSteps) * 4) <=
                         phase_capacity_bytes, ISF_ERR_ARG, "sparse_conv_phase_trace: trace buffer too small");
-      if (c_in == 256) rc = launch16<256, 8, 2, 4, 512 | 2048>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-      else if (wide) rc = launch16<128, 8, 2, 8, 512 | 2048>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-      else rc = launch16<128, 8, 2, 4, 512 | 2048>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-    } else if (c_in == 256) rc = launch16<256, 8, 2, 4, 512>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-    else if (wide) rc = launch16<128, 8, 2, 8, 512>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-    else rc = launch16<128, 8, 2, 4, 512>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
+      if (c_in == 256) rc = launch16<256, 8, 2, 4, kKernTrace | kKernPhaseTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
+      else if (wide) rc = launch16<128, 8, 2, 8, kKernTrace | kKernPhaseTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
+      else rc = launch16<128, 8, 2, 4, kKernTrace | kKernPhaseTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
+    } else if (c_in == 256) rc = launch16<256, 8, 2, 4, kKernTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
+    else if (wide) rc = launch16<128, 8, 2, 8, kKernTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
+    else rc = launch16<128, 8, 2, 4, kKernTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
     ISF_TRY(rc);
   }
   *grid_blocks = 8 * (info.full + info.half);
@@ -1414,9 +1416,8 @@ int isf_sparse_conv_forward_f16x3(const void* features_split, int num_in, int c_
   if (num_out == 0) return ISF_OK;
   ISF_REQUIRE(features_split && packed16 && nbr && out_split && ((scale == nullptr) == (shift == nullptr)),
               ISF_ERR_ARG, "sparse_conv_forward_f16x3: null pointer");
-  const int m = mode & ~(32 | 64 | 4096 | 8192 | 32768 | 65536 | 131072 | 262144 | 524288);   // bit 32 = uniform tiles (no full / half mix), combinable; 524288 = chunk split (256-column layers); 4096 / 8192 = one
-                                               // column block for the 256-column layers (4 x 32-row / 8 x 16-row waves)
-  ISF_REQUIRE(mode >= 0 && (m == 0 || m == 1 || m == 2 || m == 4 || m == 6 || m == 8 || m == 16 || m == 257), ISF_ERR_ARG,
+  const int m = mode & ~isf::kConvOptsForward;
+  ISF_REQUIRE(mode >= 0 && (isf::conv_mode_is_production(m) || isf::conv_mode_is_knockout(m)), ISF_ERR_ARG,
               "sparse_conv_forward_f16x3: mode %d (0 default, 1 single-pass f16, 257 f16 storage, diagnostics 2 / 4 / 6 / "
               "8 / 16, +32)", mode);
   return isf::sparse_conv_forward_f16x3_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride,
@@ -1432,11 +1433,11 @@ int isf_sparse_conv_tile_order(const int32_t* nbr, int nbr_stride, int num_taps,
   ISF_REQUIRE(isf::sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
               "sparse_conv_tile_order: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
   isf::Conv16LaunchInfo info;
-  if (mode & 2048) {   // the table is for isf_sparse_conv_forward_dma: its launch plan differs (workgroups per CU)
+  if (mode & ISF_CONV_MODE_DMA_PLAN) {   // the table is for isf_sparse_conv_forward_dma: its launch plan differs (workgroups per CU)
     ISF_REQUIRE(isf::sparse_conv_dma_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
                 "sparse_conv_tile_order: (Cin,Cout)=(%d,%d) has no LDS-DMA kernel", c_in, c_out);
     ISF_TRY(isf::sparse_conv_forward_dma_impl(nullptr, c_in, nullptr, num_taps, c_out, nbr, nbr_stride, num_out, nullptr,
-                                              nullptr, nullptr, 0, nullptr, mode & ~2048, isf::as_stream(stream), nullptr,
+                                              nullptr, nullptr, 0, nullptr, mode & ~ISF_CONV_MODE_DMA_PLAN, isf::as_stream(stream), nullptr,
                                               &info));
   } else {
     ISF_TRY(isf::sparse_conv_forward_f16x3_impl(nullptr, c_in, nullptr, num_taps, c_out, nbr, nbr_stride, num_out, nullptr,
@@ -1456,8 +1457,7 @@ int isf_sparse_conv_forward_f16x3_ordered(const void* features_split, int num_in
   if (num_out == 0) return ISF_OK;
   ISF_REQUIRE(features_split && packed16 && nbr && out_split && ((scale == nullptr) == (shift == nullptr)),
               ISF_ERR_ARG, "sparse_conv_forward_f16x3_ordered: null pointer");
-  const int m = mode & ~(32 | 65536 | 131072 | 262144 | 524288);
-  ISF_REQUIRE(mode >= 0 && (m == 0 || m == 1 || m == 16 || m == 257), ISF_ERR_ARG,
+  ISF_REQUIRE(mode >= 0 && isf::conv_mode_is_production(mode & ~isf::kConvOptsOrdered), ISF_ERR_ARG,
               "sparse_conv_forward_f16x3_ordered: mode %d (0, 1, 16, 257, +32, +65536, +131072)", mode);
   return isf::sparse_conv_forward_f16x3_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride,
                                              num_out, scale, shift, residual_split, relu, out_split, mode,
@@ -1471,7 +1471,7 @@ int isf_sparse_conv_tile_table(const int32_t* nbr, int nbr_stride, int num_taps,
   if (num_out == 0) return ISF_OK;
   ISF_REQUIRE(isf::sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
               "sparse_conv_tile_table: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
-  ISF_REQUIRE(mode == 0 || mode == 1 || mode == 16 || mode == 257, ISF_ERR_ARG, "sparse_conv_tile_table: mode %d", mode);
+  ISF_REQUIRE(isf::conv_mode_is_production(mode & ~isf::kConvOptsTiled), ISF_ERR_ARG, "sparse_conv_tile_table: mode %d", mode);
   isf::Conv16LaunchInfo info;   // the workgroup shape, and with it the table, depends on the mode
   ISF_TRY(isf::sparse_conv_forward_f16x3_impl(nullptr, c_in, nullptr, num_taps, c_out, nbr, nbr_stride, num_out, nullptr,
                                               nullptr, nullptr, 0, nullptr, mode, isf::as_stream(stream), nullptr, &info));
@@ -1496,10 +1496,10 @@ int isf_sparse_conv_forward_f16x3_tiled(const void* features_split, int num_in, 
   if (num_out == 0) return ISF_OK;
   ISF_REQUIRE(features_split && packed16 && nbr && out_split && ((scale == nullptr) == (shift == nullptr)),
               ISF_ERR_ARG, "sparse_conv_forward_f16x3_tiled: null pointer");
-  ISF_REQUIRE(mode == 0 || mode == 1 || mode == 16 || mode == 257, ISF_ERR_ARG,
+  ISF_REQUIRE(isf::conv_mode_is_production(mode & ~isf::kConvOptsTiled), ISF_ERR_ARG,
               "sparse_conv_forward_f16x3_tiled: mode %d (0, 1, 16, 257)", mode);
   return isf::sparse_conv_forward_f16x3_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out,
-                                             scale, shift, residual_split, relu, out_split, mode | 1024,
+                                             scale, shift, residual_split, relu, out_split, mode | isf::kConvModeTileTable,
                                              isf::as_stream(stream), table);
 }
 

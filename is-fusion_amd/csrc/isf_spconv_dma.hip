@@ -62,7 +62,7 @@ struct ConvDmaSmem {
   static constexpr int bytes = main_bytes > epi_bytes ? main_bytes : epi_bytes;   // wave masks overlay the weight stage
 };
 
-// MODE: bit 1 = single-pass f16 (hi halves only), bit 256 (with 1) = f16 storage -- as in spconv_f16x3_kernel
+// MODE: kKernF16 = single-pass f16 (hi halves only), kKernF16Rows (with kKernF16) = f16 storage -- as in spconv_f16x3_kernel
 // LINES: the neighbour table comes LINE-COMPRESSED (isf_rulebook.hip): `nbr` = lines [K / nx][nbr_stride] (row of the
 // first present neighbour of a (kz, ky) line), `lmask` [nbr_stride] (bit k: tap k present); a lane keeps its rows' masks
 // in registers and loads one int32 per LINE (one line ahead) instead of one per tap; the prologue reads one word per row
@@ -75,8 +75,8 @@ __global__ __launch_bounds__(64 * NW) void spconv_dma_kernel(
     const float* __restrict__ shift, const uint4* __restrict__ residual, uint4* __restrict__ ys, int n_out, int relu,
     Conv16Plan plan, const int32_t* __restrict__ order,
     const int32_t* __restrict__ rowmap /* nullptr | sorted launch: position -> output row (conv_row_sort_impl) */,
-    long long* __restrict__ trace /* MODE bit 512: kDmaTraceWords int64 per workgroup (isf_sparse_conv_dma_trace) */) {
-  constexpr bool HALF = (MODE & 1) != 0, F16IO = (MODE & 256) != 0, TRACE = (MODE & 512) != 0;
+    long long* __restrict__ trace /* MODE bit kKernTrace: kDmaTraceWords int64 per workgroup (isf_sparse_conv_dma_trace) */) {
+  constexpr bool HALF = (MODE & kKernF16) != 0, F16IO = (MODE & kKernF16Rows) != 0, TRACE = (MODE & kKernTrace) != 0;
   // TRACE (diagnostic instantiations only): constant-clock stamps at entry / after the prologue / after the loop / at
   // exit, and wave 0's shader-clock account of the loop: cycles at the per-step vmcnt(0), at the barrier, in the section
   // that reads the transit / weights and issues the next step's loads, in the multiply section
@@ -420,21 +420,21 @@ static int dispatch_dma(int mode, const uint4* xs, const uint4* wpk, const float
                         const int32_t* nbr, const uint32_t* lmask, int nx, int nbr_stride, int n_out, const float* scale,
                         const float* shift, const uint4* residual, int relu, uint4* ys, hipStream_t st,
                         const int32_t* order, Conv16LaunchInfo* query, const int32_t* rowmap, long long* trace) {
-  const bool balance = (mode & 32) == 0;
+  const bool balance = (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0;
 #define ISF_ARGS_DMA balance, xs, wpk, winv, K, cout, nbr, lmask, nx, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, rowmap, trace
   if (lmask) {
-    switch (mode & ~32) {
-      case 512: return launch_dma<CIN, NT, 512, true>(ISF_ARGS_DMA);   // trace (isf_sparse_conv_dma_trace)
+    switch (mode & ~kConvOptsDma) {
+      case kKernTrace: return launch_dma<CIN, NT, kKernTrace, true>(ISF_ARGS_DMA);   // isf_sparse_conv_dma_trace hands the kernel's bit over as a mode
       case 0: return launch_dma<CIN, NT, 0, true>(ISF_ARGS_DMA);
-      case 1: return launch_dma<CIN, NT, 1, true>(ISF_ARGS_DMA);
-      case 257: return launch_dma<CIN, NT, 257, true>(ISF_ARGS_DMA);
+      case ISF_CONV_MODE_F16: return launch_dma<CIN, NT, kKernF16, true>(ISF_ARGS_DMA);
+      case ISF_CONV_MODE_F16_STORAGE: return launch_dma<CIN, NT, kKernF16Rows | kKernF16, true>(ISF_ARGS_DMA);
     }
   } else {
-    switch (mode & ~32) {
-      case 512: return launch_dma<CIN, NT, 512, false>(ISF_ARGS_DMA);
+    switch (mode & ~kConvOptsDma) {
+      case kKernTrace: return launch_dma<CIN, NT, kKernTrace, false>(ISF_ARGS_DMA);
       case 0: return launch_dma<CIN, NT, 0, false>(ISF_ARGS_DMA);
-      case 1: return launch_dma<CIN, NT, 1, false>(ISF_ARGS_DMA);
-      case 257: return launch_dma<CIN, NT, 257, false>(ISF_ARGS_DMA);
+      case ISF_CONV_MODE_F16: return launch_dma<CIN, NT, kKernF16, false>(ISF_ARGS_DMA);
+      case ISF_CONV_MODE_F16_STORAGE: return launch_dma<CIN, NT, kKernF16Rows | kKernF16, false>(ISF_ARGS_DMA);
     }
   }
 #undef ISF_ARGS_DMA
@@ -509,7 +509,7 @@ int isf_sparse_conv_dma_trace(const void* features_split, int num_in, int c_in, 
               "sparse_conv_dma_trace: bad arguments");
   isf::Conv16LaunchInfo info;
   ISF_TRY(isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out,
-                                            scale, shift, residual_split, relu, out_split, 512, isf::as_stream(stream),
+                                            scale, shift, residual_split, relu, out_split, isf::kKernTrace, isf::as_stream(stream),
                                             nullptr, &info, mask, taps_per_line, nullptr, nullptr));
   const int blocks = 8 * (info.full + (info.half < 0 ? 0 : info.half));   // conv16_grid_blocks
   ISF_REQUIRE(blocks <= trace_capacity_blocks, ISF_ERR_ARG,
@@ -517,7 +517,7 @@ int isf_sparse_conv_dma_trace(const void* features_split, int num_in, int c_in, 
               trace_capacity_blocks);
   *grid_blocks = blocks;
   return isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out,
-                                           scale, shift, residual_split, relu, out_split, 512, isf::as_stream(stream),
+                                           scale, shift, residual_split, relu, out_split, isf::kKernTrace, isf::as_stream(stream),
                                            nullptr, nullptr, mask, taps_per_line, nullptr, trace);
 }
 

@@ -49,7 +49,7 @@ struct StageSmem {
   static constexpr size_t bytes(int cap_rows) { return (size_t)fixed_bytes + (size_t)cap_rows * KCH * 128; }
 };
 
-// MODE bit 1: single-pass f16 (hi halves only), as in spconv_f16x3_kernel.
+// MODE bit kKernF16: single-pass f16 (hi halves only), as in spconv_f16x3_kernel.
 template <int CIN, int NT, int RG, int NW, int MODE = 0>
 __global__ __launch_bounds__(64 * NW, (NW >= 8 ? 1 : 2)) void spconv_staged_kernel(
     const uint4* __restrict__ xs, const uint16_t* __restrict__ slots, int nbr_stride,
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(64 * NW, (NW >= 8 ? 1 : 2)) void spconv_staged_kern
     const float* __restrict__ w_inv_scale, int K, int cout, const float* __restrict__ scale,
     const float* __restrict__ shift, const uint4* __restrict__ residual, uint4* __restrict__ ys, int n_out, int relu,
     Conv16Plan plan, int cap_rows) {
-  constexpr bool HALF = (MODE & 1) != 0;
+  constexpr bool HALF = (MODE & kKernF16) != 0;
   constexpr int KCH = Conv16Step<CIN, NT>::KCH;
   using S = StageSmem<NT, RG, KCH, NW>;
   constexpr int NTHR = 64 * NW;
@@ -506,11 +506,11 @@ static int launch_staged_rows(int mode, int cap_rows, const uint4* xs, const uin
                               int cout, const uint16_t* slots, int nbr_stride, const int32_t* ulist,
                               const int32_t* ucount, int n_out, const float* scale, const float* shift,
                               const uint4* residual, int relu, uint4* ys, hipStream_t st) {
-#define ISF_ARGS_ST (mode & 32) == 0, cap_rows, xs, wpk, winv, K, cout, slots, nbr_stride, ulist, ucount, n_out, scale, shift, residual, relu, ys, st
+#define ISF_ARGS_ST (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, cap_rows, xs, wpk, winv, K, cout, slots, nbr_stride, ulist, ucount, n_out, scale, shift, residual, relu, ys, st
   const bool wide = NT == 8 && cout == 128 && n_out >= 8 * 256;   // the 8-wave shape of launch16_rows
-  if ((mode & ~32) == 1) {
-    if (wide) return launch_staged<CIN, (NT == 8 ? NT : 2), 2, 8, 1>(ISF_ARGS_ST);
-    return launch_staged<CIN, NT, 2, 4, 1>(ISF_ARGS_ST);
+  if ((mode & ~kConvOptsStaged) == ISF_CONV_MODE_F16) {
+    if (wide) return launch_staged<CIN, (NT == 8 ? NT : 2), 2, 8, kKernF16>(ISF_ARGS_ST);
+    return launch_staged<CIN, NT, 2, 4, kKernF16>(ISF_ARGS_ST);
   }
   if (wide) return launch_staged<CIN, (NT == 8 ? NT : 2), 2, 8, 0>(ISF_ARGS_ST);
   return launch_staged<CIN, NT, 2, 4, 0>(ISF_ARGS_ST);
@@ -541,8 +541,8 @@ int sparse_conv_forward_staged_impl(const void* xs, int c_in, const void* packed
   ISF_REQUIRE(sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
               "sparse_conv_staged: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
   ISF_REQUIRE(nbr_stride % 128 == 0 && nbr_stride >= n_out, ISF_ERR_ARG, "sparse_conv_staged: bad nbr_stride");
-  const int m = mode & ~32;
-  ISF_REQUIRE(m == 0 || m == 1, ISF_ERR_ARG, "sparse_conv_staged: mode %d (0 split precision, 1 single-pass f16, +32)", mode);
+  const int m = mode & ~kConvOptsStaged;
+  ISF_REQUIRE(m == 0 || m == ISF_CONV_MODE_F16, ISF_ERR_ARG, "sparse_conv_staged: mode %d (0 split precision, 1 single-pass f16, +32)", mode);
   const uint4* w = reinterpret_cast<const uint4*>(packed16);
   const float* winv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed16) +
                                                      (size_t)K * c_in * c_out * 4);

@@ -500,11 +500,11 @@ int isf_sparse_conv_backward_filter_f16x3(const void* features_split, int num_in
                                           int capacity, int num_taps, const float* grad_inv_scale, float* grad_filters,
                                           int mode, isf_stream_t stream) {
   using namespace isf;
-  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && num_taps > 0 && grad_filters && mode >= 0 && mode <= 3, ISF_ERR_ARG,
+  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && num_taps > 0 && grad_filters && mode >= 0 && mode <= (ISF_WGRAD_F16 | ISF_WGRAD_FULL_TAPS), ISF_ERR_ARG,
               "sparse_conv_backward_filter_f16x3: bad arguments (mode 0 = f16x3 split, 1 = single-pass f16, +2 = every tap "
               "list is full (dense grid): larger chunks)");
-  const bool full_taps = (mode & 2) != 0;
-  mode &= 1;
+  const bool full_taps = (mode & ISF_WGRAD_FULL_TAPS) != 0;
+  mode &= ISF_WGRAD_F16;
   ISF_REQUIRE(sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
               "sparse_conv_backward_filter_f16x3: (Cin,Cout)=(%d,%d) not built (32 / 64 / 128 / 256)", c_in, c_out);
   hipStream_t st = as_stream(stream);
@@ -539,7 +539,7 @@ int isf_sparse_conv_backward_filter_f16x3(const void* features_split, int num_in
   int rc = ISF_ERR_UNSUPPORTED;
 #define ISF_WG16(bm, bn, wm, wn)                                                                                       \
   if (BM == bm && BN == bn && WM == wm && WN == wn)                                                                    \
-    rc = mode == 1 ? launch_wgrad16<bm, bn, wm, wn, true>(x, c_in, g, c_out, indice_pairs, indice_num, capacity,       \
+    rc = mode == ISF_WGRAD_F16 ? launch_wgrad16<bm, bn, wm, wn, true>(x, c_in, g, c_out, indice_pairs, indice_num, capacity,       \
                                                           chunk_pairs, chunks, num_taps, partial, st)                  \
                    : launch_wgrad16<bm, bn, wm, wn, false>(x, c_in, g, c_out, indice_pairs, indice_num, capacity,      \
                                                            chunk_pairs, chunks, num_taps, partial, st)

@@ -99,7 +99,7 @@ class DenseConvFunction(torch.autograd.Function):
         _lib.require_cuda(rows, weight)
         cout = weight.shape[0]
         groups = _groups(weight, transpose)
-        mode = 1 if half else 0
+        mode = _lib.CONV_MODE_F16 if half else 0
         rows = rows.detach()
         saved = []
         out = None
@@ -132,8 +132,9 @@ class DenseConvFunction(torch.autograd.Function):
                                           (rb.num_in, c), sc[1:]) for _, c, _, pkt in groups]
             grad_rows = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
         if ctx.needs_input_grad[1]:
-            # (+2: every tap list of a dense grid is full -- larger reduction chunks, a third of the partial-sum traffic)
-            parts = [sp.sparse_conv_backward_filter_f16x3(xs, c, gs, cout, rb, sc[1:], (1, 3, 3, c, cout), mode=mode | 2)
+            # (WGRAD_FULL_TAPS: every tap list of a dense grid is full -- larger reduction chunks, a third of the partial-sum traffic)
+            parts = [sp.sparse_conv_backward_filter_f16x3(xs, c, gs, cout, rb, sc[1:], (1, 3, 3, c, cout),
+                                                          mode=(_lib.WGRAD_F16 if mode & _lib.CONV_MODE_F16 else 0) | _lib.WGRAD_FULL_TAPS)
                      for xs, (_, c, _, _) in zip(ctx.saved_tensors, groups)]
             g5 = (parts[0] if len(parts) == 1 else torch.cat(parts, 3)).view(3, 3, cin, cout)
             grad_w = (g5.permute(3, 2, 1, 0) if transpose else g5.permute(3, 2, 0, 1)).contiguous()

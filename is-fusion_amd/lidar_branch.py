@@ -132,7 +132,7 @@ class LidarBranch(nn.Module):
         (bev_split=True, inference: the same map as a list of dense_conv.SplitMap, one per 256-channel group -- the form the
         fusion encoder's convolutions read; isf_encoder_options.bev_format = 1).
         precision: 0 = f16x3 split MFMA (default, fp32-class), 1 = fp32 MFMA kernels, 2 = single-pass f16 (opt-in,
-        fp16-autocast accuracy); conv_diag: timing diagnostics of the conv kernels (results garbage except 16);
+        fp16-autocast accuracy); conv_diag: timing diagnostics of the conv kernels (_lib.ENC_DIAG_* bits; the knock-outs' results are garbage);
         stage_rows / stage_mask: LDS staging of the conv input rows (isf_encoder_options; 0 = library default)."""
         if self.training:
             return self.forward_train(points)

@@ -237,7 +237,7 @@ class SparseEncoder(nn.Module):
     def forward_fused(self, voxel_features, coors, batch_size, stats=None, time_layers=False, precision=0,
                       conv_diag=0, stage_rows=0, stage_mask=0):
         """precision: 0 = f16x3 split MFMA (default), 1 = fp32 MFMA, 2 = single-pass f16 (opt-in, fp16-autocast
-        accuracy); conv_diag: timing diagnostics of the conv kernels (include/isf_hip.h) -- per call, no global state"""
+        accuracy); conv_diag: timing diagnostics of the conv kernels (_lib.ENC_DIAG_* bits, include/isf_hip.h) -- per call, no global state"""
         _lib.require_cuda(voxel_features, coors)
         arr, n, _keep, _plan = self._c_plan()
         cd, H, W = self.out_channels_and_shape()

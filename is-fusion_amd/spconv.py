@@ -193,12 +193,22 @@ def from_half(xh, shape):
     return out
 
 
+def _is_f16_storage(mode):
+    """does this conv mode exchange plain f16 rows (ISF_CONV_MODE_F16_STORAGE, with or without uniform tiles)?"""
+    return (mode & ~_lib.CONV_MODE_UNIFORM_TILES) == _lib.CONV_MODE_F16_STORAGE
+
+
+def _is_production_mode(mode):
+    """a mode the LDS-DMA kernel and the tile-order tables exist for: split precision, single-pass f16 or f16 storage"""
+    return (mode & ~_lib.CONV_MODE_UNIFORM_TILES) in (0, _lib.CONV_MODE_F16, _lib.CONV_MODE_F16_STORAGE)
+
+
 def tile_order(rb, c_in, c_out, mode=0, dma=False):
     """int32 tile order of the launch sparse_conv_forward_f16x3 (dma=True: sparse_conv_forward_dma -- its launch plan
     differs) makes for this rulebook and channel shape (isf_sparse_conv_tile_order), or None when the launch is not a
     single resident round.  Cached on the rulebook per (shape, mode, kernel)."""
     cache = rb.__dict__.setdefault("_tile_order", {})
-    mode = int(mode) | (2048 if dma else 0)
+    mode = int(mode) | (_lib.CONV_MODE_DMA_PLAN if dma else 0)
     key = (int(c_in), int(c_out), mode)
     if key not in cache:
         lib = _lib.load()
@@ -248,10 +258,10 @@ def tile_table_host(work, part_groups, parts, cus=32, wgs_per_cu=3, groups_per_t
 
 def sparse_conv_forward_f16x3(features, packed16, K, c_in, c_out, rb, scale=None, shift=None, residual=None,
                               relu=False, mode=0, order=None, table=None):
-    """fp32 in / fp32 out convenience wrapper around the split-precision kernel (converts at both ends); mode 257 (f16
+    """fp32 in / fp32 out convenience wrapper around the split-precision kernel (converts at both ends); CONV_MODE_F16_STORAGE (f16
     storage) converts through f16 rows instead of split rows.  order: tile_order(rb, c_in, c_out, mode) or None."""
     _lib.require_cuda(features)
-    f16io = (mode & ~32) == 257
+    f16io = _is_f16_storage(mode)
     xs = to_half(features) if f16io else to_split(features)
     rs = None if residual is None else (to_half(residual) if f16io else to_split(residual))
     ys = torch.empty(rb.num_out * c_out * (2 if f16io else 4), dtype=torch.uint8, device=features.device)
@@ -274,7 +284,7 @@ def sparse_conv_forward_dma(features, packed16, K, c_in, c_out, rb, scale=None, 
     """sparse_conv_forward_f16x3 on the LDS-DMA gather kernel of the narrow layers (isf_sparse_conv_forward_dma:
     c_in, c_out in {32, 64}); bit-identical results."""
     _lib.require_cuda(features)
-    f16io = (mode & ~32) == 257
+    f16io = _is_f16_storage(mode)
     xs = to_half(features) if f16io else to_split(features)
     rs = None if residual is None else (to_half(residual) if f16io else to_split(residual))
     ys = torch.empty(rb.num_out * c_out * (2 if f16io else 4), dtype=torch.uint8, device=features.device)
@@ -314,7 +324,7 @@ def sparse_conv_forward_dma_lines(features, packed16, K, c_in, c_out, rb, scale=
                                   relu=False, mode=0, taps_per_line=3):
     """sparse_conv_forward_dma reading the line-compressed table (isf_sparse_conv_forward_dma_lines); bit-identical."""
     _lib.require_cuda(features)
-    f16io = (mode & ~32) == 257
+    f16io = _is_f16_storage(mode)
     xs = to_half(features) if f16io else to_split(features)
     rs = None if residual is None else (to_half(residual) if f16io else to_split(residual))
     ys = torch.empty(rb.num_out * c_out * (2 if f16io else 4), dtype=torch.uint8, device=features.device)
@@ -402,9 +412,9 @@ def sparse_conv_forward_best(features, packed16, K, c_in, c_out, rb, scale=None,
     """The kernel choice of isf_sparse_encoder_forward for one layer driven from Python (all choices give the same
     bits): the LDS-DMA gather kernel for the narrow shapes, the tile-order table for launches of one resident round
     (the one-workgroup-per-CU kernel of the 256-column shapes is an opt-in: measured slower)."""
-    if c_in <= 64 and c_out <= 64 and (mode & ~32) in (0, 1, 257):
+    if c_in <= 64 and c_out <= 64 and _is_production_mode(mode):
         return sparse_conv_forward_dma(features, packed16, K, c_in, c_out, rb, scale, shift, residual, relu, mode)
-    order = tile_order(rb, c_in, c_out, mode) if (mode & ~32) in (0, 1, 257) else None
+    order = tile_order(rb, c_in, c_out, mode) if _is_production_mode(mode) else None
     return sparse_conv_forward_f16x3(features, packed16, K, c_in, c_out, rb, scale, shift, residual, relu, mode, order)
 
 
@@ -528,7 +538,7 @@ def sparse_conv_split(xs, packed16, K, c_in, c_out, rb, ordered=True, mode=0):
     if not ordered:
         ys = torch.empty(rb.num_out * c_out * 4, dtype=torch.uint8, device=xs.device)
         args = (_lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, c_out, _lib.ptr(rb.nbr), rb.stride, rb.num_out,
-                None, None, None, 0, _lib.ptr(ys), int(mode))   # mode 1: single-pass f16 (hi halves only)
+                None, None, None, 0, _lib.ptr(ys), int(mode))   # CONV_MODE_F16: single-pass f16 (hi halves only)
         if c_in <= 64 and c_out <= 64:
             _lib.check(lib.isf_sparse_conv_forward_dma(*args, None, _lib.stream()), "isf_sparse_conv_forward_dma")
         else:
@@ -587,7 +597,7 @@ def from_split_scaled(xs, shape, mul):
 
 def sparse_conv_backward_filter_f16x3(xs, c_in, gs, c_out, rb, inv_scale, wshape, mode=0):
     """dW [*wshape] on the f16 matrix cores (isf_sparse_conv_backward_filter_f16x3): xs / gs split rows of the layer's
-    input / of its scaled output gradient, inv_scale a device float (1 / the gradient's scale); mode 1: single-pass f16."""
+    input / of its scaled output gradient, inv_scale a device float (1 / the gradient's scale); mode WGRAD_F16: single-pass f16."""
     pairs, num, cap = pair_lists(rb)
     K = pairs.shape[0]
     grad_w = torch.empty(wshape, dtype=torch.float32, device=xs.device)
@@ -692,7 +702,7 @@ class SparseConvFunction(torch.autograd.Function):
             # split rows once: the conv reads them, and so will dW in the backward pass (saved INSTEAD of the fp32 rows)
             xs = to_split(features)
             out = from_split(sparse_conv_split(xs, _packed_pair(weight, w, K, c_in, c_out)[0], K, c_in, c_out, rb, ordered=False,
-                                               mode=1 if half else 0), (rb.num_out, c_out))
+                                               mode=_lib.CONV_MODE_F16 if half else 0), (rb.num_out, c_out))
         elif _f16x3_shape(c_in, c_out):    # the inference kernel (f16x3 split MFMA): 3-4x the fp32-MFMA kernel's rate
             out = sparse_conv_forward_best(features, pack_filters_f16x3(w), K, c_in, c_out, rb)
         else:
@@ -726,11 +736,11 @@ class SparseConvFunction(torch.autograd.Function):
                 if rbt is None:      # cached: its tile-order tables are built once per rulebook, not once per layer
                     rbt = rb._rbt = _TransposedRulebook(nbr_t, st, rb.num_out, rb.num_in)
                 grad_in = from_split_scaled(sparse_conv_split(gs, ctx.packed_t, K, c_out, c_in, rbt, ordered=False,
-                                                              mode=1 if ctx.half else 0),
+                                                              mode=_lib.CONV_MODE_F16 if ctx.half else 0),
                                             (rb.num_in, c_in), sc[1:])
             if ctx.needs_input_grad[1]:
                 grad_w = sparse_conv_backward_filter_f16x3(features, c_in, gs, c_out, rb, sc[1:], ctx.wshape,
-                                                           mode=1 if ctx.half else 0)
+                                                           mode=_lib.WGRAD_F16 if ctx.half else 0)
             return grad_in, grad_w, None, None
         if ctx.needs_input_grad[0]:
             nbr_t, st = transposed_nbr(rb)

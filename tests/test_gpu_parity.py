@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from isfusion_amd import _lib
+
 pytestmark = pytest.mark.gpu
 
 VS = [0.075, 0.075, 0.2]
@@ -399,7 +401,7 @@ def test_staged_conv_bit_identical_to_gather_kernel(dev, cin, cout):
         res = T(rng.normal(0, 1, (rb.num_out, cout)).astype(np.float32), dev)
         p16 = sp.pack_filters_f16x3(T(w, dev))
         x = T(feats, dev)
-        for mode in (0, 1, 32):
+        for mode in (0, _lib.CONV_MODE_F16, _lib.CONV_MODE_UNIFORM_TILES):
             ref = sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, scale, shift, res, relu=True, mode=mode)
             assert ref.abs().max() > 0.5
             for rows in (32, 96, 256, 1 << 20):
@@ -558,7 +560,7 @@ def test_sparse_encoder_and_lidar_branch_vs_oracle(dev, oracle_mod):
 
 
 def test_chunk_split_of_the_256_column_layers(dev, oracle_mod):
-    """round 6 (opt-in: conv mode 524288 / encoder diagnostic 536870912; measured slower): a tile of a 256-column layer is
+    """round 6 (opt-in: CONV_MODE_CHUNK_SPLIT / ENC_DIAG_CHUNK_SPLIT; measured slower): a tile of a 256-column layer is
     computed by two workgroups, each over half of the 32-channel chunks; the second to arrive adds the other's accumulator
     tile (exchanged through system-scope stores / loads) and runs the epilogue.  Per output element the sum over chunks is
     (lower half) + (upper half) instead of one running sum: not the bits of the unsplit kernel, but deterministic (a + b ==
@@ -566,7 +568,7 @@ def test_chunk_split_of_the_256_column_layers(dev, oracle_mod):
     shapes, and as close to the oracle."""
     import isfusion_amd as m
     from isfusion_amd import spconv as sp, synthetic
-    KS = 536870912
+    KS = _lib.ENC_DIAG_CHUNK_SPLIT
     rng = np.random.default_rng(77)
     B, shape = 2, [9, 40, 36]
     for cin, cout in ((256, 256), (128, 256)):
@@ -579,10 +581,10 @@ def test_chunk_split_of_the_256_column_layers(dev, oracle_mod):
             rb = sp.build_rulebook(T(idx, dev), B, shape, [3, 3, 3], [1, 1, 1], [1, 1, 1], True)
             a = (T(feats, dev), sp.pack_filters_f16x3(T(w, dev)), 27, cin, cout, rb, T(scale, dev), T(shift, dev), T(res, dev))
             plain = sp.sparse_conv_forward_f16x3(*a, relu=True)
-            got = sp.sparse_conv_forward_f16x3(*a, relu=True, mode=524288)
+            got = sp.sparse_conv_forward_f16x3(*a, relu=True, mode=_lib.CONV_MODE_CHUNK_SPLIT)
             for _ in range(3):
-                assert torch.equal(sp.sparse_conv_forward_f16x3(*a, relu=True, mode=524288), got), (cin, cout, n)
-            assert torch.equal(sp.sparse_conv_forward_f16x3(*a, relu=True, mode=524288 + 32), got), (cin, cout, n)
+                assert torch.equal(sp.sparse_conv_forward_f16x3(*a, relu=True, mode=_lib.CONV_MODE_CHUNK_SPLIT), got), (cin, cout, n)
+            assert torch.equal(sp.sparse_conv_forward_f16x3(*a, relu=True, mode=_lib.CONV_MODE_CHUNK_SPLIT | _lib.CONV_MODE_UNIFORM_TILES), got), (cin, cout, n)
             assert (got - plain).abs().max().item() < 1e-4, (cin, cout, n)
             assert not torch.equal(got, plain)
             oidx, pairs, num = oracle_mod.get_indice_pairs(idx, B, shape, [3, 3, 3], [1, 1, 1], [1, 1, 1], subm=True)
@@ -594,7 +596,7 @@ def test_chunk_split_of_the_256_column_layers(dev, oracle_mod):
     rb = sp.build_rulebook(T(idx, dev), B, shape, [3, 3, 3], [1, 1, 1], [1, 1, 1], True)
     f = T(rng.normal(0, 1, (3000, 128)).astype(np.float32), dev)
     p = sp.pack_filters_f16x3(T(rng.normal(0, 0.05, (3, 3, 3, 128, 128)).astype(np.float32), dev))
-    assert torch.equal(sp.sparse_conv_forward_f16x3(f, p, 27, 128, 128, rb, mode=524288), sp.sparse_conv_forward_f16x3(f, p, 27, 128, 128, rb))
+    assert torch.equal(sp.sparse_conv_forward_f16x3(f, p, 27, 128, 128, rb, mode=_lib.CONV_MODE_CHUNK_SPLIT), sp.sparse_conv_forward_f16x3(f, p, 27, 128, 128, rb))
     # the LiDAR branch with the split on: repeatable; a frame alone == the frame in a batch; tile plans do not matter
     lb = m.LidarBranch().randomize_weights_(0).randomize_bn_(1).eval().to(dev)
     for n, frames in ((3000, 1), (60000, 2), (300000, 4)):
@@ -603,22 +605,22 @@ def test_chunk_split_of_the_256_column_layers(dev, oracle_mod):
         assert torch.isfinite(got).all() and got.abs().max().item() > 0.1
         assert (got - ref).abs().max().item() < 1e-4 * max(1.0, ref.abs().max().item()), n
         assert not torch.equal(got, ref), n
-        assert torch.equal(lb(pl, conv_diag=KS), got) and torch.equal(lb(pl, conv_diag=KS + 32), got), n
-        assert torch.equal(lb(pl, conv_diag=KS + 64), got), n
+        assert torch.equal(lb(pl, conv_diag=KS), got) and torch.equal(lb(pl, conv_diag=KS | _lib.ENC_DIAG_UNIFORM_TILES), got), n
+        assert torch.equal(lb(pl, conv_diag=KS | _lib.ENC_DIAG_LAUNCH_ORDER), got), n
         assert torch.equal(lb(pl[:1], conv_diag=KS)[0], got[0]), n
 
 
 def test_conv_neighbour_sharing_reproduces_full_gather_bits(dev):
     """the conv kernel takes a row's fragment from the right-hand lane's registers when the indices match instead of
     gathering it again (isf_spconv16.hip, load_A): the shared fragment is the fragment the load would have returned, so
-    the whole LiDAR branch must give the bits of the gather-everything reference (diagnostic 16 of isf_encoder_options)"""
+    the whole LiDAR branch must give the bits of the gather-everything reference (ENC_DIAG_NO_SHARING of isf_encoder_options)"""
     import isfusion_amd as m
     from isfusion_amd import synthetic
     lb = m.LidarBranch().randomize_weights_(0).randomize_bn_(1).eval().to(dev)
     for n in (30000, 120000):
         pl = [T(synthetic.lidar_sweeps(500 + i, n), dev) for i in range(2)]
         got = lb(pl)
-        want = lb(pl, conv_diag=16)
+        want = lb(pl, conv_diag=_lib.ENC_DIAG_NO_SHARING)
         assert torch.isfinite(got).all() and got.abs().max().item() > 0.5
         assert torch.equal(got, want), n
 
@@ -626,7 +628,7 @@ def test_conv_neighbour_sharing_reproduces_full_gather_bits(dev):
 def test_conv_tile_mix_reproduces_uniform_tile_bits(dev):
     """launches that fit the chip in one round of workgroups are cut into full and half-height tiles so that every SIMD
     gets the same number of 16-row groups (isf_spconv16.h, conv16_plan); a row's products and their order do not depend
-    on the tile it falls into, so the result must equal the uniform-tile kernel's (diagnostic 32) bit for bit -- from
+    on the tile it falls into, so the result must equal the uniform-tile kernel's (ENC_DIAG_UNIFORM_TILES) bit for bit -- from
     tiny inputs (half tiles only) to the full bench size (levels 3 / 4: two full + one half tile per CU)"""
     import isfusion_amd as m
     from isfusion_amd import synthetic
@@ -634,19 +636,19 @@ def test_conv_tile_mix_reproduces_uniform_tile_bits(dev):
     for n, frames in ((3000, 1), (60000, 2), (300000, 4)):
         pl = [T(synthetic.lidar_sweeps(700 + i, n), dev) for i in range(frames)]
         got = lb(pl)
-        want = lb(pl, conv_diag=32)
+        want = lb(pl, conv_diag=_lib.ENC_DIAG_UNIFORM_TILES)
         assert torch.isfinite(got).all() and got.abs().max().item() > 0.1
         assert torch.equal(got, want), n
-        assert torch.equal(lb(pl, conv_diag=48), want), n      # and without neighbour sharing
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_NO_SHARING | _lib.ENC_DIAG_UNIFORM_TILES), want), n      # and without neighbour sharing
         # round 6: the deep SubM layers compute their rows in the order of their tap masks (conv_row_sort_impl: a tile / a
         # 16-row group of like rows walks fewer taps); every row still gets the same products in the same order, so the
-        # un-sorted launch (diagnostic 33554432) gives the same bits
-        assert torch.equal(lb(pl, conv_diag=33554432), want), n
-        assert torch.equal(lb(pl, precision=2), lb(pl, precision=2, conv_diag=33554432)), n    # f16 storage: sorted too
-        assert torch.equal(lb(pl, conv_diag=67108864), want), n     # the narrow layers sorted as well (opt-in)
-        # round 6 (opt-in, diagnostic 16777216): the launches of several rounds (levels 0 / 1) hand their tiles out band by
+        # un-sorted launch (ENC_DIAG_NO_ROW_SORT) gives the same bits
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_NO_ROW_SORT), want), n
+        assert torch.equal(lb(pl, precision=2), lb(pl, precision=2, conv_diag=_lib.ENC_DIAG_NO_ROW_SORT)), n    # f16 storage: sorted too
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_NARROW_ROW_SORT), want), n     # the narrow layers sorted as well (opt-in)
+        # round 6 (opt-in, ENC_DIAG_BAND_ORDER): the launches of several rounds (levels 0 / 1) hand their tiles out band by
         # band in y (conv16_band_order_kernel) -- a permutation of the same tiles
-        assert torch.equal(lb(pl, conv_diag=16777216), want), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_BAND_ORDER), want), n
 
 
 @pytest.mark.parametrize("cin,cout", [(256, 256), (128, 256), (128, 128)])
@@ -671,21 +673,21 @@ def test_conv_assembly_multiply_section_reproduces_the_compiler_bits(dev, cin, c
             sh = T(rng.normal(0, 0.2, cout).astype(np.float32), dev)
             p16 = sp.pack_filters_f16x3(w)
             got = sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, sc, sh, res, relu=True)
-            ref = sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=16)
+            ref = sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=_lib.CONV_MODE_NO_SHARING)
             assert ref.abs().max() > 0.5 and torch.equal(got, ref), (n, subm)
             assert torch.equal(sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb),
-                               sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, mode=16)), (n, subm)
-            # mode 32768: the deep layers on isf_spconv_deep.hip (LDS-DMA gathers, a step's products and the next step's
+                               sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, mode=_lib.CONV_MODE_NO_SHARING)), (n, subm)
+            # CONV_MODE_DEEP: the deep layers on isf_spconv_deep.hip (LDS-DMA gathers, a step's products and the next step's
             # loads in one hand-scheduled instruction stream; opt-in)
-            assert torch.equal(sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=32768),
+            assert torch.equal(sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=_lib.CONV_MODE_DEEP),
                                ref), (n, subm)
 
 
 def test_conv_one_column_block_variants_reproduce_the_two_block_bits(dev):
-    """round 5: the 256-column layers with ONE column block per workgroup (conv mode 4096: 4 waves x 32 rows, 8192: 8 waves
-    x 16 rows; encoder diagnostic 262144 / 524288) gather a row once per tap and chunk instead of once per column block;
+    """round 5: the 256-column layers with ONE column block per workgroup (CONV_MODE_ONE_BLOCK_4W: 4 waves x 32 rows, _8W: 8 waves
+    x 16 rows; ENC_DIAG_ONE_BLOCK_4W / _8W) gather a row once per tap and chunk instead of once per column block;
     every accumulator sees the same products in the same order, so the outputs equal the production launch bit for bit.
-    So does the staggered-issue variant (encoder diagnostic 1048576).  All three measured SLOWER."""
+    So does the staggered-issue variant (ENC_DIAG_STAGGER).  All three measured SLOWER."""
     import isfusion_amd as m
     from isfusion_amd import synthetic
     lb = m.LidarBranch().randomize_weights_(0).randomize_bn_(1).eval().to(dev)
@@ -693,16 +695,16 @@ def test_conv_one_column_block_variants_reproduce_the_two_block_bits(dev):
         pl = [T(synthetic.lidar_sweeps(900 + i, n), dev) for i in range(frames)]
         want = lb(pl)
         assert torch.isfinite(want).all() and want.abs().max().item() > 0.1
-        assert torch.equal(lb(pl, conv_diag=262144), want), n
-        assert torch.equal(lb(pl, conv_diag=524288), want), n
-        assert torch.equal(lb(pl, conv_diag=262144 + 32), want), n
-        # staggered issue phases inside the deep layers' workgroups (conv mode 65536): the same products in the same order
-        assert torch.equal(lb(pl, conv_diag=1048576), want), n
-        # round 4's issue phase (index reads inside the step, four separate weight-DMA pieces; conv mode 131072) against
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_ONE_BLOCK_4W), want), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_ONE_BLOCK_8W), want), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_ONE_BLOCK_4W | _lib.ENC_DIAG_UNIFORM_TILES), want), n
+        # staggered issue phases inside the deep layers' workgroups (CONV_MODE_STAGGER): the same products in the same order
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_STAGGER), want), n
+        # round 4's issue phase (index reads inside the step, four separate weight-DMA pieces; CONV_MODE_R4_ISSUE) against
         # the production one (indices a step ahead, one M0 set-up per weight run)
-        assert torch.equal(lb(pl, conv_diag=2097152), want), n
-        # the gathered rows two steps ahead (three register sets, counted waits; conv mode 262144), 4-wave deep shapes
-        assert torch.equal(lb(pl, conv_diag=4194304), want), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_R4_ISSUE), want), n
+        # the gathered rows two steps ahead (three register sets, counted waits; CONV_MODE_TWO_AHEAD), 4-wave deep shapes
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_TWO_AHEAD), want), n
 
 
 @pytest.mark.parametrize("cin,cout", [(64, 128), (128, 128), (256, 128), (128, 256), (256, 256)])
@@ -725,8 +727,8 @@ def test_small_launch_shapes_reproduce_the_two_group_bits_and_the_oracle(dev, or
         p16 = sp.pack_filters_f16x3(T(w, dev))
         a = (T(feats, dev), p16, 27, cin, cout, rb, T(scale, dev), T(shift, dev), T(res, dev))
         got = sp.sparse_conv_forward_f16x3(*a, relu=True)
-        assert torch.equal(got, sp.sparse_conv_forward_f16x3(*a, relu=True, mode=16)), ("bits vs two-group", cin, cout, n)
-        assert torch.equal(got, sp.sparse_conv_forward_f16x3(*a, relu=True, mode=32)), ("bits vs launch order", cin, cout, n)
+        assert torch.equal(got, sp.sparse_conv_forward_f16x3(*a, relu=True, mode=_lib.CONV_MODE_NO_SHARING)), ("bits vs two-group", cin, cout, n)
+        assert torch.equal(got, sp.sparse_conv_forward_f16x3(*a, relu=True, mode=_lib.CONV_MODE_UNIFORM_TILES)), ("bits vs launch order", cin, cout, n)
         oidx, pairs, num = oracle_mod.get_indice_pairs(idx, B, shape, [3, 3, 3], [1, 1, 1], [1, 1, 1], subm=True)
         o1, o2 = lexsort4(rb.out_indices.cpu().numpy()), lexsort4(oidx)
         raw = oracle_mod.indice_conv(feats, w, pairs, num, len(oidx))[o2]
@@ -779,7 +781,7 @@ def test_conv_tile_order_is_a_per_part_permutation_and_keeps_the_bits(dev):
         w = T(rng.normal(0, (1.0 / (9 * cin)) ** 0.5, (3, 3, 3, cin, cout)).astype(np.float32), dev)
         p16 = sp.pack_filters_f16x3(w)
         res = T(rng.normal(0, 1, (n, cout)).astype(np.float32), dev)
-        for mode in (0, 1, 257):
+        for mode in (0, _lib.CONV_MODE_F16, _lib.CONV_MODE_F16_STORAGE):
             om = sp.tile_order(rb, cin, cout, mode)
             ref = sp.sparse_conv_forward_f16x3(x, p16, 27, cin, cout, rb, None, None, res, relu=True, mode=mode)
             got = sp.sparse_conv_forward_f16x3(x, p16, 27, cin, cout, rb, None, None, res, relu=True, mode=mode, order=om)
@@ -788,18 +790,18 @@ def test_conv_tile_order_is_a_per_part_permutation_and_keeps_the_bits(dev):
 
 def test_lidar_branch_tile_order_reproduces_launch_order_bits(dev):
     """the encoder builds a tile-order table per level behind the neighbour table (geometry stream) and runs the deep
-    levels' convolutions through it; diagnostic 64 switches the tables off -- same bits, at sizes where no level, the
+    levels' convolutions through it; ENC_DIAG_LAUNCH_ORDER switches the tables off -- same bits, at sizes where no level, the
     last level and the last two levels qualify"""
     import isfusion_amd as m
     from isfusion_amd import synthetic
     lb = m.LidarBranch().randomize_weights_(0).randomize_bn_(1).eval().to(dev)
     for n, frames in ((3000, 1), (60000, 2), (300000, 4)):
         pl = [T(synthetic.lidar_sweeps(900 + i, n), dev) for i in range(frames)]
-        want = lb(pl, conv_diag=64)
+        want = lb(pl, conv_diag=_lib.ENC_DIAG_LAUNCH_ORDER)
         assert torch.isfinite(want).all() and want.abs().max().item() > 0.1
         assert torch.equal(lb(pl), want), n
-        assert torch.equal(lb(pl, conv_diag=96), want), n       # uniform tiles, no order
-        assert torch.equal(lb(pl, precision=2), lb(pl, precision=2, conv_diag=64)), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_UNIFORM_TILES | _lib.ENC_DIAG_LAUNCH_ORDER), want), n       # uniform tiles, no order
+        assert torch.equal(lb(pl, precision=2), lb(pl, precision=2, conv_diag=_lib.ENC_DIAG_LAUNCH_ORDER)), n
 
 
 @pytest.mark.parametrize("cin,cout", [(64, 64), (32, 32), (64, 32), (32, 64)])
@@ -824,11 +826,11 @@ def test_dma_gather_kernel_bit_identical_to_gather_kernel(dev, cin, cout):
             sc = T(rng.random(cout, dtype=np.float32) + 0.5, dev)
             sh = T(rng.normal(0, 0.2, cout).astype(np.float32), dev)
             p16 = sp.pack_filters_f16x3(w)
-            for mode in (0, 1, 257, 32):
+            for mode in (0, _lib.CONV_MODE_F16, _lib.CONV_MODE_F16_STORAGE, _lib.CONV_MODE_UNIFORM_TILES):
                 ref = sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=mode)
                 got = sp.sparse_conv_forward_dma(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=mode)
                 assert ref.abs().max() > 0.5 and torch.equal(got, ref), (n, subm, ks, mode)
-                if mode != 32:       # the tile order of the DMA kernel's OWN launch plan (not the f16x3 plan's)
+                if mode != _lib.CONV_MODE_UNIFORM_TILES:       # the tile order of the DMA kernel's OWN launch plan (not the f16x3 plan's)
                     od = sp.tile_order(rb, cin, cout, mode, dma=True)
                     if od is not None:
                         got = sp.sparse_conv_forward_dma(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=mode, order=od)
@@ -922,7 +924,7 @@ def test_cu_unit_kernel_bit_identical_to_tile_kernel(dev, cin):
 
 
 def test_lidar_branch_cu_unit_layers_reproduce_tile_kernel_bits(dev):
-    """with diagnostic 512 the encoder runs its 256-column layers (levels 3 / 4: 128 -> 256 strided, 4 x 256 -> 256 SubM,
+    """with ENC_DIAG_CU_KERNEL the encoder runs its 256-column layers (levels 3 / 4: 128 -> 256 strided, 4 x 256 -> 256 SubM,
     the 3-tap conv_out) on the one-workgroup-per-CU kernel, unit plans built per rulebook on the geometry stream; the
     default keeps them on the tile kernel -- same bits, from a 3 k-point frame to the bench size, repeated calls too"""
     import isfusion_amd as m
@@ -932,10 +934,10 @@ def test_lidar_branch_cu_unit_layers_reproduce_tile_kernel_bits(dev):
         pl = [T(synthetic.lidar_sweeps(970 + i, n), dev) for i in range(frames)]
         want = lb(pl)
         assert torch.isfinite(want).all() and want.abs().max().item() > 0.1
-        got = lb(pl, conv_diag=512)
+        got = lb(pl, conv_diag=_lib.ENC_DIAG_CU_KERNEL)
         assert torch.equal(got, want), n
-        assert torch.equal(lb(pl, conv_diag=512), got), n
-        assert torch.equal(lb(pl, conv_diag=512 + 64 + 128), want), n       # CU kernel on, tile order / DMA gathers off
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_CU_KERNEL), got), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_CU_KERNEL | _lib.ENC_DIAG_LAUNCH_ORDER | _lib.ENC_DIAG_NARROW_GATHER), want), n       # CU kernel on, tile order / DMA gathers off
 
 
 @pytest.mark.parametrize("cin,cout", [(64, 64), (32, 32), (64, 32), (32, 64)])
@@ -967,7 +969,7 @@ def test_line_compressed_table_conv_bit_identical_and_round_trips(dev, cin, cout
             sc = T(rng.random(cout, dtype=np.float32) + 0.5, dev)
             sh = T(rng.normal(0, 0.2, cout).astype(np.float32), dev)
             p16 = sp.pack_filters_f16x3(w)
-            for mode in (0, 1, 257, 32):
+            for mode in (0, _lib.CONV_MODE_F16, _lib.CONV_MODE_F16_STORAGE, _lib.CONV_MODE_UNIFORM_TILES):
                 ref = sp.sparse_conv_forward_dma(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=mode)
                 got = sp.sparse_conv_forward_dma_lines(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=mode,
                                                        taps_per_line=tpl)
@@ -986,26 +988,26 @@ def test_line_compressed_table_conv_bit_identical_and_round_trips(dev, cin, cout
 
 def test_lidar_branch_line_tables_reproduce_dense_table_bits(dev):
     """the encoder builds the neighbour tables of its narrow levels (0 / 1: every reader runs the LDS-DMA kernel) directly
-    in the line-compressed form; diagnostic 16384 keeps dense tables -- same bits from a 3 k-point frame to the bench size,
+    in the line-compressed form; ENC_DIAG_DENSE_TABLES keeps dense tables -- same bits from a 3 k-point frame to the bench size,
     in the fp32-class and f16-storage precisions, with and without the tile-order tables"""
     import isfusion_amd as m
     from isfusion_amd import synthetic
     lb = m.LidarBranch().randomize_weights_(0).randomize_bn_(1).eval().to(dev)
     for n, frames in ((3000, 1), (60000, 2), (300000, 4), (2000, 9)):     # 9 frames: more than one fused launch holds
         pl = [T(synthetic.lidar_sweeps(990 + i, n), dev) for i in range(frames)]
-        want = lb(pl, conv_diag=16384)
+        want = lb(pl, conv_diag=_lib.ENC_DIAG_DENSE_TABLES)
         assert torch.isfinite(want).all() and want.abs().max().item() > 0.1
         assert torch.equal(lb(pl), want), n
-        assert torch.equal(lb(pl, conv_diag=64), lb(pl, conv_diag=64 + 16384)), n
-        assert torch.equal(lb(pl, precision=2), lb(pl, precision=2, conv_diag=16384)), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_LAUNCH_ORDER), lb(pl, conv_diag=_lib.ENC_DIAG_LAUNCH_ORDER | _lib.ENC_DIAG_DENSE_TABLES)), n
+        assert torch.equal(lb(pl, precision=2), lb(pl, precision=2, conv_diag=_lib.ENC_DIAG_DENSE_TABLES)), n
         # the frames are voxelized inside the VFE's byte-map marking launch (one launch for the whole batch); diagnostic
-        # 65536 = one dynamic-voxelize launch per frame + a separate marking pass
-        assert torch.equal(lb(pl, conv_diag=65536), want), n
+        # ENC_DIAG_VOXELIZE_PER_FRAME = one dynamic-voxelize launch per frame + a separate marking pass
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_VOXELIZE_PER_FRAME), want), n
         # the per-level row counts reach the host through a pinned-memory mailbox (a one-thread kernel + a host spin on
-        # the ticket); diagnostic 131072 = hipMemcpyAsync + synchronise
-        assert torch.equal(lb(pl, conv_diag=131072), want), n
+        # the ticket); ENC_DIAG_COUNTS_MEMCPY = hipMemcpyAsync + synchronise
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_COUNTS_MEMCPY), want), n
         st0 = lb(pl, want_stats=True) is not None and lb.last_stats
-        st1 = lb(pl, want_stats=True, conv_diag=16384) is not None and lb.last_stats
+        st1 = lb(pl, want_stats=True, conv_diag=_lib.ENC_DIAG_DENSE_TABLES) is not None and lb.last_stats
         assert [st0.pairs[i] for i in range(21)] == [st1.pairs[i] for i in range(21)]      # same pair counts either way
 
 
@@ -1040,7 +1042,7 @@ def test_tile_table_conv_bit_identical_and_covers_every_group(dev, cin, cout):
             sc = T(rng.random(cout, dtype=np.float32) + 0.5, dev)
             sh = T(rng.normal(0, 0.2, cout).astype(np.float32), dev)
             p16 = sp.pack_filters_f16x3(w)
-            for mode in (0, 1, 257):               # a table belongs to one mode: the workgroup shape depends on it
+            for mode in (0, _lib.CONV_MODE_F16, _lib.CONV_MODE_F16_STORAGE):               # a table belongs to one mode: the workgroup shape depends on it
                 table = sp.tile_table(rb, cin, cout, mode)
                 assert table is not None
                 ref = sp.sparse_conv_forward_f16x3(x, p16, K, cin, cout, rb, sc, sh, res, relu=True, mode=mode)
@@ -1052,7 +1054,7 @@ def test_tile_table_conv_bit_identical_and_covers_every_group(dev, cin, cout):
 
 
 def test_lidar_branch_tile_tables_reproduce_uniform_tile_bits(dev):
-    """with diagnostic 32768 the encoder gives every one-round launch of the tile kernel (levels 3 / 4; level 2 at small
+    """with ENC_DIAG_TILE_TABLES the encoder gives every one-round launch of the tile kernel (levels 3 / 4; level 2 at small
     batch) an equal-work tile table built behind the neighbour table on the geometry stream; the default keeps uniform
     tiles + the tile-order permutation -- same bits from a 3 k-point frame to the bench size, fp32-class and f16 storage"""
     import isfusion_amd as m
@@ -1062,29 +1064,29 @@ def test_lidar_branch_tile_tables_reproduce_uniform_tile_bits(dev):
         pl = [T(synthetic.lidar_sweeps(930 + i, n), dev) for i in range(frames)]
         want = lb(pl)
         assert torch.isfinite(want).all() and want.abs().max().item() > 0.1
-        assert torch.equal(lb(pl, conv_diag=32768), want), n
-        assert torch.equal(lb(pl, conv_diag=32768), want), n
-        assert torch.equal(lb(pl, conv_diag=64), want), n                    # neither tables nor the permutation
-        assert torch.equal(lb(pl, precision=2), lb(pl, precision=2, conv_diag=32768)), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_TILE_TABLES), want), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_TILE_TABLES), want), n
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_LAUNCH_ORDER), want), n                    # neither tables nor the permutation
+        assert torch.equal(lb(pl, precision=2), lb(pl, precision=2, conv_diag=_lib.ENC_DIAG_TILE_TABLES)), n
 
 
 def test_lidar_branch_dma_gather_layers_reproduce_gather_kernel_bits(dev):
-    """the encoder runs its narrow layers (levels 0 / 1) on the LDS-DMA gather kernel; diagnostic 128 keeps them on the
+    """the encoder runs its narrow layers (levels 0 / 1) on the LDS-DMA gather kernel; ENC_DIAG_NARROW_GATHER keeps them on the
     gather kernel -- same bits, in the split, single-pass f16 and f16-storage precisions"""
     import isfusion_amd as m
     from isfusion_amd import synthetic
     lb = m.LidarBranch().randomize_weights_(0).randomize_bn_(1).eval().to(dev)
     for n, frames in ((3000, 1), (60000, 2), (300000, 4)):
         pl = [T(synthetic.lidar_sweeps(950 + i, n), dev) for i in range(frames)]
-        want = lb(pl, conv_diag=128)
+        want = lb(pl, conv_diag=_lib.ENC_DIAG_NARROW_GATHER)
         assert torch.isfinite(want).all() and want.abs().max().item() > 0.1
         assert torch.equal(lb(pl), want), n
-        assert torch.equal(lb(pl, conv_diag=32), lb(pl, conv_diag=32 + 128)), n      # uniform tiles
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_UNIFORM_TILES), lb(pl, conv_diag=_lib.ENC_DIAG_UNIFORM_TILES | _lib.ENC_DIAG_NARROW_GATHER)), n      # uniform tiles
         # the voxel encoder writes its rows straight into the split format the first convolution reads (whole rows from
-        # the segmented max, rows cut by a wave boundary from a fix-up pass); diagnostic 256 = fp32 rows + conversion pass
-        assert torch.equal(lb(pl, conv_diag=256), want), n
+        # the segmented max, rows cut by a wave boundary from a fix-up pass); ENC_DIAG_VFE_FP32_ROWS = fp32 rows + conversion pass
+        assert torch.equal(lb(pl, conv_diag=_lib.ENC_DIAG_VFE_FP32_ROWS), want), n
         for prec in (2,):
-            assert torch.equal(lb(pl, precision=prec), lb(pl, precision=prec, conv_diag=128)), (n, prec)
+            assert torch.equal(lb(pl, precision=prec), lb(pl, precision=prec, conv_diag=_lib.ENC_DIAG_NARROW_GATHER)), (n, prec)
 
 
 def test_lidar_branch_with_lds_staged_convs_reproduces_gather_bits(dev):

@@ -718,8 +718,8 @@ def test_f16_storage_mode_matches_the_f16_oracle_and_is_off_by_default(dev, orac
 
 @pytest.mark.parametrize("cin,cout", [(64, 32), (32, 32), (64, 64), (128, 128), (256, 256)])
 def test_f16_storage_conv_op(dev, oracle_mod, cin, cout):
-    """isf_sparse_conv_forward_f16x3 mode 257: f16 rows in (features, residual), f16 rows out"""
-    from isfusion_amd import spconv as sp
+    """isf_sparse_conv_forward_f16x3 mode CONV_MODE_F16_STORAGE: f16 rows in (features, residual), f16 rows out"""
+    from isfusion_amd import _lib, spconv as sp
     rng = np.random.default_rng(cin + 3 * cout)
     B, shape = 2, [9, 24, 20]
     n = 1500
@@ -740,7 +740,8 @@ def test_f16_storage_conv_op(dev, oracle_mod, cin, cout):
         raw = oracle_mod.indice_conv(feats, _f16(w * sw) / sw, pairs, num, len(oidx))[o2]
         want = _f16(oracle_mod.bn_act(raw, scale, shift, res[o1], relu=True))
         got = sp.sparse_conv_forward_f16x3(T(feats, dev), sp.pack_filters_f16x3(T(w, dev)), 27, cin, cout, rb,
-                                           T(scale, dev), T(shift, dev), T(res, dev), relu=True, mode=257).cpu().numpy()
+                                           T(scale, dev), T(shift, dev), T(res, dev), relu=True,
+                                           mode=_lib.CONV_MODE_F16_STORAGE).cpu().numpy()
         # one f16 ulp of the result (fp32 sums agree to 1e-6; rounding to f16 may land on either neighbour)
         assert np.abs(got[o1] - want).max() <= 2.0 ** -10 * max(1.0, np.abs(want).max()), (cin, cout, subm)
 

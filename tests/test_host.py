@@ -598,7 +598,9 @@ def test_layer_level_kernel_choice_mirrors_the_engine(monkeypatch):
     """spconv.sparse_conv_forward_best is what SparseConvFunction (the sparse_conv_ext.indice_conv replacement) calls:
     narrow shapes go to the LDS-DMA gather kernel, wider ones to the split kernel with the rulebook's tile-order table,
     the timing diagnostics to the plain gather kernel -- the same choices isf_sparse_encoder_forward makes per layer."""
-    from isfusion_amd import spconv as sp
+    from isfusion_amd import _lib, spconv as sp
+    F16, STORAGE, NO_SHARING, NO_GATHER = (_lib.CONV_MODE_F16, _lib.CONV_MODE_F16_STORAGE, _lib.CONV_MODE_NO_SHARING,
+                                           _lib.CONV_MODE_NO_GATHER)
     calls = []
     monkeypatch.setattr(sp, "sparse_conv_forward_dma", lambda *a, **k: calls.append(("dma", a[3], a[4], a[-1])) or "dma")
     monkeypatch.setattr(sp, "sparse_conv_forward_f16x3",
@@ -607,14 +609,49 @@ def test_layer_level_kernel_choice_mirrors_the_engine(monkeypatch):
     monkeypatch.setattr(sp, "tile_order", lambda rb, ci, co, mode=0: ("order", ci, co, mode))
     rb = object()
     assert sp.sparse_conv_forward_best(None, None, 27, 64, 64, rb) == "dma"
-    assert sp.sparse_conv_forward_best(None, None, 27, 32, 64, rb, mode=257) == "dma"
+    assert sp.sparse_conv_forward_best(None, None, 27, 32, 64, rb, mode=STORAGE) == "dma"
     assert sp.sparse_conv_forward_best(None, None, 27, 64, 128, rb) == "split"
-    assert sp.sparse_conv_forward_best(None, None, 27, 256, 256, rb, mode=1) == "split"
-    assert sp.sparse_conv_forward_best(None, None, 27, 64, 64, rb, mode=16) == "split"     # diagnostic: gather kernel
-    assert sp.sparse_conv_forward_best(None, None, 27, 256, 256, rb, mode=2) == "split"
-    assert calls == [("dma", 64, 64, 0), ("dma", 32, 64, 257),
-                     ("split", 64, 128, 0, ("order", 64, 128, 0)), ("split", 256, 256, 1, ("order", 256, 256, 1)),
-                     ("split", 64, 64, 16, None), ("split", 256, 256, 2, None)]
+    assert sp.sparse_conv_forward_best(None, None, 27, 256, 256, rb, mode=F16) == "split"
+    assert sp.sparse_conv_forward_best(None, None, 27, 64, 64, rb, mode=NO_SHARING) == "split"     # diagnostic: gather kernel
+    assert sp.sparse_conv_forward_best(None, None, 27, 256, 256, rb, mode=NO_GATHER) == "split"
+    assert calls == [("dma", 64, 64, 0), ("dma", 32, 64, STORAGE),
+                     ("split", 64, 128, 0, ("order", 64, 128, 0)), ("split", 256, 256, F16, ("order", 256, 256, F16)),
+                     ("split", 64, 64, NO_SHARING, None), ("split", 256, 256, NO_GATHER, None)]
+
+
+def test_mode_and_diagnostic_names_pin_the_abi():
+    """the ISF_CONV_MODE_* / ISF_ENC_DIAG_* / ISF_WGRAD_* names of include/isf_hip.h: _lib mirrors each one with the same
+    value, the values are the ints that cross the C ABI (written out here: a renamed test can never quietly exercise
+    another path), and the single-bit names of a group do not collide"""
+    from isfusion_amd import _lib
+    pinned = {
+        "CONV_MODE": dict(F16=1, NO_GATHER=2, NO_WEIGHTS=4, NO_LOOP=8, NO_SHARING=16, UNIFORM_TILES=32, F16_ROWS=256,
+                          F16_STORAGE=257, DMA_PLAN=2048, ONE_BLOCK_4W=4096, ONE_BLOCK_8W=8192, DEEP=32768, STAGGER=65536,
+                          R4_ISSUE=131072, TWO_AHEAD=262144, CHUNK_SPLIT=524288),
+        "ENC_DIAG": dict(NO_GATHER=2, NO_WEIGHTS=4, NO_LOOP=8, NO_SHARING=16, UNIFORM_TILES=32, LAUNCH_ORDER=64,
+                         NARROW_GATHER=128, VFE_FP32_ROWS=256, CU_KERNEL=512, CU_VARIANT_SHIFT=10, CU_VARIANT_MASK=15 << 10,
+                         DENSE_TABLES=16384, TILE_TABLES=32768, VOXELIZE_PER_FRAME=65536, COUNTS_MEMCPY=131072,
+                         ONE_BLOCK_4W=262144, ONE_BLOCK_8W=524288, STAGGER=1048576, R4_ISSUE=2097152, TWO_AHEAD=4194304,
+                         DEEP=8388608, BAND_ORDER=16777216, NO_ROW_SORT=33554432, NARROW_ROW_SORT=67108864,
+                         SORT_KEY_AB=134217728, NARROW_TILES=268435456, CHUNK_SPLIT=536870912),
+        "WGRAD": dict(F16=1, FULL_TAPS=2),
+    }
+    hdr = open(os.path.join(ROOT, "include", "isf_hip.h")).read()
+    defined = {}
+    for group, name, value in re.findall(r"^#define ISF_(CONV_MODE|ENC_DIAG|WGRAD)_(\w+)\s+(\d+)\b", hdr, flags=re.M):
+        defined.setdefault(group, {})[name] = int(value)
+    assert defined == pinned
+    for group, names in pinned.items():
+        for name, value in names.items():
+            assert getattr(_lib, f"{group}_{name}") == value, (group, name)
+        mirrored = {n[len(group) + 1:] for n in vars(_lib) if n.startswith(group + "_")}
+        assert mirrored == set(names), (group, mirrored ^ set(names))
+        # composite names (F16_STORAGE, the variant field's shift and mask) aside, every name is one bit of its own
+        composite = {"F16_STORAGE", "CU_VARIANT_SHIFT", "CU_VARIANT_MASK"}
+        bits = [v for n, v in names.items() if n not in composite]
+        assert all(v > 0 and v & (v - 1) == 0 for v in bits) and len(set(bits)) == len(bits), group
+    assert pinned["CONV_MODE"]["F16_STORAGE"] == pinned["CONV_MODE"]["F16_ROWS"] | pinned["CONV_MODE"]["F16"]
+    assert pinned["ENC_DIAG"]["CU_VARIANT_MASK"] & sum(v for n, v in pinned["ENC_DIAG"].items() if "VARIANT" not in n) == 0
 
 
 def test_h2d_async_cpu_path_and_ring_bookkeeping():

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Knock-out decomposition of the sparse-conv time as one repeatable measurement:
 #   gpurun --timeout 600 -- 'bash tools/conv_knockout.sh'      (5 bench runs: about 2 GPU-minutes)
-# --conv-diag: 2 = no activation gathers, 4 = no weight DMA, 6 = neither, 8 = no main loop.  The outputs of the
+# --conv-diag (ISF_ENC_DIAG_NO_GATHER / _NO_WEIGHTS / _NO_LOOP): 2 = no activation gathers, 4 = no weight DMA, 6 = neither, 8 = no main loop.  The outputs of the
 # diagnostic kernels are garbage; only the per-kernel times are read.  The diagnostics run on the 4-wave workgroup shape.
 set -u
 mkdir -p gpurun_out
