@@ -920,6 +920,34 @@ int isf_assemble_points(const float* raw, const isf_sweep_t* sweeps, int num_swe
                         const float* point_range /* 6 host floats or NULL */, float* points_out,
                         int32_t* sample_offsets, int32_t* sample_offsets_host, isf_stream_t stream);
 
+/* camera input pre-pass: ImageAug3D + ImageNormalize for every view of a batch ---------------------------------------
+ * replaces, per batch, the dataloader-side Pillow / torchvision code of ImageAug3D.img_transform
+ * (datasets/pipelines/transforms_3d.py:82-112: img.resize(resize_dims) -> img.crop(crop) -> FLIP_LEFT_RIGHT ->
+ * img.rotate(rotate)) and ImageNormalize (:25-43: ToTensor + Normalize), as configs/isfusion/isfusion_0075voxel.py:238-352
+ * chains them.  raw = the decoded images of the batch (uint8, HWC, RGB, any size per view), uploaded untouched; one
+ * descriptor per view.  Output img_out [num_views, 3, out_h, out_w] float32, every element written, bit-exact against
+ * Pillow's 8-bit path (resize: antialiased bicubic, horizontal pass rounded to uint8 before the vertical one, 22-bit
+ * coefficients; rotate: nearest neighbour in 16.16 fixed point) followed by the 3 x 256 normalise table.
+ * tables (int32, device): per resized axis a bounds table [out][2] = (first input index, taps) and a coefficient table
+ * [out][ksize] (22 fractional bits), at the descriptor's offsets; an axis that keeps its size uses taps = 1,
+ * coefficient 2^22.  A tile whose source box the kernel cannot hold (rot[] that is no rotation, more vertical taps
+ * than the ~89 rows it holds: in / out > ~20) is written as NaN.  One asynchronous launch, no host wait. */
+typedef struct {
+  int64_t src_offset;      /* byte offset of the view's first pixel in raw */
+  int32_t src_w, src_h;
+  int32_t resize_w, resize_h; /* ImageAug3D resize_dims */
+  int32_t crop_x, crop_y;  /* crop[0], crop[1]; the crop is out_w x out_h and may leave the resized image (0 there) */
+  int32_t flip;            /* FLIP_LEFT_RIGHT after the crop */
+  int32_t rotate;          /* 0: no rotation (rotate % 360 == 0), rot[] unused */
+  int32_t rot[6];          /* Pillow's 16.16 affine: (x, y) reads ((rot2 + y rot1 + x rot0) >> 16, (rot5 + y rot4 + x rot3) >> 16) */
+  int32_t h_bounds, h_coeffs, h_ksize; /* offsets into tables (in int32) and row length of the coefficient table */
+  int32_t v_bounds, v_coeffs, v_ksize;
+} isf_image_view_t;
+
+int isf_image_prepass(const uint8_t* raw, const isf_image_view_t* views /* device */, int num_views,
+                      const int32_t* tables /* device */, const float* norm_lut /* device, 3 x 256 */, int out_h,
+                      int out_w, float* img_out, isf_stream_t stream);
+
 /* 8f #2  Point-to-Grid backward ---------------------------------------------------------------------------------
  * replaces autograd through img_fv_to_bev's F.grid_sample (fusion_encoder.py:1049-1056) + the canvas scatter (:989-1003):
  * grad_out [B, C, bev, bev] -> grad_img_nhwc [B*num_cam, H, W, C] (written completely; fp32 atomics inside).  The

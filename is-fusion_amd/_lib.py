@@ -90,6 +90,17 @@ class PointAug(ctypes.Structure):
     ]
 
 
+class ImageView(ctypes.Structure):
+    """isf_image_view_t."""
+    _fields_ = [
+        ("src_offset", ctypes.c_int64), ("src_w", ctypes.c_int32), ("src_h", ctypes.c_int32),
+        ("resize_w", ctypes.c_int32), ("resize_h", ctypes.c_int32), ("crop_x", ctypes.c_int32),
+        ("crop_y", ctypes.c_int32), ("flip", ctypes.c_int32), ("rotate", ctypes.c_int32), ("rot", ctypes.c_int32 * 6),
+        ("h_bounds", ctypes.c_int32), ("h_coeffs", ctypes.c_int32), ("h_ksize", ctypes.c_int32),
+        ("v_bounds", ctypes.c_int32), ("v_coeffs", ctypes.c_int32), ("v_ksize", ctypes.c_int32),
+    ]
+
+
 class SwinA(ctypes.Structure):
     """struct isf_swin_a: the A-operand loader of isf_swin_gemm / isf_swin_row_stats."""
     _fields_ = [("x", c_void_p), ("x2", c_void_p), ("ln_stats", c_void_p), ("ln_gamma", c_void_p), ("ln_beta", c_void_p),
@@ -273,6 +284,7 @@ SIGNATURES = {
     "isf_assemble_points": (c_int, [c_void_p, ctypes.POINTER(Sweep), c_int, c_int, ctypes.POINTER(PointAug),
                                     ctypes.POINTER(ctypes.c_float), c_void_p, c_void_p,
                                     ctypes.POINTER(ctypes.c_int32), c_void_p]),
+    "isf_image_prepass": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "isf_transpose_rulebook": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isf_sparse_conv_backward_input": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                                c_void_p, c_void_p]),
