@@ -210,13 +210,26 @@ int isf_sparse_conv_forward_packed(const float* features, int num_in, int c_in, 
                                    const float* residual, int relu, float* out, isf_stream_t stream);
 
 /* Split-precision ("f16x3") sparse convolution -------------------------------------------------------------
- * Same contract as isf_sparse_conv_forward_packed, evaluated on the f16 matrix cores with fp32-equivalent
- * accuracy: operands are carried as hi + lo f16 halves (22 significant bits), products as
- * a_lo*b_hi + a_hi*b_lo + a_hi*b_hi with fp32 accumulation.  Activations are exchanged in the SPLIT format:
+ * Same contract as isf_sparse_conv_forward_packed, evaluated on the f16 matrix cores: operands are carried as
+ * hi + lo f16 halves, hi = f16(v), lo = f16(v - hi), products as a_lo*b_hi + a_hi*b_lo + a_hi*b_hi with fp32
+ * accumulation.  Weights are scaled by a power of two into [2^12, 2^13) before the split; ACTIVATIONS ARE NOT
+ * SCALED, so the accuracy depends on their magnitude (two-sided domain; model: tests/split_model.py):
+ *   2^-3 <= |a| < 65504    both halves are normal f16 numbers: 22 significant bits, relative error 2^-22 per
+ *                          operand -- the accuracy of an fp32 matmul;
+ *   |a| < 2^-3             the lo half is an f16 subnormal: the error is ABSOLUTE, 2^-25 per element (half a
+ *                          subnormal step), i.e. relative 2^-25 / |a|; below 2^-14 the hi half is subnormal too;
+ *   |a| >= 65520           hi = +inf, lo = -inf: every output that reads the element is NaN (also +-inf and NaN
+ *                          inputs).  Loud and confined to those outputs, never finite-wrong; a split-stored
+ *                          OUTPUT above the same threshold comes back NaN, not clamped.
+ * (model - exact) / max|exact| of a 576-term dot product, N(0,1)*s activations, conv-like weights
+ * (tests/test_split_model.py::test_accuracy_table prints it):
+ *   max|a|      4.6     0.57    3.6e-2  4.5e-3  5.6e-4  2.8e-4  3.5e-5  4.4e-6  >= 65520
+ *   rel. error  9.5e-8  1.8e-7  2.5e-6  2.1e-5  1.8e-4  3.3e-4  2.3e-3  2.0e-2  NaN
+ * Activations are exchanged in the SPLIT format:
  * row-major [N, C/32] chunks of 128 bytes, a chunk = 32 channels as 4 x (8 f16 hi) followed by 4 x (8 f16 lo)
  * (same 4 bytes/element as fp32; the 16-byte pieces the four k-group lanes of an MFMA row fetch together are
  * contiguous); isf_f32_to_split / isf_split_to_f32 convert ([N, C] row-major fp32, N*C a multiple of 32).
- * |activation| must be < 65504.  Cin, Cout in {32,64,128,256}.
+ * Cin, Cout in {32,64,128,256}.
  * `mode` of isf_sparse_conv_forward_f16x3 (per call; there is no process-wide switch) is a set of ISF_CONV_MODE_* bits
  * (below): 0 = split precision (default);
  * ISF_CONV_MODE_F16 = single-pass f16 (opt-in): the same kernels fetch and multiply only the hi halves -- f16 operands, fp32

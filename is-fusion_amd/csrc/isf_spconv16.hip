@@ -1,14 +1,22 @@
-// isf_spconv16.hip -- sparse convolution forward on the f16 matrix cores with fp32-equivalent accuracy.
+// isf_spconv16.hip -- sparse convolution forward on the f16 matrix cores in split precision (fp32-class accuracy for
+// activations of magnitude >= 2^-3; the domain is spelled out below).
 //
 // Arithmetic ("f16x3 split"): every fp32 operand is carried as two halves, v = hi + lo with hi = f16(v),
-// lo = f16(v - hi) (22 significant bits), and a product is evaluated as  a_lo*b_hi + a_hi*b_lo + a_hi*b_hi
-// with v_mfma_f32_16x16x32_f16 accumulating in fp32 (the dropped a_lo*b_lo term is 2^-22 relative).
-// Measured on the CPU (tests/test_host.py::test_f16x3_numerics): same error as an fp32 matmul.  The f16
+// lo = f16(v - hi) (22 significant bits while lo is a normal f16 number), and a product is evaluated as
+// a_lo*b_hi + a_hi*b_lo + a_hi*b_hi with v_mfma_f32_16x16x32_f16 accumulating in fp32 (the dropped a_lo*b_lo term is
+// 2^-22 relative).
+// Measured on the CPU (tests/test_host.py::test_f16x3_numerics): same error as an fp32 matmul at O(1) operands.  The f16
 // MFMA pipe is 16x the fp32 MFMA rate on gfx950 (2.5 PFLOP/s vs 157 TFLOP/s dense), so three passes are
 // still 5.3x the fp32 matrix rate.  Weights are scaled by a power of two at pack time so their low halves
 // stay in the normal f16 range; activations are stored between layers already split (same 4 B/element as
-// fp32; layout: isf_common.h, "split activation format"), so the inner loop has no conversions at all.  |activation| must stay below 65504 (f16 max):
-// outside that range the result is inf/NaN, never silently wrong.
+// fp32; layout: isf_common.h, "split activation format"), so the inner loop has no conversions at all.
+// DOMAIN (activations are NOT scaled; model: tests/split_model.py, kernels: tests/test_gpu_split_domain.py):
+//   2^-3 <= |a| < 65504   relative error 2^-22 per operand (both halves normal);
+//   |a| < 2^-3            lo is an f16 subnormal: absolute error 2^-25 per element, relative 2^-25 / |a| (1.8e-4 of the
+//                         output at max|a| = 5.6e-4, 2e-2 at 4.4e-6: the table in include/isf_hip.h); hi is subnormal
+//                         too below 2^-14;
+//   |a| >= 65520          hi = +inf, lo = -inf -> NaN in every output that reads the element; never finite-wrong.  The
+//                         same holds for a split-stored result: above 65520 it is stored as NaN, not clamped.
 //
 // Structure (register-stationary; differs from the fp32 kernel in isf_spconv.hip):
 //   workgroup = 4 waves, 128 consecutive output rows x BN = 16*NT output channels;
