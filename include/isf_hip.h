@@ -266,7 +266,8 @@ int isf_sparse_conv_forward_packed(const float* features, int num_in, int c_in, 
 #define ISF_CONV_MODE_NO_WEIGHTS 4        /* timing knock-out: no weight streaming (results garbage; 6 = 2 | 4 = neither) */
 #define ISF_CONV_MODE_NO_LOOP 8           /* timing knock-out: no main loop (results garbage) */
 #define ISF_CONV_MODE_NO_SHARING 16       /* gather every row, no neighbour sharing (bit-identical) */
-#define ISF_CONV_MODE_UNIFORM_TILES 32    /* uniform row tiles, no full / half-tile mix (bit-identical; combinable) */
+#define ISF_CONV_MODE_UNIFORM_TILES 32    /* uniform row tiles, no full / half-tile mix (bit-identical; combinable); in the engine
+                                             also equal-row XCD parts for the launches of several rounds */
 #define ISF_CONV_MODE_F16_ROWS 256        /* rows are plain f16; accepted only as ISF_CONV_MODE_F16_STORAGE */
 #define ISF_CONV_MODE_F16_STORAGE 257     /* ISF_CONV_MODE_F16_ROWS | ISF_CONV_MODE_F16: f16 storage, see below */
 #define ISF_CONV_MODE_DMA_PLAN 2048       /* isf_sparse_conv_tile_order: the table is for isf_sparse_conv_forward_dma's plan */
@@ -372,6 +373,34 @@ int isf_sparse_conv_dma_trace(const void* features_split, int num_in, int c_in, 
                               int num_out, const float* scale, const float* shift, const void* residual_split, int relu,
                               void* out_split, long long* trace, int trace_capacity_blocks, int* grid_blocks,
                               isf_stream_t stream);
+/* the same launch on a part table (isf_sparse_conv_part_table below): the trace of the equal-work plan */
+int isf_sparse_conv_dma_trace_parts(const void* features_split, int num_in, int c_in, const void* packed16, int num_taps,
+                                    int taps_per_line, int c_out, const int32_t* table, const uint32_t* mask, int nbr_stride,
+                                    int num_out, const float* scale, const float* shift, const void* residual_split, int relu,
+                                    void* out_split, const int32_t* part_table, long long* trace, int trace_capacity_blocks,
+                                    int* grid_blocks, isf_stream_t stream);
+/* EQUAL-WORK PARTS for the launches of several rounds of workgroups (round 7).  A launch that does
+ * not fit the chip in one round runs uniform tiles, dealt to the 8 XCDs as 8 (4 with two column blocks) parts of equal
+ * ROWS; the steps a tile walks vary 4x with the density of the scene, an XCD cannot give work away, and the launch ends
+ * with the XCD that was dealt the most.  isf_sparse_conv_part_table builds, on the device and without a read-back, the
+ * PART TABLE of the launch the given kernel would make: the SAME uniform tiles dealt to the XCDs as contiguous runs of
+ * equal weight (steps + a measured constant per tile), every run at most `cap` tiles, and inside a run the tiles of the
+ * heaviest of four work classes first (tile order inside a class).  Layout: first tile of every part [parts + 1] | class
+ * bounds [3] | slots [parts][cap] (tile or -1).  mode: the conv's base mode (0 | ISF_CONV_MODE_F16 |
+ * ISF_CONV_MODE_F16_STORAGE), | ISF_CONV_MODE_DMA_PLAN for the LDS-DMA kernel's plan (mask: NULL for a dense table, the
+ * tap masks for a line-compressed one).  flags: 1 = treat the launch as one of several rounds whatever its size (tests),
+ * 2 = slots in tile order, 4 = the plain plan's equal-row parts (A/B of the order alone).  work: 2 x tiles ints of scratch (the tile weights come first); info: {parts, cap, tiles,
+ * table ints}, all 0 when the launch is one round (no table is built: run the plain entry point).
+ * isf_sparse_conv_forward_parts runs the launch on the table: every row is computed by the same tile with the same
+ * products in the same order -- results BIT-IDENTICAL to the plain entry points, which keep the equal-row plan.
+ * isf_sparse_encoder_forward / isf_lidar_branch_forward build these tables for their launches of several rounds. */
+int isf_sparse_conv_part_table(const int32_t* table_nbr, const uint32_t* mask, int nbr_stride, int num_taps, int num_out,
+                               int c_in, int c_out, int mode, int flags, int32_t* work, int work_capacity, int32_t* part_table,
+                               int table_capacity, int* info, isf_stream_t stream);
+int isf_sparse_conv_forward_parts(const void* features_split, int num_in, int c_in, const void* packed16, int num_taps,
+                                  int taps_per_line, int c_out, const int32_t* table_nbr, const uint32_t* mask, int nbr_stride,
+                                  int num_out, const float* scale, const float* shift, const void* residual_split, int relu,
+                                  void* out_split, int mode, const int32_t* part_table, isf_stream_t stream);
 /* The same convolution for the NARROW layers (c_in, c_out in {32, 64}) with the gathered rows brought in by LDS-DMA
  * (isf_spconv_dma.hip; mode 0 | ISF_CONV_MODE_F16 | ISF_CONV_MODE_F16_STORAGE, | ISF_CONV_MODE_UNIFORM_TILES; order: NULL or isf_sparse_conv_tile_order's table).  A gather instruction of
  * isf_sparse_conv_forward_f16x3 loads straight into the MFMA operand layout -- four different rows = four cache lines per
@@ -549,8 +578,10 @@ typedef struct isf_encoder_stats { /* filled on the host after the call (for roo
 #define ISF_ENC_DIAG_NO_WEIGHTS 4              /* -> ISF_CONV_MODE_NO_WEIGHTS */
 #define ISF_ENC_DIAG_NO_LOOP 8                 /* -> ISF_CONV_MODE_NO_LOOP */
 #define ISF_ENC_DIAG_NO_SHARING 16             /* -> ISF_CONV_MODE_NO_SHARING */
-#define ISF_ENC_DIAG_UNIFORM_TILES 32          /* -> ISF_CONV_MODE_UNIFORM_TILES; combines with all others */
-#define ISF_ENC_DIAG_LAUNCH_ORDER 64           /* tiles in launch order, no tile-order tables */
+#define ISF_ENC_DIAG_UNIFORM_TILES 32          /* -> ISF_CONV_MODE_UNIFORM_TILES; combines with all others; also: the launches of
+                                                  several rounds keep equal-ROW XCD parts (their part tables keep the plain cuts) */
+#define ISF_ENC_DIAG_LAUNCH_ORDER 64           /* tiles in launch order, no tile-order tables; also: the part tables of the
+                                                  launches of several rounds keep tile order inside a part */
 #define ISF_ENC_DIAG_NARROW_GATHER 128         /* narrow layers on the gather kernel, not the LDS-DMA kernel */
 #define ISF_ENC_DIAG_VFE_FP32_ROWS 256         /* isf_lidar_branch_forward: fp32 voxel rows + a conversion pass */
 #define ISF_ENC_DIAG_CU_KERNEL 512             /* 256-column layers on the one-workgroup-per-CU kernel (slower; opt-in) */
@@ -566,9 +597,11 @@ typedef struct isf_encoder_stats { /* filled on the host after the call (for roo
 #define ISF_ENC_DIAG_R4_ISSUE 2097152          /* -> ISF_CONV_MODE_R4_ISSUE (deep layers) */
 #define ISF_ENC_DIAG_TWO_AHEAD 4194304         /* -> ISF_CONV_MODE_TWO_AHEAD (deep layers) */
 #define ISF_ENC_DIAG_DEEP 8388608              /* -> ISF_CONV_MODE_DEEP (deep layers) */
-#define ISF_ENC_DIAG_BAND_ORDER 16777216       /* band order for the launches of several rounds (slower; opt-in) */
+#define ISF_ENC_DIAG_BAND_ORDER 16777216       /* band order for the launches of several rounds (slower; opt-in); its order is
+                                                  cut for equal-row parts: no part tables with it */
 #define ISF_ENC_DIAG_NO_ROW_SORT 33554432      /* row sort of the deep launches off (A/B) */
-#define ISF_ENC_DIAG_NARROW_ROW_SORT 67108864  /* row sort for the narrow layers too (no gain; opt-in) */
+#define ISF_ENC_DIAG_NARROW_ROW_SORT 67108864  /* row sort for the narrow layers too (no gain; opt-in); sorted inside equal-row
+                                                  parts: the narrow launches keep them (no part tables) */
 #define ISF_ENC_DIAG_SORT_KEY_AB 134217728     /* row sort key 2 instead of key 1 (A/B) */
 #define ISF_ENC_DIAG_NARROW_TILES 268435456    /* 128-column layers of the large levels on 4-wave tiles (A/B) */
 #define ISF_ENC_DIAG_CHUNK_SPLIT 536870912     /* -> ISF_CONV_MODE_CHUNK_SPLIT (256-column layers; opt-in) */

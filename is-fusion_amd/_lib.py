@@ -276,6 +276,14 @@ SIGNATURES = {
     "isf_sparse_conv_dma_trace": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                          c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                          ctypes.POINTER(c_int), c_void_p]),
+    "isf_sparse_conv_dma_trace_parts": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                               c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                               c_void_p, c_int, ctypes.POINTER(c_int), c_void_p]),
+    "isf_sparse_conv_part_table": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                           c_int, c_void_p, c_int, c_int * 4, c_void_p]),
+    "isf_sparse_conv_forward_parts": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                              c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                              c_void_p]),
     "isf_instance_gather": (c_int, [c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 10),
     "isf_head_query_init": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 14),
     "isf_head_scatter_predictions": (c_int, [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_int),

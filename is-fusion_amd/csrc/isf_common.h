@@ -312,6 +312,13 @@ int sparse_conv_forward_dma_impl(const void* xs, int c_in, const void* packed16,
 int conv16_tile_order_impl(const int32_t* nbr, int nbr_stride, int K, int n_out, const Conv16LaunchInfo& info,
                            int32_t* work /* [parts * tiles] scratch */, int32_t* order /* [parts * tiles] */,
                            hipStream_t st, const uint32_t* lmask = nullptr /* line-compressed table's masks instead of nbr */);
+// EQUAL-WORK PARTS of a launch of several rounds (isf_spconv16.h): info = the launch's UNIFORM plan (query with
+// ISF_CONV_MODE_UNIFORM_TILES); work [2 * parts * info.full] scratch; table [conv16_part_table_ints].  Run the conv with
+// mode | kConvModePartTable and the table as `order`.  raster: slots in tile order (ISF_ENC_DIAG_LAUNCH_ORDER).
+bool conv16_parts_apply(const Conv16LaunchInfo& info, bool several_rounds = false);
+int conv16_part_table_impl(const int32_t* nbr, const uint32_t* lmask, int nbr_stride, int K, int n_out, int c_in, int c_out,
+                           const Conv16LaunchInfo& info, bool raster, int32_t* work, int32_t* table, hipStream_t st,
+                           bool equal_rows = false /* the plan's own parts: the order alone (ISF_ENC_DIAG_UNIFORM_TILES) */);
 // isf_voxelize.hip: hand-written stable LSD radix sort (wave multi-split): idx_sorted = stable order of the keys' low bits
 int stable_sort_u32_impl(Arena& a, const uint32_t* keys, int n, int key_bits, int* idx_sorted, hipStream_t st);
 // ROW SORT of a deep SubM launch (round 6): the positions of a launch's part are dealt to its rows in the order of their

@@ -225,7 +225,7 @@ struct LevelState {
   StageTables cache_stage;   // staging tables of cache_nbr (slots == nullptr: not built)
   const int32_t* cache_order;   // tile order / table of cache_nbr for a (cache_order_cin -> cache_order_cout) launch, or nullptr
   int cache_order_cin, cache_order_cout;
-  bool cache_order_is_table;
+  int cache_order_kind;         // kOrderPerm | kOrderTable | kOrderParts
   const uint32_t* cache_lmask;  // non-null: cache_nbr is LINE-COMPRESSED (lines [ks0 * ks1][stride]) with these tap masks
   ConvCuPlan cache_cu;          // unit plan of cache_nbr for the one-workgroup-per-CU kernel (n_out == 0: not built)
   const int32_t* cache_rowmap;  // ROW SORT of cache_nbr (conv_row_sort_impl): position -> row, or nullptr
@@ -242,24 +242,51 @@ static int build_cu_plan(Arena& a, const int32_t* nbr, int stride, int K, int n_
   return conv_cu_plan_impl(nbr, stride, K, n_out, buf, plan, sg, cap);
 }
 
+enum { kOrderPerm = 0, kOrderTable = 1, kOrderParts = 2 };   // what a launch's `order` holds
+static int order_mode_bit(int kind) { return kind == kOrderTable ? kConvModeTileTable : (kind == kOrderParts ? kConvModePartTable : 0); }
+
 // tile order / tile table of one conv launch over a neighbour table, built behind the table on the geometry stream.  A
 // launch of the tile kernel that is resident in one round gets a TILE TABLE (conv16_table_part: the groups dealt to the
-// compute units by equal work; *is_table = true, run the conv with mode | kConvModeTileTable); the LDS-DMA kernel's launches keep the
-// permutation of uniform tiles (conv16_tile_order_impl); *order stays nullptr when neither applies.
+// compute units by equal work; *kind = kOrderTable, run the conv with mode | kConvModeTileTable); the LDS-DMA kernel's launches keep the
+// permutation of uniform tiles (conv16_tile_order_impl).  A launch of SEVERAL ROUNDS (uniform tiles) gets a PART TABLE
+// (conv16_part_table_impl: equal-work XCD parts, heavy tiles first -- in tile order when !order_ok; *kind = kOrderParts, run
+// the conv with mode | kConvModePartTable) when parts_ok.  *order stays nullptr when none applies.
 static int build_tile_order(Arena& a, const isf_conv_layer& ly, int K, const int32_t* nbr, int stride, int n_out,
                             int mode, bool dma, const int32_t** order, hipStream_t sg, const uint32_t* lmask = nullptr,
-                            bool* is_table = nullptr, bool tables = true,
-                            const int32_t* coors_out = nullptr /* [n_out][4] (b, z, y, x) of the output rows */, int band = 0) {
+                            int* kind = nullptr, bool tables = true,
+                            const int32_t* coors_out = nullptr /* [n_out][4] (b, z, y, x) of the output rows */, int band = 0,
+                            bool order_ok = true, bool parts_ok = false) {
   *order = nullptr;
-  if (is_table) *is_table = false;
+  if (kind) *kind = kOrderPerm;
   Conv16LaunchInfo info;
+  if (parts_ok && kind && n_out > 0) {   // the launch's uniform plan: several rounds?
+    const int um = mode | ISF_CONV_MODE_UNIFORM_TILES;
+    if (dma)
+      ISF_TRY(sparse_conv_forward_dma_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, nullptr,
+                                           nullptr, nullptr, 0, nullptr, um, sg, nullptr, &info));
+    else
+      ISF_TRY(sparse_conv_forward_f16x3_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, nullptr,
+                                             nullptr, nullptr, 0, nullptr, um, sg, nullptr, &info));
+    if (conv16_parts_apply(info)) {
+      const int parts = conv16_order_parts(info), T = conv16_parts_tiles(info.full, parts);
+      int32_t *work = nullptr, *table = nullptr;
+      ISF_TRY(a.alloc_n(&work, (size_t)2 * T));
+      ISF_TRY(a.alloc_n(&table, (size_t)conv16_part_table_ints(parts, conv16_parts_cap(T, parts))));
+      ISF_TRY(conv16_part_table_impl(nbr, lmask, stride, K, n_out, ly.c_in, ly.c_out, info, !order_ok, work, table, sg,
+                                     (mode & ISF_CONV_MODE_UNIFORM_TILES) != 0));
+      *order = table;
+      *kind = kOrderParts;
+      return ISF_OK;
+    }
+  }
+  if (!order_ok) return ISF_OK;
   if (dma)
     ISF_TRY(sparse_conv_forward_dma_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, nullptr,
                                          nullptr, nullptr, 0, nullptr, mode, sg, nullptr, &info));
   else
     ISF_TRY(sparse_conv_forward_f16x3_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, nullptr,
                                            nullptr, nullptr, 0, nullptr, mode, sg, nullptr, &info));
-  if (!dma && is_table && tables && !lmask && conv16_table_applies(info) && n_out >= 16 * info.cus_per_xcd) {
+  if (!dma && kind && tables && !lmask && conv16_table_applies(info) && n_out >= 16 * info.cus_per_xcd) {
     const int ng = ceil_div(n_out, 16);
     int32_t *masks = nullptr, *work = nullptr, *table = nullptr;
     ISF_TRY(a.alloc_n(&masks, (size_t)ng));
@@ -268,7 +295,7 @@ static int build_tile_order(Arena& a, const isf_conv_layer& ly, int K, const int
     ISF_TRY(conv_group_masks_impl(nbr, stride, K, n_out, masks, work, sg));
     ISF_TRY(conv16_tile_table_impl(work, n_out, info, table, sg));
     *order = table;
-    *is_table = true;
+    *kind = kOrderTable;
     return ISF_OK;
   }
   if (!conv16_order_applies(info)) {
@@ -388,7 +415,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
   L.cache_nbr = nullptr;
   L.cache_order = nullptr;
   L.cache_order_cin = L.cache_order_cout = 0;
-  L.cache_order_is_table = false;
+  L.cache_order_kind = kOrderPerm;
   L.cache_cu = ConvCuPlan();
   L.cache_lmask = nullptr;
   L.cache_rowmap = L.cache_nbr_sorted = nullptr;
@@ -441,16 +468,23 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
                              : ((stage_mask == 0 || ((stage_mask >> i) & 1u)) ? stage_opt : 0);
     StageTables stg;
     const int32_t* order = nullptr;
-    bool order_is_table = false;
+    int order_kind = kOrderPerm;
     // 256-column layers: one workgroup per CU over units of equal work (isf_spconv_cu.hip; fp32-class mode only)
     const bool cu = use16 && cu_units && srows == 0 && conv_mode == 0 && sparse_conv_cu_supported(ly.c_in, ly.c_out);
     ConvCuPlan cu_plan;
-    const bool want_order = use16 && tile_order && srows == 0 && !cu;
+    // equal-work parts for the launches of several rounds; the uniform-tiles diagnostic keeps the
+    // equal-row parts (with the launch-order diagnostic: no table at all), and so do the opt-ins whose tables are cut for
+    // them (narrow row sort, band order)
+    const bool plan_ok = use16 && srows == 0 && !cu;
+    const bool want_tile_order = plan_ok && tile_order;
     // this layer's conv mode on the tile kernel, as the launch and everything planned for the launch (row sort, tile order) see it
     const int layer_mode = conv_mode | (fp32_class && ly.c_out >= 128 ? deep_opts : 0) |
                            (chunk_split && use16 && !cu && srows == 0 && ly.c_out == 256 && ly.c_in >= 128 ? ISF_CONV_MODE_CHUNK_SPLIT : 0);
     // narrow layers: LDS-DMA gathers (isf_spconv_dma.hip); the timing diagnostics and ISF_CONV_MODE_NO_SHARING exist on the gather kernel
     const bool dma = use16 && dma_gather && srows == 0 && dg == 0 && sparse_conv_dma_supported(ly.c_in, ly.c_out);
+    const bool parts_ok = plan_ok && dg == 0 && !((conv_mode & ISF_CONV_MODE_UNIFORM_TILES) && !tile_order) && !band_order && !(dma && narrow_sort) &&
+                          (dma || (layer_mode & (ISF_CONV_MODE_DEEP | ISF_CONV_MODE_CHUNK_SPLIT)) == 0);
+    const bool want_order = want_tile_order || parts_ok;   // build_tile_order: a tile order / table, or a part table
     const uint32_t* lmask = nullptr;   // non-null: `nbr` is the line-compressed table of this layer
     const int nx = ly.ksize[2];
     // a rulebook may be line-compressed when every layer that reads it runs the LDS-DMA kernel: for a SubM table, all the
@@ -541,7 +575,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
         if (srows > 0) ISF_TRY(build_stage_tables(a, nbr, stride, K, &L.cache_stage, sg));
         L.cache_order = nullptr;
         L.cache_order_cin = L.cache_order_cout = 0;
-        L.cache_order_is_table = false;
+        L.cache_order_kind = kOrderPerm;
         L.cache_cu = ConvCuPlan();
         L.cache_rowmap = L.cache_nbr_sorted = nullptr;
         L.cache_lmask_sorted = nullptr;
@@ -554,7 +588,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
           ISF_TRY(build_tile_order(a, ly, K, sort_applies(nbr, stride, n_out) ? L.cache_nbr_sorted : nbr, stride, n_out,
                                    layer_mode, dma, &L.cache_order, sg,
                                    (L.cache_lmask && sort_applies(nbr, stride, n_out)) ? L.cache_lmask_sorted : L.cache_lmask,
-                                   &L.cache_order_is_table, tile_tables, L.coors, band_of(L.shape)));
+                                   &L.cache_order_kind, tile_tables, L.coors, band_of(L.shape), tile_order, parts_ok));
           L.cache_order_cin = ly.c_in;
           L.cache_order_cout = ly.c_out;
         }
@@ -576,7 +610,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
           ISF_TRY(build_tile_order(a, ly, K, sort_applies(nbr, stride, n_out) ? L.cache_nbr_sorted : nbr, stride, n_out,
                                    layer_mode, dma, &L.cache_order, sg,
                                    (L.cache_lmask && sort_applies(nbr, stride, n_out)) ? L.cache_lmask_sorted : L.cache_lmask,
-                                   &L.cache_order_is_table, tile_tables, L.coors, band_of(L.shape)));
+                                   &L.cache_order_kind, tile_tables, L.coors, band_of(L.shape), tile_order, parts_ok));
           L.cache_order_cin = ly.c_in;
           L.cache_order_cout = ly.c_out;
           ISF_TRY(stream_wait_stream(a, st, sg));
@@ -597,7 +631,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
       stg = L.cache_stage;
       if (want_order) {
         order = L.cache_order;
-        order_is_table = L.cache_order_is_table;
+        order_kind = L.cache_order_kind;
       }
       if (stats) stats->pairs[i] = hit ? L.cache_pairs : -(long long)i - 1;
     } else {
@@ -650,8 +684,8 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
         rowmap = rm;
       }
       if (want_order)
-        ISF_TRY(build_tile_order(a, ly, K, nbr, stride, Nx.n, layer_mode, dma, &order, sg, lmask, &order_is_table, tile_tables,
-                                 Nx.coors, band_of(Nx.shape)));
+        ISF_TRY(build_tile_order(a, ly, K, nbr, stride, Nx.n, layer_mode, dma, &order, sg, lmask, &order_kind, tile_tables,
+                                 Nx.coors, band_of(Nx.shape), tile_order, parts_ok));
       if (cu && Nx.n > 0) ISF_TRY(build_cu_plan(a, nbr, stride, K, Nx.n, &cu_plan, sg, cu_cap));
       if (stats) stats->pairs[i] = -(long long)i - 1;
       Nx.cache_cu = ConvCuPlan();
@@ -662,7 +696,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
       Nx.cache_nbr = nullptr;
       Nx.cache_order = nullptr;
       Nx.cache_order_cin = Nx.cache_order_cout = 0;
-      Nx.cache_order_is_table = false;
+      Nx.cache_order_kind = kOrderPerm;
       n_out = Nx.n;
       L = Nx;
       ISF_TRY(stream_wait_stream(a, st, sg));
@@ -686,11 +720,12 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
                                           ly.relu, y, cu_plan, st));
     else if (dma)
       ISF_TRY(sparse_conv_forward_dma_impl(x, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, ly.scale, ly.shift,
-                                           res, ly.relu, y, conv_mode, st, order, nullptr, lmask, nx, rowmap));
+                                           res, ly.relu, y, conv_mode | order_mode_bit(order_kind), st, order, nullptr, lmask,
+                                           nx, rowmap));
     else if (use16)
       ISF_TRY(sparse_conv_forward_f16x3_impl(x, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, ly.scale,
                                              ly.shift, res, ly.relu, y,
-                                             layer_mode | (order_is_table ? kConvModeTileTable : 0) |
+                                             layer_mode | order_mode_bit(order_kind) |
                                                  (ly.c_out == 256 && fp32_class ? one_block : 0),
                                              st, order, nullptr, rowmap));
     else if (sparse_conv_mfma_supported(ly.c_in, ly.c_out))

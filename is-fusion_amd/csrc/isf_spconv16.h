@@ -16,8 +16,9 @@ static constexpr int kMaxTaps = 27;
 static constexpr int kConvModeNarrowTiles = 64;   // the 128-column layers of the large levels on the 4-wave 128-row tile
                                                   // instead of the 8-wave 256-row one (A/B; the encoder's ISF_ENC_DIAG_NARROW_TILES)
 static constexpr int kConvModeTileTable = 1024;   // `order` is a tile table (isf_sparse_conv_tile_table), not a tile order
+static constexpr int kConvModePartTable = 16384;  // `order` is a part table (conv16_part_table_impl): equal-work parts of a launch of several rounds
 // what launch16_rows ignores when it compares `mode` with one of the launch variants
-static constexpr int kConvModeTileBits = ISF_CONV_MODE_UNIFORM_TILES | kConvModeTileTable;
+static constexpr int kConvModeTileBits = ISF_CONV_MODE_UNIFORM_TILES | kConvModeTileTable | kConvModePartTable;
 
 // Modes the exported entry points accept: a BASE mode (one of the values below) | any of the entry point's option bits.
 static constexpr bool conv_mode_is_production(int m) {   // valid results on the production workgroup shapes
@@ -145,6 +146,9 @@ struct Conv16Plan {
   int part_rows;    // rows per part (a multiple of 16; the parts split the rows evenly whatever the tile mix)
 };
 
+static constexpr int kPlanParts = -2;   // Conv16Plan::half of a launch that reads a PART TABLE (equal-work parts, below):
+                                        // `full` slots per part, slot j names one tile of the uniform plan or -1
+
 // tile j of part `part` -> its first row, the first row past its share (the part's end or n_out, whichever comes
 // first) and whether it is a half tile; false when the tile is empty.  Host and device: tests/test_tile_plan.py walks
 // the same arithmetic the kernel uses.
@@ -159,6 +163,17 @@ __host__ __device__ inline bool conv16_tile_rows(Conv16Plan plan, int TM, int n_
   return off < plan.part_rows && row0 < n_out;
 }
 
+// slot j of part `part` of a launch on a PART TABLE (plan.half == kPlanParts, plan.full = slots per part; the table:
+// first [parts + 1] | class bounds [3] | slots [parts][plan.full]) -> the rows of the uniform tile the slot names; false for a
+// slot without a tile.  Host and device (tests/test_part_plan.py walks a whole grid through it).
+__host__ __device__ inline bool conv16_part_tile_rows(Conv16Plan plan, int TM, int n_out, int parts, const int32_t* table,
+                                                      int part, int j, int& row0, int& row_end, bool& half) {
+  const int t = table[parts + 1 + 3 + part * plan.full + j];
+  if (t < 0) return false;
+  const int per = (plan.part_rows + TM - 1) / TM;           // tiles per part of the uniform plan
+  return conv16_tile_rows(Conv16Plan{per, 0, plan.part_rows}, TM, n_out, t / per, t - (t / per) * per, row0, row_end, half);
+}
+
 // order (optional): [parts][full + half] -- the tile workgroup slot j of a part works on (a permutation per part, built
 // by conv16_tile_order_impl so that the tiles sharing a CU add up to about the same work).
 __device__ __forceinline__ bool conv16_tile_of_block(int ncb, Conv16Plan plan, int TM, int n_out, int& cb, int& row0,
@@ -169,6 +184,7 @@ __device__ __forceinline__ bool conv16_tile_of_block(int ncb, Conv16Plan plan, i
   int j = bid >> 3;
   cb = ncb == 2 ? xcd & 1 : 0;
   const int part = ncb == 2 ? xcd >> 1 : xcd;
+  if (plan.half == kPlanParts) return conv16_part_tile_rows(plan, TM, n_out, ncb == 2 ? 4 : 8, order, part, j, row0, row_end, half);
   if (plan.half < 0) {   // tile table: (first group, groups) per slot; a tile of <= TM / 32 groups runs as a half tile
     const int g0 = order[2 * (part * plan.full + j)], ng = order[2 * (part * plan.full + j) + 1];
     row0 = g0 * 16;
@@ -247,6 +263,92 @@ static inline Conv16Plan conv16_plan(int n_out, int TM, int ncb, int wgs_per_cu,
   const int rest = groups - plan.full * gt;
   plan.half = rest > 0 ? ceil_div(rest, gt / 2) : 0;
   return plan;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// EQUAL-WORK PARTS of a launch of several rounds.  conv16_plan gives every XCD the same number of
+// ROWS; the steps a tile walks (popcount of the OR of its rows' tap masks, x 32-channel chunks) vary 4x with the density
+// of the scene, an XCD cannot give work away, and the launch ends with the XCD that was dealt the most steps (1.10 x the
+// mean on the benchmark geometry).  Here the launch's uniform tiles -- the SAME tiles, tile t = tile t % full of the plan's
+// part t / full -- are dealt to the XCDs as contiguous runs of about equal WEIGHT (steps + a constant for the tile's fixed
+// cost), and inside a run the heavy tiles go to the first workgroup slots, so that what drains last is light.  Every XCD
+// still owns one contiguous row range; every row is computed by the same tile: bit-identical.
+// PART TABLE (device, built behind the neighbour table): first[parts + 1] | class bounds [3] | slots [parts][cap], slot j of
+// part p = the tile it works on, -1 for none.  The launch passes Conv16Plan{cap, kPlanParts, part_rows} and the table as
+// `order`; its grid is 8 * cap, sized from n_out alone.
+static constexpr int kPartClasses = 4;         // work classes of the order inside a part
+// Fixed cost of a tile in steps = (intercept b of the fit loop_us = a * steps + b, + prologue + epilogue) / a, from the
+// per-workgroup trace of the launch shape on the benchmark geometry (tools/conv_trace.py --level 0 | 1,
+// profiles/r06_dma_trace.txt and profiles/r07_launch_balance.txt):
+//   32 -> 32 (level 0): (2.5 + 3.3 + 2.0) us / 0.925 us per step =  8 steps
+//   64 -> 64 (level 1): (16.1 + 2.8 + 5.6) us / 0.929 us per step = 26 steps
+// A shape without a trace of its own gets 0: its tiles are weighed by their steps alone.
+__host__ __device__ inline int conv16_tile_fixed_steps(int c_in, int c_out) {
+  if (c_in == 32 && c_out == 32) return 8;
+  if (c_in == 64 && c_out == 64) return 26;
+  return 0;
+}
+// tiles of the plan a part table deals out (plans without half tiles only)
+__host__ __device__ inline int conv16_parts_tiles(int full, int parts) { return full * parts; }
+// slots per part: the even share of the tiles + 1/8 + 1.  The census of the benchmark geometry needs +-7 % (the heaviest
+// part's tiles are 0.93 x, the lightest's 1.07 x the even share); 12.5 % covers it with room for denser scenes, and what
+// exceeds it is clamped (conv16_part_firsts), never lost.  An idle slot costs one workgroup that reads one word and exits.
+__host__ __device__ inline int conv16_parts_cap(int T, int parts) {
+  const int even = (T + parts - 1) / parts;
+  return even + (even + 7) / 8 + 1;
+}
+__host__ __device__ inline int conv16_part_table_ints(int parts, int cap) { return parts + 1 + 3 + parts * cap; }
+// W: inclusive prefix of the tile weights.  Unclamped cut k (0 < k < parts): behind the first tile whose prefix reaches
+// k / parts of the total
+__host__ __device__ inline int conv16_part_cut(const int32_t* W, int T, int parts, int k) {
+  if (k <= 0) return 0;
+  if (k >= parts) return T;
+  const long long target = (long long)k * (long long)W[T - 1];
+  int lo = 0, hi = T;                          // first t with W[t] * parts >= target
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if ((long long)W[mid] * parts >= target) hi = mid; else lo = mid + 1;
+  }
+  return lo < T ? lo + 1 : T;
+}
+// first[parts + 1]: the cuts, every part clamped to `cap` tiles -- what a part cannot hold goes to the next, and a part
+// takes at least what the parts behind it cannot hold (parts * cap >= T)
+__host__ __device__ inline void conv16_part_firsts(const int32_t* W, int T, int parts, int cap, int32_t* first) {
+  first[0] = 0;
+  for (int k = 1; k < parts; ++k) {
+    int c = conv16_part_cut(W, T, parts, k);
+    const int hi = first[k - 1] + cap, lo = T - (parts - k) * cap;
+    c = c < first[k - 1] ? first[k - 1] : c;
+    c = c > hi ? hi : c;
+    c = c < lo ? lo : c;
+    first[k] = c;
+  }
+  first[parts] = T;
+}
+// class bounds from the histogram of the tile weights (hist[w], w < nbins): bound[q] = the smallest weight with at least
+// (q + 1) / 4 of the tiles at or below it, so the classes hold about a quarter of the tiles each
+__host__ __device__ inline void conv16_class_bounds(const int32_t* hist, int nbins, int32_t bound[3]) {
+  int total = 0, acc = 0, q = 0;               // (weight 0 = a tile without rows: not counted)
+  for (int w = 1; w < nbins; ++w) total += hist[w];
+  for (int w = 1; w < nbins && q < 3; ++w) {
+    acc += hist[w];
+    while (q < 3 && (long long)acc * kPartClasses >= (long long)(q + 1) * total) bound[q++] = w;
+  }
+  while (q < 3) bound[q++] = nbins - 1;
+}
+// 0 = the heaviest class (runs first) .. 3 = the lightest
+__host__ __device__ inline int conv16_work_class(int w, const int32_t bound[3]) {
+  return (w <= bound[2]) + (w <= bound[1]) + (w <= bound[0]);
+}
+// slots of part k: its tiles by class, raster order inside a class (a stable counting sort: x / y-adjacent tiles stay
+// resident together), -1 behind them.  (The device builds the same table a wave per part: conv16_part_table_kernel.)
+__host__ __device__ inline void conv16_part_slots(const int32_t* w /* [T] tile weights */, const int32_t* first, int k, int cap,
+                                                  const int32_t bound[3], bool raster, int32_t* slots /* [cap] */) {
+  int n = 0;
+  for (int c = 0; c < (raster ? 1 : kPartClasses); ++c)
+    for (int t = first[k]; t < first[k + 1]; ++t)
+      if (raster || conv16_work_class(w[t], bound) == c) slots[n++] = t;
+  for (; n < cap; ++n) slots[n] = -1;
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -777,7 +777,7 @@ bool sparse_conv_f16x3_supported(int c_in, int c_out) {
 }
 
 template <int CIN, int NT, int RG, int NW, int MODE = 0>
-static int launch16(bool balance, bool table /* `order` is a tile table (conv16_table_part), not a permutation */, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
+static int launch16(bool balance, int table /* `order` is 1: a tile table (conv16_table_part), 2: a part table (conv16_part_table_impl), 0: a permutation */, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
                     const int32_t* nbr, int nbr_stride, int n_out, const float* scale, const float* shift,
                     const uint4* residual, int relu, uint4* ys, hipStream_t st, const int32_t* order,
                     Conv16LaunchInfo* query, long long* trace = nullptr, const int32_t* rowmap = nullptr) {
@@ -798,8 +798,13 @@ static int launch16(bool balance, bool table /* `order` is a tile table (conv16_
   const int ncb = cout / (16 * NT);
   ISF_REQUIRE(ncb == 1 || ncb == 2, ISF_ERR_UNSUPPORTED, "sparse_conv16: %d column blocks", ncb);
   Conv16Plan plan = conv16_plan(n_out, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
-                                cus_per_xcd.load(std::memory_order_relaxed), balance && RG > 1);
-  if (table && !query) plan = Conv16Plan{wgs_per_cu.load(std::memory_order_relaxed) * cus_per_xcd.load(std::memory_order_relaxed),
+                                cus_per_xcd.load(std::memory_order_relaxed), balance && RG > 1 && table != 2);
+  if (table == 2 && !query) {   // equal-work parts of the uniform plan: conv16_parts_cap slots per part
+    ISF_REQUIRE(plan.half == 0, ISF_ERR_ARG, "sparse_conv16: a part table needs the uniform plan");
+    const int parts = ncb == 2 ? 4 : 8;
+    plan = Conv16Plan{conv16_parts_cap(conv16_parts_tiles(plan.full, parts), parts), kPlanParts, plan.part_rows};
+  }
+  if (table == 1 && !query) plan = Conv16Plan{wgs_per_cu.load(std::memory_order_relaxed) * cus_per_xcd.load(std::memory_order_relaxed),
                                          -1, plan.part_rows};
   if (query) {   // what this launch would look like (conv16_tile_order_impl works on exactly these tiles)
     *query = Conv16LaunchInfo{plan.full, plan.half, plan.part_rows, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
@@ -858,7 +863,7 @@ static int launch16_rows(int mode, const uint4* xs, const uint4* wpk, const floa
   // isf_spconv_deep.hip (LDS-DMA gathers + one instruction stream per step)
   const bool use_deep = (mode & ISF_CONV_MODE_DEEP) != 0;
   mode &= ~ISF_CONV_MODE_DEEP;
-#define ISF_ARGS16 (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, (mode & kConvModeTileTable) != 0 && order != nullptr, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, nullptr, rowmap
+#define ISF_ARGS16 (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, (order == nullptr ? 0 : (mode & kConvModeTileTable) ? 1 : (mode & kConvModePartTable) ? 2 : 0), xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, nullptr, rowmap
   // ISF_CONV_MODE_ONE_BLOCK_4W / _8W (round 5 experiment, valid results, bit-identical): the 256-COLUMN layers as ONE column block
   // -- a workgroup owns all 256 output columns of its rows, so a row is gathered ONCE per tap and chunk instead of once per
   // column block.  The phase trace (profiles/r05_att_256.txt) shows the step bound by the vector-memory issue path (a
@@ -929,7 +934,7 @@ static int launch16_rows(int mode, const uint4* xs, const uint4* wpk, const floa
     if (cout == 256 && n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4>(ISF_ARGS16);
   }
   if constexpr (NT == 8 && CIN >= 128) {
-    if (use_deep && !rowmap && (mode & ~kConvModeTileBits) == 0 && sparse_conv_deep_supported(CIN, cout))
+    if (use_deep && !rowmap && (mode & ~kConvModeTileBits) == 0 && !(mode & kConvModePartTable) && sparse_conv_deep_supported(CIN, cout))
       return sparse_conv_forward_deep_impl((mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, (mode & kConvModeTileTable) != 0 && order != nullptr, xs, CIN, wpk, winv, K, cout,
                                            nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query);
   }
@@ -1165,6 +1170,128 @@ int conv16_tile_order_impl(const int32_t* nbr, int nbr_stride, int K, int n_out,
     hipLaunchKernelGGL(conv16_tile_work_kernel, dim3(parts * tiles), dim3(256), 0, st, nbr, nbr_stride, K, n_out, plan,
                        info.TM, work);
   hipLaunchKernelGGL(conv16_tile_order_kernel, dim3(parts), dim3(64), 0, st, work, tiles, info.cus_per_xcd, order);
+  ISF_LAUNCH_CHECK();
+  return ISF_OK;
+}
+
+// ------------------------------------------------------------------------------------- part table (isf_spconv16.h)
+// weight of every uniform tile of a launch: steps (popcount of the OR of its rows' tap masks x `mult` chunks) + `fixed`;
+// 0 for a tile without rows.  nbr = the dense table, or (lmask != nullptr) the line-compressed table's masks decide.
+__global__ __launch_bounds__(256) void conv16_tile_steps_kernel(const int32_t* __restrict__ nbr, const uint32_t* __restrict__ lmask,
+                                                                int nbr_stride, int K, int n_out, Conv16Plan plan, int TM,
+                                                                int mult, int fixed, int32_t* __restrict__ w) {
+  const int part = blockIdx.x / plan.full, t = blockIdx.x - part * plan.full;
+  __shared__ unsigned m_or;
+  if (threadIdx.x == 0) m_or = 0u;
+  __syncthreads();
+  int row0 = 0, row_end = 0;
+  bool half = false;
+  const bool live = conv16_tile_rows(plan, TM, n_out, part, t, row0, row_end, half);
+  if (live) {
+    unsigned m = 0u;
+    for (int r = threadIdx.x; r < TM; r += 256) {
+      const int row = row0 + r;
+      if (row < row_end) {
+        if (lmask) m |= lmask[row];
+        else
+          for (int k = 0; k < K; ++k) m |= (nbr[(size_t)k * nbr_stride + row] >= 0 ? 1u : 0u) << k;
+      }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m |= (unsigned)__shfl_xor((int)m, d, 64);
+    if ((threadIdx.x & 63) == 0 && m) atomicOr(&m_or, m);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) w[blockIdx.x] = live ? __popc(m_or) * mult + fixed : 0;
+}
+
+// one workgroup: prefix of the weights, the cuts (thread 0 walks the header's arithmetic), then a wave per part deals the
+// part's tiles to its slots by work class (stable: raster order inside a class)
+__global__ __launch_bounds__(512) void conv16_part_table_kernel(const int32_t* __restrict__ w, int T, int parts, int cap,
+                                                                int flags /* 1: slots in tile order, 2: equal-row parts (the plan's own) */,
+                                                                int32_t* __restrict__ W /* [T] scratch */,
+                                                                int32_t* __restrict__ table) {
+  __shared__ int32_t hist[256], sums[512], first_s[9], bound_s[3];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const bool raster = (flags & 1) != 0;
+  if (tid < 256) hist[tid] = 0;
+  __syncthreads();
+  const int C = (T + 511) / 512, lo = tid * C < T ? tid * C : T, hi = lo + C < T ? lo + C : T;
+  int s = 0;
+  for (int i = lo; i < hi; ++i) {
+    const int wi = w[i];
+    s += wi;
+    atomicAdd(&hist[wi < 255 ? wi : 255], 1);
+  }
+  sums[tid] = s;
+  __syncthreads();
+  for (int d = 1; d < 512; d <<= 1) {        // inclusive scan of the threads' sums
+    const int v = tid >= d ? sums[tid - d] : 0;
+    __syncthreads();
+    sums[tid] += v;
+    __syncthreads();
+  }
+  int run = sums[tid] - s;
+  for (int i = lo; i < hi; ++i) {
+    run += w[i];
+    W[i] = run;
+  }
+  __threadfence_block();
+  __syncthreads();
+  if (tid == 0) {
+    if (flags & 2)
+      for (int k = 0; k <= parts; ++k) first_s[k] = k * (T / parts);
+    else
+      conv16_part_firsts(W, T, parts, cap, first_s);
+    conv16_class_bounds(hist, 256, bound_s);
+    for (int k = 0; k <= parts; ++k) table[k] = first_s[k];
+    for (int q = 0; q < 3; ++q) table[parts + 1 + q] = bound_s[q];
+  }
+  __syncthreads();
+  for (int p = wave; p < parts; p += 8) {
+    const int f0 = first_s[p], n = first_s[p + 1] - f0;
+    int32_t* out = table + parts + 4 + (size_t)p * cap;
+    if (raster) {
+      for (int j = lane; j < cap; j += 64) out[j] = j < n ? f0 + j : -1;
+      continue;
+    }
+    int base[kPartClasses];
+#pragma unroll
+    for (int q = 0; q < kPartClasses; ++q) base[q] = 0;
+    for (int j0 = 0; j0 < n; j0 += 64) {
+      const int j = j0 + lane, c = j < n ? conv16_work_class(w[f0 + j], bound_s) : -1;
+#pragma unroll
+      for (int q = 0; q + 1 < kPartClasses; ++q) base[q + 1] += __popcll(__ballot(c == q));
+    }
+#pragma unroll
+    for (int q = 1; q < kPartClasses; ++q) base[q] += base[q - 1];     // first slot of every class
+    for (int j0 = 0; j0 < n; j0 += 64) {
+      const int j = j0 + lane, c = j < n ? conv16_work_class(w[f0 + j], bound_s) : -1;
+#pragma unroll
+      for (int q = 0; q < kPartClasses; ++q) {
+        const unsigned long long m = __ballot(c == q);
+        if (c == q) out[base[q] + __popcll(m & ((1ull << lane) - 1ull))] = f0 + j;
+        base[q] += __popcll(m);
+      }
+    }
+    for (int j = n + lane; j < cap; j += 64) out[j] = -1;
+  }
+}
+
+bool conv16_parts_apply(const Conv16LaunchInfo& info, bool several_rounds) {
+  return info.TM > 0 && info.half == 0 && info.full > 0 && (several_rounds || info.full > info.wgs_per_cu * info.cus_per_xcd);
+}
+
+int conv16_part_table_impl(const int32_t* nbr, const uint32_t* lmask, int nbr_stride, int K, int n_out, int c_in, int c_out,
+                           const Conv16LaunchInfo& info, bool raster, int32_t* work, int32_t* table, hipStream_t st,
+                           bool equal_rows) {
+  ISF_REQUIRE(info.half == 0 && info.full > 0 && info.TM > 0, ISF_ERR_ARG, "part table: the launch plan is not uniform tiles");
+  const int parts = conv16_order_parts(info), T = conv16_parts_tiles(info.full, parts), cap = conv16_parts_cap(T, parts);
+  const Conv16Plan plan{info.full, 0, info.part_rows};
+  hipLaunchKernelGGL(conv16_tile_steps_kernel, dim3(T), dim3(256), 0, st, nbr, lmask, nbr_stride, K, n_out, plan, info.TM,
+                     c_in / 32, conv16_tile_fixed_steps(c_in, c_out), work);
+  hipLaunchKernelGGL(conv16_part_table_kernel, dim3(1), dim3(512), 0, st, work, T, parts, cap, (raster ? 1 : 0) | (equal_rows ? 2 : 0),
+                     work + T, table);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
@@ -1509,6 +1636,58 @@ int isf_sparse_conv_forward_f16x3_tiled(const void* features_split, int num_in, 
   return isf::sparse_conv_forward_f16x3_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out,
                                              scale, shift, residual_split, relu, out_split, mode | isf::kConvModeTileTable,
                                              isf::as_stream(stream), table);
+}
+
+int isf_sparse_conv_part_table(const int32_t* table_nbr, const uint32_t* mask, int nbr_stride, int num_taps, int num_out,
+                               int c_in, int c_out, int mode, int flags, int32_t* work, int work_capacity, int32_t* part_table,
+                               int table_capacity, int* info, isf_stream_t stream) {
+  ISF_REQUIRE(table_nbr && work && part_table && info && num_out >= 0 && (flags & ~7) == 0, ISF_ERR_ARG,
+              "sparse_conv_part_table: bad arguments");
+  info[0] = info[1] = info[2] = info[3] = 0;
+  if (num_out == 0) return ISF_OK;
+  const bool dma = (mode & ISF_CONV_MODE_DMA_PLAN) != 0;
+  const int base = mode & ~ISF_CONV_MODE_DMA_PLAN;
+  ISF_REQUIRE(isf::conv_mode_is_production(base), ISF_ERR_ARG, "sparse_conv_part_table: mode %d", mode);
+  ISF_REQUIRE(dma ? isf::sparse_conv_dma_supported(c_in, c_out) : isf::sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
+              "sparse_conv_part_table: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
+  ISF_REQUIRE(dma || !mask, ISF_ERR_ARG, "sparse_conv_part_table: only the LDS-DMA kernel reads a line-compressed table");
+  isf::Conv16LaunchInfo li;   // the uniform plan of the launch
+  if (dma)
+    ISF_TRY(isf::sparse_conv_forward_dma_impl(nullptr, c_in, nullptr, num_taps, c_out, table_nbr, nbr_stride, num_out, nullptr,
+                                              nullptr, nullptr, 0, nullptr, base | ISF_CONV_MODE_UNIFORM_TILES,
+                                              isf::as_stream(stream), nullptr, &li));
+  else
+    ISF_TRY(isf::sparse_conv_forward_f16x3_impl(nullptr, c_in, nullptr, num_taps, c_out, table_nbr, nbr_stride, num_out, nullptr,
+                                                nullptr, nullptr, 0, nullptr, base | ISF_CONV_MODE_UNIFORM_TILES,
+                                                isf::as_stream(stream), nullptr, &li));
+  if (!isf::conv16_parts_apply(li, (flags & 1) != 0)) return ISF_OK;
+  const int parts = isf::conv16_order_parts(li), T = isf::conv16_parts_tiles(li.full, parts), cap = isf::conv16_parts_cap(T, parts);
+  ISF_REQUIRE(2 * T <= work_capacity && isf::conv16_part_table_ints(parts, cap) <= table_capacity, ISF_ERR_ARG,
+              "sparse_conv_part_table: %d tiles need %d work and %d table ints", T, 2 * T, isf::conv16_part_table_ints(parts, cap));
+  info[0] = parts; info[1] = cap; info[2] = T; info[3] = isf::conv16_part_table_ints(parts, cap);
+  return isf::conv16_part_table_impl(table_nbr, mask, nbr_stride, num_taps, num_out, c_in, c_out, li, (flags & 2) != 0, work,
+                                     part_table, isf::as_stream(stream), (flags & 4) != 0);
+}
+
+int isf_sparse_conv_forward_parts(const void* features_split, int num_in, int c_in, const void* packed16, int num_taps,
+                                  int taps_per_line, int c_out, const int32_t* table_nbr, const uint32_t* mask, int nbr_stride,
+                                  int num_out, const float* scale, const float* shift, const void* residual_split, int relu,
+                                  void* out_split, int mode, const int32_t* part_table, isf_stream_t stream) {
+  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && c_in > 0 && c_out > 0 && num_taps > 0 && part_table, ISF_ERR_ARG,
+              "sparse_conv_forward_parts: bad arguments");
+  if (num_out == 0) return ISF_OK;
+  ISF_REQUIRE(features_split && packed16 && table_nbr && out_split && ((scale == nullptr) == (shift == nullptr)), ISF_ERR_ARG,
+              "sparse_conv_forward_parts: null pointer");
+  const bool dma = (mode & ISF_CONV_MODE_DMA_PLAN) != 0;
+  const int base = mode & ~ISF_CONV_MODE_DMA_PLAN;
+  ISF_REQUIRE(isf::conv_mode_is_production(base) && (dma || !mask), ISF_ERR_ARG, "sparse_conv_forward_parts: mode %d", mode);
+  if (dma)
+    return isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table_nbr, nbr_stride, num_out,
+                                             scale, shift, residual_split, relu, out_split, base | isf::kConvModePartTable,
+                                             isf::as_stream(stream), part_table, nullptr, mask, taps_per_line);
+  return isf::sparse_conv_forward_f16x3_impl(features_split, c_in, packed16, num_taps, c_out, table_nbr, nbr_stride, num_out,
+                                             scale, shift, residual_split, relu, out_split, base | isf::kConvModePartTable,
+                                             isf::as_stream(stream), part_table);
 }
 
 // conv16_table_part walked on the host (tests, tools; no device work): work [num_groups] -> tiles [parts][wgs * cus][2]

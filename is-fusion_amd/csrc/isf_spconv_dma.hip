@@ -383,7 +383,7 @@ bool sparse_conv_dma_supported(int c_in, int c_out) {
 // 3 workgroups per CU) 64 -> 64 0.740 -> 0.768 ms per step; 4 waves x 64 rows (RG = 4: twice the MFMAs per step and
 // barrier, 3 workgroups per CU) 0.770 -> 0.865 -- the resident workgroups are what hides the loads' round trip.
 template <int CIN, int NT, int MODE, bool LINES, int NW = 4, int RG = 2>
-static int launch_dma(bool balance, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
+static int launch_dma(bool balance, bool parts /* `order` is a part table (conv16_part_table_impl) */, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
                       const int32_t* nbr, const uint32_t* lmask, int nx, int nbr_stride, int n_out, const float* scale,
                       const float* shift, const uint4* residual, int relu, uint4* ys, hipStream_t st,
                       const int32_t* order, Conv16LaunchInfo* query, const int32_t* rowmap, long long* trace) {
@@ -402,8 +402,12 @@ static int launch_dma(bool balance, const uint4* xs, const uint4* wpk, const flo
     wgs_per_cu.store(occ > 0 ? occ : 1, std::memory_order_release);
   }
   const int ncb = cout / (16 * NT);
-  const Conv16Plan plan = conv16_plan(n_out, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
-                                      cus_per_xcd.load(std::memory_order_relaxed), balance);
+  Conv16Plan plan = conv16_plan(n_out, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
+                                cus_per_xcd.load(std::memory_order_relaxed), balance && !parts);
+  if (parts && !query) {   // equal-work parts of the uniform plan: conv16_parts_cap slots per part
+    const int np = ncb == 2 ? 4 : 8;
+    plan = Conv16Plan{conv16_parts_cap(conv16_parts_tiles(plan.full, np), np), kPlanParts, plan.part_rows};
+  }
   if (query) {
     *query = Conv16LaunchInfo{plan.full, plan.half, plan.part_rows, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
                               cus_per_xcd.load(std::memory_order_relaxed)};
@@ -420,8 +424,9 @@ static int dispatch_dma(int mode, const uint4* xs, const uint4* wpk, const float
                         const int32_t* nbr, const uint32_t* lmask, int nx, int nbr_stride, int n_out, const float* scale,
                         const float* shift, const uint4* residual, int relu, uint4* ys, hipStream_t st,
                         const int32_t* order, Conv16LaunchInfo* query, const int32_t* rowmap, long long* trace) {
-  const bool balance = (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0;
-#define ISF_ARGS_DMA balance, xs, wpk, winv, K, cout, nbr, lmask, nx, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, rowmap, trace
+  const bool balance = (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, parts = (mode & kConvModePartTable) != 0 && order != nullptr;
+  mode &= ~kConvModePartTable;
+#define ISF_ARGS_DMA balance, parts, xs, wpk, winv, K, cout, nbr, lmask, nx, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, rowmap, trace
   if (lmask) {
     switch (mode & ~kConvOptsDma) {
       case kKernTrace: return launch_dma<CIN, NT, kKernTrace, true>(ISF_ARGS_DMA);   // isf_sparse_conv_dma_trace hands the kernel's bit over as a mode
@@ -519,6 +524,32 @@ int isf_sparse_conv_dma_trace(const void* features_split, int num_in, int c_in, 
   return isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out,
                                            scale, shift, residual_split, relu, out_split, isf::kKernTrace, isf::as_stream(stream),
                                            nullptr, nullptr, mask, taps_per_line, nullptr, trace);
+}
+
+// the same with the launch on a part table (isf_sparse_conv_part_table): the trace of the equal-work plan
+int isf_sparse_conv_dma_trace_parts(const void* features_split, int num_in, int c_in, const void* packed16, int num_taps,
+                                    int taps_per_line, int c_out, const int32_t* table, const uint32_t* mask, int nbr_stride,
+                                    int num_out, const float* scale, const float* shift, const void* residual_split, int relu,
+                                    void* out_split, const int32_t* part_table, long long* trace, int trace_capacity_blocks,
+                                    int* grid_blocks, isf_stream_t stream) {
+  ISF_REQUIRE(num_in >= 0 && num_out > 0 && features_split && packed16 && table && out_split && trace && grid_blocks &&
+                  part_table && trace_capacity_blocks > 0 && ((scale == nullptr) == (shift == nullptr)), ISF_ERR_ARG,
+              "sparse_conv_dma_trace_parts: bad arguments");
+  isf::Conv16LaunchInfo info;   // the uniform plan the table was built for
+  ISF_TRY(isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out,
+                                            scale, shift, residual_split, relu, out_split,
+                                            isf::kKernTrace | ISF_CONV_MODE_UNIFORM_TILES, isf::as_stream(stream), nullptr, &info,
+                                            mask, taps_per_line, nullptr, nullptr));
+  const int parts = isf::conv16_order_parts(info);
+  const int blocks = 8 * isf::conv16_parts_cap(isf::conv16_parts_tiles(info.full, parts), parts);
+  ISF_REQUIRE(info.half == 0 && blocks <= trace_capacity_blocks, ISF_ERR_ARG,
+              "sparse_conv_dma_trace_parts: the launch has %d workgroups, the trace buffer holds %d", blocks,
+              trace_capacity_blocks);
+  *grid_blocks = blocks;
+  return isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out,
+                                           scale, shift, residual_split, relu, out_split,
+                                           isf::kKernTrace | isf::kConvModePartTable, isf::as_stream(stream), part_table, nullptr,
+                                           mask, taps_per_line, nullptr, trace);
 }
 
 }  // extern "C"

@@ -336,6 +336,60 @@ def sparse_conv_forward_dma_lines(features, packed16, K, c_in, c_out, rb, scale=
     return from_half(ys, (rb.num_out, c_out)) if f16io else from_split(ys, (rb.num_out, c_out))
 
 
+class PartTable:
+    """isf_sparse_conv_part_table's result: table int32 [parts + 1 + 3 + parts * cap] (first tile of every part | class
+    bounds | slots), weights int32 [tiles] (steps + the fixed cost per tile; 0 = a tile without rows)."""
+
+    def __init__(self, table, weights, parts, cap, tiles):
+        self.table, self.weights, self.parts, self.cap, self.tiles = table, weights, parts, cap, tiles
+
+
+def part_table(rb, c_in, c_out, mode=0, dma=True, lines=False, several_rounds=False, raster=False, equal_rows=False):
+    """PartTable of the launch the LDS-DMA kernel (dma=True; lines: on the line-compressed table) or the tile kernel would
+    make for this rulebook (equal-work XCD parts, heavy tiles first; raster: tile order inside a part; equal_rows: the
+    plain plan's equal-row parts, for A/B of the order alone), or None when the
+    launch is one round of workgroups and several_rounds is not set."""
+    lib = _lib.load()
+    K = rb.nbr.numel() // rb.stride
+    dev = rb.nbr.device
+    table_nbr, mask = rb.nbr, None
+    if lines:
+        table_nbr, mask, _flag = rulebook_lines(rb, 3)
+    tiles_max = 8 * ((rb.num_out + 8 * 64 - 1) // (8 * 64) + 1)         # 64-row tiles: the smallest the kernels use
+    work = torch.zeros((2 * tiles_max,), dtype=torch.int32, device=dev)
+    table = torch.zeros((12 + tiles_max + tiles_max // 8 + 32,), dtype=torch.int32, device=dev)
+    info = (ctypes.c_int * 4)()
+    _lib.check(lib.isf_sparse_conv_part_table(_lib.ptr(table_nbr), _lib.ptr(mask), rb.stride, K, rb.num_out, c_in, c_out,
+                                              int(mode) | (_lib.CONV_MODE_DMA_PLAN if dma else 0),
+                                              (1 if several_rounds else 0) | (2 if raster else 0) | (4 if equal_rows else 0), _lib.ptr(work),
+                                              work.numel(), _lib.ptr(table), table.numel(), info, _lib.stream()),
+               "isf_sparse_conv_part_table")
+    parts, cap, tiles, ints = (int(v) for v in info)
+    return PartTable(table[:ints], work[:tiles], parts, cap, tiles) if ints else None
+
+
+def sparse_conv_forward_parts(features, packed16, K, c_in, c_out, rb, pt, scale=None, shift=None, residual=None, relu=False,
+                              mode=0, dma=True, lines=False, split_out=False):
+    """the launch of sparse_conv_forward_dma (dma=True) / _dma_lines (lines) / _f16x3 on the part table `pt`
+    (isf_sparse_conv_forward_parts); bit-identical to them.  split_out: the raw output rows (uint8) instead of fp32."""
+    _lib.require_cuda(features)
+    f16io = _is_f16_storage(mode)
+    xs = to_half(features) if f16io else to_split(features)
+    rs = None if residual is None else (to_half(residual) if f16io else to_split(residual))
+    ys = torch.empty(rb.num_out * c_out * (2 if f16io else 4), dtype=torch.uint8, device=features.device)
+    table_nbr, mask, nx = rb.nbr, None, 0
+    if lines:
+        table_nbr, mask, _flag = rulebook_lines(rb, 3)
+        nx = 3
+    _lib.check(_lib.load().isf_sparse_conv_forward_parts(
+        _lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, nx, c_out, _lib.ptr(table_nbr), _lib.ptr(mask), rb.stride,
+        rb.num_out, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(rs), int(bool(relu)), _lib.ptr(ys),
+        int(mode) | (_lib.CONV_MODE_DMA_PLAN if dma else 0), _lib.ptr(pt.table), _lib.stream()), "isf_sparse_conv_forward_parts")
+    if split_out:
+        return ys
+    return from_half(ys, (rb.num_out, c_out)) if f16io else from_split(ys, (rb.num_out, c_out))
+
+
 CU_CAP8_VARIANTS = (9, 15)      # isf_conv_cu_plan.variant values that work on units of <= 8 groups
 
 
@@ -437,7 +491,7 @@ def sparse_conv_trace(xs, packed16, K, c_in, c_out, rb, scale=None, shift=None, 
 
 
 def sparse_conv_dma_trace(xs, packed16, K, c_in, c_out, rb, scale=None, shift=None, residual_split=None, relu=False,
-                          lines=True):
+                          lines=True, part_table=None):
     """DIAGNOSTIC (isf_sparse_conv_dma_trace): one production launch of a narrow layer (c_in, c_out in {32, 64}) on split
     rows `xs` -> (out_split, trace int64 [workgroups, 16]): the eight columns of sparse_conv_trace + wave 0's shader-clock
     cycles at the per-step vmcnt(0) / at the barrier / in the read-and-issue section / in the multiply section, and of the
@@ -452,6 +506,14 @@ def sparse_conv_dma_trace(xs, packed16, K, c_in, c_out, rb, scale=None, shift=No
             table, mask, nx = lt[0], lt[1], 3
     cap = 8 * 1024
     trace = torch.zeros((cap * 16,), dtype=torch.int64, device=xs.device)
+    n = ctypes.c_int(0)
+    if part_table is not None:     # the launch on its equal-work parts (part_table(rb, c_in, c_out, lines=lines))
+        _lib.check(lib.isf_sparse_conv_dma_trace_parts(
+            _lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, nx, c_out, _lib.ptr(table),
+            _lib.ptr(mask) if mask is not None else None, stride, rb.num_out, _lib.ptr(scale), _lib.ptr(shift),
+            _lib.ptr(residual_split), int(bool(relu)), _lib.ptr(ys), _lib.ptr(part_table.table), _lib.ptr(trace), cap,
+            ctypes.byref(n), _lib.stream()), "isf_sparse_conv_dma_trace_parts")
+        return ys, trace[:n.value * 16].view(n.value, 16)
     n = ctypes.c_int(0)
     _lib.check(lib.isf_sparse_conv_dma_trace(_lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, nx, c_out, _lib.ptr(table),
                                              _lib.ptr(mask) if mask is not None else None, stride, rb.num_out,

@@ -73,6 +73,20 @@ def describe(name, tr):
           f"{np.percentile(fin, 90):.1f} max {fin.max():.1f}")
     print(f"   steps per CU: mean {work.mean():.0f} max {work.max():.0f}; corr(CU finish, CU steps) "
           f"{np.corrcoef(fin, work)[0, 1]:.3f}; busy span mean {busy.mean():.1f}")
+    # per XCD: an XCD cannot give work away, so a launch ends with the XCD that was dealt the most
+    xi = xcc.astype(np.int64) & 0xf
+    xs = np.unique(xi)
+    xfin = np.array([(t3[xi == c].max() - base) * TICK_US for c in xs])
+    xsteps = np.array([steps[xi == c].sum() for c in xs])
+    xstart = np.array([(t0[xi == c].max() - base) * TICK_US for c in xs])
+    print("   per XCD   " + " ".join(f"{int(c):>7d}" for c in xs))
+    print("   last end  " + " ".join(f"{v:7.1f}" for v in xfin) + "   us")
+    print("   last start" + " ".join(f"{v:7.1f}" for v in xstart) + "   us")
+    print("   steps     " + " ".join(f"{int(v):7d}" for v in xsteps) + f"   heaviest {xsteps.max() / xsteps.mean():.3f} x mean")
+    print("   tiles     " + " ".join(f"{int((xi == c).sum()):7d}" for c in xs))
+    if len(xs) > 2:
+        print(f"   XCD finish spread {xfin.max() - xfin.min():.1f} us; corr(XCD finish, XCD steps) {np.corrcoef(xfin, xsteps)[0, 1]:.3f}; "
+              f"launch span / mean CU finish {span / fin.mean():.3f}")
     return span
 
 
@@ -82,23 +96,43 @@ def main_narrow(args, rb, dev):
     import torch
     from isfusion_amd import spconv
     C = 32 if args.level == 0 else 64
+    Ci, C = args.cin or C, args.cout or C      # (the level's SubM shape unless --cin / --cout name another narrow shape)
     g = torch.Generator(device="cpu").manual_seed(0)
-    x = torch.randn(rb.num_in, C, generator=g).to(dev)
-    w = (torch.randn(3, 3, 3, C, C, generator=g) * (1.0 / (9 * C)) ** 0.5).to(dev)
+    x = torch.randn(rb.num_in, Ci, generator=g).to(dev)
+    w = (torch.randn(3, 3, 3, Ci, C, generator=g) * (1.0 / (9 * Ci)) ** 0.5).to(dev)
     packed = spconv.pack_filters_f16x3(w)
     xs = spconv.to_split(x)
     scale, shift = torch.ones(C, device=dev), torch.zeros(C, device=dev)
     res = spconv.to_split(torch.randn(rb.num_out, C, generator=g).to(dev))
-    print(f"level {args.level}: {rb.num_out} rows, {C} -> {C}, {'dense table' if args.dense_table else 'line table'}")
+    print(f"level {args.level}: {rb.num_out} rows, {Ci} -> {C}, {'dense table' if args.dense_table else 'line table'}")
     spans = []
     for r in range(args.reps + 2):
-        ys, tr = spconv.sparse_conv_dma_trace(xs, packed, 27, C, C, rb, scale, shift, res, True, lines=not args.dense_table)
+        ys, tr = spconv.sparse_conv_dma_trace(xs, packed, 27, Ci, C, rb, scale, shift, res, True, lines=not args.dense_table)
         torch.cuda.synchronize()
         if r >= 2:
             spans.append((tr[:, 3].max() - tr[tr[:, 3] != 0][:, 0].min()).item() * TICK_US)
     print(f"-- launch span over {args.reps} runs: " + " ".join(f"{s:.1f}" for s in spans) + " us")
     t = tr.cpu().numpy()
     describe("narrow launch", t[:, :8])
+    # the same launch on its part table (equal-work XCD parts; heavy tiles first / in tile order): DESIGN.md section 5.3
+    for raster, even in ((False, False), (True, False), (False, True)):
+        pt = spconv.part_table(rb, Ci, C, lines=not args.dense_table, raster=raster, equal_rows=even)
+        if pt is None:
+            print("   (one round of workgroups: no part table)")
+            break
+        spans = []
+        for r in range(args.reps + 2):
+            ys2, tr2 = spconv.sparse_conv_dma_trace(xs, packed, 27, Ci, C, rb, scale, shift, res, True, lines=not args.dense_table,
+                                                    part_table=pt)
+            torch.cuda.synchronize()
+            if r >= 2:
+                spans.append((tr2[:, 3].max() - tr2[tr2[:, 3] != 0][:, 0].min()).item() * TICK_US)
+        name = ("equal-row parts, " if even else "equal-work parts, ") + ("tile order" if raster else "heavy classes first")
+        print(f"-- {name}: launch span over {args.reps} runs: " + " ".join(f"{s:.1f}" for s in spans) + " us"
+              f"; output equal to the plain launch's: {bool(torch.equal(ys2, ys))}")
+        first = pt.table[:pt.parts + 1].cpu().numpy()
+        print(f"   {pt.tiles} tiles, cap {pt.cap} per part; tiles per part " + " ".join(str(int(b - a)) for a, b in zip(first, first[1:])))
+        describe(name, tr2.cpu().numpy()[:, :8])
     t = t[t[:, 3] != 0]
     cyc = t[:, 8:12].astype(np.float64)
     steps = np.maximum(t[:, 4].astype(np.float64), 1)
@@ -123,6 +157,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", type=int, default=3, choices=[0, 1, 2, 3])
     ap.add_argument("--dense-table", action="store_true", help="levels 0 / 1: the dense neighbour table instead of lines")
+    ap.add_argument("--cin", type=int, default=0, help="levels 0 / 1: input channels (32 | 64) instead of the level's")
+    ap.add_argument("--cout", type=int, default=0, help="levels 0 / 1: output channels (32 | 64) instead of the level's")
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--points", type=int, default=300000)
     ap.add_argument("--reps", type=int, default=5)
