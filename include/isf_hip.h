@@ -966,6 +966,64 @@ int isf_assemble_points(const float* raw, const isf_sweep_t* sweeps, int num_swe
                         const float* point_range /* 6 host floats or NULL */, float* points_out,
                         int32_t* sample_offsets, int32_t* sample_offsets_host, isf_stream_t stream);
 
+/* GT-paste, point side: isf_assemble_points with ObjectSampleV2 folded in --------------------------------------------
+ * replaces, per batch, ObjectSampleV2.remove_points_in_boxes and the concatenation behind it
+ * (datasets/pipelines/transforms_3d.py:1299-1312, :1359-1361), box_np_ops.points_in_rbbox's per-point loop
+ * (core/bbox/box_np_ops.py:718-753, numba on one core) and the translate of every sampled object
+ * (datasets/pipelines/dbsampler.py:769-777).  isf_assemble_points plus two things:
+ *   - a descriptor with is_sweep == ISF_SWEEP_PASTED is a database object: xyz += float32(translation[k]) (one float32
+ *     add per coordinate, BasePoints.translate), fifth column kept as stored, no pose, not tested against the boxes.
+ *     The caller lists a sample's pasted objects FIRST (points.cat([sampled_points, points]), :1361);
+ *   - planes [box_offsets[batch]][6][4] (host, float32): the inward plane equations (n0, n1, n2, d) of each sample's
+ *     removal boxes (surface_equ_3d of corner_to_surfaces_3d, box_np_ops.py:404-423, :694-715); box_offsets
+ *     [batch + 1] (host).  Key-frame and sweep points are tested AFTER the sensor pose and BEFORE the augmentation and
+ *     dropped when, for some box, all six x n0 + y n1 + z n2 + d (float32, left to right, no contraction) are < 0.
+ * More than ISF_PASTE_MAX_BOXES boxes on one sample -> ISF_ERR_UNSUPPORTED before any launch.  Augmentation, range
+ * filter, compaction, outputs and the single stream synchronisation are isf_assemble_points'. */
+#define ISF_SWEEP_PASTED 2
+#define ISF_PASTE_MAX_BOXES 64
+int isf_assemble_points_paste(const float* raw, const isf_sweep_t* sweeps, int num_sweeps, int batch_size,
+                              const isf_point_aug_t* aug /* [batch] or NULL */,
+                              const float* point_range /* 6 host floats or NULL */,
+                              const float* planes /* host */, const int32_t* box_offsets /* host, [batch + 1] */,
+                              float* points_out, int32_t* sample_offsets, int32_t* sample_offsets_host,
+                              isf_stream_t stream);
+
+/* GT-paste, image side: in place on the uploaded uint8 views, before isf_image_prepass ---------------------------------
+ * replaces, per batch, the far-to-near loop of MMDataBaseSamplerV2.sample_all (datasets/pipelines/dbsampler.py:779-831)
+ * with its PIL -> numpy -> PIL round trip of a whole image per object, and paste_obj_v2 (:902-928).  raw holds the
+ * views and, behind them, the database patches (uint8 HWC RGB).  One descriptor per view with the range of its
+ * operations and their bounding box; a thread owns a pixel and applies the operations that hold it in order, so
+ * overlapping rectangles give one deterministic result.  Every byte is numpy's:
+ *   ISF_PASTE_MIX    (:814) v = (uint8) trunc(mixup * orig + one_minus_mixup * v) in float64, orig = the byte before
+ *                    any operation of this call;
+ *   ISF_PASTE_PATCH  (:921-925) v = (uint8) trunc((float32) v * paste_mask) in float64, paste_mask = one_minus_mixup
+ *                    inside the mask rectangle and 1 outside; then v += (uint8) trunc((float32)(mixup_f32 * (float32)
+ *                    patch) * mask) with uint8 wrap-around.
+ * Rectangles are resolved on the host (numpy slice semantics) and lie inside the view.  max_ops_per_view above
+ * ISF_PASTE_MAX_OPS -> ISF_ERR_UNSUPPORTED before any launch.  One asynchronous launch, no host wait. */
+#define ISF_PASTE_MIX 0
+#define ISF_PASTE_PATCH 1
+#define ISF_PASTE_MAX_OPS 256
+typedef struct {
+  int64_t src_offset;      /* byte offset of the view's first pixel in raw */
+  int32_t width, height;
+  int32_t op_begin, op_end; /* this view's operations, in the order the reference applies them */
+  int32_t box_x0, box_y0, box_x1, box_y1; /* bounding box of their rectangles: columns [x0, x1), rows [y0, y1) */
+} isf_paste_view_t;
+
+typedef struct {
+  int64_t patch_offset;    /* ISF_PASTE_PATCH: byte offset in raw of the patch pixel that lands on (x0, y0) */
+  int32_t kind;
+  int32_t x0, y0, x1, y1;  /* columns [x0, x1), rows [y0, y1) of the view */
+  int32_t mask_x0, mask_y0, mask_x1, mask_y1; /* ISF_PASTE_PATCH: where obj_mask is 1 (view coordinates) */
+  int32_t patch_pitch;     /* pixels per patch row */
+} isf_paste_op_t;
+
+int isf_image_paste(uint8_t* raw /* device, in place */, const isf_paste_view_t* views /* device */, int num_views,
+                    const isf_paste_op_t* ops /* device */, int max_ops_per_view, int max_box_w, int max_box_h,
+                    double mixup, double one_minus_mixup, float mixup_f32, isf_stream_t stream);
+
 /* camera input pre-pass: ImageAug3D + ImageNormalize for every view of a batch ---------------------------------------
  * replaces, per batch, the dataloader-side Pillow / torchvision code of ImageAug3D.img_transform
  * (datasets/pipelines/transforms_3d.py:82-112: img.resize(resize_dims) -> img.crop(crop) -> FLIP_LEFT_RIGHT ->

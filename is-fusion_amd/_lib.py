@@ -101,6 +101,29 @@ class ImageView(ctypes.Structure):
     ]
 
 
+class PasteView(ctypes.Structure):
+    """isf_paste_view_t."""
+    _fields_ = [
+        ("src_offset", ctypes.c_int64), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+        ("op_begin", ctypes.c_int32), ("op_end", ctypes.c_int32), ("box_x0", ctypes.c_int32),
+        ("box_y0", ctypes.c_int32), ("box_x1", ctypes.c_int32), ("box_y1", ctypes.c_int32),
+    ]
+
+
+class PasteOp(ctypes.Structure):
+    """isf_paste_op_t."""
+    _fields_ = [
+        ("patch_offset", ctypes.c_int64), ("kind", ctypes.c_int32), ("x0", ctypes.c_int32), ("y0", ctypes.c_int32),
+        ("x1", ctypes.c_int32), ("y1", ctypes.c_int32), ("mask_x0", ctypes.c_int32), ("mask_y0", ctypes.c_int32),
+        ("mask_x1", ctypes.c_int32), ("mask_y1", ctypes.c_int32), ("patch_pitch", ctypes.c_int32),
+    ]
+
+
+SWEEP_PASTED = 2            # ISF_SWEEP_PASTED
+PASTE_MIX, PASTE_PATCH = 0, 1
+PASTE_MAX_BOXES, PASTE_MAX_OPS = 64, 256
+
+
 class SwinA(ctypes.Structure):
     """struct isf_swin_a: the A-operand loader of isf_swin_gemm / isf_swin_row_stats."""
     _fields_ = [("x", c_void_p), ("x2", c_void_p), ("ln_stats", c_void_p), ("ln_gamma", c_void_p), ("ln_beta", c_void_p),
@@ -293,6 +316,12 @@ SIGNATURES = {
                                     ctypes.POINTER(ctypes.c_float), c_void_p, c_void_p,
                                     ctypes.POINTER(ctypes.c_int32), c_void_p]),
     "isf_image_prepass": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "isf_assemble_points_paste": (c_int, [c_void_p, ctypes.POINTER(Sweep), c_int, c_int, ctypes.POINTER(PointAug),
+                                          ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                                          ctypes.POINTER(ctypes.c_int32), c_void_p, c_void_p,
+                                          ctypes.POINTER(ctypes.c_int32), c_void_p]),
+    "isf_image_paste": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, ctypes.c_double,
+                                ctypes.c_double, ctypes.c_float, c_void_p]),
     "isf_transpose_rulebook": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "isf_sparse_conv_backward_input": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                                c_void_p, c_void_p]),

@@ -24,6 +24,13 @@
 //   4. every output pixel picks its (rotated, flipped, cropped) source from that piece or 0, looks up the normalise
 //      table and is stored: a wave writes one 256-byte run of one channel plane per store.
 // No float arithmetic on the device, no atomics, no host data: the call is one asynchronous launch.
+//
+// isf_image_paste runs before it, in place on the same uploaded bytes: the image side of the multi-modal GT-paste
+//   MMDataBaseSamplerV2.sample_all   datasets/pipelines/dbsampler.py:779-831  (far-to-near loop: real-GT mix-back, :814)
+//   MMDataBaseSamplerV2.paste_obj_v2 dbsampler.py:902-928                     (patch with a 5 % soft margin)
+// A thread owns one pixel of one view and applies, in plan order, every operation whose rectangle holds it: overlapping
+// rectangles need no ordering between threads.  float64 / float32 products and sums are written with the _rn
+// intrinsics, so nothing is contracted and every byte is what numpy stores.
 #include <limits.h>
 
 #include "isf_common.h"
@@ -185,9 +192,70 @@ __global__ __launch_bounds__(kImgThreads) void image_prepass_kernel(const uint8_
   }
 }
 
+constexpr int kPasteTileW = 64, kPasteTileH = 4;
+
+__global__ __launch_bounds__(kPasteTileW * kPasteTileH) void image_paste_kernel(
+    uint8_t* __restrict__ raw, const isf_paste_view_t* __restrict__ views, const isf_paste_op_t* __restrict__ ops,
+    double mixup, double one_minus_mixup, float mixup_f32) {
+  const isf_paste_view_t& vw = views[blockIdx.z];      // uniform: scalar loads
+  const int x = vw.box_x0 + blockIdx.x * kPasteTileW + threadIdx.x;
+  const int y = vw.box_y0 + blockIdx.y * kPasteTileH + threadIdx.y;
+  if (x >= vw.box_x1 || y >= vw.box_y1 || x >= vw.width || y >= vw.height) return;
+  uint8_t* px = raw + vw.src_offset + ((size_t)y * vw.width + x) * 3;
+  uint8_t orig[3], v[3];
+  bool loaded = false;
+  for (int i = vw.op_begin; i < vw.op_end; ++i) {
+    const isf_paste_op_t& op = ops[i];                 // uniform index: scalar loads
+    if (x < op.x0 || x >= op.x1 || y < op.y0 || y >= op.y1) continue;
+    if (!loaded) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) orig[c] = v[c] = px[c];
+      loaded = true;
+    }
+    if (op.kind == ISF_PASTE_MIX) {
+      // img[rows, cols] = mixup * origin_img[rows, cols] + (1 - mixup) * img[rows, cols]: float64, stored as uint8
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        v[c] = (uint8_t)(int)__dadd_rn(__dmul_rn(mixup, (double)orig[c]), __dmul_rn(one_minus_mixup, (double)v[c]));
+    } else {
+      const bool inner = x >= op.mask_x0 && x < op.mask_x1 && y >= op.mask_y0 && y < op.mask_y1;
+      const double paste_mask = inner ? one_minus_mixup : 1.0, mask = inner ? 1.0 : 0.0;
+      const uint8_t* pp = raw + op.patch_offset + ((size_t)(y - op.y0) * op.patch_pitch + (x - op.x0)) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const uint8_t kept = (uint8_t)(int)__dmul_rn((double)(float)v[c], paste_mask);
+        const uint8_t add = (uint8_t)(int)__dmul_rn((double)__fmul_rn(mixup_f32, (float)pp[c]), mask);
+        v[c] = (uint8_t)(kept + add);                  // uint8 += wraps
+      }
+    }
+  }
+  if (loaded) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) px[c] = v[c];
+  }
+}
+
 }  // namespace isf
 
 extern "C" {
+
+int isf_image_paste(uint8_t* raw, const isf_paste_view_t* views, int num_views, const isf_paste_op_t* ops,
+                    int max_ops_per_view, int max_box_w, int max_box_h, double mixup, double one_minus_mixup,
+                    float mixup_f32, isf_stream_t stream) {
+  using namespace isf;
+  ISF_REQUIRE(num_views >= 0 && num_views <= 65535 && max_ops_per_view >= 0 && max_box_w >= 0 && max_box_h >= 0,
+              ISF_ERR_ARG, "image_paste: bad sizes");
+  ISF_REQUIRE(max_ops_per_view <= ISF_PASTE_MAX_OPS, ISF_ERR_UNSUPPORTED,
+              "image_paste: %d operations on one view, at most %d are walked", max_ops_per_view, ISF_PASTE_MAX_OPS);
+  if (num_views == 0 || max_ops_per_view == 0 || max_box_w == 0 || max_box_h == 0) return ISF_OK;
+  ISF_REQUIRE(raw && views && ops, ISF_ERR_ARG, "image_paste: null pointer");
+  const dim3 grid(ceil_div(max_box_w, kPasteTileW), ceil_div(max_box_h, kPasteTileH), num_views);
+  ISF_REQUIRE(grid.y <= 65535, ISF_ERR_ARG, "image_paste: region too tall");
+  hipLaunchKernelGGL(image_paste_kernel, grid, dim3(kPasteTileW, kPasteTileH), 0, as_stream(stream), raw, views, ops,
+                     mixup, one_minus_mixup, mixup_f32);
+  ISF_LAUNCH_CHECK();
+  return ISF_OK;
+}
 
 int isf_image_prepass(const uint8_t* raw, const isf_image_view_t* views, int num_views, const int32_t* tables,
                       const float* norm_lut, int out_h, int out_w, float* img_out, isf_stream_t stream) {

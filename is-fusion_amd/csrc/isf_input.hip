@@ -14,6 +14,11 @@
 // ballot + popcount give the in-block rank, kept points are packed in LDS and written back coalesced.
 // pass 1 counts, an exclusive scan over the per-block counts places the blocks, pass 2 recomputes and writes
 // (recomputing is cheaper than a round trip of the transformed points through HBM).
+//
+// isf_assemble_points_paste is the same three launches with the GT-paste of ObjectSampleV2 folded in
+// (transforms_3d.py:1348-1361): database objects are a third descriptor kind (translated, never posed or tested),
+// and key-frame / sweep points that fall inside a sampled box are dropped between the pose and the augmentation.
+// The sample's box planes sit in LDS; every lane reads the same plane at the same time (a broadcast).
 #include <algorithm>
 
 #include "isf_common.h"
@@ -22,6 +27,7 @@ namespace isf {
 
 constexpr int kInBlock = 256;   // points per workgroup
 constexpr int kDim = 5;         // x, y, z, intensity, time
+constexpr int kPlaneFloats = 24;   // 6 planes x (n0, n1, n2, d) per removal box
 
 struct SweepDev {               // device copy of isf_sweep_t + the block prefix
   double rot[9];
@@ -48,10 +54,21 @@ struct AugDev {
 // -> keep flag; p[] holds the transformed point.  Arithmetic types follow the reference: float64 for the sensor pose
 // (numpy promotes the float32 points against the float64 matrices and rounds on every store), float32 for the
 // augmentation (torch ops on the float32 cloud).
+//
+// PASTE: sw.is_sweep == ISF_SWEEP_PASTED is a database object (BasePoints.translate: one float32 add per coordinate,
+// fifth column as stored; not tested against the boxes).  Every other point is tested after its pose against the
+// sample's `num_boxes` removal boxes (points_in_rbbox -> _points_in_convex_polygon_3d_jit, box_np_ops.py:746-752:
+// inside <=> all six x n0 + y n1 + z n2 + d < 0, float32, left to right, nothing contracted).
+template <bool PASTE>
 __device__ __forceinline__ bool transform_point(float p[kDim], const SweepDev& sw, const AugDev* __restrict__ aug,
-                                                const float* __restrict__ range, bool use_range) {
+                                                const float* __restrict__ range, bool use_range,
+                                                const float* planes, int num_boxes) {
   bool keep = true;
-  if (sw.is_sweep) {
+  if (PASTE && sw.is_sweep == ISF_SWEEP_PASTED) {
+    p[0] = __fadd_rn(p[0], (float)sw.trans[0]);
+    p[1] = __fadd_rn(p[1], (float)sw.trans[1]);
+    p[2] = __fadd_rn(p[2], (float)sw.trans[2]);
+  } else if (sw.is_sweep) {
     if (sw.remove_close) keep = !(fabsf(p[0]) < sw.close_radius && fabsf(p[1]) < sw.close_radius);
     const double x = p[0], y = p[1], z = p[2];
     const float rx = (float)(x * sw.rot[0] + y * sw.rot[1] + z * sw.rot[2]);
@@ -63,6 +80,21 @@ __device__ __forceinline__ bool transform_point(float p[kDim], const SweepDev& s
     p[4] = sw.time_lag;
   } else {
     p[4] = 0.f;
+  }
+  if (PASTE && sw.is_sweep != ISF_SWEEP_PASTED) {
+    const float x = p[0], y = p[1], z = p[2];
+    for (int b = 0; b < num_boxes && keep; ++b) {
+      const float* q = planes + b * kPlaneFloats;
+      bool inside = true;
+#pragma unroll
+      for (int k = 0; k < 6 && inside; ++k) {
+        const float s = __fadd_rn(
+            __fadd_rn(__fadd_rn(__fmul_rn(x, q[4 * k]), __fmul_rn(y, q[4 * k + 1])), __fmul_rn(z, q[4 * k + 2])),
+            q[4 * k + 3]);
+        inside = s < 0.f;
+      }
+      keep = !inside;
+    }
   }
   if (aug) {
     const AugDev& a = aug[sw.sample];
@@ -85,14 +117,17 @@ __device__ __forceinline__ bool transform_point(float p[kDim], const SweepDev& s
 
 struct RangeArg { float r[6]; int use; };
 
-template <bool WRITE>
+template <bool WRITE, bool PASTE>
 __global__ __launch_bounds__(kInBlock) void assemble_kernel(const float* __restrict__ raw,
                                                             const SweepDev* __restrict__ sweeps, int num_sweeps,
                                                             const AugDev* __restrict__ aug, RangeArg rng,
+                                                            const float* __restrict__ planes,
+                                                            const int* __restrict__ box_offsets,
                                                             uint32_t* __restrict__ block_counts,
                                                             const uint32_t* __restrict__ block_offsets,
                                                             float* __restrict__ out) {
   __shared__ float tile[kInBlock * kDim];
+  __shared__ float box_planes[PASTE ? ISF_PASTE_MAX_BOXES * kPlaneFloats : 1];
   __shared__ int wave_count[kInBlock / 64];
   const int blk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // the sweep this workgroup belongs to: last sweep whose block_begin <= blk (sweeps without points own no block)
@@ -106,13 +141,20 @@ __global__ __launch_bounds__(kInBlock) void assemble_kernel(const float* __restr
   const int n = min(kInBlock, sw.num_points - start);
   const float* src = raw + (sw.first_point + start) * (long long)kDim;
   for (int i = tid; i < n * kDim; i += kInBlock) tile[i] = src[i];
+  int num_boxes = 0;
+  if (PASTE && sw.is_sweep != ISF_SWEEP_PASTED) {
+    const int first = box_offsets[sw.sample];
+    num_boxes = min(box_offsets[sw.sample + 1] - first, ISF_PASTE_MAX_BOXES);   // the host refuses more
+    for (int i = tid; i < num_boxes * kPlaneFloats; i += kInBlock)
+      box_planes[i] = planes[(size_t)first * kPlaneFloats + i];
+  }
   __syncthreads();
   float p[kDim];
   bool keep = false;
   if (tid < n) {
 #pragma unroll
     for (int c = 0; c < kDim; ++c) p[c] = tile[tid * kDim + c];
-    keep = transform_point(p, sw, aug, rng.r, rng.use != 0);
+    keep = transform_point<PASTE>(p, sw, aug, rng.r, rng.use != 0, box_planes, num_boxes);
   }
   const unsigned long long mask = __ballot(keep);
   if (lane == 0) wave_count[wave] = __popcll(mask);
@@ -147,16 +189,29 @@ __global__ void sample_offsets_kernel(const uint32_t* __restrict__ block_offsets
   sample_offsets[b] = (int32_t)block_offsets[min(blk, num_blocks)];   // block_offsets[num_blocks] = total
 }
 
-}  // namespace isf
-
-extern "C" {
-
-int isf_assemble_points(const float* raw, const isf_sweep_t* sweeps, int num_sweeps, int batch_size,
-                        const isf_point_aug_t* aug, const float* point_range, float* points_out,
-                        int32_t* sample_offsets, int32_t* sample_offsets_host, isf_stream_t stream) {
-  using namespace isf;
+// both entries; planes == nullptr is isf_assemble_points (the kernels it launches hold no paste code)
+static int assemble_points(const float* raw, const isf_sweep_t* sweeps, int num_sweeps, int batch_size,
+                           const isf_point_aug_t* aug, const float* point_range, const float* planes,
+                           const int32_t* box_offsets, float* points_out, int32_t* sample_offsets,
+                           int32_t* sample_offsets_host, isf_stream_t stream) {
   ISF_REQUIRE(num_sweeps >= 0 && batch_size > 0, ISF_ERR_ARG, "assemble_points: bad sizes");
   ISF_REQUIRE(sample_offsets, ISF_ERR_ARG, "assemble_points: null sample_offsets");
+  const bool paste = box_offsets != nullptr;
+  int total_boxes = 0;
+  if (paste) {
+    ISF_REQUIRE(box_offsets[0] == 0, ISF_ERR_ARG, "assemble_points_paste: box_offsets must start at 0");
+    for (int b = 0; b < batch_size; ++b) {
+      const int nb = box_offsets[b + 1] - box_offsets[b];
+      ISF_REQUIRE(nb >= 0, ISF_ERR_ARG, "assemble_points_paste: box_offsets must ascend (sample %d)", b);
+      ISF_REQUIRE(nb <= ISF_PASTE_MAX_BOXES, ISF_ERR_UNSUPPORTED,
+                  "assemble_points_paste: sample %d has %d removal boxes, at most %d fit", b, nb, ISF_PASTE_MAX_BOXES);
+    }
+    total_boxes = box_offsets[batch_size];
+    ISF_REQUIRE(total_boxes == 0 || planes, ISF_ERR_ARG, "assemble_points_paste: null planes");
+    for (int i = 0; i < num_sweeps; ++i)
+      ISF_REQUIRE(sweeps[i].is_sweep >= 0 && sweeps[i].is_sweep <= ISF_SWEEP_PASTED, ISF_ERR_ARG,
+                  "assemble_points_paste: sweep %d has kind %d", i, sweeps[i].is_sweep);
+  }
   hipStream_t st = as_stream(stream);
   std::vector<SweepDev> dev(num_sweeps);
   std::vector<int> first_block(batch_size + 1, 0);
@@ -228,13 +283,32 @@ int isf_assemble_points(const float* raw, const isf_sweep_t* sweeps, int num_swe
   RangeArg rng;
   rng.use = point_range != nullptr;
   for (int k = 0; k < 6; ++k) rng.r[k] = point_range ? point_range[k] : 0.f;
+  float* d_planes = nullptr;
+  int* d_boxes = nullptr;
+  if (paste) {
+    ISF_TRY(a.alloc_n(&d_boxes, (size_t)batch_size + 1));
+    ISF_TRY(a.alloc_n(&d_planes, (size_t)std::max(total_boxes, 1) * kPlaneFloats));
+    ISF_HIP_TRY(hipMemcpyAsync(d_boxes, box_offsets, sizeof(int) * (batch_size + 1), hipMemcpyHostToDevice, st));
+    if (total_boxes)
+      ISF_HIP_TRY(hipMemcpyAsync(d_planes, planes, sizeof(float) * kPlaneFloats * total_boxes, hipMemcpyHostToDevice,
+                                 st));
+  }
 
-  hipLaunchKernelGGL((assemble_kernel<false>), dim3(num_blocks), dim3(kInBlock), 0, st, raw, d_sweeps, live, d_aug,
-                     rng, d_counts, (const uint32_t*)nullptr, (float*)nullptr);
+  if (paste)
+    hipLaunchKernelGGL((assemble_kernel<false, true>), dim3(num_blocks), dim3(kInBlock), 0, st, raw, d_sweeps, live,
+                       d_aug, rng, d_planes, d_boxes, d_counts, (const uint32_t*)nullptr, (float*)nullptr);
+  else
+    hipLaunchKernelGGL((assemble_kernel<false, false>), dim3(num_blocks), dim3(kInBlock), 0, st, raw, d_sweeps, live,
+                       d_aug, rng, (const float*)nullptr, (const int*)nullptr, d_counts, (const uint32_t*)nullptr,
+                       (float*)nullptr);
   ISF_LAUNCH_CHECK();
   ISF_TRY(scan_u32_exclusive(a, d_counts, d_offsets, (size_t)num_blocks, st));
-  hipLaunchKernelGGL((assemble_kernel<true>), dim3(num_blocks), dim3(kInBlock), 0, st, raw, d_sweeps, live, d_aug, rng,
-                     d_counts, d_offsets, points_out);
+  if (paste)
+    hipLaunchKernelGGL((assemble_kernel<true, true>), dim3(num_blocks), dim3(kInBlock), 0, st, raw, d_sweeps, live,
+                       d_aug, rng, d_planes, d_boxes, d_counts, d_offsets, points_out);
+  else
+    hipLaunchKernelGGL((assemble_kernel<true, false>), dim3(num_blocks), dim3(kInBlock), 0, st, raw, d_sweeps, live,
+                       d_aug, rng, (const float*)nullptr, (const int*)nullptr, d_counts, d_offsets, points_out);
   ISF_LAUNCH_CHECK();
   hipLaunchKernelGGL(sample_offsets_kernel, dim3(ceil_div(batch_size + 1, 64)), dim3(64), 0, st, d_offsets, num_blocks,
                      d_first, batch_size, sample_offsets);
@@ -246,6 +320,29 @@ int isf_assemble_points(const float* raw, const isf_sweep_t* sweeps, int num_swe
                                hipMemcpyDeviceToHost, st));
   ISF_HIP_TRY(hipStreamSynchronize(st));
   return ISF_OK;
+}
+
+}  // namespace isf
+
+extern "C" {
+
+int isf_assemble_points(const float* raw, const isf_sweep_t* sweeps, int num_sweeps, int batch_size,
+                        const isf_point_aug_t* aug, const float* point_range, float* points_out,
+                        int32_t* sample_offsets, int32_t* sample_offsets_host, isf_stream_t stream) {
+  return isf::assemble_points(raw, sweeps, num_sweeps, batch_size, aug, point_range, nullptr, nullptr, points_out,
+                              sample_offsets, sample_offsets_host, stream);
+}
+
+int isf_assemble_points_paste(const float* raw, const isf_sweep_t* sweeps, int num_sweeps, int batch_size,
+                              const isf_point_aug_t* aug, const float* point_range, const float* planes,
+                              const int32_t* box_offsets, float* points_out, int32_t* sample_offsets,
+                              int32_t* sample_offsets_host, isf_stream_t stream) {
+  if (!box_offsets) {
+    isf::set_error("assemble_points_paste: null box_offsets");
+    return ISF_ERR_ARG;
+  }
+  return isf::assemble_points(raw, sweeps, num_sweeps, batch_size, aug, point_range, planes, box_offsets, points_out,
+                              sample_offsets, sample_offsets_host, stream);
 }
 
 }  // extern "C"

@@ -126,10 +126,12 @@ class MultiSweepPointLoader:
             at += a.size
         return host
 
-    def __call__(self, results_list, aug=None):
+    def __call__(self, results_list, aug=None, paste=None):
         """results_list: one dict per sample with the reference's keys -- 'pts_filename' (path or float32 [P, 5]
         array), 'timestamp' (s), 'sweeps': [dict(data_path (path or array), timestamp (us), sensor2lidar_rotation,
-        sensor2lidar_translation)].  aug: None or one dict per sample (draw_train_aug).
+        sensor2lidar_translation)].  aug: None or one dict per sample (draw_train_aug).  paste: None or per sample a
+        gt_paste.GTPastePlan or None (ObjectSampleV2, transforms_3d.py:1348-1361: the plan's objects come first, and
+        frame points inside a sampled box are dropped after the sensor pose; isf_assemble_points_paste).
         -> list of float32 [N_b, 5] device tensors (views of one buffer), in the reference's point order."""
         if self.device.type != "cuda":
             raise _lib.IsfError("MultiSweepPointLoader runs on the GPU only (isf_assemble_points); no CPU fallback")
@@ -137,12 +139,15 @@ class MultiSweepPointLoader:
         B = len(results_list)
         arrays, descs, row = [], [], 0
 
+        if paste is not None and len(paste) != B:
+            raise _lib.IsfError(f"paste holds {len(paste)} plans for {B} samples")
+
         def add(arr, sample, is_sweep, lag=0.0, rot=None, trans=None):
             nonlocal row
             assert arr.size % POINT_DIM == 0, "sweep files hold float32 [P, 5]"
             d = _lib.Sweep()
             d.first_point, d.num_points, d.sample, d.is_sweep = row, arr.size // POINT_DIM, sample, int(is_sweep)
-            d.remove_close, d.close_radius = int(self.remove_close and is_sweep), self.close_radius
+            d.remove_close, d.close_radius = int(self.remove_close and is_sweep == 1), self.close_radius
             d.time_lag = float(np.float32(lag))
             r = np.eye(3) if rot is None else np.asarray(rot, dtype=np.float64)
             t = np.zeros(3) if trans is None else np.asarray(trans, dtype=np.float64)
@@ -152,7 +157,14 @@ class MultiSweepPointLoader:
             descs.append(d)
             row += d.num_points
 
+        planes, box_offsets = [], [0]
         for b, res in enumerate(results_list):
+            plan = paste[b] if paste is not None else None
+            if plan is not None:
+                for obj in plan.objects:      # the float32 translation travels in the descriptor's float64 slot
+                    add(self._read(obj["points"]), b, _lib.SWEEP_PASTED, trans=np.asarray(obj["translation"], np.float32))
+                planes.append(np.asarray(plan.planes, np.float32).reshape(-1, 24))
+            box_offsets.append(box_offsets[-1] + (0 if plan is None else planes[-1].shape[0]))
             add(self._read(res["pts_filename"]), b, False)
             sweeps = res.get("sweeps", [])
             for i in self._choose(len(sweeps)):
@@ -180,8 +192,16 @@ class MultiSweepPointLoader:
         if self.point_cloud_range is not None:
             rng = (ctypes.c_float * 6)(*self.point_cloud_range)
         with torch.cuda.device(self.device):
-            _lib.check(lib.isf_assemble_points(_lib.ptr(raw), sw_arr, len(descs), B, aug_arr, rng, _lib.ptr(out),
-                                               _lib.ptr(offsets), host_offsets, _lib.stream()), "isf_assemble_points")
+            if paste is None:
+                _lib.check(lib.isf_assemble_points(_lib.ptr(raw), sw_arr, len(descs), B, aug_arr, rng, _lib.ptr(out),
+                                                   _lib.ptr(offsets), host_offsets, _lib.stream()),
+                           "isf_assemble_points")
+            else:
+                flat = np.ascontiguousarray(np.concatenate(planes) if planes else np.zeros((0, 24), np.float32))
+                _lib.check(lib.isf_assemble_points_paste(
+                    _lib.ptr(raw), sw_arr, len(descs), B, aug_arr, rng,
+                    flat.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), (ctypes.c_int32 * (B + 1))(*box_offsets),
+                    _lib.ptr(out), _lib.ptr(offsets), host_offsets, _lib.stream()), "isf_assemble_points_paste")
         pts = [out[host_offsets[b]:host_offsets[b + 1]] for b in range(B)]
         if self.shuffle:        # PointShuffle: BasePoints.shuffle = tensor[randperm] (base_points.py, torch RNG)
             pts = [p[torch.randperm(p.shape[0], device=p.device)] for p in pts]
@@ -458,9 +478,70 @@ class MultiViewImageLoader:
             buf = torch.empty(max(nbytes, 1), dtype=torch.uint8).pin_memory()
         return buf
 
-    def stage(self, results_list, aug=None):
-        """Host half of a call: draws, descriptors and tables, and the two uploads from pinned memory.  -> dict for
-        launch() (device buffers `raw` and `par`, the views' count and layout, `img_aug_matrix`)."""
+    def _paste_ops(self, paste, imgs, B, N, total):
+        """Host half of isf_image_paste: the plans' rectangle operations as descriptors, their patches placed behind
+        the images (from byte `total` on) -> (PasteView bytes, PasteOp bytes, patches [(offset, array)], new total,
+        (max ops on a view, max box width, max box height), mixup) or None when no plan touches an image."""
+        if len(paste) != B:
+            raise _lib.IsfError(f"paste holds {len(paste)} plans for {B} samples")
+        views, ops, patches, offset, mixups = [], [], [], 0, set()
+        most = box_w = box_h = 0
+        for b in range(B):
+            plan = paste[b]
+            per_view = [[] for _ in range(N)]
+            where = {}
+            for op in (plan.image_ops if plan is not None else []):
+                if not 0 <= op["view"] < N:
+                    raise _lib.IsfError(f"GT-paste operation on view {op['view']} of {N}")
+                mixups.add(float(plan.mixup))
+                d = _lib.PasteOp()
+                (d.y0, d.y1), (d.x0, d.x1) = op["rows"], op["cols"]
+                if op["kind"] == "patch":
+                    k = op["object"]
+                    if k not in where:
+                        patch = plan.objects[k]["patch"]
+                        where[k] = total
+                        patches.append((total, patch))
+                        total += patch.size
+                    ph, pw = plan.objects[k]["patch"].shape[:2]
+                    if d.y1 - d.y0 > ph or d.x1 - d.x0 > pw:
+                        raise _lib.IsfError(f"GT-paste: a {d.y1 - d.y0} x {d.x1 - d.x0} rectangle reads past its "
+                                            f"{ph} x {pw} patch")
+                    d.kind, d.patch_offset, d.patch_pitch = _lib.PASTE_PATCH, where[k], pw
+                    (d.mask_y0, d.mask_y1), (d.mask_x0, d.mask_x1) = op["mask_rows"], op["mask_cols"]
+                else:
+                    d.kind = _lib.PASTE_MIX
+                per_view[op["view"]].append(d)
+            for v in range(N):
+                im, mine = imgs[b * N + v], per_view[v]
+                H, W = im.shape[:2]
+                pv = _lib.PasteView()
+                pv.src_offset, pv.width, pv.height = offset, W, H
+                pv.op_begin, pv.op_end = len(ops), len(ops) + len(mine)
+                if mine:
+                    if any(d.x0 < 0 or d.y0 < 0 or d.x1 > W or d.y1 > H or d.x0 >= d.x1 or d.y0 >= d.y1 for d in mine):
+                        raise _lib.IsfError("GT-paste: an operation's rectangle leaves its view")
+                    pv.box_x0, pv.box_y0 = min(d.x0 for d in mine), min(d.y0 for d in mine)
+                    pv.box_x1, pv.box_y1 = max(d.x1 for d in mine), max(d.y1 for d in mine)
+                    box_w, box_h = max(box_w, pv.box_x1 - pv.box_x0), max(box_h, pv.box_y1 - pv.box_y0)
+                most = max(most, len(mine))
+                ops.extend(mine)
+                views.append(pv)
+                offset += im.size
+        if not ops:
+            return None
+        if len(mixups) != 1:
+            raise _lib.IsfError(f"the plans of one batch share one mixup; got {sorted(mixups)}")
+        if most > _lib.PASTE_MAX_OPS:
+            raise _lib.IsfError(f"GT-paste: {most} operations on one view, at most {_lib.PASTE_MAX_OPS} are walked")
+        return (b"".join(bytes(v) for v in views), b"".join(bytes(d) for d in ops), patches, total,
+                (most, box_w, box_h), mixups.pop())
+
+    def stage(self, results_list, aug=None, paste=None):
+        """Host half of a call: draws, descriptors and tables, and the two uploads from pinned memory.  paste: None or
+        per sample a gt_paste.GTPastePlan or None; the plans' patches are uploaded behind the images and their
+        operations behind the tables.  -> dict for launch() (device buffers `raw` and `par`, the views' count and
+        layout, `img_aug_matrix`)."""
         if self.device.type != "cuda":
             raise _lib.IsfError("MultiViewImageLoader runs on the GPU only (isf_image_prepass); no CPU fallback")
         B = len(results_list)
@@ -482,6 +563,9 @@ class MultiViewImageLoader:
         if self._uploaded is not None:
             self._uploaded.synchronize()
         total = sum(im.size for im in imgs)
+        pasted = None if paste is None else self._paste_ops(paste, imgs, B, N, total)
+        if pasted is not None:
+            total = pasted[3]
         self._pinned_img = self._pin(self._pinned_img, total)
         host = self._pinned_img.numpy()
         at = 0
@@ -490,6 +574,16 @@ class MultiViewImageLoader:
             at += im.size
         vbytes = np.frombuffer(b"".join(bytes(v) for v in views), dtype=np.uint8)
         params = np.concatenate([vbytes, tables.view(np.uint8), self._lut.reshape(-1).view(np.uint8)])
+        extra = {}
+        if pasted is not None:
+            pv_bytes, op_bytes, patches, _, limits, mixup = pasted
+            for where, patch in patches:
+                host[where:where + patch.size] = patch.reshape(-1)
+            pad = (-params.size) % 8                      # the descriptors hold 64-bit offsets
+            extra = dict(paste=dict(views_at=params.size + pad, ops_at=params.size + pad + len(pv_bytes), limits=limits,
+                                    mixup=mixup))
+            params = np.concatenate([params, np.zeros(pad, np.uint8), np.frombuffer(pv_bytes, dtype=np.uint8),
+                                     np.frombuffer(op_bytes, dtype=np.uint8)])
         self._pinned_par = self._pin(self._pinned_par, params.size)
         self._pinned_par.numpy()[:params.size] = params
         with torch.cuda.device(self.device):
@@ -499,12 +593,28 @@ class MultiViewImageLoader:
                 self._uploaded = torch.cuda.Event()
             self._uploaded.record()
         return dict(raw=raw, par=par, tables_at=vbytes.size, lut_at=vbytes.size + tables.size * 4, batch=B, views=N,
-                    img_aug_matrix=matrices.view(B, N, 4, 4), draws=draws)
+                    img_aug_matrix=matrices.view(B, N, 4, 4), draws=draws, **extra)
+
+    def paste(self, staged):
+        """Device half of the GT-paste: one isf_image_paste launch, in place on staged['raw'] (a no-op for a batch whose
+        plans touch no image).  launch() calls it; it is separate so that the pasted bytes can be looked at."""
+        p = staged.pop("paste", None)
+        if p is None:
+            return
+        base = staged["par"].data_ptr()
+        mixup = float(p["mixup"])
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().isf_image_paste(
+                _lib.ptr(staged["raw"]), base + p["views_at"], staged["batch"] * staged["views"], base + p["ops_at"],
+                p["limits"][0], p["limits"][1], p["limits"][2], mixup, 1 - mixup, float(np.float32(mixup)),
+                _lib.stream()), "isf_image_paste")
 
     def launch(self, staged, out=None):
-        """Device half: one isf_image_prepass launch over staged buffers -> img [B, N, 3, fH, fW] float32"""
+        """Device half: one isf_image_prepass launch over staged buffers (after isf_image_paste when the batch carries
+        GT-paste plans) -> img [B, N, 3, fH, fW] float32"""
         fH, fW = self.final_dim
         B, N = staged["batch"], staged["views"]
+        self.paste(staged)
         with torch.cuda.device(self.device):
             if out is None:
                 out = torch.empty((B * N, 3, fH, fW), dtype=torch.float32, device=self.device)
@@ -517,12 +627,14 @@ class MultiViewImageLoader:
                        "isf_image_prepass")
         return out.view(B, N, 3, fH, fW)
 
-    def __call__(self, results_list, aug=None, out=None):
+    def __call__(self, results_list, aug=None, out=None, paste=None):
         """results_list: one dict per sample with 'img' = its views, each uint8 [H, W, 3] RGB (an array or anything
         np.asarray turns into one; sizes may differ per view).  aug: None (one sample_augmentation((W, H)) draw per view,
         in sample then view order) or per sample a list of (resize, resize_dims, crop, flip, rotate) per view.
         out: None or a contiguous float32 device tensor of B * N * 3 * fH * fW elements to write into.
+        paste: None or per sample a gt_paste.GTPastePlan or None: the image side of ObjectSampleV2 (dbsampler.py:779-831)
+        runs on the uploaded bytes before the pre-pass.
         -> (img [B, N, 3, fH, fW] float32 on the device, img_aug_matrix [B, N, 4, 4] float32).  Two uploads from pinned
-        memory and one launch; nothing is read back."""
-        staged = self.stage(results_list, aug)
+        memory and one launch (two with plans); nothing is read back."""
+        staged = self.stage(results_list, aug, paste)
         return self.launch(staged, out), staged["img_aug_matrix"]

@@ -2,7 +2,7 @@
 all-reduce over xGMI on the GRADIENTS only -- the forward has no collective):
 
     python tools/train_step.py --gpus N [--batch 2] [--points 60000] [--steps 3] [--bf16] [--autocast]
-                               [--optimizer sgd|config] [--max-iters M]
+                               [--optimizer sgd|config] [--max-iters M] [--gt-paste]
 
 starts N ranks by itself (isfusion_amd.launch.self_launch: a re-exec under torch.distributed.run on 127.0.0.1; fewer
 than N visible GPUs is an error) -- the reference's tools/run-nus.sh:11-13; under a launcher it runs as the rank it is:
@@ -16,7 +16,10 @@ isfusion_amd.norm.NaiveSyncBatchNorm where the reference uses naiveSyncBN (cross
 [2C] per layer, whenever the world size is > 1), plain BatchNorm (local-shard statistics) elsewhere.  The default loss is a stand-in (feature energy + heat-map mean); --loss detection trains
 on the detection head's real losses (ISFusionPtsPath.forward_train: targets, Hungarian assignment and losses on the HIP
 kernels) against the synthetic scenes' boxes (synthetic.scene_boxes).  Prints one JSON line per rank 0 with ms per step.
-Also runs on a single GPU without torchrun (world size 1)."""
+--gt-paste (with --loss detection) puts ObjectSampleV2 in front of every step: a small database built from other
+synthetic scenes' boxes, one isfusion_amd.gt_paste plan per frame, and the points through
+MultiSweepPointLoader(paste=...) (isf_assemble_points_paste); the step then trains on the pasted points and the
+concatenated boxes.  Also runs on a single GPU without torchrun (world size 1)."""
 import argparse
 import json
 import os
@@ -35,6 +38,24 @@ RECIPE = dict(optimizer=dict(type="AdamW", lr=0.0001, weight_decay=0.01,
               lr_config=dict(policy="cyclic", target_ratio=(10, 0.0001), cyclic_times=1, step_ratio_up=0.4),
               momentum_config=dict(policy="cyclic", target_ratio=(0.8947368421052632, 1), cyclic_times=1,
                                    step_ratio_up=0.4))
+
+
+def gt_paste_database(first_seed, scenes=4, points_per_object=24):
+    """A GT-paste database from the boxes of `scenes` synthetic scenes no rank trains on: every box becomes an entry
+    whose points (float32 [n, 5], centred on the box as the database files are) fill it uniformly."""
+    import numpy as np
+    from isfusion_amd import synthetic
+    rng = np.random.default_rng(first_seed)
+    names, db = ("car", "truck"), dict(car=[], truck=[])
+    for seed in range(first_seed, first_seed + scenes):
+        for box, label in zip(*synthetic.scene_boxes(seed)):
+            pts = np.zeros((points_per_object, 5), np.float32)
+            pts[:, :3] = rng.uniform(-0.45, 0.45, (points_per_object, 3)) * box[3:6]
+            pts[:, 2] += box[5] * 0.5
+            pts[:, 3] = rng.integers(0, 256, points_per_object)
+            db[names[label]].append(dict(name=names[label], path=pts, box3d_lidar=box, num_points_in_gt=points_per_object,
+                                         box2d_camera=np.zeros(5, np.float32), difficulty=0))
+    return db
 
 
 def main():
@@ -63,7 +84,12 @@ def main():
                          "TrainingRecipe: mmcv per-parameter groups, fused AdamW + grad clip 0.01, cyclic lr / momentum)")
     ap.add_argument("--max-iters", type=int, default=0,
                     help="iterations the cyclic schedules span with --optimizer config (0 = --steps + 1)")
+    ap.add_argument("--gt-paste", action="store_true",
+                    help="ObjectSampleV2 in front of every step (needs --loss detection): a synthetic database, one "
+                         "GT-paste plan per frame, points through isf_assemble_points_paste")
     a = ap.parse_args()
+    if a.gt_paste and a.loss != "detection":
+        ap.error("--gt-paste pastes ground truth: it needs --loss detection")
     from isfusion_amd import launch, synthetic
     if a.stock_dense:
         from isfusion_amd import dense_train
@@ -119,12 +145,30 @@ def main():
     if detection:
         scenes = [synthetic.scene_boxes(9000 + 100 * rank + i) for i in range(a.batch)]
         gt = ([torch.from_numpy(b).to(dev) for b, _ in scenes], [torch.from_numpy(l).to(dev) for _, l in scenes])
+    paste = None
+    if a.gt_paste:
+        import numpy as np
+        from isfusion_amd.gt_paste import GTPasteSampler
+        from isfusion_amd.input_pipeline import MultiSweepPointLoader
+        np.random.seed(1234 + rank)
+        # the scenes hold ~38 boxes each, so the per-class ceilings sit above that: a dozen candidates per frame
+        sampler = GTPasteSampler(db_infos=gt_paste_database(9900), rate=1.0, classes=["car", "truck"],
+                                 sample_groups=dict(car=40, truck=20), sample_2d=False)
+        loader = MultiSweepPointLoader(test_mode=True, device=dev)
+        frames = [dict(pts_filename=p.cpu().numpy(), timestamp=0.0, sweeps=[]) for p in pts]
+
+        def paste():
+            results = [dict(gt_bboxes_3d=b, gt_labels_3d=l) for b, l in scenes]
+            plans = [sampler.sample(r) for r in results]
+            return (loader(frames, paste=plans), ([torch.from_numpy(r["gt_bboxes_3d"]).to(dev) for r in results],
+                                                  [torch.from_numpy(r["gt_labels_3d"]).to(dev) for r in results]),
+                    sum(len(p.objects) for p in plans if p is not None))
     inp = synthetic.fusion_inputs(7 + rank, a.batch)
     img = tuple(torch.from_numpy(x).to(dev).to(torch.bfloat16 if a.bf16 else torch.float32) for x in inp["img_feats"])
     kw = dict(lidar2img=torch.from_numpy(inp["lidar2img"]), img_aug_matrix=torch.from_numpy(inp["img_aug_matrix"]),
               lidar_aug_matrix=torch.from_numpy(inp["lidar_aug_matrix"]))
     metas = [dict(input_shape=inp["input_shape"]) for _ in range(a.batch)]
-    losses, norms, t0 = [], [], None
+    losses, norms, pasted, t0 = [], [], [], None
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 2)]   # per-step GPU time stamps (no extra sync)
     for step in range(a.steps + 1):
         marks[step].record()
@@ -132,6 +176,9 @@ def main():
             torch.cuda.synchronize()
             dist.barrier()
             t0 = time.perf_counter()
+        if paste is not None:
+            pts, gt, count = paste()
+            pasted.append(count)
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=a.autocast):
             if detection:
                 ld = ddp(pts, img, metas, kw, gt)
@@ -154,7 +201,8 @@ def main():
     if rank == 0:
         print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss,
                           "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses],
-                          "optimizer": a.optimizer, **({"grad_norm": [round(n, 6) for n in norms]} if recipe else {})}))
+                          "optimizer": a.optimizer, **({"grad_norm": [round(n, 6) for n in norms]} if recipe else {}),
+                          **({"gt_paste_objects": pasted} if paste is not None else {})}))
     dist.destroy_process_group()
 
 
