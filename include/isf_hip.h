@@ -605,6 +605,9 @@ typedef struct isf_encoder_stats { /* filled on the host after the call (for roo
 #define ISF_ENC_DIAG_SORT_KEY_AB 134217728     /* row sort key 2 instead of key 1 (A/B) */
 #define ISF_ENC_DIAG_NARROW_TILES 268435456    /* 128-column layers of the large levels on 4-wave tiles (A/B) */
 #define ISF_ENC_DIAG_CHUNK_SPLIT 536870912     /* -> ISF_CONV_MODE_CHUNK_SPLIT (256-column layers; opt-in) */
+#define ISF_ENC_DIAG_BEV_ONE_PASS (1 << 30)    /* 1073741824: the fp32 BEV map written whole by the final kernel, zeros included,
+                                                  instead of zeros early on the geometry stream + occupied 16-cell segments
+                                                  last (A/B and bit-identity reference; bit-identical) */
 typedef struct isf_encoder_options {
   int precision;
   int diagnostic;
@@ -639,6 +642,18 @@ int isf_lidar_branch_forward(const float* points, const int64_t* point_offsets_h
                              float* spatial_features, int out_shape_host[4],
                              isf_encoder_stats* stats_host, int time_layers,
                              const isf_encoder_options* options /* may be NULL */, isf_stream_t stream);
+
+/* The same call over frames that are NOT concatenated: frame_points_host[b] is the device pointer of frame b's
+ * [P_b, in_channels] fp32 block (contiguous rows; 4-byte alignment suffices, so a view into a larger buffer will do; may be
+ * NULL for a frame without points), point_offsets_host the running sums of the P_b as above.  Saves the caller's
+ * concatenation pass (a read and a write of every point).  batch_size <= 8; larger batches: concatenate and call
+ * isf_lidar_branch_forward.  Results are bit-identical to the concatenated call. */
+int isf_lidar_branch_forward_frames(const float* const* frame_points_host, const int64_t* point_offsets_host, int batch_size,
+                                    const isf_vfe_params* vfe_host, const int sparse_shape_host[3],
+                                    const isf_conv_layer* layers_host, int num_layers,
+                                    float* spatial_features, int out_shape_host[4],
+                                    isf_encoder_stats* stats_host, int time_layers,
+                                    const isf_encoder_options* options /* may be NULL */, isf_stream_t stream);
 
 /* ===================================================================================================
  * HSF / IGF rows (A8, A10-A14).  Dense 3x3 convolutions around them stay stock

@@ -157,6 +157,9 @@ ENC_DIAG_DENSE_TABLES, ENC_DIAG_TILE_TABLES, ENC_DIAG_VOXELIZE_PER_FRAME, ENC_DI
 ENC_DIAG_ONE_BLOCK_4W, ENC_DIAG_ONE_BLOCK_8W, ENC_DIAG_STAGGER, ENC_DIAG_R4_ISSUE = 262144, 524288, 1048576, 2097152
 ENC_DIAG_TWO_AHEAD, ENC_DIAG_DEEP, ENC_DIAG_BAND_ORDER, ENC_DIAG_NO_ROW_SORT = 4194304, 8388608, 16777216, 33554432
 ENC_DIAG_NARROW_ROW_SORT, ENC_DIAG_SORT_KEY_AB, ENC_DIAG_NARROW_TILES, ENC_DIAG_CHUNK_SPLIT = 67108864, 134217728, 268435456, 536870912
+# ISF_ENC_DIAG_BEV_ONE_PASS (1 << 30): the fp32 BEV map in one pass -- the A/B partner and bit-identity reference of the default's
+# two passes (zeros early on the geometry stream, occupied segments last); tests/test_gpu_branch_io.py pins name and value
+BEV_ONE_PASS_DIAG = 1 << 30
 # ISF_WGRAD_*: bits of isf_sparse_conv_backward_filter_f16x3's `mode`
 WGRAD_F16, WGRAD_FULL_TAPS = 1, 2
 
@@ -273,6 +276,10 @@ SIGNATURES = {
                                          ctypes.POINTER(VfeParams), _I3, ctypes.POINTER(ConvLayer), c_int,
                                          c_void_p, _I4, ctypes.POINTER(EncoderStats), c_int,
                                          ctypes.POINTER(EncoderOptions), c_void_p]),
+    "isf_lidar_branch_forward_frames": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int64), c_int,
+                                                ctypes.POINTER(VfeParams), _I3, ctypes.POINTER(ConvLayer), c_int,
+                                                c_void_p, _I4, ctypes.POINTER(EncoderStats), c_int,
+                                                ctypes.POINTER(EncoderOptions), c_void_p]),
     "isf_packed_linear_bytes": (ctypes.c_size_t, [c_int, c_int]),
     "isf_pack_linear": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "isf_pack_linear_transposed": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -107,9 +107,13 @@ struct OccIndex {
 int occ_create(Arena& a, OccIndex* occ, int B, int D, int H, int W, hipStream_t st, bool zero = true);
 size_t occ_bits_bytes(const OccIndex& occ);   // bytes occ_create(zero = true) clears
 // atomic-free marking through persistent byte maps (writes EVERY bitmap word: create with zero = false)
-int occ_mark_coords4_bytemap(Arena& a, const OccIndex& occ, const int32_t* coors4, int n, hipStream_t st);
+int occ_mark_coords4_bytemap(Arena& a, const OccIndex& occ, const int32_t* coors4, int n, hipStream_t st,
+                             uint32_t* block_sums = nullptr /* occ_scan_block_sums: the pack pass leaves the blocks' popcounts */);
 int scan_u32_exclusive(Arena& a, const uint32_t* in, uint32_t* out, size_t n, hipStream_t st);
-int occ_scan(Arena& a, const OccIndex& occ, hipStream_t st);                           // prefix + total
+// prefix + total.  block_sums: the blocks' popcounts are there already (the byte-map pack pass wrote them: no count launch);
+// clear: counters [0, total] are zeroed in the prefix launch (one per rank + one; at least total + 1 allocated)
+int occ_scan(Arena& a, const OccIndex& occ, hipStream_t st, uint32_t* block_sums = nullptr, uint32_t* clear = nullptr);
+int occ_scan_block_sums(Arena& a, const OccIndex& occ, uint32_t** sums);   // the buffer `block_sums` of occ_scan
 int occ_mark_coords4(const OccIndex& occ, const int32_t* coors4, int n, hipStream_t st);
 // coords of all set bits in rank order -> out [total,4]
 int occ_compact_coords4(const OccIndex& occ, int32_t* out, hipStream_t st);
@@ -216,16 +220,50 @@ static inline VoxGeom make_geom(const float vs[3], const float range[6]) {
 }
 
 
-// B <= kVoxMaxBatch frames of one launch: frame b owns points [off[b], off[b + 1])
+// B <= kVoxMaxBatch frames of one launch: frame b owns points [off[b], off[b + 1]) and holds them as one [P_b, C] fp32 block
+// at base[b] -- the frames need not be adjacent in memory (isf_lidar_branch_forward_frames), and a base may be a view that
+// is only 4-byte aligned: the kernels read points with scalar loads
 static constexpr int kVoxMaxBatch = 8;
 struct VoxBatch {
   long long off[kVoxMaxBatch + 1];
+  const float* base[kVoxMaxBatch];
   int B;
 };
+struct VoxFrame {
+  const float* base;
+  long long first, end;
+  int b;
+};
+// the frame that holds point i (a running index over all frames): a walk over <= 8 offsets
+__device__ __forceinline__ VoxFrame vox_frame(const VoxBatch& vb, long long i) {
+  VoxFrame f = {vb.base[0], vb.off[0], vb.off[1], 0};
+#pragma unroll
+  for (int k = 1; k < kVoxMaxBatch; ++k)
+    if (k < vb.B && i >= vb.off[k])   // (an empty frame shares its offset with the next one: the last match owns i)
+      f = VoxFrame{vb.base[k], vb.off[k], vb.off[k + 1], k};
+  return f;
+}
+// point i = blockIdx.x * blockDim.x + threadIdx.x of a frame table: its frame and its C floats.  The workgroup's first
+// point decides for all its threads (scalar work) unless the workgroup lies across a frame boundary: those threads walk
+// themselves.
+__device__ __forceinline__ const float* vox_point(const VoxBatch& vb, long long i, int C, int& b) {
+  VoxFrame f = vox_frame(vb, (long long)blockIdx.x * blockDim.x);
+  if (i >= f.end) f = vox_frame(vb, i);
+  b = f.b;
+  return f.base + (size_t)(i - f.first) * C;
+}
+// the table of ONE block of P points (the concatenated layout)
+static inline VoxBatch vox_one_block(const float* points, long long P) {
+  VoxBatch vb = {};
+  vb.off[1] = P;
+  vb.base[0] = points;
+  vb.B = 1;
+  return vb;
+}
 // dynamic voxelization of ALL frames + byte-map marking of the level-0 occupancy index in ONE launch (the LiDAR branch ran
 // one voxelize launch per frame and re-read the coordinates in a separate mark launch); coors4 [P, 4] is written here.
-int occ_voxelize_mark_bytemap(Arena& a, const OccIndex& occ, const float* points, int P, int C, const VoxGeom& g,
-                              const VoxBatch& vb, int32_t* coors4, hipStream_t st);
+int occ_voxelize_mark_bytemap(Arena& a, const OccIndex& occ, int P, int C, const VoxGeom& g, const VoxBatch& vb,
+                              int32_t* coors4, hipStream_t st, uint32_t* block_sums = nullptr /* as occ_mark_coords4_bytemap */);
 
 // ----------------------------------------------------------------------------- internal ops (arena-aware)
 // isf_voxelize.hip
@@ -242,7 +280,9 @@ int dynamic_vfe_impl(Arena& a, const float* points, const int32_t* coors4, int P
                      void* voxel_feats_split = nullptr /* [P, c2] rows in the split format as well (whole rows are written
                      there INSTEAD of voxel_feats; rows cut by a wave boundary in both) */,
                      const VoxBatch* voxelize = nullptr /* non-null: coors4 is an OUTPUT -- the frames are voxelized (vs,
-                     range) inside the byte-map marking launch (occ_voxelize_mark_bytemap) */);
+                     range) inside the byte-map marking launch (occ_voxelize_mark_bytemap) */,
+                     const VoxBatch* frames = nullptr /* non-null: the points live in these per-frame blocks (`points` is
+                     not read); null: `voxelize`'s blocks, or without it the one block `points` */);
 // isf_rulebook.hip
 int build_perm(Arena& a, const OccIndex& occ, const int32_t* coors4, int n, int32_t** perm_out,
                hipStream_t st);
@@ -384,6 +424,7 @@ int half_to_f32_impl(const void* xh, size_t n_elems, float* x, hipStream_t st);
 // fmt: 0 = fp32 rows, 1 = split rows, 2 = f16 rows
 int sparse_to_dense_bev_impl(Arena& a, const void* feats, int fmt, const int32_t* indices, int n, int C,
                              int B, int D, int H, int W, float* out, const OccIndex* occ,
-                             hipStream_t st);
+                             hipStream_t st,
+                             bool skip_empty = false /* split rows of an index: the caller's zero pass writes the empty segments */);
 
 }  // namespace isf

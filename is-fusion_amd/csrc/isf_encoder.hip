@@ -9,10 +9,87 @@ namespace isf {
 // ----------------------------------------------------------------------------------------- dense BEV
 // out[b, c*D + z, y, x] = feats[row(b,z,y,x), c] or 0.  Dense-stationary: a workgroup owns 64 consecutive
 // x cells of one (b, y) line, looks the <= 64*D rows up in the occupancy index, transposes 64x64 blocks
-// through LDS and writes 256-B runs; every output element is written exactly once (no memset pass).
+// through LDS and writes 256-B runs; every output element is written exactly once.  ONE PASS (SKIP = false): this kernel
+// writes the whole map, zeros included.  TWO PASSES (SKIP = true, the encoder's fp32 map of split rows): the H * W cells of
+// a (b, z) plane are cut into SEGMENTS of kBevSeg = 32 cells that are 128-byte lines of the buffer (the cut is shifted by
+// where the plane starts in memory: bev_plane_shift; a segment runs across row ends).  A segment without an occupied cell
+// is all zeros in every channel of its z and is written by bev_zero_empty_kernel, which the encoder runs on its geometry
+// stream beside the convolutions (the occupancy index of the last level exists long before its rows do); this kernel then
+// writes the other segments only.  Both kernels decide with bev_segment_empty on the same index bits, so every element
+// still has exactly one writer and the two need no order between them.  (Segments of 16 cells aligned to the rows -- 70 %
+// of them empty on the benchmark geometry -- were measured first: the two kernels then share 128-byte lines, and the half
+// lines cost each of them a whole one: second pass 42 us for 30 % of the bytes, convolutions beside the zero pass +31 us.)
 static constexpr int kDenseX = 64;
+static constexpr int kBevSeg = 32;           // cells per segment: one 128-byte line of a channel plane
+static constexpr int kBevZeroBlocks = 256;   // grid of the zero pass: about one workgroup per CU, it must not crowd the convs
 
-template <int FMT>   // 0 fp32 rows, 1 split rows, 2 f16 rows
+// where the segments of plane (b, z) are cut: the plane's first float (channel c = 0; plane0 = ((b * C) * D + z) * H * W)
+// modulo a line.  The planes of the other channels follow at multiples of D * H * W floats: the same cut is line-aligned
+// for them too when that is a multiple of 32 (any cut is correct).
+__device__ __forceinline__ int bev_plane_shift(const float* out, size_t plane0) {
+  return (int)(((reinterpret_cast<uintptr_t>(out) >> 2) + plane0) & (kBevSeg - 1));
+}
+
+// segment k of a plane = its cells [32 k - shift, 32 k - shift + 32) that exist (0 <= cell < HW): no occupied one among
+// them?  (false for a segment without cells.)  plane_cell0: the plane's first cell in the index; the range may straddle
+// two words of it.
+__device__ __forceinline__ bool bev_segment_empty(const unsigned long long* __restrict__ bits,
+                                                  unsigned long long plane_cell0, int HW, int shift, int k) {
+  const int lo = kBevSeg * k - shift < 0 ? 0 : kBevSeg * k - shift;
+  const int hi = kBevSeg * k - shift + kBevSeg > HW ? HW : kBevSeg * k - shift + kBevSeg;
+  if (lo >= hi) return false;
+  const unsigned long long cell0 = plane_cell0 + lo;
+  const int len = hi - lo;   // <= 32
+  const size_t w = (size_t)(cell0 >> 6);
+  const int s = (int)(cell0 & 63);
+  unsigned long long m = bits[w] >> s;
+  if (s + len > 64) m |= bits[w + 1] << (64 - s);   // (then the range's last cell lies in word w + 1: in bounds)
+  m &= (1ull << len) - 1;
+  return m == 0;
+}
+
+// zero pass of the two-pass map: a workgroup takes (plane, group of 8 segments) units (grid-stride); a wave's lanes are the
+// 8 x 8 float4 pieces of the group -- 1 KiB of one channel plane -- and the waves take the channels in turn
+__global__ __launch_bounds__(256) void bev_zero_empty_kernel(int B, int C, int D, int HW,
+                                                             const unsigned long long* __restrict__ bits,
+                                                             float* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int groups = ((HW + 2 * kBevSeg - 2) / kBevSeg + 7) / 8;   // covers the segments of any shift
+  const long long units = (long long)B * D * groups;
+  const bool vec_ok = ((size_t)D * HW) % 4 == 0;   // float4 pieces stay 16-byte aligned in every channel plane
+  for (long long u = blockIdx.x; u < units; u += gridDim.x) {
+    const int g = (int)(u % groups);
+    const long long bz = u / groups;   // b * D + z
+    const int z = (int)(bz % D);
+    const size_t plane0 = ((size_t)(bz / D) * C * D + z) * HW;
+    const int shift = bev_plane_shift(out, plane0);
+    const int k = g * 8 + (lane >> 3);
+    const int p0 = kBevSeg * k - shift + 4 * (lane & 7);   // first cell of this lane's piece (pieces are 16-byte aligned)
+    if (p0 + 4 <= 0 || p0 >= HW) continue;
+    if (!bev_segment_empty(bits, (unsigned long long)bz * HW, HW, shift, k)) continue;
+    const bool whole = vec_ok && p0 >= 0 && p0 + 4 <= HW;
+    for (int c = wv; c < C; c += 4) {
+      float* o = out + plane0 + (size_t)c * D * HW;   // plane (b, c, z)
+      if (whole) {
+        *reinterpret_cast<float4*>(o + p0) = make_float4(0.f, 0.f, 0.f, 0.f);
+      } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (p0 + e >= 0 && p0 + e < HW) o[p0 + e] = 0.f;
+      }
+    }
+  }
+}
+
+// the zero pass of out = [B, C * D, H, W] for the index `occ` of (B, D, H, W)
+static int bev_zero_empty_impl(const OccIndex& occ, int C, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(bev_zero_empty_kernel, dim3(kBevZeroBlocks), dim3(256), 0, st, occ.B, C, occ.D, occ.H * occ.W, occ.bits,
+                     out);
+  ISF_LAUNCH_CHECK();
+  return ISF_OK;
+}
+
+template <int FMT, bool SKIP = false>   // 0 fp32 rows, 1 split rows, 2 f16 rows; SKIP: the empty segments are not written here
 __global__ __launch_bounds__(256) void dense_bev_kernel(const void* __restrict__ feats_v, int C, int D,
                                                         int H, int W,
                                                         const unsigned long long* __restrict__ bits,
@@ -21,21 +98,33 @@ __global__ __launch_bounds__(256) void dense_bev_kernel(const void* __restrict__
                                                         float* __restrict__ out) {
   __shared__ float tile[64][kDenseX + 1];
   __shared__ int rows[kDenseX];
+  __shared__ int keep[kDenseX + 1];   // SKIP: this x cell's segment is written here; [kDenseX]: any of them
   const int xt = blockIdx.x, y = blockIdx.y, b = blockIdx.z;
   const int x0 = xt * kDenseX;
   const int t = threadIdx.x;
   for (int z = 0; z < D; ++z) {
     __syncthreads();
-    if (t < kDenseX) {
+    if (t < kDenseX) {   // (wave 0, all of it)
       int r = -1;
+      bool kp = false;
       const int x = x0 + t;
       if (x < W) {
         r = occ_lookup(bits, prefix, (((unsigned long long)b * D + z) * H + y) * W + x);
         if (r >= 0 && perm) r = perm[r];
+        if (SKIP) {
+          const int shift = bev_plane_shift(out, ((size_t)b * C * D + z) * H * W);
+          kp = !bev_segment_empty(bits, ((unsigned long long)b * D + z) * H * W, H * W, shift, (y * W + x + shift) / kBevSeg);
+        }
       }
       rows[t] = r;
+      if (SKIP) {
+        keep[t] = kp;
+        const unsigned long long any = __ballot(kp);
+        if (t == 0) keep[kDenseX] = any != 0;
+      }
     }
     __syncthreads();
+    if (SKIP && !keep[kDenseX]) continue;   // nothing of this z to write here (the same for every thread: the barriers stay aligned)
     for (int c0 = 0; c0 < C; c0 += 64) {
       if (FMT != 0) {
         // split format: row = C/8 units of (hi8 | lo8) f16 (f16 rows: hi8 only); thread -> (row xx = t/8 + 32*j, unit t%8)
@@ -76,7 +165,7 @@ __global__ __launch_bounds__(256) void dense_bev_kernel(const void* __restrict__
       __syncthreads();
       // store: lane -> x, wave -> channel stripe
       const int lane = t & 63, wv = t >> 6;
-      if (x0 + lane < W) {
+      if (x0 + lane < W && !(SKIP && !keep[lane])) {
         for (int cc = wv; cc < 64 && c0 + cc < C; cc += 4) {
           const size_t ch = (size_t)(c0 + cc) * D + z;
           out[(((size_t)b * C * D + ch) * H + y) * W + x0 + lane] = tile[cc][lane];
@@ -88,7 +177,8 @@ __global__ __launch_bounds__(256) void dense_bev_kernel(const void* __restrict__
 }
 
 int sparse_to_dense_bev_impl(Arena& a, const void* feats, int fmt, const int32_t* indices, int n, int C,
-                             int B, int D, int H, int W, float* out, const OccIndex* occ_in, hipStream_t st) {
+                             int B, int D, int H, int W, float* out, const OccIndex* occ_in, hipStream_t st,
+                             bool skip_empty /* split rows of an index: bev_zero_empty_impl writes the empty segments */) {
   ISF_REQUIRE(C % (fmt ? 32 : 4) == 0, ISF_ERR_UNSUPPORTED, "dense: channels %d not a multiple of %d", C,
               fmt ? 32 : 4);
   OccIndex occ;
@@ -104,7 +194,12 @@ int sparse_to_dense_bev_impl(Arena& a, const void* feats, int fmt, const int32_t
     perm = p;
   }
   dim3 grid(ceil_div(W, kDenseX), H, B);
-  if (fmt == 1)
+  ISF_REQUIRE(!skip_empty || (fmt == 1 && occ_in && (long long)H * W < (1ll << 30)), ISF_ERR_ARG,
+              "dense: two passes need split rows + index");
+  if (fmt == 1 && skip_empty)
+    hipLaunchKernelGGL((dense_bev_kernel<1, true>), grid, dim3(256), 0, st, feats, C, D, H, W, occ.bits, occ.prefix,
+                       perm, out);
+  else if (fmt == 1)
     hipLaunchKernelGGL(dense_bev_kernel<1>, grid, dim3(256), 0, st, feats, C, D, H, W, occ.bits, occ.prefix,
                        perm, out);
   else if (fmt == 2)
@@ -361,7 +456,8 @@ static constexpr int kEncDiagKnown =
     ISF_ENC_DIAG_STAGGER | ISF_ENC_DIAG_R4_ISSUE | ISF_ENC_DIAG_TWO_AHEAD | ISF_ENC_DIAG_DEEP | ISF_ENC_DIAG_NARROW_TILES |
     ISF_ENC_DIAG_LAUNCH_ORDER | ISF_ENC_DIAG_NARROW_GATHER | ISF_ENC_DIAG_CU_KERNEL | ISF_ENC_DIAG_CU_VARIANT_MASK |
     ISF_ENC_DIAG_DENSE_TABLES | ISF_ENC_DIAG_TILE_TABLES | ISF_ENC_DIAG_COUNTS_MEMCPY | ISF_ENC_DIAG_BAND_ORDER | ISF_ENC_DIAG_NO_ROW_SORT |
-    ISF_ENC_DIAG_NARROW_ROW_SORT | ISF_ENC_DIAG_SORT_KEY_AB | ISF_ENC_DIAG_VFE_FP32_ROWS | ISF_ENC_DIAG_VOXELIZE_PER_FRAME;
+    ISF_ENC_DIAG_NARROW_ROW_SORT | ISF_ENC_DIAG_SORT_KEY_AB | ISF_ENC_DIAG_VFE_FP32_ROWS | ISF_ENC_DIAG_VOXELIZE_PER_FRAME |
+    ISF_ENC_DIAG_BEV_ONE_PASS;
 
 int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0, int n0, int B,
                                 const int shape0[3], const OccIndex* occ0, const isf_conv_layer* layers,
@@ -425,6 +521,11 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
   bool use16 = precision != 1;
   for (int i = 0; i < num_layers; ++i)
     use16 = use16 && layers[i].packed16 && sparse_conv_f16x3_supported(layers[i].c_in, layers[i].c_out);
+  // the fp32 BEV map of split rows in two passes (dense_bev_kernel): zeros early on the geometry stream, the occupied
+  // segments last
+  const bool bev_two_pass = !on(ISF_ENC_DIAG_BEV_ONE_PASS) && use16 && !f16io && (!opt || opt->bev_format == 0) &&
+                            spatial_features != nullptr;
+  bool bev_zeroed = false;
   const void* outputs[32];
   int out_rows[32];
   const void* x = x0;
@@ -701,6 +802,14 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
       L = Nx;
       ISF_TRY(stream_wait_stream(a, st, sg));
     }
+    if (bev_two_pass && i == num_layers - 1 && (long long)L.shape[1] * L.shape[2] < (1ll << 30)) {
+      // L is the output level and the last convolution no longer waits for `sg`: the zero segments of the map are written
+      // beside the convolutions still queued on `st` (a strided last layer has built the index above; the buffer is free:
+      // `sg` started behind everything the caller had queued on `st`); the join before dense_bev_kernel covers this launch
+      ISF_TRY(ensure_occ(a, L, B, sg));
+      ISF_TRY(bev_zero_empty_impl(L.occ, ly.c_out, spatial_features, sg));
+      bev_zeroed = true;
+    }
     void* y = nullptr;
     ISF_TRY(a.alloc(&y, (size_t)std::max(n_out, 1) * ly.c_out * 4));
     const void* res = nullptr;
@@ -755,7 +864,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
     ISF_REQUIRE(!opt || opt->bev_format == 0, ISF_ERR_ARG, "sparse_encoder: bev_format %d (0 fp32 map, 1 split token matrices)",
                 opt->bev_format);
     ISF_TRY(sparse_to_dense_bev_impl(a, x, use16 ? (f16io ? 2 : 1) : 0, L.coors, L.n, c_last, B, L.shape[0], L.shape[1],
-                                     L.shape[2], spatial_features, &L.occ, st));
+                                     L.shape[2], spatial_features, &L.occ, st, bev_zeroed));
   }
   if (stats) stats->precision = use16 ? 1 : 0;
   if (out_shape) { out_shape[0] = c_last * L.shape[0]; out_shape[1] = L.shape[1]; out_shape[2] = L.shape[2]; out_shape[3] = L.n; }
@@ -849,15 +958,13 @@ static bool encoder_takes_split_input(const isf_conv_layer* layers, int num_laye
   return true;
 }
 
-int isf_lidar_branch_forward(const float* points, const int64_t* point_offsets_host, int batch_size,
-                             const isf_vfe_params* vfe_host, const int sparse_shape_host[3],
+// the LiDAR branch over B frames: one concatenated block (`points`) or one block per frame (`frame_points`, B <= kVoxMaxBatch)
+static int lidar_branch_impl(const float* points, const float* const* frame_points, const int64_t* point_offsets_host,
+                             int batch_size, const isf_vfe_params* vfe_host, const int sparse_shape_host[3],
                              const isf_conv_layer* layers_host, int num_layers, float* spatial_features,
                              int out_shape_host[4], isf_encoder_stats* stats_host, int time_layers,
                              const isf_encoder_options* options, isf_stream_t stream) {
   using namespace isf;
-  ISF_REQUIRE(points && point_offsets_host && batch_size > 0 && vfe_host && sparse_shape_host && layers_host &&
-                  spatial_features,
-              ISF_ERR_ARG, "lidar_branch_forward: bad arguments");
   hipStream_t st = as_stream(stream);
   Arena& a = arena_for_stream(as_stream(stream));
   ISF_TRY(a.reset());
@@ -867,21 +974,26 @@ int isf_lidar_branch_forward(const float* points, const int64_t* point_offsets_h
   const int Cin = vfe_host->in_channels;
   int32_t* coors4 = nullptr;
   ISF_TRY(a.alloc_n(&coors4, (size_t)P * 4));
-  // batches of up to 8 frames: voxelized inside the byte-map marking launch of the VFE (one launch instead of B + 1 and
-  // one pass over the coordinates less); ISF_ENC_DIAG_VOXELIZE_PER_FRAME and larger batches: one dynamic_voxelize launch per frame
-  VoxBatch vb;
-  vb.B = batch_size;
-  const bool fused_vox = batch_size <= kVoxMaxBatch && !(options && (options->diagnostic & ISF_ENC_DIAG_VOXELIZE_PER_FRAME));
+  // batches of up to 8 frames: one frame table {offsets, base pointers} for every kernel that reads points, and the frames
+  // are voxelized inside the byte-map marking launch of the VFE (one launch instead of B + 1 and one pass over the
+  // coordinates less); ISF_ENC_DIAG_VOXELIZE_PER_FRAME and larger batches: one dynamic_voxelize launch per frame
+  const bool table = batch_size <= kVoxMaxBatch;
+  VoxBatch vb = table ? VoxBatch() : vox_one_block(points, P);   // (larger batches: concatenated, one block)
+  if (table) vb.B = batch_size;
+  const bool fused_vox = table && !(options && (options->diagnostic & ISF_ENC_DIAG_VOXELIZE_PER_FRAME));
   for (int b = 0; b < batch_size; ++b) {
     const int64_t lo = point_offsets_host[b], hi = point_offsets_host[b + 1];
     ISF_REQUIRE(hi >= lo, ISF_ERR_ARG, "lidar_branch_forward: bad offsets");
-    if (fused_vox) {
+    const float* base = frame_points ? frame_points[b] : points + lo * Cin;
+    ISF_REQUIRE(base || hi == lo, ISF_ERR_ARG, "lidar_branch_forward: frame %d has no points pointer", b);
+    if (table) {
       vb.off[b] = lo;
       vb.off[b + 1] = hi;
-    } else {
-      ISF_TRY(dynamic_voxelize_impl(points + lo * Cin, (int)(hi - lo), Cin, vfe_host->voxel_size,
-                                    vfe_host->coors_range, coors4 + lo * 4, 4, 1, b, st));
+      vb.base[b] = base;
     }
+    if (!fused_vox && hi > lo)
+      ISF_TRY(dynamic_voxelize_impl(base, (int)(hi - lo), Cin, vfe_host->voxel_size, vfe_host->coors_range, coors4 + lo * 4,
+                                    4, 1, b, st));
   }
   float* vf = nullptr;
   int32_t* vc = nullptr;
@@ -896,16 +1008,42 @@ int isf_lidar_branch_forward(const float* points, const int64_t* point_offsets_h
   if (encoder_takes_split_input(layers_host, num_layers, options) && vfe_host->c2 == layers_host[0].c_in &&
       !(options && (options->diagnostic & ISF_ENC_DIAG_VFE_FP32_ROWS)))   // fp32 rows + the conversion pass (same bits)
     ISF_TRY(a.alloc(&vf_split, (size_t)P * vfe_host->c2 * 4));
-  ISF_TRY(dynamic_vfe_impl(a, points, coors4, P, Cin, batch_size, vfe_host->voxel_size, vfe_host->coors_range,
+  ISF_TRY(dynamic_vfe_impl(a, nullptr, coors4, P, Cin, batch_size, vfe_host->voxel_size, vfe_host->coors_range,
                            vfe_host->w1, vfe_host->scale1, vfe_host->shift1, vfe_host->c1, vfe_host->w2,
                            vfe_host->scale2, vfe_host->shift2, vfe_host->c2, vf, vc, nullptr, &n0, &occ0,
-                           sparse_shape_host[0], st, &coords_ready, vf_split, fused_vox ? &vb : nullptr));
+                           sparse_shape_host[0], st, &coords_ready, vf_split, fused_vox ? &vb : nullptr, &vb));
   ISF_REQUIRE(n0 > 0, ISF_ERR_ARG, "lidar_branch_forward: no point falls inside the voxel grid");
   const bool occ_ok = occ0.D == sparse_shape_host[0] && occ0.H == sparse_shape_host[1] &&
                       occ0.W == sparse_shape_host[2];
   return sparse_encoder_forward_impl(a, vf, vc, n0, batch_size, sparse_shape_host, occ_ok ? &occ0 : nullptr,
                                      layers_host, num_layers, spatial_features, out_shape_host, stats_host,
                                      time_layers, options, st, occ_ok ? coords_ready : nullptr, vf_split);
+}
+
+int isf_lidar_branch_forward(const float* points, const int64_t* point_offsets_host, int batch_size,
+                             const isf_vfe_params* vfe_host, const int sparse_shape_host[3],
+                             const isf_conv_layer* layers_host, int num_layers, float* spatial_features,
+                             int out_shape_host[4], isf_encoder_stats* stats_host, int time_layers,
+                             const isf_encoder_options* options, isf_stream_t stream) {
+  ISF_REQUIRE(points && point_offsets_host && batch_size > 0 && vfe_host && sparse_shape_host && layers_host &&
+                  spatial_features,
+              ISF_ERR_ARG, "lidar_branch_forward: bad arguments");
+  return lidar_branch_impl(points, nullptr, point_offsets_host, batch_size, vfe_host, sparse_shape_host, layers_host,
+                           num_layers, spatial_features, out_shape_host, stats_host, time_layers, options, stream);
+}
+
+int isf_lidar_branch_forward_frames(const float* const* frame_points_host, const int64_t* point_offsets_host, int batch_size,
+                                    const isf_vfe_params* vfe_host, const int sparse_shape_host[3],
+                                    const isf_conv_layer* layers_host, int num_layers, float* spatial_features,
+                                    int out_shape_host[4], isf_encoder_stats* stats_host, int time_layers,
+                                    const isf_encoder_options* options, isf_stream_t stream) {
+  ISF_REQUIRE(frame_points_host && point_offsets_host && batch_size > 0 && vfe_host && sparse_shape_host && layers_host &&
+                  spatial_features,
+              ISF_ERR_ARG, "lidar_branch_forward_frames: bad arguments");
+  ISF_REQUIRE(batch_size <= isf::kVoxMaxBatch, ISF_ERR_UNSUPPORTED,
+              "lidar_branch_forward_frames: %d frames (at most %d; concatenate larger batches)", batch_size, isf::kVoxMaxBatch);
+  return lidar_branch_impl(nullptr, frame_points_host, point_offsets_host, batch_size, vfe_host, sparse_shape_host,
+                           layers_host, num_layers, spatial_features, out_shape_host, stats_host, time_layers, options, stream);
 }
 
 }  // extern "C"

@@ -362,7 +362,8 @@ __device__ __forceinline__ uint32_t scan_look_behind(const uint32_t* __restrict_
 template <bool SUMS>
 __global__ __launch_bounds__(kScanThreads) void occ_write_prefix_kernel(
     const unsigned long long* __restrict__ bits, size_t nwords,
-    const uint32_t* __restrict__ block_offsets, uint32_t* __restrict__ prefix, int* __restrict__ total) {
+    const uint32_t* __restrict__ block_offsets, uint32_t* __restrict__ prefix, int* __restrict__ total,
+    uint32_t* __restrict__ clear /* or nullptr: one counter per rank + one; a block zeroes those of its own ranks */) {
   __shared__ uint32_t lds[kScanThreads / 64];
   const size_t w0 = (size_t)blockIdx.x * kWordsPerBlock + (size_t)threadIdx.x * kWordsPerThread;
   uint32_t pc[kWordsPerThread];
@@ -373,6 +374,10 @@ __global__ __launch_bounds__(kScanThreads) void occ_write_prefix_kernel(
   const uint32_t base = SUMS ? scan_look_behind(block_offsets, lds) : block_offsets[blockIdx.x];
   uint32_t ex = block_exclusive_scan(c, lds, &tot) + base;
   if (SUMS && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = (int)(base + tot);
+  if (clear) {   // ranks [base, base + tot) are this block's; the last block adds counter [total]
+    const uint32_t n = tot + (blockIdx.x == gridDim.x - 1 ? 1u : 0u);
+    for (uint32_t i = threadIdx.x; i < n; i += kScanThreads) clear[base + i] = 0u;
+  }
 #pragma unroll
   for (int i = 0; i < kWordsPerThread; ++i) {
     if (w0 + i < nwords) prefix[w0 + i] = ex;
@@ -420,10 +425,14 @@ __global__ void occ_bytemap_mark_kernel(const int32_t* __restrict__ coors4, int 
 __global__ __launch_bounds__(256) void occ_bytemap_pack_kernel(unsigned char* __restrict__ fine,
                                                                unsigned char* __restrict__ coarse,
                                                                size_t nwords_alloc,
-                                                               unsigned long long* __restrict__ bits) {
-  // thread -> 4 consecutive words (one 4-byte load of the coarse map)
+                                                               unsigned long long* __restrict__ bits,
+                                                               uint32_t* __restrict__ block_sums) {
+  // thread -> 4 consecutive words (one 4-byte load of the coarse map); a workgroup covers the kWordsPerBlock words of one
+  // block of occ_scan and, with `block_sums`, leaves their popcount there: what occ_block_count_kernel would re-read the
+  // bitmap for (the grid covers nwords_alloc, a multiple of kWordsPerBlock, exactly: no thread leaves before the barrier)
+  static_assert(kWordsPerBlock == 256 * 4, "the pack kernel's workgroup is one scan block");
+  __shared__ uint32_t wave_sums[4];
   const size_t w0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (w0 >= nwords_alloc) return;
   const unsigned int c4 = *reinterpret_cast<const unsigned int*>(coarse + w0);
   unsigned long long out[4] = {0ull, 0ull, 0ull, 0ull};
   if (c4) {
@@ -449,21 +458,28 @@ __global__ __launch_bounds__(256) void occ_bytemap_pack_kernel(unsigned char* __
   }
   reinterpret_cast<ulonglong2*>(bits + w0)[0] = make_ulonglong2(out[0], out[1]);
   reinterpret_cast<ulonglong2*>(bits + w0)[1] = make_ulonglong2(out[2], out[3]);
+  if (block_sums) {
+    uint32_t c = __popcll(out[0]) + __popcll(out[1]) + __popcll(out[2]) + __popcll(out[3]);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = wave_sums[0] + wave_sums[1] + wave_sums[2] + wave_sums[3];
+  }
 }
 
 // voxelize + mark: thread -> point; the frame of a point by a walk over <= 8 offsets; coordinates exactly as
 // dynamic_voxelize_kernel computes them (voxel_of_point), (b, z, y, x) or (b, -1, -1, -1)
-__global__ __launch_bounds__(256) void occ_voxelize_mark_kernel(const float* __restrict__ points, int P, int C, VoxGeom g,
-                                                                VoxBatch vb, int D, int32_t* __restrict__ coors4,
+__global__ __launch_bounds__(256) void occ_voxelize_mark_kernel(int P, int C, VoxGeom g, VoxBatch vb, int D,
+                                                                int32_t* __restrict__ coors4,
                                                                 unsigned char* __restrict__ fine,
                                                                 unsigned char* __restrict__ coarse) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
-  int b = 0;
-#pragma unroll
-  for (int k = 1; k < kVoxMaxBatch; ++k) b += (k < vb.B && (long long)i >= vb.off[k]) ? 1 : 0;
+  int b;
+  const float* p = vox_point(vb, i, C, b);
   int cx, cy, cz;
-  const bool ok = voxel_of_point(points + (size_t)i * C, g.vx, g.vy, g.vz, g.x0, g.y0, g.z0, g.gx, g.gy, g.gz, cx, cy, cz);
+  const bool ok = voxel_of_point(p, g.vx, g.vy, g.vz, g.x0, g.y0, g.z0, g.gx, g.gy, g.gz, cx, cy, cz);
   reinterpret_cast<int4*>(coors4)[i] = ok ? make_int4(b, cz, cy, cx) : make_int4(b, -1, -1, -1);
   if (ok && cz < D) {
     const unsigned long long cell = (((unsigned long long)b * D + cz) * g.gy + cy) * g.gx + cx;
@@ -491,8 +507,8 @@ static int occ_bytemaps_ensure(Arena& a, const OccIndex& occ, hipStream_t st, si
   return ISF_OK;
 }
 
-int occ_voxelize_mark_bytemap(Arena& a, const OccIndex& occ, const float* points, int P, int C, const VoxGeom& g,
-                              const VoxBatch& vb, int32_t* coors4, hipStream_t st) {
+int occ_voxelize_mark_bytemap(Arena& a, const OccIndex& occ, int P, int C, const VoxGeom& g, const VoxBatch& vb,
+                              int32_t* coors4, hipStream_t st, uint32_t* block_sums) {
   ISF_REQUIRE(vb.B >= 1 && vb.B <= kVoxMaxBatch && vb.B == occ.B && g.gy == occ.H && g.gx == occ.W && g.gz <= occ.D,
               ISF_ERR_ARG, "voxelize + mark: %d frames, grid %d x %d x %d vs index %d x %d x %d", vb.B, g.gz, g.gy, g.gx,
               occ.D, occ.H, occ.W);
@@ -500,15 +516,16 @@ int occ_voxelize_mark_bytemap(Arena& a, const OccIndex& occ, const float* points
   ISF_TRY(occ_bytemaps_ensure(a, occ, st, &alloc_words));
   ByteMaps& bm = a.bytemaps;
   if (P > 0)
-    hipLaunchKernelGGL(occ_voxelize_mark_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, points, P, C, g, vb, occ.D, coors4,
-                       bm.fine, bm.coarse);
+    hipLaunchKernelGGL(occ_voxelize_mark_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, P, C, g, vb, occ.D, coors4, bm.fine,
+                       bm.coarse);
   hipLaunchKernelGGL(occ_bytemap_pack_kernel, dim3(ceil_div((long long)(alloc_words / 4), 256)), dim3(256), 0, st,
-                     bm.fine, bm.coarse, alloc_words, occ.bits);
+                     bm.fine, bm.coarse, alloc_words, occ.bits, block_sums);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
 
-int occ_mark_coords4_bytemap(Arena& a, const OccIndex& occ, const int32_t* coors4, int n, hipStream_t st) {
+int occ_mark_coords4_bytemap(Arena& a, const OccIndex& occ, const int32_t* coors4, int n, hipStream_t st,
+                             uint32_t* block_sums) {
   ByteMaps& bm = a.bytemaps;
   const size_t alloc_words = round_up(occ.nwords, kWordsPerBlock);
   if (bm.words < alloc_words) {  // (re)allocate the persistent maps; zeroed once, kept zero by the pack pass
@@ -527,7 +544,7 @@ int occ_mark_coords4_bytemap(Arena& a, const OccIndex& occ, const int32_t* coors
     hipLaunchKernelGGL(occ_bytemap_mark_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, coors4, n, occ.B, occ.D,
                        occ.H, occ.W, bm.fine, bm.coarse);
   hipLaunchKernelGGL(occ_bytemap_pack_kernel, dim3(ceil_div((long long)(alloc_words / 4), 256)), dim3(256), 0, st,
-                     bm.fine, bm.coarse, alloc_words, occ.bits);
+                     bm.fine, bm.coarse, alloc_words, occ.bits, block_sums);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
@@ -570,19 +587,25 @@ int fill_many(hipStream_t st, int n, void* const* ptrs, const size_t* bytes, con
   return ISF_OK;
 }
 
-int occ_scan(Arena& a, const OccIndex& occ, hipStream_t st) {
+int occ_scan_block_sums(Arena& a, const OccIndex& occ, uint32_t** sums) {
+  return a.alloc_n(sums, (size_t)ceil_div((long long)occ.nwords, kWordsPerBlock) + 1);
+}
+
+int occ_scan(Arena& a, const OccIndex& occ, hipStream_t st, uint32_t* block_sums, uint32_t* clear) {
   const int nblocks = ceil_div((long long)occ.nwords, kWordsPerBlock);
-  uint32_t* sums = nullptr;
-  ISF_TRY(a.alloc_n(&sums, (size_t)nblocks + 1));
-  hipLaunchKernelGGL(occ_block_count_kernel, dim3(nblocks), dim3(kScanThreads), 0, st, occ.bits,
-                     occ.nwords, sums);
+  uint32_t* sums = block_sums;
+  if (!sums) {
+    ISF_TRY(occ_scan_block_sums(a, occ, &sums));
+    hipLaunchKernelGGL(occ_block_count_kernel, dim3(nblocks), dim3(kScanThreads), 0, st, occ.bits,
+                       occ.nwords, sums);
+  }
   if (nblocks <= kLookBehindBlocks) {
     hipLaunchKernelGGL(occ_write_prefix_kernel<true>, dim3(nblocks), dim3(kScanThreads), 0, st, occ.bits, occ.nwords, sums,
-                       occ.prefix, occ.total);
+                       occ.prefix, occ.total, clear);
   } else {
     hipLaunchKernelGGL(occ_scan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, nblocks, occ.total);
     hipLaunchKernelGGL(occ_write_prefix_kernel<false>, dim3(nblocks), dim3(kScanThreads), 0, st, occ.bits, occ.nwords, sums,
-                       occ.prefix, occ.total);
+                       occ.prefix, occ.total, clear);
   }
   ISF_LAUNCH_CHECK();
   return ISF_OK;

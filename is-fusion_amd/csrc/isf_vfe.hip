@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void vfe_count_kernel(const int32_t* __restric
 // an index (measured FETCH_SIZE of the gathering version: 146 + 328 + 437 MB for 24 MB of points).
 static constexpr int kRec = 8;   // floats per record
 template <int CIN>
-__global__ __launch_bounds__(256) void vfe_order_kernel(const float* __restrict__ points,
+__global__ __launch_bounds__(256) void vfe_order_kernel(VoxBatch frames /* where the points live */,
                                                         const int32_t* __restrict__ pt2vox,
                                                         const int32_t* __restrict__ slot, int P,
                                                         const uint32_t* __restrict__ start,
@@ -168,8 +168,10 @@ __global__ __launch_bounds__(256) void vfe_order_kernel(const float* __restrict_
   float r[kRec];
 #pragma unroll
   for (int k = 0; k < kRec; ++k) r[k] = 0.f;
+  int b;
+  const float* p = vox_point(frames, i, CIN, b);
 #pragma unroll
-  for (int k = 0; k < CIN; ++k) r[k] = points[(size_t)i * CIN + k];
+  for (int k = 0; k < CIN; ++k) r[k] = p[k];
   r[kRec - 1] = __int_as_float(v);
   float4* o = reinterpret_cast<float4*>(recs + (size_t)(start[v] + slot[i]) * kRec);
   o[0] = make_float4(r[0], r[1], r[2], r[3]);
@@ -702,16 +704,24 @@ static int vfe_run(Arena& a, const float* points, const int32_t* coors4, int P, 
                    VfeGeom g, const float* w1, const float* scale1, const float* shift1, const float* w2,
                    const float* scale2, const float* shift2, float* voxel_feats, int32_t* voxel_coors,
                    int32_t* pt2vox_out, int* n_host, OccIndex* occ_out, int d_alloc, hipStream_t st,
-                   hipEvent_t* coords_ready, void* voxel_feats_split, const VoxBatch* voxelize, const VoxGeom* vgeom) {
+                   hipEvent_t* coords_ready, void* voxel_feats_split, const VoxBatch* voxelize, const VoxGeom* vgeom,
+                   const VoxBatch* frames_in) {
   const int F = CIN + 6;
+  const VoxBatch frames = frames_in ? *frames_in : (voxelize ? *voxelize : vox_one_block(points, P));
   OccIndex occ;
   // d_alloc > grid z lets the sparse encoder (sparse_shape[0] = grid z + 1) reuse this index for level 0
   ISF_TRY(occ_create(a, &occ, B, d_alloc > grid[2] ? d_alloc : grid[2], grid[1], grid[0], st, false));
+  // the pack pass of the marking leaves the scan's block popcounts (no count launch over the 42 MB bitmap it just wrote),
+  // and the scan's prefix launch zeroes the N + 1 per-voxel point counters that are used (N is known on the device only:
+  // a fill from the host had to cover the worst case of one voxel per point, P + 1)
+  uint32_t *occ_sums = nullptr, *cnt = nullptr;
+  ISF_TRY(occ_scan_block_sums(a, occ, &occ_sums));
+  ISF_TRY(a.alloc_n(&cnt, (size_t)P + 1));
   if (voxelize)   // the frames are voxelized inside the marking launch; coors4 is written there
-    ISF_TRY(occ_voxelize_mark_bytemap(a, occ, points, P, CIN, *vgeom, *voxelize, const_cast<int32_t*>(coors4), st));
+    ISF_TRY(occ_voxelize_mark_bytemap(a, occ, P, CIN, *vgeom, *voxelize, const_cast<int32_t*>(coors4), st, occ_sums));
   else
-    ISF_TRY(occ_mark_coords4_bytemap(a, occ, coors4, P, st));
-  ISF_TRY(occ_scan(a, occ, st));
+    ISF_TRY(occ_mark_coords4_bytemap(a, occ, coors4, P, st, occ_sums));
+  ISF_TRY(occ_scan(a, occ, st, occ_sums, cnt));
   float *sc1, *sc2;
   uint2* w1p;
   uint4* w2p;
@@ -740,13 +750,11 @@ static int vfe_run(Arena& a, const float* points, const int32_t* coors4, int P, 
   if (!pt2vox) ISF_TRY(a.alloc_n(&pt2vox, (size_t)P));
   int32_t* slot;
   float* recs;
-  uint32_t *cnt, *start;
+  uint32_t* start;
   float4* mean4;
   float* vmax1;
   ISF_TRY(a.alloc_n(&slot, (size_t)P));
   ISF_TRY(a.alloc_n(&recs, (size_t)P * kRec));
-  ISF_TRY(a.alloc_n(&cnt, (size_t)P + 1));
-  ISF_HIP_TRY(hipMemsetAsync(cnt, 0, ((size_t)P + 1) * sizeof(uint32_t), st));
   hipLaunchKernelGGL(vfe_count_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, coors4, P, occ.D, occ.H, occ.W,
                      occ.bits, occ.prefix, pt2vox, slot, cnt, voxel_coors);
   ISF_LAUNCH_CHECK();
@@ -763,7 +771,7 @@ static int vfe_run(Arena& a, const float* points, const int32_t* coors4, int P, 
   ISF_TRY(a.alloc_n(&mean4, (size_t)N));
   ISF_TRY(a.alloc_n(&vmax1, (size_t)N * kC));
   ISF_TRY(scan_u32_exclusive(a, cnt, start, (size_t)N, st));  // start[N] = number of in-range points
-  hipLaunchKernelGGL(vfe_order_kernel<CIN>, dim3(ceil_div(P, 256)), dim3(256), 0, st, points, pt2vox, slot, P, start,
+  hipLaunchKernelGGL(vfe_order_kernel<CIN>, dim3(ceil_div(P, 256)), dim3(256), 0, st, frames, pt2vox, slot, P, start,
                      recs);
   hipLaunchKernelGGL(vfe_mean_kernel<CIN>, dim3(ceil_div(P, 256)), dim3(256), 0, st, recs, start, N, mean4);
   const int* n_valid = reinterpret_cast<const int*>(start + N);
@@ -797,7 +805,8 @@ int dynamic_vfe_impl(Arena& a, const float* points, const int32_t* coors4, int P
                      const float* shift1, int c1, const float* w2, const float* scale2,
                      const float* shift2, int c2, float* voxel_feats, int32_t* voxel_coors,
                      int32_t* pt2vox, int* num_voxels_host, OccIndex* occ_out, int grid_d_alloc,
-                     hipStream_t st, hipEvent_t* coords_ready, void* voxel_feats_split, const VoxBatch* voxelize) {
+                     hipStream_t st, hipEvent_t* coords_ready, void* voxel_feats_split, const VoxBatch* voxelize,
+                     const VoxBatch* frames) {
   ISF_REQUIRE(c1 == kC && c2 == kC, ISF_ERR_UNSUPPORTED,
               "dynamic_vfe: feat_channels (%d,%d) not built; this build has (64,64)", c1, c2);
   ISF_REQUIRE(Cin == 4 || Cin == 5, ISF_ERR_UNSUPPORTED, "dynamic_vfe: in_channels %d not built (4|5)", Cin);
@@ -812,10 +821,10 @@ int dynamic_vfe_impl(Arena& a, const float* points, const int32_t* coors4, int P
   if (Cin == 5)
     return vfe_run<5>(a, points, coors4, P, B, grid, g, w1, scale1, shift1, w2, scale2, shift2,
                       voxel_feats, voxel_coors, pt2vox, num_voxels_host, occ_out, grid_d_alloc, st, coords_ready,
-                      voxel_feats_split, voxelize, &vg);
+                      voxel_feats_split, voxelize, &vg, frames);
   return vfe_run<4>(a, points, coors4, P, B, grid, g, w1, scale1, shift1, w2, scale2, shift2, voxel_feats,
                     voxel_coors, pt2vox, num_voxels_host, occ_out, grid_d_alloc, st, coords_ready, voxel_feats_split,
-                    voxelize, &vg);
+                    voxelize, &vg, frames);
 }
 
 }  // namespace isf

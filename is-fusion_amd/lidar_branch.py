@@ -2,8 +2,8 @@
 
     dynamic_voxelize(pts) -> DynamicVFE -> SparseEncoder -> spatial_features [B, 512, 180, 180]
 
-``LidarBranch.forward`` is ONE C call (isf_lidar_branch_forward): no per-sample Python loop, no
-``coors[-1,0].item()`` sync; the only host syncs left are the data-dependent voxel counts (one per
+``LidarBranch.forward`` is ONE C call (isf_lidar_branch_forward_frames over the frames where they lie, or
+isf_lidar_branch_forward over their concatenation): no per-sample Python loop, no ``coors[-1,0].item()`` sync; the only host syncs left are the data-dependent voxel counts (one per
 resolution level).  The sub-modules are the drop-in ``DynamicVFE`` / ``SparseEncoder`` classes, so a
 reference state dict (keys ``pts_voxel_encoder.*`` / ``pts_middle_encoder.*``) loads directly.
 """
@@ -127,27 +127,35 @@ class LidarBranch(nn.Module):
         return self.pts_middle_encoder.forward_modules(vf, vc, len(points))[0]
 
     def forward(self, points, time_layers=False, want_stats=False, precision=0, conv_diag=0, stage_rows=0,
-                stage_mask=0, out=None, bev_split=False):
+                stage_mask=0, out=None, bev_split=False, by_pointer=True):
         """points: list of [P_i, C] tensors (one per sample) -> spatial_features [B, C*D, H, W]
         (bev_split=True, inference: the same map as a list of dense_conv.SplitMap, one per 256-channel group -- the form the
         fusion encoder's convolutions read; isf_encoder_options.bev_format = 1).
         precision: 0 = f16x3 split MFMA (default, fp32-class), 1 = fp32 MFMA kernels, 2 = single-pass f16 (opt-in,
         fp16-autocast accuracy); conv_diag: timing diagnostics of the conv kernels (_lib.ENC_DIAG_* bits; the knock-outs' results are garbage);
-        stage_rows / stage_mask: LDS staging of the conv input rows (isf_encoder_options; 0 = library default)."""
+        stage_rows / stage_mask: LDS staging of the conv input rows (isf_encoder_options; 0 = library default);
+        by_pointer=False: concatenate the frames even where the engine could read them in place (A/B, tests)."""
         if self.training:
             return self.forward_train(points)
         with torch.no_grad():
             return self.forward_eval(points, time_layers, want_stats, precision, conv_diag, stage_rows, stage_mask, out,
-                                     bev_split)
+                                     bev_split, by_pointer)
 
     def forward_eval(self, points, time_layers=False, want_stats=False, precision=0, conv_diag=0, stage_rows=0,
-                     stage_mask=0, out=None, bev_split=False):
-        pts = torch.cat(points, dim=0).contiguous().float()
-        _lib.require_cuda(pts)
+                     stage_mask=0, out=None, bev_split=False, by_pointer=True):
         vfe = self.pts_voxel_encoder
-        if pts.size(1) != vfe.raw_in_channels:
-            raise _lib.IsfError(f"LidarBranch: points have {pts.size(1)} columns, the voxel encoder expects "
-                                f"{vfe.raw_in_channels}")
+        # frames by pointer (isf_lidar_branch_forward_frames): no concatenation pass over the points when every frame
+        # is already what the kernels read; anything else is concatenated (and converted) as before
+        dev = points[0].device if len(points) else None
+        by_frame = by_pointer and 1 <= len(points) <= 8 and all(
+            p.is_cuda and p.device == dev and p.dtype == torch.float32 and p.dim() == 2 and
+            p.size(1) == vfe.raw_in_channels and p.is_contiguous() for p in points)
+        pts = None if by_frame else torch.cat(points, dim=0).contiguous().float()
+        if pts is not None:
+            _lib.require_cuda(pts)
+            if pts.size(1) != vfe.raw_in_channels:
+                raise _lib.IsfError(f"LidarBranch: points have {pts.size(1)} columns, the voxel encoder expects "
+                                    f"{vfe.raw_in_channels}")
         if not vfe._fusable():
             raise _lib.IsfError("LidarBranch: the one-call engine implements the IS-Fusion DynamicVFE configuration "
                                 "(2 layers of 64, cluster + voxel centre, max pooling, no distance feature); build the "
@@ -161,16 +169,22 @@ class LidarBranch(nn.Module):
         vp, _keep2 = self._vfe_params()
         cd, H, W = me.out_channels_and_shape()
         if out is None:    # out: a caller-owned [B, C*D, H, W] buffer (the detector's HIP-graph input)
-            out = torch.empty((B, cd, H, W), dtype=torch.float32, device=pts.device)
+            out = torch.empty((B, cd, H, W), dtype=torch.float32, device=points[0].device if by_frame else pts.device)
         assert tuple(out.shape) == (B, cd, H, W) and out.is_contiguous() and out.dtype == torch.float32
         oshape = (ctypes.c_int * 4)()
         stats = _lib.EncoderStats() if (want_stats or time_layers) else None
         lib = _lib.load()
-        _lib.check(lib.isf_lidar_branch_forward(
-            _lib.ptr(pts), (ctypes.c_int64 * len(offs))(*offs), B, ctypes.byref(vp), _lib.i3(me.sparse_shape),
+        if by_frame:
+            entry, name = lib.isf_lidar_branch_forward_frames, "isf_lidar_branch_forward_frames"
+            src = (ctypes.c_void_p * B)(*[p.data_ptr() if p.size(0) else None for p in points])
+        else:
+            entry, name = lib.isf_lidar_branch_forward, "isf_lidar_branch_forward"
+            src = _lib.ptr(pts)
+        _lib.check(entry(
+            src, (ctypes.c_int64 * len(offs))(*offs), B, ctypes.byref(vp), _lib.i3(me.sparse_shape),
             arr, n, _lib.ptr(out), oshape, ctypes.byref(stats) if stats is not None else None,
             int(bool(time_layers)), _lib.encoder_options(precision, conv_diag, stage_rows, stage_mask, int(bool(bev_split))),
-            _lib.stream()), "isf_lidar_branch_forward")
+            _lib.stream()), name)
         self.last_stats = stats
         if bev_split:     # the buffer holds cd / 256 split-format token matrices [B*H*W, 256] (same bytes as the fp32 map)
             from .dense_conv import SplitMap
