@@ -306,16 +306,68 @@ int sparse_conv_forward_generic_impl(const float* x, int c_in, const float* w, i
                                      const int32_t* nbr, int nbr_stride, int n_out, const float* scale,
                                      const float* shift, const float* residual, int relu, float* y,
                                      hipStream_t st);
-// isf_spconv16.hip
+// isf_spconv16.hip and its siblings: ONE FORWARD CONVOLUTION of the f16x3 family.  This struct is the only way such a
+// convolution crosses a function boundary inside the library: the exported entries fill one (conv_call below + the
+// options by name), sparse_conv_forward_*_impl and the dispatch / launch templates under them pass it on by reference.
+// Plans that belong to one kernel travel beside it (ConvCuPlan; the staged kernel's slots / ulist / ucount / stage_rows).
+struct ConvCall {
+  // the problem
+  const void* xs = nullptr;         // input rows: split format ([N][C/32] chunks), plain f16 rows in the f16-storage mode
+  int c_in = 0;
+  const void* packed16 = nullptr;   // pack_filters16_impl's buffer: fragments + header (conv_weights)
+  int K = 0, c_out = 0;
+  const int32_t* nbr = nullptr;     // [K][nbr_stride] neighbour table (with lmask: lines [K / nx][nbr_stride]; by position
+  int nbr_stride = 0, n_out = 0;    // with rowmap; the staged kernel reads its slots instead)
+  // the epilogue: y = act(acc * scale + shift + residual)
+  const float* scale = nullptr;
+  const float* shift = nullptr;
+  const void* residual = nullptr;
+  int relu = 0;
+  void* ys = nullptr;
+  // how
+  int mode = 0;                     // ISF_CONV_MODE_* bits (+ isf_spconv16.h's internal ones)
+  const int32_t* order = nullptr;   // tile order; a tile table with kConvModeTileTable, a part table with kConvModePartTable
+  const int32_t* rowmap = nullptr;  // sorted launch: position -> output row (conv_row_sort_impl)
+  const uint32_t* lmask = nullptr;  // LDS-DMA kernel: nbr is a line-compressed table with these tap masks,
+  int nx = 0;                       // nx taps per line
+  long long* trace = nullptr;       // the trace instantiations' records (isf_sparse_conv_trace, isf_sparse_conv_dma_trace)
+  hipStream_t st = nullptr;
+};
+// the arguments the exported entries have in common, in the C interface's order; everything under "how" but the mode by name
+static inline ConvCall conv_call(const void* xs, int c_in, const void* packed16, int K, int c_out, const int32_t* nbr,
+                                 int nbr_stride, int n_out, const float* scale, const float* shift, const void* residual,
+                                 int relu, void* ys, int mode, hipStream_t st) {
+  ConvCall c;
+  c.xs = xs; c.c_in = c_in; c.packed16 = packed16; c.K = K; c.c_out = c_out; c.nbr = nbr; c.nbr_stride = nbr_stride;
+  c.n_out = n_out; c.scale = scale; c.shift = shift; c.residual = residual; c.relu = relu; c.ys = ys; c.mode = mode;
+  c.st = st;
+  return c;
+}
+// packed16 = K * c_in * c_out * 4 bytes of fragments followed by a 64-byte header that starts with 1 / (the pack-time scale)
+struct ConvWeights {
+  const uint4* wpk;
+  const float* winv;
+};
+static inline ConvWeights conv_weights(const ConvCall& c) {
+  const char* p = reinterpret_cast<const char*>(c.packed16);
+  return {reinterpret_cast<const uint4*>(p), reinterpret_cast<const float*>(p + (size_t)c.K * c.c_in * c.c_out * 4)};
+}
+// What every exported forward entry checks first.  required: the entry's own tables / plans, which must be there even for
+// an empty launch; pointers: the neighbour table (or what the entry reads in its place).  *run = false: nothing to compute.
+static inline int conv_entry_check(const char* entry, const ConvCall& c, int num_in, bool required, bool pointers, bool* run) {
+  *run = false;
+  ISF_REQUIRE(num_in >= 0 && c.n_out >= 0 && c.c_in > 0 && c.c_out > 0 && c.K > 0 && required, ISF_ERR_ARG,
+              "%s: bad arguments", entry);
+  if (c.n_out == 0) return ISF_OK;
+  ISF_REQUIRE(c.xs && c.packed16 && pointers && c.ys && ((c.scale == nullptr) == (c.shift == nullptr)), ISF_ERR_ARG,
+              "%s: null pointer", entry);
+  *run = true;
+  return ISF_OK;
+}
 bool sparse_conv_f16x3_supported(int c_in, int c_out);
-int sparse_conv_forward_f16x3_impl(const void* xs, int c_in, const void* packed16, int K, int c_out,
-                                   const int32_t* nbr, int nbr_stride, int n_out, const float* scale,
-                                   const float* shift, const void* residual, int relu, void* ys,
-                                   int mode /* ISF_CONV_MODE_* bits (+ isf_spconv16.h's internal ones) */, hipStream_t st,
-                                   const int32_t* order = nullptr, struct Conv16LaunchInfo* query = nullptr,
-                                   const int32_t* rowmap = nullptr /* sorted launch: position -> output row (conv_row_sort_impl) */);
-// How a launch of that kernel is cut into tiles (query != nullptr: filled instead of launching), and the per-part tile
-// order that evens out the work of the tiles sharing a CU (conv16_tile_order_impl; nullptr = slot j works on tile j).
+int sparse_conv_forward_f16x3_impl(const ConvCall& c);
+// How a launch is cut into tiles (conv16_launch_info), and the per-part tile order that evens out the work of the tiles
+// sharing a CU (conv16_tile_order_impl; nullptr = slot j works on tile j).
 struct Conv16LaunchInfo {
   int full, half, part_rows;   // Conv16Plan
   int TM, ncb, wgs_per_cu, cus_per_xcd;
@@ -334,6 +386,11 @@ static inline bool conv16_table_applies(const Conv16LaunchInfo& i) {
 static inline int conv16_table_ints(const Conv16LaunchInfo& i) {
   return conv16_order_parts(i) * 2 * i.wgs_per_cu * i.cus_per_xcd;
 }
+// The shape of the launch sparse_conv_forward_f16x3_impl / _dma_impl would make of n_out rows in `mode` -- a query, not a
+// launch: the function that picks the kernel instantiation of a launch answers it, so the two cannot disagree.  Checks the
+// channels (ISF_ERR_UNSUPPORTED) and the mode (ISF_ERR_ARG); n_out <= 0 gives zeros.
+enum ConvKernel { kConvKernelTile, kConvKernelDma, kConvKernelDmaLines /* the LDS-DMA kernel on a line-compressed table */ };
+int conv16_launch_info(ConvKernel kernel, int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info);
 int conv16_tile_table_impl(const int32_t* group_work, int n_out, const Conv16LaunchInfo& info, int32_t* table,
                            hipStream_t st);
 // isf_spconv_cu.hip: per 16-row group the taps through which one of its rows has a neighbour (masks) and their count (work)
@@ -342,17 +399,12 @@ int conv_group_masks_impl(const int32_t* nbr, int nbr_stride, int K, int n_out, 
 // isf_spconv_dma.hip: the same convolution for the narrow layers (<= 64 channels in and out) with the gathered rows
 // brought in by LDS-DMA, one cache line per lane quad; bit-identical to sparse_conv_forward_f16x3_impl
 bool sparse_conv_dma_supported(int c_in, int c_out);
-int sparse_conv_forward_dma_impl(const void* xs, int c_in, const void* packed16, int K, int c_out, const int32_t* nbr,
-                                 int nbr_stride, int n_out, const float* scale, const float* shift,
-                                 const void* residual, int relu, void* ys, int mode, hipStream_t st,
-                                 const int32_t* order = nullptr, Conv16LaunchInfo* query = nullptr,
-                                 const uint32_t* lmask = nullptr /* line-compressed table: nbr = lines */, int nx = 0,
-                                 const int32_t* rowmap = nullptr /* sorted launch: position -> output row */,
-                                 long long* trace = nullptr /* mode kKernTrace: per-workgroup trace (isf_sparse_conv_dma_trace) */);
+int sparse_conv_forward_dma_impl(const ConvCall& c);   // c.lmask / c.nx: line-compressed table; mode kKernTrace: c.trace
+int conv_dma_launch_info(bool lines, int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info);   // conv16_launch_info's
 int conv16_tile_order_impl(const int32_t* nbr, int nbr_stride, int K, int n_out, const Conv16LaunchInfo& info,
                            int32_t* work /* [parts * tiles] scratch */, int32_t* order /* [parts * tiles] */,
                            hipStream_t st, const uint32_t* lmask = nullptr /* line-compressed table's masks instead of nbr */);
-// EQUAL-WORK PARTS of a launch of several rounds (isf_spconv16.h): info = the launch's UNIFORM plan (query with
+// EQUAL-WORK PARTS of a launch of several rounds (isf_spconv16.h): info = the launch's UNIFORM plan (conv16_launch_info with
 // ISF_CONV_MODE_UNIFORM_TILES); work [2 * parts * info.full] scratch; table [conv16_part_table_ints].  Run the conv with
 // mode | kConvModePartTable and the table as `order`.  raster: slots in tile order (ISF_ENC_DIAG_LAUNCH_ORDER).
 bool conv16_parts_apply(const Conv16LaunchInfo& info, bool several_rounds = false);
@@ -381,12 +433,10 @@ bool conv16_band_order_applies(const Conv16LaunchInfo& info);
 int conv16_band_order_impl(const int32_t* coors4, int n_out, const Conv16LaunchInfo& info, int band, int32_t* order /* [parts * tiles] */,
                            hipStream_t st);
 // isf_spconv_deep.hip (round 6): the deep layers' 4-wave two-group launches with LDS-DMA gathers and one hand-scheduled
-// instruction stream per step; the tile kernel's plan / order / query semantics; bit-identical to it
+// instruction stream per step; the tile kernel's plan / order / launch-info semantics; bit-identical to it
 bool sparse_conv_deep_supported(int c_in, int c_out);
-int sparse_conv_forward_deep_impl(bool balance, bool table, const uint4* xs, int c_in, const uint4* wpk, const float* winv,
-                                  int K, int c_out, const int32_t* nbr, int nbr_stride, int n_out, const float* scale,
-                                  const float* shift, const uint4* residual, int relu, uint4* ys, hipStream_t st,
-                                  const int32_t* order, Conv16LaunchInfo* query);
+int sparse_conv_forward_deep_impl(const ConvCall& c);
+int conv_deep_launch_info(int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info);   // conv16_launch_info's
 // isf_spconv_cu.hip: the same convolution for the 256-column layers as one workgroup per compute unit over units of equal
 // matrix work (plan built once per rulebook); bit-identical to sparse_conv_forward_f16x3_impl
 struct ConvCuPlan {
@@ -403,17 +453,12 @@ bool sparse_conv_cu_supported(int c_in, int c_out);
 size_t conv_cu_plan_ints(int n_out);      // enough for either shape
 int conv_cu_plan_impl(const int32_t* nbr, int nbr_stride, int K, int n_out, int32_t* buf /* conv_cu_plan_ints(n_out) */,
                       ConvCuPlan* plan, hipStream_t st, int cap = 16);
-int sparse_conv_forward_cu_impl(const void* xs, int c_in, const void* packed16, int K, int c_out, const int32_t* nbr,
-                                int nbr_stride, int n_out, const float* scale, const float* shift, const void* residual,
-                                int relu, void* ys, const ConvCuPlan& plan, hipStream_t st);
+int sparse_conv_forward_cu_impl(const ConvCall& c, const ConvCuPlan& plan);
 // isf_spconv_stage.hip (LDS-staged input rows; staging tables of a rulebook)
 int stage_tables_impl(const int32_t* nbr, int nbr_stride, int K, uint16_t* slots, int32_t* ulist, int32_t* ucount,
                       hipStream_t st);
-int sparse_conv_forward_staged_impl(const void* xs, int c_in, const void* packed16, int K, int c_out,
-                                    const uint16_t* slots, int nbr_stride, const int32_t* ulist,
-                                    const int32_t* ucount, int n_out, const float* scale, const float* shift,
-                                    const void* residual, int relu, void* ys, int stage_rows, int mode,
-                                    hipStream_t st);
+int sparse_conv_forward_staged_impl(const ConvCall& c /* c.nbr is not read */, const uint16_t* slots, const int32_t* ulist,
+                                    const int32_t* ucount, int stage_rows);
 int pack_filters16_impl(Arena& a, const float* w, int K, int cin, int cout, void* packed16, hipStream_t st,
                         bool transposed = false /* w = [K][cout][cin], the per-tap transpose of the packed filter */);
 int f32_to_split_impl(const float* x, size_t n_elems, void* xs, hipStream_t st);

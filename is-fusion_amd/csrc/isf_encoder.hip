@@ -1,6 +1,6 @@
 // isf_encoder.hip -- A7: dense BEV write-out, SparseEncoder.forward and the fused LiDAR branch.
 #include "isf_common.h"
-#include "isf_spconv16.h"   // the conv mode bits that stay inside the library
+#include "isf_spconv_launch.h"   // the conv mode bits that stay inside the library, what a launch's `order` holds
 
 #include <algorithm>
 
@@ -337,9 +337,6 @@ static int build_cu_plan(Arena& a, const int32_t* nbr, int stride, int K, int n_
   return conv_cu_plan_impl(nbr, stride, K, n_out, buf, plan, sg, cap);
 }
 
-enum { kOrderPerm = 0, kOrderTable = 1, kOrderParts = 2 };   // what a launch's `order` holds
-static int order_mode_bit(int kind) { return kind == kOrderTable ? kConvModeTileTable : (kind == kOrderParts ? kConvModePartTable : 0); }
-
 // tile order / tile table of one conv launch over a neighbour table, built behind the table on the geometry stream.  A
 // launch of the tile kernel that is resident in one round gets a TILE TABLE (conv16_table_part: the groups dealt to the
 // compute units by equal work; *kind = kOrderTable, run the conv with mode | kConvModeTileTable); the LDS-DMA kernel's launches keep the
@@ -353,15 +350,10 @@ static int build_tile_order(Arena& a, const isf_conv_layer& ly, int K, const int
                             bool order_ok = true, bool parts_ok = false) {
   *order = nullptr;
   if (kind) *kind = kOrderPerm;
+  const ConvKernel kernel = dma ? kConvKernelDma : kConvKernelTile;
   Conv16LaunchInfo info;
   if (parts_ok && kind && n_out > 0) {   // the launch's uniform plan: several rounds?
-    const int um = mode | ISF_CONV_MODE_UNIFORM_TILES;
-    if (dma)
-      ISF_TRY(sparse_conv_forward_dma_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, nullptr,
-                                           nullptr, nullptr, 0, nullptr, um, sg, nullptr, &info));
-    else
-      ISF_TRY(sparse_conv_forward_f16x3_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, nullptr,
-                                             nullptr, nullptr, 0, nullptr, um, sg, nullptr, &info));
+    ISF_TRY(conv16_launch_info(kernel, ly.c_in, ly.c_out, n_out, mode | ISF_CONV_MODE_UNIFORM_TILES, &info));
     if (conv16_parts_apply(info)) {
       const int parts = conv16_order_parts(info), T = conv16_parts_tiles(info.full, parts);
       int32_t *work = nullptr, *table = nullptr;
@@ -375,12 +367,7 @@ static int build_tile_order(Arena& a, const isf_conv_layer& ly, int K, const int
     }
   }
   if (!order_ok) return ISF_OK;
-  if (dma)
-    ISF_TRY(sparse_conv_forward_dma_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, nullptr,
-                                         nullptr, nullptr, 0, nullptr, mode, sg, nullptr, &info));
-  else
-    ISF_TRY(sparse_conv_forward_f16x3_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, nullptr,
-                                           nullptr, nullptr, 0, nullptr, mode, sg, nullptr, &info));
+  ISF_TRY(conv16_launch_info(kernel, ly.c_in, ly.c_out, n_out, mode, &info));
   if (!dma && kind && tables && !lmask && conv16_table_applies(info) && n_out >= 16 * info.cus_per_xcd) {
     const int ng = ceil_div(n_out, 16);
     int32_t *masks = nullptr, *work = nullptr, *table = nullptr;
@@ -609,18 +596,14 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
     const bool sort_ok = row_sort && use16 && !cu && srows == 0 && ly.conv_type == ISF_CONV_SUBM && K == 27 &&
                          sort_mode_ok && L.n >= sort_min_rows && (dma ? narrow_sort : ly.c_out >= 128);
     const int32_t* rowmap = nullptr;
-    auto launch_info = [&](const int32_t* table, int tstride, int rows, Conv16LaunchInfo* info) -> int {
-      if (dma)
-        return sparse_conv_forward_dma_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, table, tstride, rows, nullptr, nullptr,
-                                            nullptr, 0, nullptr, conv_mode, sg, nullptr, info);
-      return sparse_conv_forward_f16x3_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, table, tstride, rows, nullptr, nullptr,
-                                            nullptr, 0, nullptr, layer_mode, sg, nullptr, info);
+    auto launch_info = [&](int rows, Conv16LaunchInfo* info) -> int {
+      return conv16_launch_info(dma ? kConvKernelDma : kConvKernelTile, ly.c_in, ly.c_out, rows, dma ? conv_mode : layer_mode, info);
     };
     auto ensure_row_sort = [&](const int32_t* table, int tstride, int rows, bool* built) -> int {
       *built = false;
       if (!sort_ok || L.cache_rowmap) return ISF_OK;   // (sorted for another plan: this layer keeps the plain table)
       Conv16LaunchInfo info;
-      ISF_TRY(launch_info(table, tstride, rows, &info));
+      ISF_TRY(launch_info(rows, &info));
       int32_t *rm = nullptr, *ns = nullptr;
       ISF_TRY(a.alloc_n(&rm, (size_t)tstride));
       if (L.cache_lmask) {
@@ -645,7 +628,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
     auto sort_applies = [&](const int32_t* table, int tstride, int rows) -> bool {   // this layer's plan == the sort's plan
       if (!sort_ok || !L.cache_rowmap) return false;
       Conv16LaunchInfo info;
-      if (launch_info(table, tstride, rows, &info) != ISF_OK) return false;
+      if (launch_info(rows, &info) != ISF_OK) return false;
       return info.part_rows == L.cache_sort_part_rows;
     };
     if (ly.conv_type == ISF_CONV_SUBM) {
@@ -775,8 +758,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
       if (row_sort && use16 && !dma && !cu && srows == 0 && !lmask && ly.c_out >= 128 && K == 27 && sort_mode_ok &&
           Nx.n >= sort_min_rows) {
         Conv16LaunchInfo info;
-        ISF_TRY(sparse_conv_forward_f16x3_impl(nullptr, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, Nx.n, nullptr, nullptr,
-                                               nullptr, 0, nullptr, layer_mode, sg, nullptr, &info));
+        ISF_TRY(conv16_launch_info(kConvKernelTile, ly.c_in, ly.c_out, Nx.n, layer_mode, &info));
         int32_t *rm = nullptr, *ns = nullptr;
         ISF_TRY(a.alloc_n(&rm, (size_t)stride));
         ISF_TRY(a.alloc_n(&ns, (size_t)K * stride));
@@ -820,24 +802,25 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
       res = outputs[ly.residual_from];
     }
     if (!ev.empty()) ISF_HIP_TRY(hipEventRecord(ev[2 * i], st));
+    ConvCall call = conv_call(x, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, ly.scale, ly.shift, res, ly.relu, y,
+                              conv_mode, st);
     if (use16 && srows > 0)
-      ISF_TRY(sparse_conv_forward_staged_impl(x, ly.c_in, ly.packed16, K, ly.c_out, stg.slots, stride, stg.ulist,
-                                              stg.ucount, n_out, ly.scale, ly.shift, res, ly.relu, y, srows, conv_mode,
-                                              st));
+      ISF_TRY(sparse_conv_forward_staged_impl(call, stg.slots, stg.ulist, stg.ucount, srows));
     else if (cu && n_out > 0 && ((cu_plan.variant = cu_variant), true))
-      ISF_TRY(sparse_conv_forward_cu_impl(x, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, ly.scale, ly.shift, res,
-                                          ly.relu, y, cu_plan, st));
-    else if (dma)
-      ISF_TRY(sparse_conv_forward_dma_impl(x, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, ly.scale, ly.shift,
-                                           res, ly.relu, y, conv_mode | order_mode_bit(order_kind), st, order, nullptr, lmask,
-                                           nx, rowmap));
-    else if (use16)
-      ISF_TRY(sparse_conv_forward_f16x3_impl(x, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, ly.scale,
-                                             ly.shift, res, ly.relu, y,
-                                             layer_mode | order_mode_bit(order_kind) |
-                                                 (ly.c_out == 256 && fp32_class ? one_block : 0),
-                                             st, order, nullptr, rowmap));
-    else if (sparse_conv_mfma_supported(ly.c_in, ly.c_out))
+      ISF_TRY(sparse_conv_forward_cu_impl(call, cu_plan));
+    else if (use16) {   // the LDS-DMA kernel or the tile kernel, on the order / table and the row sort built for this launch
+      call.order = order;
+      call.rowmap = rowmap;
+      if (dma) {
+        call.mode = conv_mode | order_mode_bit(order_kind);
+        call.lmask = lmask;
+        call.nx = nx;
+        ISF_TRY(sparse_conv_forward_dma_impl(call));
+      } else {
+        call.mode = layer_mode | order_mode_bit(order_kind) | (ly.c_out == 256 && fp32_class ? one_block : 0);
+        ISF_TRY(sparse_conv_forward_f16x3_impl(call));
+      }
+    } else if (sparse_conv_mfma_supported(ly.c_in, ly.c_out))
       ISF_TRY(sparse_conv_forward_packed_impl(reinterpret_cast<const float*>(x), n_in, ly.c_in, ly.packed, K,
                                               ly.c_out, nbr, stride, n_out, ly.scale, ly.shift,
                                               reinterpret_cast<const float*>(res), ly.relu,

@@ -29,7 +29,7 @@
 //   one barrier per step; taps that no row of the tile uses are skipped by the whole workgroup, taps that a
 //   16-row group does not use are skipped by that wave (wave-uniform branch);
 //   epilogue: LDS transpose, y = act(acc*scale + shift + residual), rows written once in split format.
-#include "isf_spconv16.h"
+#include "isf_spconv_launch.h"
 #include "isf_spconv16_mult.h"
 
 #include <stdlib.h>
@@ -776,50 +776,29 @@ bool sparse_conv_f16x3_supported(int c_in, int c_out) {
          (c_out == 32 || c_out == 64 || c_out == 128 || c_out == 256);
 }
 
+// One instantiation of the kernel: launches `c`, or with `query` reports how that launch would be cut (conv16_launch_info;
+// c then carries the channels, the row count and the mode alone).
 template <int CIN, int NT, int RG, int NW, int MODE = 0>
-static int launch16(bool balance, int table /* `order` is 1: a tile table (conv16_table_part), 2: a part table (conv16_part_table_impl), 0: a permutation */, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
-                    const int32_t* nbr, int nbr_stride, int n_out, const float* scale, const float* shift,
-                    const uint4* residual, int relu, uint4* ys, hipStream_t st, const int32_t* order,
-                    Conv16LaunchInfo* query, long long* trace = nullptr, const int32_t* rowmap = nullptr) {
+static int launch16(const ConvCall& c, Conv16LaunchInfo* query) {
   using S = Conv16Smem<NT, RG, Conv16Step<CIN, NT>::KCH, NW>;
   auto kern = spconv_f16x3_kernel<CIN, NT, RG, NW, MODE>;
-  static std::atomic<int> wgs_per_cu{0}, cus_per_xcd{0};   // of this instantiation on this device family
-  if (wgs_per_cu.load(std::memory_order_acquire) == 0) {
-    if (S::bytes > 48 * 1024)
-      ISF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, S::bytes));
-    int dev = 0, cus = 0, occ = 0;
-    ISF_HIP_TRY(hipGetDevice(&dev));
-    ISF_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    ISF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * NW, S::bytes));
-    cus_per_xcd.store(cus >= 8 ? cus / 8 : 1, std::memory_order_relaxed);
-    wgs_per_cu.store(occ > 0 ? occ : 1, std::memory_order_release);
-  }
-  const int ncb = cout / (16 * NT);
+  static ConvSlots slots;
+  ISF_TRY(conv_kernel_slots(slots, reinterpret_cast<const void*>(kern), 64 * NW, S::bytes, S::bytes));
+  const int ncb = c.c_out / (16 * NT);
   ISF_REQUIRE(ncb == 1 || ncb == 2, ISF_ERR_UNSUPPORTED, "sparse_conv16: %d column blocks", ncb);
-  Conv16Plan plan = conv16_plan(n_out, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
-                                cus_per_xcd.load(std::memory_order_relaxed), balance && RG > 1 && table != 2);
-  if (table == 2 && !query) {   // equal-work parts of the uniform plan: conv16_parts_cap slots per part
-    ISF_REQUIRE(plan.half == 0, ISF_ERR_ARG, "sparse_conv16: a part table needs the uniform plan");
-    const int parts = ncb == 2 ? 4 : 8;
-    plan = Conv16Plan{conv16_parts_cap(conv16_parts_tiles(plan.full, parts), parts), kPlanParts, plan.part_rows};
-  }
-  if (table == 1 && !query) plan = Conv16Plan{wgs_per_cu.load(std::memory_order_relaxed) * cus_per_xcd.load(std::memory_order_relaxed),
-                                         -1, plan.part_rows};
-  if (query) {   // what this launch would look like (conv16_tile_order_impl works on exactly these tiles)
-    *query = Conv16LaunchInfo{plan.full, plan.half, plan.part_rows, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
-                              cus_per_xcd.load(std::memory_order_relaxed)};
-    return ISF_OK;
-  }
+  const Conv16Plan plan = conv16_launch_plan(c, S::TM, ncb, slots, RG > 1, query);
+  if (query) return ISF_OK;   // the shape was asked for (conv16_tile_order_impl works on exactly these tiles)
   float* ks_scratch = nullptr;
   unsigned* ks_count = nullptr;
   int grid = conv16_grid_blocks(plan);
   if constexpr ((MODE & kKernChunkSplit) != 0) {   // chunk split: two workgroups per tile, their exchange buffers from the workspace
-    ISF_TRY(ksplit_buffers(arena_for_stream(st), (size_t)grid * 2 * NW * RG * NT * 1024, grid, &ks_scratch, &ks_count, st));
+    ISF_TRY(ksplit_buffers(arena_for_stream(c.st), (size_t)grid * 2 * NW * RG * NT * 1024, grid, &ks_scratch, &ks_count, c.st));
     grid *= 2;
   }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), S::bytes, st, xs, nbr, nbr_stride, wpk, winv, K,
-                     cout, scale, shift, residual, ys, n_out, relu, plan, order, trace, rowmap, ks_scratch, ks_count);
+  const ConvWeights w = conv_weights(c);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), S::bytes, c.st, reinterpret_cast<const uint4*>(c.xs), c.nbr, c.nbr_stride,
+                     w.wpk, w.winv, c.K, c.c_out, c.scale, c.shift, reinterpret_cast<const uint4*>(c.residual),
+                     reinterpret_cast<uint4*>(c.ys), c.n_out, c.relu, plan, c.order, c.trace, c.rowmap, ks_scratch, ks_count);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
@@ -851,11 +830,12 @@ static int conv16_device_cus() {
   return c;
 }
 
+// THE instantiation choice of the tile kernel: every launch and every launch-info query (`query`, see launch16) of a
+// (CIN, 16 * NT columns per block) shape comes through here.
 template <int CIN, int NT>
-static int launch16_rows(int mode, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
-                         const int32_t* nbr, int nbr_stride, int n_out, const float* scale, const float* shift,
-                         const uint4* residual, int relu, uint4* ys, hipStream_t st, const int32_t* order,
-                         Conv16LaunchInfo* query, const int32_t* rowmap = nullptr) {
+static int launch16_rows(const ConvCall& c, Conv16LaunchInfo* query) {
+  int mode = c.mode;
+  const int cout = c.c_out, n_out = c.n_out;
   // kConvModeNarrowTiles (A/B): the 128-column layers of the large levels on the 4-wave 128-row tile instead of the 8-wave 256-row one
   const bool narrow_tiles = (mode & kConvModeNarrowTiles) != 0;
   mode &= ~kConvModeNarrowTiles;
@@ -863,7 +843,6 @@ static int launch16_rows(int mode, const uint4* xs, const uint4* wpk, const floa
   // isf_spconv_deep.hip (LDS-DMA gathers + one instruction stream per step)
   const bool use_deep = (mode & ISF_CONV_MODE_DEEP) != 0;
   mode &= ~ISF_CONV_MODE_DEEP;
-#define ISF_ARGS16 (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, (order == nullptr ? 0 : (mode & kConvModeTileTable) ? 1 : (mode & kConvModePartTable) ? 2 : 0), xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, nullptr, rowmap
   // ISF_CONV_MODE_ONE_BLOCK_4W / _8W (round 5 experiment, valid results, bit-identical): the 256-COLUMN layers as ONE column block
   // -- a workgroup owns all 256 output columns of its rows, so a row is gathered ONCE per tap and chunk instead of once per
   // column block.  The phase trace (profiles/r05_att_256.txt) shows the step bound by the vector-memory issue path (a
@@ -874,156 +853,147 @@ static int launch16_rows(int mode, const uint4* xs, const uint4* wpk, const floa
   // rule below (the choice does not change the arithmetic); other shapes / modes ignore the bit
   if constexpr (NT == 8 && CIN >= 128) {
     if ((mode & ISF_CONV_MODE_CHUNK_SPLIT) && cout == 256 && (mode & ~(kConvModeTileBits | ISF_CONV_MODE_CHUNK_SPLIT)) == 0) {
-      if (n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4, kKernChunkSplit>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, kKernChunkSplit>(ISF_ARGS16);
+      if (n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4, kKernChunkSplit>(c, query);
+      return launch16<CIN, NT, 2, 4, kKernChunkSplit>(c, query);
     }
   }
   mode &= ~ISF_CONV_MODE_CHUNK_SPLIT;
   if constexpr (NT == 8 && CIN >= 128) {
     constexpr int one_block = ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W;
-    if ((mode & one_block) && cout == 256 && (mode & ~(kConvModeTileBits | one_block)) == 0 && !rowmap) {
-      if (mode & ISF_CONV_MODE_ONE_BLOCK_8W)
-        return launch16<CIN, 16, 1, 8>(false, false, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual,
-                                       relu, ys, st, nullptr, query);
-      return launch16<CIN, 16, 2, 4>((mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, false, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift,
-                                     residual, relu, ys, st, nullptr, query);
+    if ((mode & one_block) && cout == 256 && (mode & ~(kConvModeTileBits | one_block)) == 0 && !c.rowmap) {
+      ConvCall one = c;
+      one.order = nullptr;
+      if (mode & ISF_CONV_MODE_ONE_BLOCK_8W) {   // (one group per wave: no half tiles)
+        one.mode |= ISF_CONV_MODE_UNIFORM_TILES;
+        return launch16<CIN, 16, 1, 8>(one, query);
+      }
+      return launch16<CIN, 16, 2, 4>(one, query);
     }
   }
   mode &= ~(ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W);
   if constexpr (NT == 8 && CIN >= 128) {   // ISF_CONV_MODE_TWO_AHEAD: gathered rows two steps ahead (A2 loop; 4-wave shapes)
-    if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_TWO_AHEAD && !(cout == 128 && n_out >= 8 * 256)) return launch16<CIN, NT, 2, 4, kKernTwoAhead>(ISF_ARGS16);
+    if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_TWO_AHEAD && !(cout == 128 && n_out >= 8 * 256)) return launch16<CIN, NT, 2, 4, kKernTwoAhead>(c, query);
   }
   mode &= ~ISF_CONV_MODE_TWO_AHEAD;
   if constexpr (NT == 8) {   // ISF_CONV_MODE_R4_ISSUE: round 4's issue phase (index reads in the step, four separate DMA pieces): A/B
     if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_R4_ISSUE) {
-      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, kKernR4Issue>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, kKernR4Issue>(ISF_ARGS16);
+      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, kKernR4Issue>(c, query);
+      return launch16<CIN, NT, 2, 4, kKernR4Issue>(c, query);
     }
   }
   mode &= ~ISF_CONV_MODE_R4_ISSUE;
   if constexpr (NT == 8) {   // ISF_CONV_MODE_STAGGER: staggered issue phases (deep layers; valid results, bit-identical)
     if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_STAGGER) {
-      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, kKernStagger>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, kKernStagger>(ISF_ARGS16);
+      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, kKernStagger>(c, query);
+      return launch16<CIN, NT, 2, 4, kKernStagger>(c, query);
     }
   }
   mode &= ~ISF_CONV_MODE_STAGGER;
   switch (mode & ~kConvModeTileBits) {   // single-pass f16 (opt-in) and the timing diagnostics run on the 4-wave shape
     case 0: break;
-    case ISF_CONV_MODE_F16: return launch16<CIN, NT, 2, 4, kKernF16>(ISF_ARGS16);
-    case ISF_CONV_MODE_NO_GATHER: return launch16<CIN, NT, 2, 4, kKernNoGather>(ISF_ARGS16);
-    case ISF_CONV_MODE_NO_WEIGHTS: return launch16<CIN, NT, 2, 4, kKernNoWeights>(ISF_ARGS16);
-    case ISF_CONV_MODE_NO_GATHER | ISF_CONV_MODE_NO_WEIGHTS: return launch16<CIN, NT, 2, 4, kKernNoGather | kKernNoWeights>(ISF_ARGS16);
-    case ISF_CONV_MODE_NO_LOOP: return launch16<CIN, NT, 2, 4, kKernNoLoop>(ISF_ARGS16);
+    case ISF_CONV_MODE_F16: return launch16<CIN, NT, 2, 4, kKernF16>(c, query);
+    case ISF_CONV_MODE_NO_GATHER: return launch16<CIN, NT, 2, 4, kKernNoGather>(c, query);
+    case ISF_CONV_MODE_NO_WEIGHTS: return launch16<CIN, NT, 2, 4, kKernNoWeights>(c, query);
+    case ISF_CONV_MODE_NO_GATHER | ISF_CONV_MODE_NO_WEIGHTS: return launch16<CIN, NT, 2, 4, kKernNoGather | kKernNoWeights>(c, query);
+    case ISF_CONV_MODE_NO_LOOP: return launch16<CIN, NT, 2, 4, kKernNoLoop>(c, query);
     case ISF_CONV_MODE_F16_STORAGE:   // f16 storage (+ single-pass f16 arithmetic), production workgroup shapes
-      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, kKernF16Rows | kKernF16>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, kKernF16Rows | kKernF16>(ISF_ARGS16);
+      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, kKernF16Rows | kKernF16>(c, query);
+      return launch16<CIN, NT, 2, 4, kKernF16Rows | kKernF16>(c, query);
     case ISF_CONV_MODE_NO_SHARING:   // no neighbour sharing, production workgroup shapes
-      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, kKernNoSharing>(ISF_ARGS16);
-      return launch16<CIN, NT, 2, 4, kKernNoSharing>(ISF_ARGS16);
+      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, kKernNoSharing>(c, query);
+      return launch16<CIN, NT, 2, 4, kKernNoSharing>(c, query);
     default:
       ISF_REQUIRE(false, ISF_ERR_ARG, "sparse_conv16: mode %d (single-pass precision and the diagnostics {2,4,6,8} "
                   "are not combinable)", mode);
   }
   if constexpr (NT == 8) {   // small launches: one 16-row group per wave (see conv16_device_cus above)
-    if (cout == 128 && n_out >= 8 * 256 && n_out <= 256 * conv16_device_cus()) return launch16<CIN, NT, 1, 8>(ISF_ARGS16);
+    if (cout == 128 && n_out >= 8 * 256 && n_out <= 256 * conv16_device_cus()) return launch16<CIN, NT, 1, 8>(c, query);
   }
   if (NT == 8 && cout == 128 && n_out >= 8 * 256 && !narrow_tiles)
-    return launch16<CIN, (NT == 8 ? NT : 2), 2, 8>(ISF_ARGS16);
+    return launch16<CIN, (NT == 8 ? NT : 2), 2, 8>(c, query);
   if constexpr (NT == 8 && CIN >= 128) {
-    if (cout == 256 && n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4>(ISF_ARGS16);
+    if (cout == 256 && n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4>(c, query);
   }
   if constexpr (NT == 8 && CIN >= 128) {
-    if (use_deep && !rowmap && (mode & ~kConvModeTileBits) == 0 && !(mode & kConvModePartTable) && sparse_conv_deep_supported(CIN, cout))
-      return sparse_conv_forward_deep_impl((mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, (mode & kConvModeTileTable) != 0 && order != nullptr, xs, CIN, wpk, winv, K, cout,
-                                           nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query);
+    if (use_deep && !c.rowmap && (mode & ~kConvModeTileBits) == 0 && !(mode & kConvModePartTable) && sparse_conv_deep_supported(CIN, cout))
+      return query ? conv_deep_launch_info(CIN, cout, n_out, c.mode, query) : sparse_conv_forward_deep_impl(c);
   }
-  return launch16<CIN, NT, 2, 4>(ISF_ARGS16);
-#undef ISF_ARGS16
+  return launch16<CIN, NT, 2, 4>(c, query);
 }
 
 template <int CIN>
-static int dispatch16(int mode, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
-                      const int32_t* nbr, int nbr_stride, int n_out, const float* scale, const float* shift,
-                      const uint4* residual, int relu, uint4* ys, hipStream_t st, const int32_t* order,
-                      Conv16LaunchInfo* query, const int32_t* rowmap) {
-  switch (cout) {
-    case 32:  return launch16_rows<CIN, 2>(mode, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, rowmap);
-    case 64:  return launch16_rows<CIN, 4>(mode, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, rowmap);
+static int dispatch16(const ConvCall& c, Conv16LaunchInfo* query) {
+  switch (c.c_out) {
+    case 32:  return launch16_rows<CIN, 2>(c, query);
+    case 64:  return launch16_rows<CIN, 4>(c, query);
     case 128:
-    case 256: return launch16_rows<CIN, 8>(mode, xs, wpk, winv, K, cout, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, rowmap);
+    case 256: return launch16_rows<CIN, 8>(c, query);
   }
   return ISF_ERR_UNSUPPORTED;
 }
 
-// packed16 = K*Cin*Cout*4 bytes of fragments followed by a 64-byte header
-int sparse_conv_forward_f16x3_impl(const void* xs, int c_in, const void* packed16, int K, int c_out,
-                                   const int32_t* nbr, int nbr_stride, int n_out, const float* scale,
-                                   const float* shift, const void* residual, int relu, void* ys, int mode,
-                                   hipStream_t st, const int32_t* order, Conv16LaunchInfo* query, const int32_t* rowmap) {
-  if (n_out <= 0) {
-    if (query) *query = Conv16LaunchInfo{0, 0, 0, 0, 0, 0, 0};
-    return ISF_OK;
-  }
-  ISF_REQUIRE(K >= 1 && K <= kMaxTaps, ISF_ERR_UNSUPPORTED, "sparse_conv16: %d taps (max 27)", K);
-  ISF_REQUIRE(sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
-              "sparse_conv16: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
-  ISF_REQUIRE(nbr_stride % 128 == 0 && nbr_stride >= n_out, ISF_ERR_ARG, "sparse_conv16: bad nbr_stride");
-  const uint4* w = reinterpret_cast<const uint4*>(packed16);
-  const float* winv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed16) +
-                                                     (size_t)K * c_in * c_out * 4);
-  const uint4* x = reinterpret_cast<const uint4*>(xs);
-  const uint4* r = reinterpret_cast<const uint4*>(residual);
-  uint4* y = reinterpret_cast<uint4*>(ys);
-  switch (c_in) {
-    case 32:  return dispatch16<32>(mode, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, query, rowmap);
-    case 64:  return dispatch16<64>(mode, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, query, rowmap);
-    case 128: return dispatch16<128>(mode, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, query, rowmap);
-    case 256: return dispatch16<256>(mode, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, query, rowmap);
+static int run16(const ConvCall& c, Conv16LaunchInfo* query) {
+  switch (c.c_in) {
+    case 32:  return dispatch16<32>(c, query);
+    case 64:  return dispatch16<64>(c, query);
+    case 128: return dispatch16<128>(c, query);
+    case 256: return dispatch16<256>(c, query);
   }
   return ISF_ERR_UNSUPPORTED;
 }
 
-// per-workgroup trace of one launch (production workgroup shape of the two deep channel shapes): where the time of a
-// launch goes -- tools/conv_trace.py
-int sparse_conv_trace_impl(const void* xs, int c_in, const void* packed16, int K, int c_out, const int32_t* nbr,
-                           int nbr_stride, int n_out, const float* scale, const float* shift, const void* residual,
-                           int relu, void* ys, const int32_t* order, long long* trace, int trace_capacity_blocks,
-                           int* grid_blocks, hipStream_t st, bool phase = false, size_t phase_capacity_bytes = 0,
-                           int* waves_per_block = nullptr) {
-  ISF_REQUIRE((c_in == 256 && c_out == 256) || (c_in == 128 && c_out == 128), ISF_ERR_UNSUPPORTED,
-              "sparse_conv_trace: built for 128 -> 128 and 256 -> 256, got %d -> %d", c_in, c_out);
-  ISF_REQUIRE(K >= 1 && K <= kMaxTaps && n_out > 0 && nbr_stride % 128 == 0 && nbr_stride >= n_out, ISF_ERR_ARG,
+int sparse_conv_forward_f16x3_impl(const ConvCall& c) {
+  if (c.n_out <= 0) return ISF_OK;
+  ISF_TRY(conv_check_problem("sparse_conv16", c.c_in, c.c_out, sparse_conv_f16x3_supported(c.c_in, c.c_out), c.K, c.nbr_stride, c.n_out));
+  return run16(c, nullptr);
+}
+
+// The trace instantiations (c.mode = kKernTrace, + kKernPhaseTrace for the per-wave phase records): the production
+// workgroup shape of the two deep channel shapes.  As launch16_rows: launch, or with `query` the launch's shape.
+static int trace16(const ConvCall& c, Conv16LaunchInfo* query) {
+  const bool wide = c.c_out == 128 && c.n_out >= 8 * 256;
+  if (c.mode & kKernPhaseTrace) {
+    if (c.c_in == 256) return launch16<256, 8, 2, 4, kKernTrace | kKernPhaseTrace>(c, query);
+    if (wide) return launch16<128, 8, 2, 8, kKernTrace | kKernPhaseTrace>(c, query);
+    return launch16<128, 8, 2, 4, kKernTrace | kKernPhaseTrace>(c, query);
+  }
+  if (c.c_in == 256) return launch16<256, 8, 2, 4, kKernTrace>(c, query);
+  if (wide) return launch16<128, 8, 2, 8, kKernTrace>(c, query);
+  return launch16<128, 8, 2, 4, kKernTrace>(c, query);
+}
+
+int conv16_launch_info(ConvKernel kernel, int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info) {
+  *info = Conv16LaunchInfo{0, 0, 0, 0, 0, 0, 0};
+  if (n_out <= 0) return ISF_OK;
+  if (kernel != kConvKernelTile) return conv_dma_launch_info(kernel == kConvKernelDmaLines, c_in, c_out, n_out, mode, info);
+  ISF_REQUIRE(sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED, "sparse_conv16: (Cin,Cout)=(%d,%d) not built",
+              c_in, c_out);
+  ConvCall q;
+  q.c_in = c_in; q.c_out = c_out; q.n_out = n_out; q.mode = mode;
+  return (mode & kKernTrace) ? trace16(q, info) : run16(q, info);
+}
+
+// per-workgroup trace of one launch: where the time of a launch goes -- tools/conv_trace.py.  c.mode: trace16's
+static int sparse_conv_trace_impl(const ConvCall& c, int trace_capacity_blocks, int* grid_blocks, size_t phase_capacity_bytes = 0,
+                                  int* waves_per_block = nullptr) {
+  const bool phase = (c.mode & kKernPhaseTrace) != 0;
+  ISF_REQUIRE((c.c_in == 256 && c.c_out == 256) || (c.c_in == 128 && c.c_out == 128), ISF_ERR_UNSUPPORTED,
+              "sparse_conv_trace: built for 128 -> 128 and 256 -> 256, got %d -> %d", c.c_in, c.c_out);
+  ISF_REQUIRE(c.K >= 1 && c.K <= kMaxTaps && c.n_out > 0 && c.nbr_stride % 128 == 0 && c.nbr_stride >= c.n_out, ISF_ERR_ARG,
               "sparse_conv_trace: bad arguments");
-  const uint4* w = reinterpret_cast<const uint4*>(packed16);
-  const float* winv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed16) + (size_t)K * c_in * c_out * 4);
-  const uint4* x = reinterpret_cast<const uint4*>(xs);
-  const uint4* r = reinterpret_cast<const uint4*>(residual);
-  uint4* y = reinterpret_cast<uint4*>(ys);
+  // the per-wave phase records sit behind the per-workgroup records: [grid][8] int64, then dwords
+  const int nw = (c.c_in == 256 || !(c.c_out == 128 && c.n_out >= 8 * 256)) ? 4 : 8;
+  if (phase && waves_per_block) *waves_per_block = nw;
   Conv16LaunchInfo info;
-  const bool wide = c_out == 128 && n_out >= 8 * 256;
-  for (int pass = 0; pass < 2; ++pass) {   // pass 0: the launch shape (grid size), pass 1: launch
-    Conv16LaunchInfo* q = pass == 0 ? &info : nullptr;
-    if (pass == 1)   // the kernel writes trace + 8 * blockIdx.x for every workgroup of the grid (unchecked before)
-      ISF_REQUIRE(8 * (info.full + info.half) <= trace_capacity_blocks, ISF_ERR_ARG,
-                  "sparse_conv_trace: the launch has %d workgroups, the trace buffer holds %d", 8 * (info.full + info.half),
-                  trace_capacity_blocks);
-    int rc;
-    if (phase) {   // the per-wave phase records sit behind the per-workgroup records: [grid][8] int64, then dwords
-      const int nw = (c_in == 256 || !wide) ? 4 : 8;
-      if (waves_per_block) *waves_per_block = nw;
-      if (pass == 1)
-        ISF_REQUIRE((size_t)8 * (info.full + info.half) * (64 + (size_t)nw * (kPhaseHdr + kPhaseStep * kPhaseMaxSteps) * 4) <=
-                        phase_capacity_bytes, ISF_ERR_ARG, "sparse_conv_phase_trace: trace buffer too small");
-      if (c_in == 256) rc = launch16<256, 8, 2, 4, kKernTrace | kKernPhaseTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-      else if (wide) rc = launch16<128, 8, 2, 8, kKernTrace | kKernPhaseTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-      else rc = launch16<128, 8, 2, 4, kKernTrace | kKernPhaseTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-    } else if (c_in == 256) rc = launch16<256, 8, 2, 4, kKernTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-    else if (wide) rc = launch16<128, 8, 2, 8, kKernTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-    else rc = launch16<128, 8, 2, 4, kKernTrace>(true, false, x, w, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, r, relu, y, st, order, q, trace);
-    ISF_TRY(rc);
-  }
-  *grid_blocks = 8 * (info.full + info.half);
+  ISF_TRY(conv16_launch_info(kConvKernelTile, c.c_in, c.c_out, c.n_out, c.mode, &info));
+  // the kernel writes trace + 8 * blockIdx.x for every workgroup of the grid (unchecked before)
+  const int blocks = 8 * (info.full + info.half);
+  ISF_REQUIRE(blocks <= trace_capacity_blocks, ISF_ERR_ARG,
+              "sparse_conv_trace: the launch has %d workgroups, the trace buffer holds %d", blocks, trace_capacity_blocks);
+  ISF_REQUIRE(!phase || (size_t)blocks * (64 + (size_t)nw * (kPhaseHdr + kPhaseStep * kPhaseMaxSteps) * 4) <= phase_capacity_bytes,
+              ISF_ERR_ARG, "sparse_conv_phase_trace: trace buffer too small");
+  ISF_TRY(trace16(c, nullptr));
+  *grid_blocks = blocks;
   return ISF_OK;
 }
 
@@ -1146,7 +1116,7 @@ __global__ void conv16_tile_table_kernel(const int32_t* __restrict__ work, int n
   (void)conv16_table_part(work, G0, G1, cus, wgs_per_cu, gt, tiles + (size_t)part * 2 * wgs_per_cu * cus);   // fits: checked
 }                                                                                                               // on the host
 
-// tile table of a launch (info from the launch query); group_work [ceil(n_out / 16)] from conv_group_masks_impl;
+// tile table of a launch (info from conv16_launch_info); group_work [ceil(n_out / 16)] from conv_group_masks_impl;
 // table: conv16_table_ints(info) int32.  Only for launches conv16_table_applies() accepts.
 int conv16_tile_table_impl(const int32_t* group_work, int n_out, const Conv16LaunchInfo& info, int32_t* table,
                            hipStream_t st) {
@@ -1546,18 +1516,16 @@ int isf_sparse_conv_forward_f16x3(const void* features_split, int num_in, int c_
                                   int num_taps, int c_out, const int32_t* nbr, int nbr_stride, int num_out,
                                   const float* scale, const float* shift, const void* residual_split, int relu,
                                   void* out_split, int mode, isf_stream_t stream) {
-  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && c_in > 0 && c_out > 0 && num_taps > 0, ISF_ERR_ARG,
-              "sparse_conv_forward_f16x3: bad arguments");
-  if (num_out == 0) return ISF_OK;
-  ISF_REQUIRE(features_split && packed16 && nbr && out_split && ((scale == nullptr) == (shift == nullptr)),
-              ISF_ERR_ARG, "sparse_conv_forward_f16x3: null pointer");
+  const isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale, shift,
+                                         residual_split, relu, out_split, mode, isf::as_stream(stream));
+  bool run;
+  ISF_TRY(isf::conv_entry_check("sparse_conv_forward_f16x3", c, num_in, true, nbr != nullptr, &run));
+  if (!run) return ISF_OK;
   const int m = mode & ~isf::kConvOptsForward;
   ISF_REQUIRE(mode >= 0 && (isf::conv_mode_is_production(m) || isf::conv_mode_is_knockout(m)), ISF_ERR_ARG,
               "sparse_conv_forward_f16x3: mode %d (0 default, 1 single-pass f16, 257 f16 storage, diagnostics 2 / 4 / 6 / "
               "8 / 16, +32)", mode);
-  return isf::sparse_conv_forward_f16x3_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride,
-                                             num_out, scale, shift, residual_split, relu, out_split, mode,
-                                             isf::as_stream(stream));
+  return isf::sparse_conv_forward_f16x3_impl(c);
 }
 
 int isf_sparse_conv_tile_order(const int32_t* nbr, int nbr_stride, int num_taps, int num_out, int c_in, int c_out,
@@ -1567,17 +1535,14 @@ int isf_sparse_conv_tile_order(const int32_t* nbr, int nbr_stride, int num_taps,
   if (num_out == 0) return ISF_OK;
   ISF_REQUIRE(isf::sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
               "sparse_conv_tile_order: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
+  // the table may be for isf_sparse_conv_forward_dma: its launch plan differs (workgroups per CU)
+  const bool dma = (mode & ISF_CONV_MODE_DMA_PLAN) != 0;
+  ISF_REQUIRE(!dma || isf::sparse_conv_dma_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
+              "sparse_conv_tile_order: (Cin,Cout)=(%d,%d) has no LDS-DMA kernel", c_in, c_out);
+  ISF_TRY(isf::conv_check_problem("sparse_conv_tile_order", c_in, c_out, true, num_taps, nbr_stride, num_out));
   isf::Conv16LaunchInfo info;
-  if (mode & ISF_CONV_MODE_DMA_PLAN) {   // the table is for isf_sparse_conv_forward_dma: its launch plan differs (workgroups per CU)
-    ISF_REQUIRE(isf::sparse_conv_dma_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
-                "sparse_conv_tile_order: (Cin,Cout)=(%d,%d) has no LDS-DMA kernel", c_in, c_out);
-    ISF_TRY(isf::sparse_conv_forward_dma_impl(nullptr, c_in, nullptr, num_taps, c_out, nbr, nbr_stride, num_out, nullptr,
-                                              nullptr, nullptr, 0, nullptr, mode & ~ISF_CONV_MODE_DMA_PLAN, isf::as_stream(stream), nullptr,
-                                              &info));
-  } else {
-    ISF_TRY(isf::sparse_conv_forward_f16x3_impl(nullptr, c_in, nullptr, num_taps, c_out, nbr, nbr_stride, num_out, nullptr,
-                                                nullptr, nullptr, 0, nullptr, mode, isf::as_stream(stream), nullptr, &info));
-  }
+  ISF_TRY(isf::conv16_launch_info(dma ? isf::kConvKernelDma : isf::kConvKernelTile, c_in, c_out, num_out,
+                                  mode & ~ISF_CONV_MODE_DMA_PLAN, &info));
   if (!isf::conv16_order_applies(info)) return ISF_OK;
   *num_entries = isf::conv16_order_parts(info) * isf::conv16_order_tiles(info);
   return isf::conv16_tile_order_impl(nbr, nbr_stride, num_taps, num_out, info, work, order, isf::as_stream(stream));
@@ -1587,16 +1552,15 @@ int isf_sparse_conv_forward_f16x3_ordered(const void* features_split, int num_in
                                           int num_taps, int c_out, const int32_t* nbr, int nbr_stride, int num_out,
                                           const float* scale, const float* shift, const void* residual_split, int relu,
                                           void* out_split, int mode, const int32_t* order, isf_stream_t stream) {
-  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && c_in > 0 && c_out > 0 && num_taps > 0, ISF_ERR_ARG,
-              "sparse_conv_forward_f16x3_ordered: bad arguments");
-  if (num_out == 0) return ISF_OK;
-  ISF_REQUIRE(features_split && packed16 && nbr && out_split && ((scale == nullptr) == (shift == nullptr)),
-              ISF_ERR_ARG, "sparse_conv_forward_f16x3_ordered: null pointer");
+  isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale, shift,
+                                   residual_split, relu, out_split, mode, isf::as_stream(stream));
+  c.order = order;
+  bool run;
+  ISF_TRY(isf::conv_entry_check("sparse_conv_forward_f16x3_ordered", c, num_in, true, nbr != nullptr, &run));
+  if (!run) return ISF_OK;
   ISF_REQUIRE(mode >= 0 && isf::conv_mode_is_production(mode & ~isf::kConvOptsOrdered), ISF_ERR_ARG,
               "sparse_conv_forward_f16x3_ordered: mode %d (0, 1, 16, 257, +32, +65536, +131072)", mode);
-  return isf::sparse_conv_forward_f16x3_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride,
-                                             num_out, scale, shift, residual_split, relu, out_split, mode,
-                                             isf::as_stream(stream), order);
+  return isf::sparse_conv_forward_f16x3_impl(c);
 }
 
 int isf_sparse_conv_tile_table(const int32_t* nbr, int nbr_stride, int num_taps, int num_out, int c_in, int c_out,
@@ -1607,9 +1571,9 @@ int isf_sparse_conv_tile_table(const int32_t* nbr, int nbr_stride, int num_taps,
   ISF_REQUIRE(isf::sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
               "sparse_conv_tile_table: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
   ISF_REQUIRE(isf::conv_mode_is_production(mode & ~isf::kConvOptsTiled), ISF_ERR_ARG, "sparse_conv_tile_table: mode %d", mode);
+  ISF_TRY(isf::conv_check_problem("sparse_conv_tile_table", c_in, c_out, true, num_taps, nbr_stride, num_out));
   isf::Conv16LaunchInfo info;   // the workgroup shape, and with it the table, depends on the mode
-  ISF_TRY(isf::sparse_conv_forward_f16x3_impl(nullptr, c_in, nullptr, num_taps, c_out, nbr, nbr_stride, num_out, nullptr,
-                                              nullptr, nullptr, 0, nullptr, mode, isf::as_stream(stream), nullptr, &info));
+  ISF_TRY(isf::conv16_launch_info(isf::kConvKernelTile, c_in, c_out, num_out, mode, &info));
   if (!isf::conv16_table_applies(info)) return ISF_OK;
   // `table` holds 3072 ints (include/isf_hip.h): 8 parts x 2 x (workgroups per CU x CUs per XCD <= 192); a device with
   // more slots per XCD is refused instead of written past the buffer
@@ -1626,16 +1590,15 @@ int isf_sparse_conv_forward_f16x3_tiled(const void* features_split, int num_in, 
                                         int num_taps, int c_out, const int32_t* nbr, int nbr_stride, int num_out,
                                         const float* scale, const float* shift, const void* residual_split, int relu,
                                         void* out_split, int mode, const int32_t* table, isf_stream_t stream) {
-  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && c_in > 0 && c_out > 0 && num_taps > 0 && table, ISF_ERR_ARG,
-              "sparse_conv_forward_f16x3_tiled: bad arguments");
-  if (num_out == 0) return ISF_OK;
-  ISF_REQUIRE(features_split && packed16 && nbr && out_split && ((scale == nullptr) == (shift == nullptr)),
-              ISF_ERR_ARG, "sparse_conv_forward_f16x3_tiled: null pointer");
+  isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale, shift,
+                                   residual_split, relu, out_split, mode | isf::kConvModeTileTable, isf::as_stream(stream));
+  c.order = table;
+  bool run;
+  ISF_TRY(isf::conv_entry_check("sparse_conv_forward_f16x3_tiled", c, num_in, table != nullptr, nbr != nullptr, &run));
+  if (!run) return ISF_OK;
   ISF_REQUIRE(isf::conv_mode_is_production(mode & ~isf::kConvOptsTiled), ISF_ERR_ARG,
               "sparse_conv_forward_f16x3_tiled: mode %d (0, 1, 16, 257)", mode);
-  return isf::sparse_conv_forward_f16x3_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out,
-                                             scale, shift, residual_split, relu, out_split, mode | isf::kConvModeTileTable,
-                                             isf::as_stream(stream), table);
+  return isf::sparse_conv_forward_f16x3_impl(c);
 }
 
 int isf_sparse_conv_part_table(const int32_t* table_nbr, const uint32_t* mask, int nbr_stride, int num_taps, int num_out,
@@ -1651,15 +1614,10 @@ int isf_sparse_conv_part_table(const int32_t* table_nbr, const uint32_t* mask, i
   ISF_REQUIRE(dma ? isf::sparse_conv_dma_supported(c_in, c_out) : isf::sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
               "sparse_conv_part_table: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
   ISF_REQUIRE(dma || !mask, ISF_ERR_ARG, "sparse_conv_part_table: only the LDS-DMA kernel reads a line-compressed table");
+  ISF_TRY(isf::conv_check_problem("sparse_conv_part_table", c_in, c_out, true, num_taps, nbr_stride, num_out));
   isf::Conv16LaunchInfo li;   // the uniform plan of the launch
-  if (dma)
-    ISF_TRY(isf::sparse_conv_forward_dma_impl(nullptr, c_in, nullptr, num_taps, c_out, table_nbr, nbr_stride, num_out, nullptr,
-                                              nullptr, nullptr, 0, nullptr, base | ISF_CONV_MODE_UNIFORM_TILES,
-                                              isf::as_stream(stream), nullptr, &li));
-  else
-    ISF_TRY(isf::sparse_conv_forward_f16x3_impl(nullptr, c_in, nullptr, num_taps, c_out, table_nbr, nbr_stride, num_out, nullptr,
-                                                nullptr, nullptr, 0, nullptr, base | ISF_CONV_MODE_UNIFORM_TILES,
-                                                isf::as_stream(stream), nullptr, &li));
+  ISF_TRY(isf::conv16_launch_info(dma ? isf::kConvKernelDma : isf::kConvKernelTile, c_in, c_out, num_out,
+                                  base | ISF_CONV_MODE_UNIFORM_TILES, &li));
   if (!isf::conv16_parts_apply(li, (flags & 1) != 0)) return ISF_OK;
   const int parts = isf::conv16_order_parts(li), T = isf::conv16_parts_tiles(li.full, parts), cap = isf::conv16_parts_cap(T, parts);
   ISF_REQUIRE(2 * T <= work_capacity && isf::conv16_part_table_ints(parts, cap) <= table_capacity, ISF_ERR_ARG,
@@ -1673,21 +1631,19 @@ int isf_sparse_conv_forward_parts(const void* features_split, int num_in, int c_
                                   int taps_per_line, int c_out, const int32_t* table_nbr, const uint32_t* mask, int nbr_stride,
                                   int num_out, const float* scale, const float* shift, const void* residual_split, int relu,
                                   void* out_split, int mode, const int32_t* part_table, isf_stream_t stream) {
-  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && c_in > 0 && c_out > 0 && num_taps > 0 && part_table, ISF_ERR_ARG,
-              "sparse_conv_forward_parts: bad arguments");
-  if (num_out == 0) return ISF_OK;
-  ISF_REQUIRE(features_split && packed16 && table_nbr && out_split && ((scale == nullptr) == (shift == nullptr)), ISF_ERR_ARG,
-              "sparse_conv_forward_parts: null pointer");
   const bool dma = (mode & ISF_CONV_MODE_DMA_PLAN) != 0;
   const int base = mode & ~ISF_CONV_MODE_DMA_PLAN;
+  isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, table_nbr, nbr_stride, num_out, scale, shift,
+                                   residual_split, relu, out_split, base | isf::kConvModePartTable, isf::as_stream(stream));
+  c.order = part_table;
+  bool run;
+  ISF_TRY(isf::conv_entry_check("sparse_conv_forward_parts", c, num_in, part_table != nullptr, table_nbr != nullptr, &run));
+  if (!run) return ISF_OK;
   ISF_REQUIRE(isf::conv_mode_is_production(base) && (dma || !mask), ISF_ERR_ARG, "sparse_conv_forward_parts: mode %d", mode);
-  if (dma)
-    return isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table_nbr, nbr_stride, num_out,
-                                             scale, shift, residual_split, relu, out_split, base | isf::kConvModePartTable,
-                                             isf::as_stream(stream), part_table, nullptr, mask, taps_per_line);
-  return isf::sparse_conv_forward_f16x3_impl(features_split, c_in, packed16, num_taps, c_out, table_nbr, nbr_stride, num_out,
-                                             scale, shift, residual_split, relu, out_split, base | isf::kConvModePartTable,
-                                             isf::as_stream(stream), part_table);
+  if (!dma) return isf::sparse_conv_forward_f16x3_impl(c);
+  c.lmask = mask;
+  c.nx = taps_per_line;
+  return isf::sparse_conv_forward_dma_impl(c);
 }
 
 // conv16_table_part walked on the host (tests, tools; no device work): work [num_groups] -> tiles [parts][wgs * cus][2]
@@ -1713,9 +1669,11 @@ int isf_sparse_conv_trace(const void* features_split, int num_in, int c_in, cons
   ISF_REQUIRE(num_in >= 0 && features_split && packed16 && nbr && out_split && trace && grid_blocks &&
                   trace_capacity_blocks > 0 &&
                   ((scale == nullptr) == (shift == nullptr)), ISF_ERR_ARG, "sparse_conv_trace: bad arguments");
-  return isf::sparse_conv_trace_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale,
-                                     shift, residual_split, relu, out_split, order, trace, trace_capacity_blocks,
-                                     grid_blocks, isf::as_stream(stream));
+  isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale, shift,
+                                   residual_split, relu, out_split, isf::kKernTrace, isf::as_stream(stream));
+  c.order = order;
+  c.trace = trace;
+  return isf::sparse_conv_trace_impl(c, trace_capacity_blocks, grid_blocks);
 }
 
 /* DIAGNOSTIC: isf_sparse_conv_trace plus per-WAVE phase stamps (shader clock, s_memtime) of every step of the multiply
@@ -1731,9 +1689,11 @@ int isf_sparse_conv_phase_trace(const void* features_split, int num_in, int c_in
                   dwords_per_wave && ((scale == nullptr) == (shift == nullptr)), ISF_ERR_ARG,
               "sparse_conv_phase_trace: bad arguments");
   *dwords_per_wave = isf::kPhaseHdr + isf::kPhaseStep * isf::kPhaseMaxSteps;
-  return isf::sparse_conv_trace_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale,
-                                     shift, residual_split, relu, out_split, order, trace, 1 << 30, grid_blocks,
-                                     isf::as_stream(stream), true, trace_bytes, waves_per_block);
+  isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale, shift,
+                                   residual_split, relu, out_split, isf::kKernTrace | isf::kKernPhaseTrace, isf::as_stream(stream));
+  c.order = order;
+  c.trace = trace;
+  return isf::sparse_conv_trace_impl(c, 1 << 30, grid_blocks, trace_bytes, waves_per_block);
 }
 
 }  // extern "C"

@@ -583,20 +583,18 @@ int conv_cu_plan_impl(const int32_t* nbr, int nbr_stride, int K, int n_out, int3
   return ISF_OK;
 }
 
-int sparse_conv_forward_cu_impl(const void* xs, int c_in, const void* packed16, int K, int c_out, const int32_t* nbr,
-                                int nbr_stride, int n_out, const float* scale, const float* shift, const void* residual,
-                                int relu, void* ys, const ConvCuPlan& plan, hipStream_t st) {
+int sparse_conv_forward_cu_impl(const ConvCall& c, const ConvCuPlan& plan) {
+  const int n_out = c.n_out;
   if (n_out <= 0) return ISF_OK;
-  ISF_REQUIRE(sparse_conv_cu_supported(c_in, c_out), ISF_ERR_UNSUPPORTED, "sparse_conv_cu: (Cin,Cout)=(%d,%d) not built",
-              c_in, c_out);
-  ISF_REQUIRE(K >= 1 && K <= kMaxTaps && nbr_stride >= n_out, ISF_ERR_ARG, "sparse_conv_cu: bad rulebook");
+  ISF_REQUIRE(sparse_conv_cu_supported(c.c_in, c.c_out), ISF_ERR_UNSUPPORTED, "sparse_conv_cu: (Cin,Cout)=(%d,%d) not built",
+              c.c_in, c.c_out);
+  ISF_REQUIRE(c.K >= 1 && c.K <= kMaxTaps && c.nbr_stride >= n_out, ISF_ERR_ARG, "sparse_conv_cu: bad rulebook");
   ISF_REQUIRE(plan.group_masks && plan.units && plan.num_units && plan.n_out == n_out && plan.max_units > 0, ISF_ERR_ARG,
               "sparse_conv_cu: the unit plan was built for %d rows, the launch has %d", plan.n_out, n_out);
   ISF_REQUIRE(plan.cap == conv_cu_variant_cap(plan.variant), ISF_ERR_ARG,
               "sparse_conv_cu: variant %d works on units of <= %d groups, the plan was cut for %d", plan.variant,
               conv_cu_variant_cap(plan.variant), plan.cap);
-  const uint4* w = reinterpret_cast<const uint4*>(packed16);
-  const float* winv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed16) + (size_t)K * c_in * c_out * 4);
+  const ConvWeights w = conv_weights(c);
   const dim3 grid(8 * ceil_div(plan.max_units, 8));
   // variant (0 = round 4's production shape): 1 / 2 / 3 = no gathers / no weight loads / neither (results garbage, timing
   // only); 4 / 5 = 4 waves at prefetch depth 1 / 2, 6 / 7 = 8 waves at depth 1 / 2 (results valid); round 6, assembly
@@ -613,9 +611,9 @@ int sparse_conv_forward_cu_impl(const void* xs, int c_in, const void* packed16, 
                                       smem_bytes));                                                                     \
       attr_set.store(1, std::memory_order_release);                                                                     \
     }                                                                                                                   \
-    hipLaunchKernelGGL(kern, grid, dim3(64 * WW), smem_bytes, st, reinterpret_cast<const uint4*>(xs), nbr,           \
-                       nbr_stride, w, winv, K, scale, shift, reinterpret_cast<const uint4*>(residual),                  \
-                       reinterpret_cast<uint4*>(ys), n_out, relu, plan.group_masks, plan.units, plan.num_units);        \
+    hipLaunchKernelGGL(kern, grid, dim3(64 * WW), smem_bytes, c.st, reinterpret_cast<const uint4*>(c.xs), c.nbr,     \
+                       c.nbr_stride, w.wpk, w.winv, c.K, c.scale, c.shift, reinterpret_cast<const uint4*>(c.residual),  \
+                       reinterpret_cast<uint4*>(c.ys), n_out, c.relu, plan.group_masks, plan.units, plan.num_units);    \
   } while (0)
 #define ISF_CU_VARIANTS(CI)                                                                                             \
   switch (plan.variant) {                                                                                               \
@@ -637,7 +635,7 @@ int sparse_conv_forward_cu_impl(const void* xs, int c_in, const void* packed16, 
     case 15: ISF_CU_LAUNCH(CI, 4, 2, 0, true, 8, true); break;                                                                \
     default: ISF_REQUIRE(false, ISF_ERR_ARG, "sparse_conv_cu: variant %d", plan.variant);                               \
   }
-  if (c_in == 128) { ISF_CU_VARIANTS(128) } else { ISF_CU_VARIANTS(256) }
+  if (c.c_in == 128) { ISF_CU_VARIANTS(128) } else { ISF_CU_VARIANTS(256) }
 #undef ISF_CU_VARIANTS
 #undef ISF_CU_LAUNCH
   ISF_LAUNCH_CHECK();
@@ -675,11 +673,11 @@ int isf_sparse_conv_forward_cu(const void* features_split, int num_in, int c_in,
                                int c_out, const int32_t* nbr, int nbr_stride, int num_out, const float* scale,
                                const float* shift, const void* residual_split, int relu, void* out_split,
                                const isf_conv_cu_plan* plan, isf_stream_t stream) {
-  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && c_in > 0 && c_out > 0 && num_taps > 0 && plan, ISF_ERR_ARG,
-              "sparse_conv_forward_cu: bad arguments");
-  if (num_out == 0) return ISF_OK;
-  ISF_REQUIRE(features_split && packed16 && nbr && out_split && ((scale == nullptr) == (shift == nullptr)), ISF_ERR_ARG,
-              "sparse_conv_forward_cu: null pointer");
+  const isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale, shift,
+                                         residual_split, relu, out_split, 0, isf::as_stream(stream));
+  bool run;
+  ISF_TRY(isf::conv_entry_check("sparse_conv_forward_cu", c, num_in, plan != nullptr, nbr != nullptr, &run));
+  if (!run) return ISF_OK;
   isf::ConvCuPlan p;
   p.group_masks = plan->group_masks;
   p.units = reinterpret_cast<const int2*>(plan->units);
@@ -688,8 +686,7 @@ int isf_sparse_conv_forward_cu(const void* features_split, int num_in, int c_in,
   p.n_out = plan->num_out;
   p.variant = plan->variant;
   p.cap = plan->cap;
-  return isf::sparse_conv_forward_cu_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale,
-                                          shift, residual_split, relu, out_split, p, isf::as_stream(stream));
+  return isf::sparse_conv_forward_cu_impl(c, p);
 }
 
 // the plan arithmetic on the host (tests / tools: no device work): work [num_groups] -> units [max_units][2]

@@ -17,10 +17,9 @@
 // whose tile plan, tile order, column-block / XCD mapping, epilogue and ORDER OF OPERATIONS per accumulator (chunk outer,
 // taps inner, a_lo b_hi -> a_hi b_lo -> a_hi b_hi) it keeps: results are BIT-IDENTICAL to spconv_f16x3_kernel.
 // Replaces, like it, the reference's per-tap gather -> GEMM -> scatter-add (spconv_ops.h:260-361).
-#include "isf_spconv16.h"
+#include "isf_spconv_launch.h"
 #include "isf_spconv_deep_asm.h"
 
-#include <atomic>
 
 namespace isf {
 
@@ -218,54 +217,39 @@ bool sparse_conv_deep_supported(int c_in, int c_out) {
   return (c_in == 128 || c_in == 256) && (c_out == 128 || c_out == 256);
 }
 
-// the tile kernel's launch (launch16<CIN, 8, 2, 4>): same plan, same tile order tables, same query
+// the tile kernel's launch (launch16<CIN, 8, 2, 4>): same plan, same tile order tables, same launch info
 template <int CIN>
-static int launch_deep(bool balance, bool table, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
-                       const int32_t* nbr, int nbr_stride, int n_out, const float* scale, const float* shift,
-                       const uint4* residual, int relu, uint4* ys, hipStream_t st, const int32_t* order,
-                       Conv16LaunchInfo* query) {
+static int launch_deep(const ConvCall& c, Conv16LaunchInfo* query) {
   constexpr int NW = 4;
   using S = ConvDeepSmem<NW>;
   auto kern = spconv_deep_kernel<CIN, NW>;
-  static std::atomic<int> wgs_per_cu{0}, cus_per_xcd{0};
-  if (wgs_per_cu.load(std::memory_order_acquire) == 0) {
-    if (S::bytes > 48 * 1024)
-      ISF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, S::bytes));
-    int dev = 0, cus = 0, occ = 0;
-    ISF_HIP_TRY(hipGetDevice(&dev));
-    ISF_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    ISF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * NW, S::bytes));
-    cus_per_xcd.store(cus >= 8 ? cus / 8 : 1, std::memory_order_relaxed);
-    wgs_per_cu.store(occ > 0 ? occ : 1, std::memory_order_release);
-  }
-  const int ncb = cout / 128;
+  static ConvSlots slots;
+  ISF_TRY(conv_kernel_slots(slots, reinterpret_cast<const void*>(kern), 64 * NW, S::bytes, S::bytes));
+  const int ncb = c.c_out / 128;
   ISF_REQUIRE(ncb == 1 || ncb == 2, ISF_ERR_UNSUPPORTED, "sparse_conv_deep: %d column blocks", ncb);
-  Conv16Plan plan = conv16_plan(n_out, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
-                                cus_per_xcd.load(std::memory_order_relaxed), balance);
-  if (table && !query) plan = Conv16Plan{wgs_per_cu.load(std::memory_order_relaxed) * cus_per_xcd.load(std::memory_order_relaxed),
-                                         -1, plan.part_rows};
-  if (query) {
-    *query = Conv16LaunchInfo{plan.full, plan.half, plan.part_rows, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
-                              cus_per_xcd.load(std::memory_order_relaxed)};
-    return ISF_OK;
-  }
-  hipLaunchKernelGGL(kern, dim3(conv16_grid_blocks(plan)), dim3(64 * NW), S::bytes, st, xs, nbr, nbr_stride, wpk, winv, K,
-                     cout, scale, shift, residual, ys, n_out, relu, plan, order);
+  const Conv16Plan plan = conv16_launch_plan(c, S::TM, ncb, slots, true, query);
+  if (query) return ISF_OK;
+  const ConvWeights w = conv_weights(c);
+  hipLaunchKernelGGL(kern, dim3(conv16_grid_blocks(plan)), dim3(64 * NW), S::bytes, c.st, reinterpret_cast<const uint4*>(c.xs),
+                     c.nbr, c.nbr_stride, w.wpk, w.winv, c.K, c.c_out, c.scale, c.shift,
+                     reinterpret_cast<const uint4*>(c.residual), reinterpret_cast<uint4*>(c.ys), c.n_out, c.relu, plan, c.order);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
 
-int sparse_conv_forward_deep_impl(bool balance, bool table, const uint4* xs, int c_in, const uint4* wpk, const float* winv,
-                                  int K, int c_out, const int32_t* nbr, int nbr_stride, int n_out, const float* scale,
-                                  const float* shift, const uint4* residual, int relu, uint4* ys, hipStream_t st,
-                                  const int32_t* order, Conv16LaunchInfo* query) {
-  ISF_REQUIRE(sparse_conv_deep_supported(c_in, c_out), ISF_ERR_UNSUPPORTED, "sparse_conv_deep: (Cin,Cout)=(%d,%d) not built",
-              c_in, c_out);
-  if (c_in == 128)
-    return launch_deep<128>(balance, table, xs, wpk, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys,
-                            st, order, query);
-  return launch_deep<256>(balance, table, xs, wpk, winv, K, c_out, nbr, nbr_stride, n_out, scale, shift, residual, relu, ys, st,
-                          order, query);
+static int run_deep(const ConvCall& c, Conv16LaunchInfo* query) {
+  ISF_REQUIRE(sparse_conv_deep_supported(c.c_in, c.c_out), ISF_ERR_UNSUPPORTED, "sparse_conv_deep: (Cin,Cout)=(%d,%d) not built",
+              c.c_in, c.c_out);
+  return c.c_in == 128 ? launch_deep<128>(c, query) : launch_deep<256>(c, query);
+}
+
+// c: a launch the tile kernel's dispatch hands over (checked there; no row map, no part table)
+int sparse_conv_forward_deep_impl(const ConvCall& c) { return run_deep(c, nullptr); }
+
+int conv_deep_launch_info(int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info) {
+  ConvCall q;
+  q.c_in = c_in; q.c_out = c_out; q.n_out = n_out; q.mode = mode;
+  return run_deep(q, info);
 }
 
 }  // namespace isf

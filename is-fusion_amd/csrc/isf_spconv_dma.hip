@@ -27,9 +27,8 @@
 //     5 / 6 workgroups per CU instead of 3;
 //   * rows without a neighbour read a zero line instead of being masked (the DMA writes every lane's 16 bytes); no
 //     neighbour sharing (every row is fetched, at a quarter of the cost).
-#include "isf_spconv16.h"
+#include "isf_spconv_launch.h"
 
-#include <atomic>
 
 namespace isf {
 
@@ -382,93 +381,80 @@ bool sparse_conv_dma_supported(int c_in, int c_out) {
 // 4 waves x 32 rows per workgroup.  Measured slower (profiles/r03_dma_gather.txt): 8 waves (one weight stage per 256 rows,
 // 3 workgroups per CU) 64 -> 64 0.740 -> 0.768 ms per step; 4 waves x 64 rows (RG = 4: twice the MFMAs per step and
 // barrier, 3 workgroups per CU) 0.770 -> 0.865 -- the resident workgroups are what hides the loads' round trip.
+// One instantiation: launches `c`, or with `query` reports how that launch would be cut (conv_dma_launch_info).
 template <int CIN, int NT, int MODE, bool LINES, int NW = 4, int RG = 2>
-static int launch_dma(bool balance, bool parts /* `order` is a part table (conv16_part_table_impl) */, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
-                      const int32_t* nbr, const uint32_t* lmask, int nx, int nbr_stride, int n_out, const float* scale,
-                      const float* shift, const uint4* residual, int relu, uint4* ys, hipStream_t st,
-                      const int32_t* order, Conv16LaunchInfo* query, const int32_t* rowmap, long long* trace) {
+static int launch_dma(const ConvCall& c, Conv16LaunchInfo* query) {
   using S = ConvDmaSmem<NT, NW, RG>;
   auto kern = spconv_dma_kernel<CIN, NT, NW, MODE, RG, LINES>;
-  static std::atomic<int> wgs_per_cu{0}, cus_per_xcd{0};
-  if (wgs_per_cu.load(std::memory_order_acquire) == 0) {
-    if (S::bytes > 48 * 1024)
-      ISF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      S::bytes));
-    int dev = 0, cus = 0, occ = 0;
-    ISF_HIP_TRY(hipGetDevice(&dev));
-    ISF_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    ISF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * NW, S::bytes));
-    cus_per_xcd.store(cus >= 8 ? cus / 8 : 1, std::memory_order_relaxed);
-    wgs_per_cu.store(occ > 0 ? occ : 1, std::memory_order_release);
-  }
-  const int ncb = cout / (16 * NT);
-  Conv16Plan plan = conv16_plan(n_out, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
-                                cus_per_xcd.load(std::memory_order_relaxed), balance && !parts);
-  if (parts && !query) {   // equal-work parts of the uniform plan: conv16_parts_cap slots per part
-    const int np = ncb == 2 ? 4 : 8;
-    plan = Conv16Plan{conv16_parts_cap(conv16_parts_tiles(plan.full, np), np), kPlanParts, plan.part_rows};
-  }
-  if (query) {
-    *query = Conv16LaunchInfo{plan.full, plan.half, plan.part_rows, S::TM, ncb, wgs_per_cu.load(std::memory_order_relaxed),
-                              cus_per_xcd.load(std::memory_order_relaxed)};
-    return ISF_OK;
-  }
-  hipLaunchKernelGGL(kern, dim3(conv16_grid_blocks(plan)), dim3(64 * NW), S::bytes, st, xs, nbr, lmask, nx, nbr_stride, wpk,
-                     winv, K, cout, scale, shift, residual, ys, n_out, relu, plan, order, rowmap, trace);
+  static ConvSlots slots;
+  ISF_TRY(conv_kernel_slots(slots, reinterpret_cast<const void*>(kern), 64 * NW, S::bytes, S::bytes));
+  const Conv16Plan plan = conv16_launch_plan(c, S::TM, c.c_out / (16 * NT), slots, true, query);
+  if (query) return ISF_OK;
+  const ConvWeights w = conv_weights(c);
+  hipLaunchKernelGGL(kern, dim3(conv16_grid_blocks(plan)), dim3(64 * NW), S::bytes, c.st, reinterpret_cast<const uint4*>(c.xs),
+                     c.nbr, c.lmask, c.nx, c.nbr_stride, w.wpk, w.winv, c.K, c.c_out, c.scale, c.shift,
+                     reinterpret_cast<const uint4*>(c.residual), reinterpret_cast<uint4*>(c.ys), c.n_out, c.relu, plan, c.order,
+                     c.rowmap, c.trace);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
 
+// THE instantiation choice of the LDS-DMA kernel: every launch and every launch-info query comes through here.
+// lines: the line-compressed table's instantiations (a launch: c.lmask != nullptr)
 template <int CIN, int NT>
-static int dispatch_dma(int mode, const uint4* xs, const uint4* wpk, const float* winv, int K, int cout,
-                        const int32_t* nbr, const uint32_t* lmask, int nx, int nbr_stride, int n_out, const float* scale,
-                        const float* shift, const uint4* residual, int relu, uint4* ys, hipStream_t st,
-                        const int32_t* order, Conv16LaunchInfo* query, const int32_t* rowmap, long long* trace) {
-  const bool balance = (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, parts = (mode & kConvModePartTable) != 0 && order != nullptr;
-  mode &= ~kConvModePartTable;
-#define ISF_ARGS_DMA balance, parts, xs, wpk, winv, K, cout, nbr, lmask, nx, nbr_stride, n_out, scale, shift, residual, relu, ys, st, order, query, rowmap, trace
-  if (lmask) {
+static int dispatch_dma(const ConvCall& c, bool lines, Conv16LaunchInfo* query) {
+  const int mode = c.mode & ~kConvModePartTable;
+  if (lines) {
     switch (mode & ~kConvOptsDma) {
-      case kKernTrace: return launch_dma<CIN, NT, kKernTrace, true>(ISF_ARGS_DMA);   // isf_sparse_conv_dma_trace hands the kernel's bit over as a mode
-      case 0: return launch_dma<CIN, NT, 0, true>(ISF_ARGS_DMA);
-      case ISF_CONV_MODE_F16: return launch_dma<CIN, NT, kKernF16, true>(ISF_ARGS_DMA);
-      case ISF_CONV_MODE_F16_STORAGE: return launch_dma<CIN, NT, kKernF16Rows | kKernF16, true>(ISF_ARGS_DMA);
+      case kKernTrace: return launch_dma<CIN, NT, kKernTrace, true>(c, query);   // isf_sparse_conv_dma_trace hands the kernel's bit over as a mode
+      case 0: return launch_dma<CIN, NT, 0, true>(c, query);
+      case ISF_CONV_MODE_F16: return launch_dma<CIN, NT, kKernF16, true>(c, query);
+      case ISF_CONV_MODE_F16_STORAGE: return launch_dma<CIN, NT, kKernF16Rows | kKernF16, true>(c, query);
     }
   } else {
     switch (mode & ~kConvOptsDma) {
-      case kKernTrace: return launch_dma<CIN, NT, kKernTrace, false>(ISF_ARGS_DMA);
-      case 0: return launch_dma<CIN, NT, 0, false>(ISF_ARGS_DMA);
-      case ISF_CONV_MODE_F16: return launch_dma<CIN, NT, kKernF16, false>(ISF_ARGS_DMA);
-      case ISF_CONV_MODE_F16_STORAGE: return launch_dma<CIN, NT, kKernF16Rows | kKernF16, false>(ISF_ARGS_DMA);
+      case kKernTrace: return launch_dma<CIN, NT, kKernTrace, false>(c, query);
+      case 0: return launch_dma<CIN, NT, 0, false>(c, query);
+      case ISF_CONV_MODE_F16: return launch_dma<CIN, NT, kKernF16, false>(c, query);
+      case ISF_CONV_MODE_F16_STORAGE: return launch_dma<CIN, NT, kKernF16Rows | kKernF16, false>(c, query);
     }
   }
-#undef ISF_ARGS_DMA
   ISF_REQUIRE(false, ISF_ERR_ARG, "sparse_conv_dma: mode %d (0, 1, 257, +32)", mode);
 }
 
-int sparse_conv_forward_dma_impl(const void* xs, int c_in, const void* packed16, int K, int c_out, const int32_t* nbr,
-                                 int nbr_stride, int n_out, const float* scale, const float* shift,
-                                 const void* residual, int relu, void* ys, int mode, hipStream_t st,
-                                 const int32_t* order, Conv16LaunchInfo* query, const uint32_t* lmask, int nx,
-                                 const int32_t* rowmap, long long* trace) {
-  if (n_out <= 0) {
-    if (query) *query = Conv16LaunchInfo{0, 0, 0, 0, 0, 0, 0};
-    return ISF_OK;
-  }
-  ISF_REQUIRE(K >= 1 && K <= kMaxTaps, ISF_ERR_UNSUPPORTED, "sparse_conv_dma: %d taps (max 27)", K);
+static int run_dma(const ConvCall& c, bool lines, Conv16LaunchInfo* query) {
+  if (c.c_in == 32) return c.c_out == 32 ? dispatch_dma<32, 2>(c, lines, query) : dispatch_dma<32, 4>(c, lines, query);
+  return c.c_out == 32 ? dispatch_dma<64, 2>(c, lines, query) : dispatch_dma<64, 4>(c, lines, query);
+}
+
+static int check_dma(const ConvCall& c) {
+  ISF_TRY(conv_check_problem("sparse_conv_dma", c.c_in, c.c_out, sparse_conv_dma_supported(c.c_in, c.c_out), c.K, c.nbr_stride,
+                             c.n_out));
+  ISF_REQUIRE(!c.lmask || ((c.nx == 1 || c.nx == 3) && c.K % c.nx == 0), ISF_ERR_ARG, "sparse_conv_dma: %d taps in lines of %d",
+              c.K, c.nx);
+  return ISF_OK;
+}
+
+int sparse_conv_forward_dma_impl(const ConvCall& c) {
+  if (c.n_out <= 0) return ISF_OK;
+  ISF_TRY(check_dma(c));
+  return run_dma(c, c.lmask != nullptr, nullptr);
+}
+
+int conv_dma_launch_info(bool lines, int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info) {
   ISF_REQUIRE(sparse_conv_dma_supported(c_in, c_out), ISF_ERR_UNSUPPORTED, "sparse_conv_dma: (Cin,Cout)=(%d,%d) not built",
               c_in, c_out);
-  ISF_REQUIRE(nbr_stride % 128 == 0 && nbr_stride >= n_out, ISF_ERR_ARG, "sparse_conv_dma: bad nbr_stride");
-  ISF_REQUIRE(!lmask || ((nx == 1 || nx == 3) && K % nx == 0), ISF_ERR_ARG, "sparse_conv_dma: %d taps in lines of %d", K, nx);
-  const uint4* w = reinterpret_cast<const uint4*>(packed16);
-  const float* winv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed16) + (size_t)K * c_in * c_out * 4);
-  const uint4* x = reinterpret_cast<const uint4*>(xs);
-  const uint4* r = reinterpret_cast<const uint4*>(residual);
-  uint4* y = reinterpret_cast<uint4*>(ys);
-#define ISF_CALL_DMA(CI, NTT) dispatch_dma<CI, NTT>(mode, x, w, winv, K, c_out, nbr, lmask, nx, nbr_stride, n_out, scale, shift, r, relu, y, st, order, query, rowmap, trace)
-  if (c_in == 32) return c_out == 32 ? ISF_CALL_DMA(32, 2) : ISF_CALL_DMA(32, 4);
-  return c_out == 32 ? ISF_CALL_DMA(64, 2) : ISF_CALL_DMA(64, 4);
-#undef ISF_CALL_DMA
+  ConvCall q;
+  q.c_in = c_in; q.c_out = c_out; q.n_out = n_out; q.mode = mode;
+  return run_dma(q, lines, info);
+}
+
+// the trace launch of the two entries below: c.mode holds kKernTrace; `blocks` of the launch-info query must fit the buffer
+static int trace_dma(const char* entry, const ConvCall& c, int blocks, int trace_capacity_blocks, int* grid_blocks) {
+  ISF_REQUIRE(blocks <= trace_capacity_blocks, ISF_ERR_ARG, "%s: the launch has %d workgroups, the trace buffer holds %d", entry,
+              blocks, trace_capacity_blocks);
+  *grid_blocks = blocks;
+  return sparse_conv_forward_dma_impl(c);
 }
 
 }  // namespace isf
@@ -479,14 +465,12 @@ int isf_sparse_conv_forward_dma(const void* features_split, int num_in, int c_in
                                 int c_out, const int32_t* nbr, int nbr_stride, int num_out, const float* scale,
                                 const float* shift, const void* residual_split, int relu, void* out_split, int mode,
                                 const int32_t* order, isf_stream_t stream) {
-  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && c_in > 0 && c_out > 0 && num_taps > 0, ISF_ERR_ARG,
-              "sparse_conv_forward_dma: bad arguments");
-  if (num_out == 0) return ISF_OK;
-  ISF_REQUIRE(features_split && packed16 && nbr && out_split && ((scale == nullptr) == (shift == nullptr)), ISF_ERR_ARG,
-              "sparse_conv_forward_dma: null pointer");
-  return isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out,
-                                           scale, shift, residual_split, relu, out_split, mode, isf::as_stream(stream),
-                                           order, nullptr);
+  isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, nbr, nbr_stride, num_out, scale, shift,
+                                   residual_split, relu, out_split, mode, isf::as_stream(stream));
+  c.order = order;
+  bool run;
+  ISF_TRY(isf::conv_entry_check("sparse_conv_forward_dma", c, num_in, true, nbr != nullptr, &run));
+  return run ? isf::sparse_conv_forward_dma_impl(c) : ISF_OK;
 }
 
 int isf_sparse_conv_forward_dma_lines(const void* features_split, int num_in, int c_in, const void* packed16, int num_taps,
@@ -494,14 +478,13 @@ int isf_sparse_conv_forward_dma_lines(const void* features_split, int num_in, in
                                       int nbr_stride, int num_out, const float* scale, const float* shift,
                                       const void* residual_split, int relu, void* out_split, int mode,
                                       isf_stream_t stream) {
-  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && c_in > 0 && c_out > 0 && num_taps > 0, ISF_ERR_ARG,
-              "sparse_conv_forward_dma_lines: bad arguments");
-  if (num_out == 0) return ISF_OK;
-  ISF_REQUIRE(features_split && packed16 && lines && mask && out_split && ((scale == nullptr) == (shift == nullptr)),
-              ISF_ERR_ARG, "sparse_conv_forward_dma_lines: null pointer");
-  return isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, lines, nbr_stride, num_out,
-                                           scale, shift, residual_split, relu, out_split, mode, isf::as_stream(stream),
-                                           nullptr, nullptr, mask, taps_per_line);
+  isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, lines, nbr_stride, num_out, scale, shift,
+                                   residual_split, relu, out_split, mode, isf::as_stream(stream));
+  c.lmask = mask;
+  c.nx = taps_per_line;
+  bool run;
+  ISF_TRY(isf::conv_entry_check("sparse_conv_forward_dma_lines", c, num_in, true, lines && mask, &run));
+  return run ? isf::sparse_conv_forward_dma_impl(c) : ISF_OK;
 }
 
 int isf_sparse_conv_dma_trace(const void* features_split, int num_in, int c_in, const void* packed16, int num_taps,
@@ -512,18 +495,16 @@ int isf_sparse_conv_dma_trace(const void* features_split, int num_in, int c_in, 
   ISF_REQUIRE(num_in >= 0 && num_out > 0 && features_split && packed16 && table && out_split && trace && grid_blocks &&
                   trace_capacity_blocks > 0 && ((scale == nullptr) == (shift == nullptr)), ISF_ERR_ARG,
               "sparse_conv_dma_trace: bad arguments");
+  isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out, scale, shift,
+                                   residual_split, relu, out_split, isf::kKernTrace, isf::as_stream(stream));
+  c.lmask = mask;
+  c.nx = taps_per_line;
+  c.trace = trace;
+  ISF_TRY(isf::check_dma(c));
   isf::Conv16LaunchInfo info;
-  ISF_TRY(isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out,
-                                            scale, shift, residual_split, relu, out_split, isf::kKernTrace, isf::as_stream(stream),
-                                            nullptr, &info, mask, taps_per_line, nullptr, nullptr));
-  const int blocks = 8 * (info.full + (info.half < 0 ? 0 : info.half));   // conv16_grid_blocks
-  ISF_REQUIRE(blocks <= trace_capacity_blocks, ISF_ERR_ARG,
-              "sparse_conv_dma_trace: the launch has %d workgroups, the trace buffer holds %d", blocks,
-              trace_capacity_blocks);
-  *grid_blocks = blocks;
-  return isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out,
-                                           scale, shift, residual_split, relu, out_split, isf::kKernTrace, isf::as_stream(stream),
-                                           nullptr, nullptr, mask, taps_per_line, nullptr, trace);
+  ISF_TRY(isf::conv16_launch_info(mask ? isf::kConvKernelDmaLines : isf::kConvKernelDma, c_in, c_out, num_out, c.mode, &info));
+  return isf::trace_dma("sparse_conv_dma_trace", c, 8 * (info.full + info.half) /* conv16_grid_blocks */, trace_capacity_blocks,
+                        grid_blocks);
 }
 
 // the same with the launch on a part table (isf_sparse_conv_part_table): the trace of the equal-work plan
@@ -535,21 +516,20 @@ int isf_sparse_conv_dma_trace_parts(const void* features_split, int num_in, int 
   ISF_REQUIRE(num_in >= 0 && num_out > 0 && features_split && packed16 && table && out_split && trace && grid_blocks &&
                   part_table && trace_capacity_blocks > 0 && ((scale == nullptr) == (shift == nullptr)), ISF_ERR_ARG,
               "sparse_conv_dma_trace_parts: bad arguments");
+  isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out, scale, shift,
+                                   residual_split, relu, out_split, isf::kKernTrace | isf::kConvModePartTable,
+                                   isf::as_stream(stream));
+  c.order = part_table;
+  c.lmask = mask;
+  c.nx = taps_per_line;
+  c.trace = trace;
+  ISF_TRY(isf::check_dma(c));
   isf::Conv16LaunchInfo info;   // the uniform plan the table was built for
-  ISF_TRY(isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out,
-                                            scale, shift, residual_split, relu, out_split,
-                                            isf::kKernTrace | ISF_CONV_MODE_UNIFORM_TILES, isf::as_stream(stream), nullptr, &info,
-                                            mask, taps_per_line, nullptr, nullptr));
+  ISF_TRY(isf::conv16_launch_info(mask ? isf::kConvKernelDmaLines : isf::kConvKernelDma, c_in, c_out, num_out,
+                                  isf::kKernTrace | ISF_CONV_MODE_UNIFORM_TILES, &info));
   const int parts = isf::conv16_order_parts(info);
-  const int blocks = 8 * isf::conv16_parts_cap(isf::conv16_parts_tiles(info.full, parts), parts);
-  ISF_REQUIRE(info.half == 0 && blocks <= trace_capacity_blocks, ISF_ERR_ARG,
-              "sparse_conv_dma_trace_parts: the launch has %d workgroups, the trace buffer holds %d", blocks,
-              trace_capacity_blocks);
-  *grid_blocks = blocks;
-  return isf::sparse_conv_forward_dma_impl(features_split, c_in, packed16, num_taps, c_out, table, nbr_stride, num_out,
-                                           scale, shift, residual_split, relu, out_split,
-                                           isf::kKernTrace | isf::kConvModePartTable, isf::as_stream(stream), part_table, nullptr,
-                                           mask, taps_per_line, nullptr, trace);
+  return isf::trace_dma("sparse_conv_dma_trace_parts", c, 8 * isf::conv16_parts_cap(isf::conv16_parts_tiles(info.full, parts), parts),
+                        trace_capacity_blocks, grid_blocks);
 }
 
 }  // extern "C"

@@ -22,7 +22,7 @@
 // 4 lo) are stored at piece position p ^ ((S >> 1) & 7): the 16 rows of an MFMA row group then fall on 16 different
 // bank quads when their slots are consecutive (ds_read_b128 serves 16 lanes per LDS cycle over 64 banks), and a quad of
 // DMA lanes still reads one contiguous 64-byte half of the row's chunk.
-#include "isf_spconv16.h"
+#include "isf_spconv_launch.h"
 
 #include <map>
 #include <mutex>
@@ -457,103 +457,84 @@ int stage_tables_impl(const int32_t* nbr, int nbr_stride, int K, uint16_t* slots
 }
 
 // ------------------------------------------------------------------------------------------ launch
+// the staging tables of a rulebook and the LDS rows a tile may stage: what the staged kernel reads in place of c.nbr
+struct StagePlan {
+  const uint16_t* slots;
+  const int32_t* ulist;
+  const int32_t* ucount;
+  int cap_rows;
+};
+
 template <int CIN, int NT, int RG, int NW, int MODE>
-static int launch_staged(bool balance, int cap_rows, const uint4* xs, const uint4* wpk, const float* winv, int K,
-                         int cout, const uint16_t* slots, int nbr_stride, const int32_t* ulist, const int32_t* ucount,
-                         int n_out, const float* scale, const float* shift, const uint4* residual, int relu, uint4* ys,
-                         hipStream_t st) {
+static int launch_staged(const ConvCall& c, const StagePlan& sp) {
   using S = StageSmem<NT, RG, Conv16Step<CIN, NT>::KCH, NW>;
   constexpr int KCH = Conv16Step<CIN, NT>::KCH;
   auto kern = spconv_staged_kernel<CIN, NT, RG, NW, MODE>;
   constexpr int max_lds = 160 * 1024;
   int max_cap = (int)((max_lds - S::fixed_bytes) / (KCH * 128)) & ~31;
   if (max_cap > 1280) max_cap = 1280;
-  if (cap_rows > max_cap) cap_rows = max_cap;
+  int cap_rows = sp.cap_rows > max_cap ? max_cap : sp.cap_rows;
   cap_rows &= ~31;                                   // up to 4 units, each a multiple of 8 rows
   ISF_REQUIRE(cap_rows >= 32, ISF_ERR_ARG, "sparse_conv_staged: %d LDS rows (>= 32)", cap_rows);
   const size_t bytes = S::bytes(cap_rows);
   // occupancy of this instantiation at this LDS size (the tile plan deals workgroups per CU)
   static std::mutex mu;
-  static std::map<int, int> occ_of_cap;
-  static int cus_per_xcd = 0;
-  int wgs_per_cu = 0;
+  static std::map<int, ConvSlots> slots_of_cap;
+  int wgs_per_cu = 0, cus_per_xcd = 0;
   {
     std::lock_guard<std::mutex> lk(mu);
-    auto it = occ_of_cap.find(cap_rows);
-    if (it == occ_of_cap.end()) {
-      ISF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      max_lds));
-      int dev = 0, cus = 0, occ = 0;
-      ISF_HIP_TRY(hipGetDevice(&dev));
-      ISF_HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-      ISF_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, 64 * NW, bytes));
-      cus_per_xcd = cus >= 8 ? cus / 8 : 1;
-      it = occ_of_cap.emplace(cap_rows, occ > 0 ? occ : 1).first;
-    }
-    wgs_per_cu = it->second;
+    ConvSlots& slots = slots_of_cap[cap_rows];
+    ISF_TRY(conv_kernel_slots(slots, reinterpret_cast<const void*>(kern), 64 * NW, bytes, max_lds));
+    wgs_per_cu = slots.wgs_per_cu.load(std::memory_order_relaxed);
+    cus_per_xcd = slots.cus_per_xcd.load(std::memory_order_relaxed);
   }
-  const int ncb = cout / (16 * NT);
+  const int ncb = c.c_out / (16 * NT);
   ISF_REQUIRE(ncb == 1 || ncb == 2, ISF_ERR_UNSUPPORTED, "sparse_conv_staged: %d column blocks", ncb);
-  const Conv16Plan plan = conv16_plan(n_out, S::TM, ncb, wgs_per_cu, cus_per_xcd, balance, kUnitRows / 16);
-  hipLaunchKernelGGL(kern, dim3(conv16_grid_blocks(plan)), dim3(64 * NW), bytes, st, xs, slots, nbr_stride, ulist,
-                     ucount, wpk, winv, K, cout, scale, shift, residual, ys, n_out, relu, plan, cap_rows);
+  const Conv16Plan plan = conv16_plan(c.n_out, S::TM, ncb, wgs_per_cu, cus_per_xcd, (c.mode & ISF_CONV_MODE_UNIFORM_TILES) == 0,
+                                      kUnitRows / 16);
+  const ConvWeights w = conv_weights(c);
+  hipLaunchKernelGGL(kern, dim3(conv16_grid_blocks(plan)), dim3(64 * NW), bytes, c.st, reinterpret_cast<const uint4*>(c.xs),
+                     sp.slots, c.nbr_stride, sp.ulist, sp.ucount, w.wpk, w.winv, c.K, c.c_out, c.scale, c.shift,
+                     reinterpret_cast<const uint4*>(c.residual), reinterpret_cast<uint4*>(c.ys), c.n_out, c.relu, plan, cap_rows);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
 
 template <int CIN, int NT>
-static int launch_staged_rows(int mode, int cap_rows, const uint4* xs, const uint4* wpk, const float* winv, int K,
-                              int cout, const uint16_t* slots, int nbr_stride, const int32_t* ulist,
-                              const int32_t* ucount, int n_out, const float* scale, const float* shift,
-                              const uint4* residual, int relu, uint4* ys, hipStream_t st) {
-#define ISF_ARGS_ST (mode & ISF_CONV_MODE_UNIFORM_TILES) == 0, cap_rows, xs, wpk, winv, K, cout, slots, nbr_stride, ulist, ucount, n_out, scale, shift, residual, relu, ys, st
-  const bool wide = NT == 8 && cout == 128 && n_out >= 8 * 256;   // the 8-wave shape of launch16_rows
-  if ((mode & ~kConvOptsStaged) == ISF_CONV_MODE_F16) {
-    if (wide) return launch_staged<CIN, (NT == 8 ? NT : 2), 2, 8, kKernF16>(ISF_ARGS_ST);
-    return launch_staged<CIN, NT, 2, 4, kKernF16>(ISF_ARGS_ST);
+static int launch_staged_rows(const ConvCall& c, const StagePlan& sp) {
+  const bool wide = NT == 8 && c.c_out == 128 && c.n_out >= 8 * 256;   // the 8-wave shape of launch16_rows
+  if ((c.mode & ~kConvOptsStaged) == ISF_CONV_MODE_F16) {
+    if (wide) return launch_staged<CIN, (NT == 8 ? NT : 2), 2, 8, kKernF16>(c, sp);
+    return launch_staged<CIN, NT, 2, 4, kKernF16>(c, sp);
   }
-  if (wide) return launch_staged<CIN, (NT == 8 ? NT : 2), 2, 8, 0>(ISF_ARGS_ST);
-  return launch_staged<CIN, NT, 2, 4, 0>(ISF_ARGS_ST);
-#undef ISF_ARGS_ST
+  if (wide) return launch_staged<CIN, (NT == 8 ? NT : 2), 2, 8, 0>(c, sp);
+  return launch_staged<CIN, NT, 2, 4, 0>(c, sp);
 }
 
 template <int CIN>
-static int dispatch_staged(int mode, int cap_rows, const uint4* xs, const uint4* wpk, const float* winv, int K,
-                           int cout, const uint16_t* slots, int nbr_stride, const int32_t* ulist,
-                           const int32_t* ucount, int n_out, const float* scale, const float* shift,
-                           const uint4* residual, int relu, uint4* ys, hipStream_t st) {
-  switch (cout) {
-    case 32:  return launch_staged_rows<CIN, 2>(mode, cap_rows, xs, wpk, winv, K, cout, slots, nbr_stride, ulist, ucount, n_out, scale, shift, residual, relu, ys, st);
-    case 64:  return launch_staged_rows<CIN, 4>(mode, cap_rows, xs, wpk, winv, K, cout, slots, nbr_stride, ulist, ucount, n_out, scale, shift, residual, relu, ys, st);
+static int dispatch_staged(const ConvCall& c, const StagePlan& sp) {
+  switch (c.c_out) {
+    case 32:  return launch_staged_rows<CIN, 2>(c, sp);
+    case 64:  return launch_staged_rows<CIN, 4>(c, sp);
     case 128:
-    case 256: return launch_staged_rows<CIN, 8>(mode, cap_rows, xs, wpk, winv, K, cout, slots, nbr_stride, ulist, ucount, n_out, scale, shift, residual, relu, ys, st);
+    case 256: return launch_staged_rows<CIN, 8>(c, sp);
   }
   return ISF_ERR_UNSUPPORTED;
 }
 
-int sparse_conv_forward_staged_impl(const void* xs, int c_in, const void* packed16, int K, int c_out,
-                                    const uint16_t* slots, int nbr_stride, const int32_t* ulist,
-                                    const int32_t* ucount, int n_out, const float* scale, const float* shift,
-                                    const void* residual, int relu, void* ys, int stage_rows, int mode,
-                                    hipStream_t st) {
-  if (n_out <= 0) return ISF_OK;
-  ISF_REQUIRE(K >= 1 && K <= kMaxTaps, ISF_ERR_UNSUPPORTED, "sparse_conv_staged: %d taps (max 27)", K);
-  ISF_REQUIRE(sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
-              "sparse_conv_staged: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
-  ISF_REQUIRE(nbr_stride % 128 == 0 && nbr_stride >= n_out, ISF_ERR_ARG, "sparse_conv_staged: bad nbr_stride");
-  const int m = mode & ~kConvOptsStaged;
-  ISF_REQUIRE(m == 0 || m == ISF_CONV_MODE_F16, ISF_ERR_ARG, "sparse_conv_staged: mode %d (0 split precision, 1 single-pass f16, +32)", mode);
-  const uint4* w = reinterpret_cast<const uint4*>(packed16);
-  const float* winv = reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed16) +
-                                                     (size_t)K * c_in * c_out * 4);
-  const uint4* x = reinterpret_cast<const uint4*>(xs);
-  const uint4* r = reinterpret_cast<const uint4*>(residual);
-  uint4* y = reinterpret_cast<uint4*>(ys);
-  switch (c_in) {
-    case 32:  return dispatch_staged<32>(mode, stage_rows, x, w, winv, K, c_out, slots, nbr_stride, ulist, ucount, n_out, scale, shift, r, relu, y, st);
-    case 64:  return dispatch_staged<64>(mode, stage_rows, x, w, winv, K, c_out, slots, nbr_stride, ulist, ucount, n_out, scale, shift, r, relu, y, st);
-    case 128: return dispatch_staged<128>(mode, stage_rows, x, w, winv, K, c_out, slots, nbr_stride, ulist, ucount, n_out, scale, shift, r, relu, y, st);
-    case 256: return dispatch_staged<256>(mode, stage_rows, x, w, winv, K, c_out, slots, nbr_stride, ulist, ucount, n_out, scale, shift, r, relu, y, st);
+int sparse_conv_forward_staged_impl(const ConvCall& c, const uint16_t* slots, const int32_t* ulist, const int32_t* ucount,
+                                    int stage_rows) {
+  if (c.n_out <= 0) return ISF_OK;
+  ISF_TRY(conv_check_problem("sparse_conv_staged", c.c_in, c.c_out, sparse_conv_f16x3_supported(c.c_in, c.c_out), c.K,
+                             c.nbr_stride, c.n_out));
+  const int m = c.mode & ~kConvOptsStaged;
+  ISF_REQUIRE(m == 0 || m == ISF_CONV_MODE_F16, ISF_ERR_ARG, "sparse_conv_staged: mode %d (0 split precision, 1 single-pass f16, +32)", c.mode);
+  const StagePlan sp{slots, ulist, ucount, stage_rows};
+  switch (c.c_in) {
+    case 32:  return dispatch_staged<32>(c, sp);
+    case 64:  return dispatch_staged<64>(c, sp);
+    case 128: return dispatch_staged<128>(c, sp);
+    case 256: return dispatch_staged<256>(c, sp);
   }
   return ISF_ERR_UNSUPPORTED;
 }
@@ -576,15 +557,11 @@ int isf_sparse_conv_forward_staged(const void* features_split, int num_in, int c
                                    const int32_t* ulist, const int32_t* ucount, int num_out, const float* scale,
                                    const float* shift, const void* residual_split, int relu, void* out_split,
                                    int stage_rows, int mode, isf_stream_t stream) {
-  ISF_REQUIRE(num_in >= 0 && num_out >= 0 && c_in > 0 && c_out > 0 && num_taps > 0, ISF_ERR_ARG,
-              "sparse_conv_forward_staged: bad arguments");
-  if (num_out == 0) return ISF_OK;
-  ISF_REQUIRE(features_split && packed16 && slots && ulist && ucount && out_split &&
-                  ((scale == nullptr) == (shift == nullptr)),
-              ISF_ERR_ARG, "sparse_conv_forward_staged: null pointer");
-  return isf::sparse_conv_forward_staged_impl(features_split, c_in, packed16, num_taps, c_out, slots, nbr_stride, ulist,
-                                              ucount, num_out, scale, shift, residual_split, relu, out_split,
-                                              stage_rows, mode, isf::as_stream(stream));
+  const isf::ConvCall c = isf::conv_call(features_split, c_in, packed16, num_taps, c_out, nullptr, nbr_stride, num_out, scale,
+                                         shift, residual_split, relu, out_split, mode, isf::as_stream(stream));
+  bool run;
+  ISF_TRY(isf::conv_entry_check("sparse_conv_forward_staged", c, num_in, true, slots && ulist && ucount, &run));
+  return run ? isf::sparse_conv_forward_staged_impl(c, slots, ulist, ucount, stage_rows) : ISF_OK;
 }
 
 }  // extern "C"
