@@ -21,12 +21,10 @@ Activations travel through a stack as fp32 token rows ([B*H*W, C], token = (b*H 
 No CPU fallback: layers the kernels do not tile (channel counts outside 32 / 64 / 128 / 256 per <= 256-channel input group,
 e.g. the 10-class heat-map conv) run on the stock module, everything else fails loudly without the HIP library.
 """
-import weakref
-
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, derived
 from . import spconv as sp
 from .dense_conv import grid_rulebook
 from .norm import bn1d_relu
@@ -37,7 +35,6 @@ _amp_fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _amp_bwd = torch.amp.custom_bwd(device_type="cuda")
 
 _rulebooks = {}
-_packed = {}          # (id(weight), transpose) -> (version, data_ptr, [(offset, channels, fwd filters, dX filters)], weakref)
 
 
 def dense_rulebook(device, B, H, W, stride):
@@ -63,11 +60,11 @@ def supported(conv):
 
 def _groups(weight, transpose):
     """packed (forward, dX) filters per <= 256-channel input group of a Conv2d weight [Cout, Cin, 3, 3], once per
-    parameter version (torch.optim steps bump Tensor._version; `.data` writes do not: spconv.drop_packed_pairs)."""
-    key = (id(weight), bool(transpose))
-    hit = _packed.get(key)
-    if hit is not None and hit[3]() is weight and hit[0] == weight._version and hit[1] == weight.data_ptr():
-        return hit[2]
+    parameter version: [(offset, channels, forward filters, dX filters)] (derived.param_store, with the sparse convs'
+    switch spconv.PACKED_PAIR_CACHE)."""
+    s = derived.param_store(weight, sp.PACKED_PAIR_CACHE)
+    if ("groups", bool(transpose)) in s:
+        return s["groups", bool(transpose)]
     w = weight.detach().float()
     cout, cin = w.shape[:2]
     # taps enumerated (ky, kx); transpose: (kx, ky) = the convolution of the spatially transposed map on the
@@ -80,14 +77,8 @@ def _groups(weight, transpose):
         wk = w5[:, :, off:off + c].contiguous().view(1, 3, 3, c, cout)
         groups.append((off, c, sp.pack_filters_f16x3(wk), sp.pack_filters_f16x3(wk, transposed=True)))
         off += c
-    if len(_packed) > 256:
-        _packed.clear()
-    _packed[key] = (weight._version, weight.data_ptr(), groups, weakref.ref(weight))
+    s["groups", bool(transpose)] = groups
     return groups
-
-
-def drop_packed():
-    _packed.clear()
 
 
 class DenseConvFunction(torch.autograd.Function):
@@ -180,7 +171,8 @@ def usable(seq):
 def conv_stack(seq, x, transpose=False):
     """training-mode forward of an nn.Sequential of (Conv2d 3x3 [, BatchNorm2d] [, ReLU])* -- a ConvModule, a SECONDV2
     block, a single Conv2d -- on [B, C, H, W] (or a list of such maps = their channel concatenation); returns an NCHW view
-    of token-major rows.  transpose=True: the stack
+    of token-major rows.  Weights written through `.data` need fusion_ops.drop_caches(module) before the next call (the
+    packed filters are keyed on Tensor._version).  transpose=True: the stack
     applied to x.permute(0, 1, 3, 2), result permuted back (what the reference does around its instance branch,
     fusion_encoder.py:1093,1139) without transposing anything.  Stacks the kernels do not cover run on the stock modules."""
     single = not isinstance(seq, nn.Sequential)

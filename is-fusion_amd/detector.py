@@ -13,7 +13,7 @@ img_neck (GeneralizedLSSFPN), and takes images instead of camera features (DESIG
 """
 import torch
 
-from . import _lib
+from . import _lib, derived
 from torch import nn
 
 from .fusion_encoder import ISFusionEncoder
@@ -53,6 +53,7 @@ class ISFusionPtsPath(nn.Module):
         # the one-call engine is kept OUT of the module tree; its two sub-modules are registered here under the
         # reference's attribute names (shared objects), so state-dict keys are pts_voxel_encoder.* / pts_middle_encoder.*
         object.__setattr__(self, "_lidar", lidar)
+        derived.also_below(self, lidar)               # freeze() and drop_caches() reach it all the same
         self.pts_voxel_encoder = lidar.pts_voxel_encoder
         self.pts_middle_encoder = lidar.pts_middle_encoder
         fe = dict(fusion_encoder or ISFUSION_0075_FUSION["fusion_encoder"])
@@ -78,15 +79,13 @@ class ISFusionPtsPath(nn.Module):
     def freeze(self, flag=True):
         """Inference deployment (weights static): every module below skips its per-call "did a parameter change?" scan
         of the packed-weight caches -- about 0.4 ms of host time per forward, which at small batch is GPU idle time."""
-        from . import fusion_ops as ops
-        self._lidar.freeze(flag)
-        ops.freeze(self, flag)
+        derived.freeze(self, flag)                    # (the LiDAR branch with it: derived.also_below)
         return self
 
     def train(self, mode=True):
         """Entering training mode ends the freeze (optimizer steps are about to change the weights): the packed caches
         and the captured HIP graphs below this module are dropped here, not at the next forward that happens to look."""
-        if mode and self.__dict__.get("_isf_frozen", False):
+        if mode and derived.flagged(self):
             self.freeze(False)
         return super().train(mode)
 

@@ -264,23 +264,23 @@ class SECONDV2(nn.Module):
 
     dense_conv = "hip"   # "hip": f16x3 MFMA kernel of the sparse encoder on the dense grid; "stock": MIOpen
 
-    def _packed(self, name, seq):
+    def _packed(self, seq):
+        """the stack's layers packed for the dense-grid kernels (dense_conv.pack_sequential), once per version of ITS
+        parameters"""
         from .dense_conv import pack_sequential
-        from .fusion_ops import frozen, param_key
-        cache = self.__dict__.setdefault("_isf_packed", {})
-        dev = next(seq.parameters()).device
-        key = (dev, None if name in cache and frozen(self) else param_key(seq))
-        if name not in cache or cache[name][0][0] != dev or (key[1] is not None and cache[name][0][1] != key[1]):
-            cache[name] = ((dev, key[1] if key[1] is not None else param_key(seq)), pack_sequential(seq))
-        return cache[name][1]
+        from .derived import store
+        s = store(seq, next(seq.parameters()).device)
+        if "packed" not in s:
+            s["packed"] = pack_sequential(seq)
+        return s["packed"]
 
-    def _run(self, name, seq, x):
+    def _run(self, seq, x):
         """x: [B, C, H, W] fp32 or a dense_conv.SplitMap -> SplitMap (hip) / tensor (stock)"""
         from .dense_conv import SplitMap
         if self.dense_conv != "hip":
             return seq(x)
         m = x if isinstance(x, SplitMap) else SplitMap.from_nchw(x)
-        for layer in self._packed(name, seq):
+        for layer in self._packed(seq):
             m = layer(m)
         return m
 
@@ -304,12 +304,12 @@ class SECONDV2(nn.Module):
             x1 = run(self.blocks[0], x)
             return x1, run(self.blocks[1], run(self.ds_layer, x1))
         if stage == "stage1":
-            feat = self._run("b0", self.blocks[0], x[0] if isinstance(x, (list, tuple)) else x)
-            return nchw(self._run("ds", self.ds_layer, feat)), None, nchw(feat)
+            feat = self._run(self.blocks[0], x[0] if isinstance(x, (list, tuple)) else x)
+            return nchw(self._run(self.ds_layer, feat)), None, nchw(feat)
         if stage == "stage2":
-            return None, None, nchw(self._run("b1", self.blocks[1], x[0] if isinstance(x, (list, tuple)) else x))
-        x1 = self._run("b0", self.blocks[0], x)
-        return nchw(x1), nchw(self._run("b1", self.blocks[1], self._run("ds", self.ds_layer, x1)))
+            return None, None, nchw(self._run(self.blocks[1], x[0] if isinstance(x, (list, tuple)) else x))
+        x1 = self._run(self.blocks[0], x)
+        return nchw(x1), nchw(self._run(self.blocks[1], self._run(self.ds_layer, x1)))
 
 
 def seeded_state_dict(module, seed):
@@ -386,13 +386,13 @@ class SECONDFPN(nn.Module):
         assert up.kernel_size == (1, 1) and up.stride == (1, 1) and up.bias is None
         return w[:, :, 0, 0] * scale[:, None], shift, 1
 
-    def forward_tokens(self, x, linear_relu, cached=False):
+    def forward_tokens(self, x, linear_relu, folded=None):
         """the "hip" data path with the GEMM injected: linear_relu(x [B, Cin, H, W], weight, bias) -> relu(tokens W^T +
         b) as [B*H*W, N] rows ((b, y, x) order).  (tests/test_host.py runs it with a torch GEMM against the modules.)"""
         out = None
         c0 = 0
         for i in range(len(self.deblocks)):
-            w, b, s = self._folded_cached(i) if cached else self._folded(i)
+            w, b, s = (folded or self._folded)(i)
             B, _, H, W = x[i].shape
             y = linear_relu(x[i], w, b)                                   # [B*H*W, s*s*Cout], column = (dy*s + dx)*Cout + co
             cout = y.shape[1] // (s * s)
@@ -405,27 +405,22 @@ class SECONDFPN(nn.Module):
         return [out]
 
     def _linear_relu(self):
-        """the injected GEMM of forward_tokens on the fused linear kernel, weights packed once per parameter version"""
+        """(the injected GEMM of forward_tokens on the fused linear kernel, _folded) with the packed weights and the
+        folded levels made once per parameter version"""
         from . import fusion_ops as ops
-        cache = self.__dict__.setdefault("_isf_packed", {})
-        pk = None if cache and ops.frozen(self) else ops.param_key(self)
-        if pk is not None and cache.get("_key") != pk:
-            cache.clear()
-            cache["_key"] = pk
+        cache = ops._cache(self, self.deblocks[0][0].weight.device)
 
         def linear_relu(t, w, b):
             key = (w.shape[0], w.shape[1], t.device)
             if key not in cache:
                 cache[key] = ops.PackedLinear(w.to(t.device), b.to(t.device))
             return ops.linear(t.float(), cache[key], act=ops.ACT_RELU)
-        return linear_relu
 
-    def _folded_cached(self, i):
-        """_folded(i) once per parameter version (the cache _linear_relu() has just validated)"""
-        cache = self.__dict__.setdefault("_isf_packed", {})
-        if ("folded", i) not in cache:
-            cache[("folded", i)] = self._folded(i)
-        return cache[("folded", i)]
+        def folded(i):
+            if ("folded", i) not in cache:
+                cache[("folded", i)] = self._folded(i)
+            return cache[("folded", i)]
+        return linear_relu, folded
 
     @torch.no_grad()
     def forward_split(self, x):
@@ -436,10 +431,10 @@ class SECONDFPN(nn.Module):
         from .dense_conv import SplitMap
         from .spconv import to_split
         assert len(x) == len(self.in_channels) and not self.training
-        linear_relu = self._linear_relu()
+        linear_relu, folded = self._linear_relu()
         maps = []
         for i in range(len(self.deblocks)):
-            w, b, s = self._folded_cached(i)
+            w, b, s = folded(i)
             if isinstance(x[i], SplitMap):                                # token rows: the row-major GEMM (column-split
                 B, H, W = x[i].B, x[i].H, x[i].W                          # launches for the 90 x 90 level), no NCHW map
                 y = linear_relu(x[i].to_rows(), w, b)
@@ -457,7 +452,7 @@ class SECONDFPN(nn.Module):
         assert len(x) == len(self.in_channels)
         if self.dense_conv == "hip" and not self.training:
             with torch.no_grad():
-                return self.forward_tokens(x, self._linear_relu(), cached=True)
+                return self.forward_tokens(x, *self._linear_relu())
         ups = [d(x[i]) for i, d in enumerate(self.deblocks)]
         out = torch.cat(ups, dim=1) if len(ups) > 1 else ups[0]
         return [out.permute(0, 1, 3, 2).contiguous()]

@@ -10,6 +10,8 @@ import ctypes
 import torch
 
 from . import _lib
+# derived state (packed weights, tables, plans) follows one policy, derived.py; the names callers know stay here
+from .derived import drop as drop_caches, freeze, frozen, param_key, store as _cache  # noqa: F401
 
 # the HIP kernels compute in fp32: under torch.autocast (the reference trains with mixed precision) inputs are cast
 # to fp32 on the way in and autocast is off inside forward / backward
@@ -78,86 +80,6 @@ def linear(x, pl, *, table=None, index=None, act=ACT_NONE, residual=None, ln=Non
         _lib.ptr(b) if b is not None else None, eps, _lib.ptr(y), ldy, x_hw, res_hw, y_hw, _lib.stream()),
         "isf_linear_forward")
     return y
-
-
-def drop_caches(module, *_):
-    """Forget everything below `module` that was derived from its parameters: packed-weight / table caches, the
-    SparseEncoder's C plan, the LidarBranch's folded VFE parameters and captured HIP graphs (their kernels hold
-    pointers into the packed copies)."""
-    for sub in module.modules():
-        d = sub.__dict__
-        d.pop("_isf_cache", None)
-        d.pop("_isf_packed", None)
-        if d.get("_plan") is not None:
-            d["_plan"] = None
-        if d.get("_vfe_cache") is not None:
-            d["_vfe_cache"] = None
-        if isinstance(d.get("_graphs"), dict):
-            d["_graphs"].clear()
-
-
-def param_key(module):
-    """(version, address) of every parameter and buffer below `module`: changes whenever one of them is replaced or
-    written in place -- by load_state_dict (mmcv's load_checkpoint recurses over _load_from_state_dict and never fires
-    the post hooks), an optimizer step or a manual copy_()."""
-    return tuple((t._version, t.data_ptr()) for t in list(module.parameters()) + list(module.buffers()))
-
-
-def _unfreeze_on_load(module, *_):
-    """load_state_dict pre-hook (fires inside every module's _load_from_state_dict, so also under mmcv's
-    load_checkpoint): new weights are coming, the packed copies must be re-derived."""
-    freeze(module.__dict__.get("_isf_freeze_root", module), False)
-
-
-def freeze(module, flag=True):
-    """Inference deployments: skip the per-call "did a parameter change?" scan of the caches below `module`.
-    The skip ends by itself when weights can change: a load_state_dict anywhere below `module`, or a forward in
-    training mode (see frozen()), clears it -- call freeze() again once the weights are final.
-
-    Every change of the flag -- freezing, unfreezing, the load_state_dict hook -- DROPS the derived state below
-    `module` (drop_caches): a frozen cache is used without looking at the parameters, so it must have been packed after
-    the freeze; load_state_dict -> freeze() -> forward, or train() -> optimizer steps -> eval() -> freeze(), would
-    otherwise reuse copies packed from the old weights (and replay HIP graphs that point into them)."""
-    drop_caches(module)
-    for sub in module.modules():
-        sub.__dict__["_isf_frozen"] = bool(flag)
-        if hasattr(sub, "_frozen"):          # SparseEncoder / LidarBranch keep their own flag
-            sub._frozen = bool(flag)
-        if flag and "_isf_freeze_root" not in sub.__dict__:
-            sub.__dict__["_isf_freeze_root"] = module
-            sub._register_load_state_dict_pre_hook(_unfreeze_on_load, with_module=True)
-        elif flag:
-            sub.__dict__["_isf_freeze_root"] = module
-    return module
-
-
-def frozen(module):
-    """True when `module`'s caches may be used without checking the parameters.  A module seen in training mode loses
-    the flag (an optimizer step is about to change its weights; a later eval() then re-validates by key)."""
-    if not module.__dict__.get("_isf_frozen", False):
-        return False
-    if module.training:
-        module.__dict__["_isf_frozen"] = False
-        if hasattr(module, "_frozen"):
-            module._frozen = False
-        return False
-    return True
-
-
-def _cache(module, device):
-    """Per-module cache of packed weights / tables derived from its parameters, dropped when the device or any
-    parameter / buffer below the module changed (SparseEncoder._c_plan keys its plan the same way)."""
-    c = module.__dict__.get("_isf_cache")
-    key = None if (c is not None and frozen(module)) else param_key(module)
-    if c is None or c.get("device") != device or (key is not None and c.get("_key") != key):
-        c = {"device": device, "_key": key if key is not None else param_key(module)}
-        module.__dict__["_isf_cache"] = c
-    return c
-
-
-def watch_parameters(module):
-    """kept for callers that cache outside _cache(): nothing to register, validity is checked through param_key"""
-    return module
 
 
 def to_tokens(x):

@@ -12,7 +12,7 @@ import ctypes
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, derived
 from .norm import fold_bn
 from .sparse_encoder import SparseEncoder
 from .voxel_encoder import DynamicVFE
@@ -47,8 +47,6 @@ class LidarBranch(nn.Module):
         self.pts_voxel_encoder = DynamicVFE(**ve)
         self.pts_middle_encoder = SparseEncoder(**me)
         self.last_stats = None
-        self._vfe_cache = None
-        self._vfe_key = None
 
     def randomize_bn_(self, seed=0):
         """Random but well-conditioned BN running statistics / affine parameters (bench + parity tests:
@@ -85,20 +83,17 @@ class LidarBranch(nn.Module):
 
     def freeze(self, flag=True):
         """Skip the per-call parameter-change scans (weights are static at inference).  Ends by itself on a
-        load_state_dict below this module or a forward in training mode (fusion_ops.freeze / frozen)."""
-        from . import fusion_ops as ops
-        self._frozen = bool(flag)
-        ops.freeze(self, flag)
+        load_state_dict below this module or a forward in training mode (derived.freeze / frozen)."""
+        derived.freeze(self, flag)
         return self
 
     def _vfe_params(self):
+        """(isf_vfe_params block, the tensors it points into): the VFE's linears with BatchNorm folded, rebuilt when a
+        parameter / buffer of the VFE changed"""
         vfe = self.pts_voxel_encoder
-        from .fusion_ops import frozen
-        if self._vfe_cache is not None and getattr(self, "_frozen", False) and frozen(self):
-            return self._vfe_cache
-        key = tuple((p._version, p.data_ptr()) for p in list(vfe.parameters()) + list(vfe.buffers()))
-        if self._vfe_cache is not None and self._vfe_key == key:
-            return self._vfe_cache
+        s = derived.store(self, vfe.vfe_layers[0].linear.weight.device, source=vfe)
+        if "vfe" in s:
+            return s["vfe"]
         l1, l2 = vfe.vfe_layers
         s1, b1 = fold_bn(l1.norm)
         s2, b2 = fold_bn(l2.norm)
@@ -112,9 +107,8 @@ class LidarBranch(nn.Module):
             p.voxel_size[j] = float(self.voxel_size[j])
         for j in range(6):
             p.coors_range[j] = float(self.point_cloud_range[j])
-        self._vfe_cache = (p, (w1, w2, s1, b1, s2, b2))
-        self._vfe_key = key
-        return self._vfe_cache
+        s["vfe"] = (p, (w1, w2, s1, b1, s2, b2))
+        return s["vfe"]
 
     def forward_train(self, points):
         """training mode: the reference's composition -- dynamic voxelize, DynamicVFE module path

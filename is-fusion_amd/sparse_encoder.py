@@ -15,7 +15,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, derived
 from .norm import fold_bn
 from .sparse_block import SparseBasicBlock, make_sparse_convmodule
 from .spconv import SparseConvolution, SparseConvTensor, SparseSequential
@@ -80,9 +80,6 @@ class SparseEncoder(nn.Module):
         self.conv_out = make_sparse_convmodule(out_ch, output_channels, kernel_size=(3, 1, 1), stride=(2, 1, 1),
                                                norm_cfg=norm_cfg, padding=0, indice_key="spconv_down2",
                                                conv_type="SparseConv3d")
-        self._plan = None
-        self._plan_key = None
-        self._frozen = False
 
     def _make_encoder_layers(self, norm_cfg, in_channels, block_type):
         """Stage layout of sparse_encoder.py:142-216."""
@@ -176,20 +173,16 @@ class SparseEncoder(nn.Module):
 
     def freeze(self, flag=True):
         """Inference deployments: skip the per-call "did a parameter change?" scan (about 130 tensors).  Ends by itself
-        on a load_state_dict below this module or a forward in training mode (fusion_ops.freeze / frozen)."""
-        from . import fusion_ops as ops
-        self._frozen = bool(flag)
-        ops.freeze(self, flag)
+        on a load_state_dict below this module or a forward in training mode (derived.freeze / frozen)."""
+        derived.freeze(self, flag)
         return self
 
-    def _c_plan(self):
-        """ctypes array of isf_conv_layer, rebuilt when a parameter / buffer changed."""
-        from .fusion_ops import frozen
-        if self._plan is not None and self._frozen and frozen(self):
-            return self._plan
-        key = tuple((p._version, p.data_ptr()) for p in list(self.parameters()) + list(self.buffers()))
-        if self._plan is not None and self._plan_key == key:
-            return self._plan
+    def _derived(self):
+        """this encoder's store with "plan" (ctypes array of isf_conv_layer, its length, what it points into, the
+        exported plan) and "out_shape", rebuilt when a parameter / buffer changed."""
+        s = derived.store(self, next(self.parameters()).device)
+        if "plan" in s:
+            return s
         plan = self.export_plan()
         n = len(plan["layers"])
         arr = (_lib.ConvLayer * n)()
@@ -210,15 +203,16 @@ class SparseEncoder(nn.Module):
             c.packed, c.scale, c.shift = packed.data_ptr(), scale.data_ptr(), shift.data_ptr()
             c.relu = int(L["relu"])
             c.residual_from = -2 if L["residual_from"] is None else int(L["residual_from"])
-        self._plan = (arr, n, keep, plan)
-        self._plan_key = key
-        self._out_shape = self._compute_out_shape(plan)
-        return self._plan
+        s["out_shape"] = self._compute_out_shape(plan)
+        s["plan"] = (arr, n, keep, plan)
+        return s
+
+    def _c_plan(self):
+        return self._derived()["plan"]
 
     def out_channels_and_shape(self):
         """(C*D, H, W) of spatial_features for this configuration."""
-        self._c_plan()
-        return self._out_shape
+        return self._derived()["out_shape"]
 
     def _compute_out_shape(self, plan):
         shape = list(self.sparse_shape)

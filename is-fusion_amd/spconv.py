@@ -14,13 +14,11 @@ Differences that matter to a maintainer:
 import ctypes
 import math
 
-import weakref
-
 import numpy as np
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, derived
 
 # the HIP kernels compute in fp32: under torch.autocast (the reference trains with mixed precision) inputs are cast
 # to fp32 on the way in and autocast is off inside forward / backward
@@ -708,38 +706,24 @@ class _TransposedRulebook:
         self.nbr, self.stride, self.num_in, self.num_out = nbr_t, stride_t, num_out, num_in
 
 
-_PACKED_PAIRS = {}   # id(weight parameter) -> (version, data_ptr, packed forward filters, packed transposed filters, weakref)
-
-
-# The cache below is keyed on (parameter identity, Tensor._version, data_ptr).  torch.optim steps, load_state_dict and
-# every in-place op on the parameter bump _version; writes through `.data` (p.data.copy_(), EMA swaps, fp16 copy-back of
-# older mmcv optim wrappers) do NOT -- after such an update call drop_packed_pairs() (or set PACKED_PAIR_CACHE = False for
-# the run: 5 more launches per layer and step), otherwise forward and dX keep multiplying with the old filters.
+# Packed copies follow derived.py's rule: they are keyed on the parameter's version counter and address.  torch.optim
+# steps, load_state_dict and every in-place op move that key; writes through `.data` (p.data.copy_(), EMA swaps, fp16
+# copy-back of older mmcv optim wrappers) do NOT -- after such a write call fusion_ops.drop_caches(module), otherwise
+# forward and dX keep multiplying with the old filters.  False: the two autograd Functions (sparse convs here, dense convs
+# in dense_train.py) pack on every call and keep nothing (5 more launches per layer and step).
 PACKED_PAIR_CACHE = True
 
-
-def drop_packed_pairs():
-    """Forget every cached (forward, transposed) packed-filter pair: call after updating sparse-conv weights through
-    `.data` (which does not bump Tensor._version, the cache's change detector)."""
-    _PACKED_PAIRS.clear()
+drop_packed_pairs = derived.drop_all     # every parameter's packed filters, sparse and dense convs alike
 
 
 def _packed_pair(weight, w, K, c_in, c_out):
     """(packed filters of the forward conv, packed per-tap TRANSPOSED filters of the dX conv) of a weight parameter,
     packed once per parameter version: the forward pass packs both, the backward pass finds its half here instead of
     transposing + packing again (5 launches per layer and step)."""
-    if not PACKED_PAIR_CACHE:
-        return pack_filters_f16x3(w), pack_filters_f16x3(w, transposed=True)
-    key = id(weight)
-    hit = _PACKED_PAIRS.get(key)
-    # the weak reference tells a live parameter from a new tensor that reuses a dead one's id / address / version 0
-    if hit is not None and hit[4]() is weight and hit[0] == weight._version and hit[1] == weight.data_ptr():
-        return hit[2], hit[3]
-    pair = (pack_filters_f16x3(w), pack_filters_f16x3(w, transposed=True))    # (no transposed copy: the pack kernel reads it)
-    if len(_PACKED_PAIRS) > 256:
-        _PACKED_PAIRS.clear()
-    _PACKED_PAIRS[key] = (weight._version, weight.data_ptr(), pair[0], pair[1], weakref.ref(weight))
-    return pair
+    s = derived.param_store(weight, PACKED_PAIR_CACHE)
+    if "pair" not in s:
+        s["pair"] = (pack_filters_f16x3(w), pack_filters_f16x3(w, transposed=True))    # (no transposed copy: the pack kernel reads it)
+    return s["pair"]
 
 
 class SparseConvFunction(torch.autograd.Function):
@@ -859,10 +843,6 @@ class SparseConvolution(SparseModule):
             self.bias = nn.Parameter(torch.empty(out_channels))
         else:
             self.register_parameter("bias", None)
-        self._packed = None
-        self._packed_key = None
-        self._packed16 = None
-        self._packed16_key = None
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -887,21 +867,19 @@ class SparseConvolution(SparseModule):
                                       error_msgs)
 
     def packed_weight(self):
-        key = (self.weight._version, self.weight.data_ptr(), self.weight.device)
-        if self._packed is None or self._packed_key != key:
-            self._packed = pack_filters(self.weight)
-            self._packed_key = key
-        return self._packed
+        s = derived.store(self, self.weight.device)
+        if "packed" not in s:
+            s["packed"] = pack_filters(self.weight)
+        return s["packed"]
 
     def packed16_weight(self):
         """Split-precision packing, or None when (Cin, Cout) is outside the f16x3 kernel's shapes."""
         if not f16x3_supported(self.in_channels, self.out_channels):
             return None
-        key = (self.weight._version, self.weight.data_ptr(), self.weight.device)
-        if self._packed16 is None or self._packed16_key != key:
-            self._packed16 = pack_filters_f16x3(self.weight)
-            self._packed16_key = key
-        return self._packed16
+        s = derived.store(self, self.weight.device)
+        if "packed16" not in s:
+            s["packed16"] = pack_filters_f16x3(self.weight)
+        return s["packed16"]
 
     def rulebook_for(self, x):
         key = ("subm" if self.subm else "conv", tuple(self.kernel_size), tuple(self.stride),

@@ -578,20 +578,19 @@ def test_freeze_after_a_weight_change_never_reuses_the_old_packed_copies():
         net[1].weight.mul_(2.0)
     ops.freeze(net)
     assert "packed" not in ops._cache(net[1], dev)
-    # derived state kept outside _cache(): plan / VFE fold / captured graphs are dropped with the flag change
+    # what SparseEncoder / LidarBranch keep (plan, VFE fold) and captured graphs are dropped with the flag change
     class Holder(torch.nn.Module):
         def __init__(self):
             super().__init__()
             self.lin = torch.nn.Linear(2, 2)
-            self._plan, self._vfe_cache, self._frozen = "plan", "vfe", False
             self.__dict__["_graphs"] = {("k",): "captured"}
     h = Holder().eval()
+    ops._cache(h, dev).update(plan="plan", vfe="vfe")
     ops.freeze(h)
-    assert h._plan is None and h._vfe_cache is None and h._graphs == {} and h._frozen is True
-    h._plan, h._graphs[("k",)] = "plan2", "g2"
+    assert "plan" not in ops._cache(h, dev) and "vfe" not in ops._cache(h, dev) and h._graphs == {} and ops.frozen(h)
+    ops._cache(h, dev)["plan"], h._graphs[("k",)] = "plan2", "g2"
     h.lin.load_state_dict(h.lin.state_dict())
-    assert h._plan is None and h._graphs == {} and h._frozen is False
-
+    assert "plan" not in ops._cache(h, dev) and h._graphs == {} and not ops.frozen(h)
 
 
 def test_layer_level_kernel_choice_mirrors_the_engine(monkeypatch):
