@@ -1278,12 +1278,39 @@ typedef struct isf_swin_a {
 int isf_swin_gemm(const isf_swin_a* a, int num_rows, int k, const void* packed_weight, int out_features,
                   const float* scale, const float* shift, int activation, const float* residual, float* y, int ldy,
                   int y_hw, isf_stream_t stream);
+/* isf_swin_gemm_rowscale: isf_swin_gemm with a per-sample factor on the branch output, for DropPath in training
+ *   (mmcv DropPath on ShiftWindowMSA's output, swin.py:251, and on FFN's layers): y = act((A . W^T) * scale + shift) *
+ *   row_scale[r / rows_per_sample] + residual.  ROWS loader without the LayerNorm prologue; num_rows is a multiple of
+ *   rows_per_sample.  row_scale all 1 gives isf_swin_gemm's result bit for bit; a 0 leaves the residual row. */
+int isf_swin_gemm_rowscale(const isf_swin_a* a, int num_rows, int k, const void* packed_weight, int out_features,
+                           const float* scale, const float* shift, int activation, const float* residual,
+                           const float* row_scale, int rows_per_sample, float* y, int ldy, int y_hw,
+                           isf_stream_t stream);
 int isf_swin_row_stats(const isf_swin_a* a, int num_rows, int k, float eps, float* stats, isf_stream_t stream);
 int isf_swin_layernorm(const float* x, int num_rows, int channels, const float* gamma, const float* beta, float eps,
                        float* y, int y_hw, isf_stream_t stream);
 int isf_swin_window_attention(const float* qkv, const float* qkv_bias, const float* rel_bias, int batch, int height,
                               int width, int channels, int heads, int window, int shift, float scale, float* out,
                               isf_stream_t stream);
+
+/* Backward of the neck's top-down step (isf_swin_train.hip) --------------------------------------------------
+ * The 1x1 lateral conv over cat([fine, F.interpolate(coarse, bilinear, align_corners=True)]) (generalized_lss.py:83-100)
+ * under autograd: upsample_bilinear2d_backward + cat backward + the conv's wgrad / dgrad.  With output-gradient token
+ * rows G [batch*height*width, N]:  dW[:, :C1] = G^T . fine,  dW[:, C1:] = (up^T G)^T . coarse,
+ * dcoarse = (up^T G) . W[:, C1:] (isf_swin_gemm, ROWS loader, weight packed by isf_pack_linear_transposed).
+ * isf_upsample_rows_adjoint: g2 [batch*height2*width2, channels] = up^T g, the adjoint of the UPCAT loader's bilinear
+ *   sample (same float expressions for the taps); gather form, fixed summation order, no atomics.  channels % 4 == 0.
+ * isf_rows_weight_grad: dw[n, kk] (row stride ldw) = *inv_scale * sum_r g[r, n] * x[r, kk] for g rows [num_rows,
+ *   out_features] and x rows [num_rows, ldx] (x_hw == 0) or an NCHW map [num_rows / x_hw, k, x_hw] (x_hw > 0).  f16
+ *   hi/lo split of both operands (g pre-scaled by a power of two, isf_grad_rescale; inv_scale NULL = 1), fp32 accumulate.
+ *   workspace: fp32 [num_chunks, out_features, k] with num_chunks = isf_rows_weight_grad_chunks(num_rows, out_features,
+ *   k); the chunks' partial sums are added in chunk order: bit-identical run to run. */
+int isf_upsample_rows_adjoint(const float* g, int batch, int height, int width, int channels, int height2, int width2,
+                              float* g2, isf_stream_t stream);
+int isf_rows_weight_grad_chunks(int num_rows, int out_features, int k);
+int isf_rows_weight_grad(const float* g, const float* x, int ldx, int x_hw, int num_rows, int out_features, int k,
+                         const float* inv_scale, float* workspace, int num_chunks, float* dw, int ldw,
+                         isf_stream_t stream);
 
 /* Fused AdamW with global-norm gradient clipping (isf_optim.hip) ---------------------------------------------
  * isf_optim_grad_sumsq + isf_optim_adamw replace, together, mmcv OptimizerHook.clip_grads (mmcv/runner/hooks/

@@ -390,6 +390,12 @@ SIGNATURES = {
     "isf_bbox_mapping_back": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int_p, c_int_p, c_float_p, c_void_p]),
     "isf_swin_gemm": (c_int, [ctypes.POINTER(SwinA), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                               c_void_p, c_int, c_int, c_void_p]),
+    "isf_swin_gemm_rowscale": (c_int, [ctypes.POINTER(SwinA), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                       c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    "isf_upsample_rows_adjoint": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "isf_rows_weight_grad_chunks": (c_int, [c_int, c_int, c_int]),
+    "isf_rows_weight_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_int, c_void_p]),
     "isf_swin_row_stats": (c_int, [ctypes.POINTER(SwinA), c_int, c_int, ctypes.c_float, c_void_p, c_void_p]),
     "isf_swin_layernorm": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_int,
                                    c_void_p]),

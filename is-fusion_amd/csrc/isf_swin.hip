@@ -12,7 +12,8 @@
 //                                 and gamma / beta are permuted to it, so the product equals nn.Unfold's c*4 + kh*2 + kw
 //                          UPCAT  [fine NCHW | bilinear(align_corners) upsample of the coarse NCHW] channel concat
 //                        epilogue: * scale + shift (bias / folded BN), ReLU or exact GELU, + residual rows, stored as rows
-//                        or NCHW.  arithmetic: f16 hi/lo split of both operands, 3 x v_mfma_f32_16x16x32_f16 per
+//                        or NCHW.  isf_swin_gemm_rowscale (training, DropPath): the branch output of sample r / rows_per_sample
+//                        is multiplied by row_scale[sample] before the residual is added.  arithmetic: f16 hi/lo split of both operands, 3 x v_mfma_f32_16x16x32_f16 per
 //                        product, fp32 accumulate (as isf_linear.hip); weights packed by isf_pack_linear.
 //                        tiling: workgroup 128 rows x 64 columns, 4 waves of 32 x 64; A (split into hi / lo halves by
 //                        the loader) and B staged through a double-buffered LDS ring, one 32-deep K step per stage.
@@ -98,6 +99,8 @@ struct SwinEpi {
   const float* residual;  // [M, N] rows or null
   int act;                // 0 none, 1 relu, 2 gelu (erf)
   int ldy, y_hw;          // y_hw > 0: y is [B, N, y_hw]
+  const float* row_scale; // RS kernels: [num_rows / rows_per_sample] factor on the branch output (DropPath keep / keep_prob)
+  int rows_per_sample;
 };
 
 constexpr int SW_BM = 128;   // rows per workgroup (columns: 4 tiles of 16)
@@ -110,7 +113,7 @@ __device__ __forceinline__ void swin_a_slot(int t, int i, int& rl, int& kg) {
   else { rl = t & 127; kg = ((t >> 7) << 1) + i; }
 }
 
-template <int MODE, bool LN>
+template <int MODE, bool LN, bool RS = false>
 __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int K, const uint4* __restrict__ wp,
                                                          const float* __restrict__ w_inv_scale, int N, SwinEpi ep,
                                                          float* __restrict__ y) {
@@ -214,6 +217,7 @@ __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int
         float z = acc[g][nt][j] * winv * sc + sh;
         if (ep.act == 1) z = fmaxf(z, 0.f);
         else if (ep.act == 2) z = 0.5f * z * (1.f + erff(z * 0.70710678118654752440f));
+        if (RS) z *= ep.row_scale[r / ep.rows_per_sample];
         if (ep.residual) z += ep.residual[(size_t)r * N + n];
         if (ep.y_hw) {
           const int b = r / ep.y_hw, pos = r - b * ep.y_hw;
@@ -413,9 +417,10 @@ static int swin_check_a(const isf_swin_a* a, int M, int K, bool gemm) {
 
 extern "C" {
 
-int isf_swin_gemm(const isf_swin_a* a, int num_rows, int k, const void* packed_weight, int out_features,
-                  const float* scale, const float* shift, int activation, const float* residual, float* y, int ldy,
-                  int y_hw, isf_stream_t stream) {
+static int swin_gemm_launch(const isf_swin_a* a, int num_rows, int k, const void* packed_weight, int out_features,
+                            const float* scale, const float* shift, int activation, const float* residual,
+                            const float* row_scale, int rows_per_sample, float* y, int ldy, int y_hw,
+                            isf_stream_t stream) {
   using namespace isf;
   ISF_REQUIRE(num_rows >= 0 && out_features > 0 && out_features % 16 == 0, ISF_ERR_ARG,
               "swin_gemm: bad sizes (rows %d, out %d)", num_rows, out_features);
@@ -427,16 +432,24 @@ int isf_swin_gemm(const isf_swin_a* a, int num_rows, int k, const void* packed_w
               ISF_ERR_ARG, "swin_gemm: LayerNorm prologue needs rows / merge mode and gamma, beta");
   ISF_REQUIRE(y_hw > 0 ? num_rows % y_hw == 0 : ldy >= out_features, ISF_ERR_ARG, "swin_gemm: bad output layout");
   ISF_REQUIRE(activation >= 0 && activation <= 2, ISF_ERR_ARG, "swin_gemm: activation %d", activation);
+  ISF_REQUIRE(!row_scale || (a->mode == ISF_SWIN_A_ROWS && !ln && rows_per_sample > 0 &&
+                             num_rows % rows_per_sample == 0),
+              ISF_ERR_ARG, "swin_gemm_rowscale: rows mode without LayerNorm, rows %d a multiple of rows_per_sample %d",
+              num_rows, rows_per_sample);
   const uint4* wp = reinterpret_cast<const uint4*>(packed_weight);
   const float* winv =
       reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed_weight) + (size_t)out_features * k * 4);
-  SwinEpi ep{scale, shift, residual, activation, ldy, y_hw};
+  SwinEpi ep{scale, shift, residual, activation, ldy, y_hw, row_scale, rows_per_sample};
   hipStream_t st = as_stream(stream);
   const dim3 grid(ceil_div(out_features / 16, 4), ceil_div(num_rows, SW_BM)), block(256);
-#define ISF_SWIN_GEMM(MODE_, LN_) \
-  hipLaunchKernelGGL((swin_gemm_kernel<MODE_, LN_>), grid, block, 0, st, *a, num_rows, k, wp, winv, out_features, ep, y)
+#define ISF_SWIN_GEMM(MODE_, ...) \
+  hipLaunchKernelGGL((swin_gemm_kernel<MODE_, __VA_ARGS__>), grid, block, 0, st, *a, num_rows, k, wp, winv, out_features, ep, y)
   switch (a->mode) {
-    case ISF_SWIN_A_ROWS: if (ln) ISF_SWIN_GEMM(ISF_SWIN_A_ROWS, true); else ISF_SWIN_GEMM(ISF_SWIN_A_ROWS, false); break;
+    case ISF_SWIN_A_ROWS:
+      if (row_scale) ISF_SWIN_GEMM(ISF_SWIN_A_ROWS, false, true);
+      else if (ln) ISF_SWIN_GEMM(ISF_SWIN_A_ROWS, true);
+      else ISF_SWIN_GEMM(ISF_SWIN_A_ROWS, false);
+      break;
     case ISF_SWIN_A_MERGE: if (ln) ISF_SWIN_GEMM(ISF_SWIN_A_MERGE, true); else ISF_SWIN_GEMM(ISF_SWIN_A_MERGE, false); break;
     case ISF_SWIN_A_PATCH: ISF_SWIN_GEMM(ISF_SWIN_A_PATCH, false); break;
     case ISF_SWIN_A_UPCAT: ISF_SWIN_GEMM(ISF_SWIN_A_UPCAT, false); break;
@@ -444,6 +457,22 @@ int isf_swin_gemm(const isf_swin_a* a, int num_rows, int k, const void* packed_w
 #undef ISF_SWIN_GEMM
   ISF_LAUNCH_CHECK();
   return ISF_OK;
+}
+
+int isf_swin_gemm(const isf_swin_a* a, int num_rows, int k, const void* packed_weight, int out_features,
+                  const float* scale, const float* shift, int activation, const float* residual, float* y, int ldy,
+                  int y_hw, isf_stream_t stream) {
+  return swin_gemm_launch(a, num_rows, k, packed_weight, out_features, scale, shift, activation, residual, nullptr, 0, y,
+                          ldy, y_hw, stream);
+}
+
+int isf_swin_gemm_rowscale(const isf_swin_a* a, int num_rows, int k, const void* packed_weight, int out_features,
+                           const float* scale, const float* shift, int activation, const float* residual,
+                           const float* row_scale, int rows_per_sample, float* y, int ldy, int y_hw,
+                           isf_stream_t stream) {
+  ISF_REQUIRE(row_scale, ISF_ERR_ARG, "swin_gemm_rowscale: null row_scale");
+  return swin_gemm_launch(a, num_rows, k, packed_weight, out_features, scale, shift, activation, residual, row_scale,
+                          rows_per_sample, y, ldy, y_hw, stream);
 }
 
 int isf_swin_row_stats(const isf_swin_a* a, int num_rows, int k, float eps, float* stats, isf_stream_t stream) {

@@ -428,8 +428,10 @@ class ISFusionPtsPath(nn.Module):
 
 class ISFusionDetector(ISFusionPtsPath):
     """The whole model of isfusion.py: the camera branch (img_backbone = SwinTransformer, img_neck =
-    GeneralizedLSSFPN, swin.py / generalized_lss.py) in front of ISFusionPtsPath.  Images in, boxes out; the
-    ISFusionPtsPath methods keep their signatures (they take camera features).  Inference only."""
+    GeneralizedLSSFPN, swin.py / generalized_lss.py) in front of ISFusionPtsPath.  Images in, boxes out (eval mode) or
+    losses out (forward_train); the ISFusionPtsPath methods keep their signatures (they take camera features).
+    Training needs detach=True, as the shipped config sets it: the backbone runs its training-mode forward (stochastic
+    depth) without a backward, the neck trains."""
 
     def __init__(self, img_backbone=None, img_neck=None, detach=False, **pts_kwargs):
         super().__init__(**pts_kwargs)
@@ -464,6 +466,12 @@ class ISFusionDetector(ISFusionPtsPath):
             meta.update(input_shape=input_shape)
         assert img.dim() == 5
         B, N, C, H, W = img.size()
+        if self.training:
+            if not self.detach:
+                raise NotImplementedError("ISFusionDetector: training with detach=False needs the Swin backbone's "
+                                          "backward, which is not built (the shipped config has detach=True)")
+            img_feats = self.img_backbone.forward_train(img.reshape(B * N, C, H, W).float())
+            return self.img_neck.forward_train(img_feats) if self.with_img_neck else img_feats
         img_feats = self.img_backbone(img.reshape(B * N, C, H, W).float())
         if self.detach:
             img_feats = [f.detach() for f in img_feats]
@@ -476,9 +484,14 @@ class ISFusionDetector(ISFusionPtsPath):
         img_feats = self.extract_img_feat(img, img_metas)
         return img_feats, self.extract_pts_feat(points, img_feats, img_metas, **kwargs)
 
-    def forward_train(self, *args, **kwargs):
-        raise NotImplementedError("ISFusionDetector.forward_train: training the camera branch (neck backward, "
-                                  "DropPath in the backbone) is not implemented; train ISFusionPtsPath on features")
+    def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None, gt_labels=None,
+                      gt_bboxes=None, img=None, proposals=None, gt_bboxes_ignore=None, **kwargs):
+        """isfusion.py:184-241: camera branch (extract_img_feat, training mode) -> the points branch's forward_train on
+        its features -> the loss dict of the points branch.  The config has no image head, so forward_img_train adds
+        nothing (gt_labels / gt_bboxes / proposals / gt_bboxes_ignore are accepted and unused)."""
+        assert self.training, "call .train() first (eval mode runs the inference engine)"
+        img_feats = self.extract_img_feat(img, img_metas)
+        return ISFusionPtsPath.forward_train(self, points, img_feats, img_metas, gt_bboxes_3d, gt_labels_3d, **kwargs)
 
     @torch.no_grad()
     def simple_test(self, points, img_metas, img=None, rescale=False, **kwargs):

@@ -1,5 +1,7 @@
 """Camera backbone: the reference's SwinTransformer (mmdet3d/models/backbones/swin.py, with PatchEmbed / PatchMerging of
-models/utils/transformer.py) on the HIP kernels of isf_swin.hip.  Inference only (eval mode).
+models/utils/transformer.py) on the HIP kernels of isf_swin.hip.  ``forward`` is the eval-mode forward;
+``forward_train`` is the training-mode forward (stochastic depth) without a backward: the shipped config detaches the
+backbone's outputs (``detach=True``, isfusion.py:76-77), so training needs no gradient through it.
 
 Same sub-module names, parameters and buffers as the reference, so an IS-Fusion checkpoint's ``img_backbone.*`` loads
 with ``strict=True`` (187 entries for configs/isfusion/isfusion_0075voxel.py, mmcv FFN naming ``ffn.layers.0.0`` /
@@ -33,8 +35,10 @@ def _a(mode, x, *, ldx=0, n=0, c=0, h=0, w=0, x2=None, c2=0, h2=0, w2=0, stats=N
     return s, (x, x2, stats, g, b)
 
 
-def gemm(a, rows, k, pl, *, scale=None, shift=None, act=ACT_NONE, residual=None, out_nchw=None):
-    """isf_swin_gemm: act((A W^T) * scale + shift) + residual -> [rows, N], or [B, N, H, W] for out_nchw=(B, H, W)"""
+def gemm(a, rows, k, pl, *, scale=None, shift=None, act=ACT_NONE, residual=None, out_nchw=None, row_scale=None):
+    """isf_swin_gemm: act((A W^T) * scale + shift) + residual -> [rows, N], or [B, N, H, W] for out_nchw=(B, H, W).
+    row_scale [samples] (isf_swin_gemm_rowscale): the branch output of sample r // (rows // samples) is multiplied by
+    row_scale[sample] before the residual is added (DropPath)."""
     s, keep = a
     N = pl.out_features
     dev = keep[0].device
@@ -47,6 +51,13 @@ def gemm(a, rows, k, pl, *, scale=None, shift=None, act=ACT_NONE, residual=None,
         ldy, y_hw = N, 0
     if residual is not None:
         assert residual.is_contiguous() and tuple(residual.shape) == (rows, N)
+    if row_scale is not None:
+        assert row_scale.dtype == torch.float32 and row_scale.is_contiguous() and rows % row_scale.numel() == 0
+        _lib.check(_lib.load().isf_swin_gemm_rowscale(ctypes.byref(s), rows, k, _lib.ptr(pl.packed), N, _lib.ptr(scale),
+                                                      _lib.ptr(shift), act, _lib.ptr(residual), _lib.ptr(row_scale),
+                                                      rows // row_scale.numel(), _lib.ptr(y), ldy, y_hw,
+                                                      _lib.stream()), "isf_swin_gemm_rowscale")
+        return y
     _lib.check(_lib.load().isf_swin_gemm(ctypes.byref(s), rows, k, _lib.ptr(pl.packed), N, _lib.ptr(scale),
                                          _lib.ptr(shift), act, _lib.ptr(residual), _lib.ptr(y), ldy, y_hw,
                                          _lib.stream()), "isf_swin_gemm")
@@ -92,8 +103,8 @@ def _ln_only(norm_cfg):
 
 
 def _training_error(what):
-    return NotImplementedError(f"{what}: training-mode forward (DropPath, dropout, backward) is not implemented; "
-                               "the camera branch runs in eval() mode only")
+    return NotImplementedError(f"{what}: forward() is the eval() mode forward; in training mode call forward_train "
+                               "(stochastic depth / batch-statistics BatchNorm)")
 
 
 class WindowMSA(nn.Module):
@@ -181,8 +192,10 @@ class SwinBlock(nn.Module):
                     fc1=PackedLinear(l1.weight), fc1_b=l1.bias.detach(), fc2=PackedLinear(l2.weight),
                     fc2_b=l2.bias.detach())
 
-    def run(self, p, x, B, H, W):
-        """x: token rows [B*H*W, C] -> the block's output rows"""
+    def run(self, p, x, B, H, W, keep=(None, None)):
+        """x: token rows [B*H*W, C] -> the block's output rows.  keep: per-image DropPath factors [B] (keep / keep_prob)
+        of the attention and the FFN branch, or None: the branch output is multiplied by them after window reverse /
+        un-shift and before the identity is added (swin.py:251, mmcv FFN)."""
         M, C = x.shape
         m = self.attn.w_msa
         ln1 = (self.norm1.weight.detach(), self.norm1.bias.detach())
@@ -190,12 +203,12 @@ class SwinBlock(nn.Module):
         qkv = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln1), M, C, p["qkv"], shift=p["qkv_b"])
         att = window_attention(qkv, p["qkv_b"], p["rel"], B, H, W, C, m.num_heads, self.attn.window_size,
                                self.attn.shift_size, m.scale)
-        x = gemm(_a(_lib.SWIN_A_ROWS, att, ldx=C), M, C, p["proj"], shift=p["proj_b"], residual=x)
+        x = gemm(_a(_lib.SWIN_A_ROWS, att, ldx=C), M, C, p["proj"], shift=p["proj_b"], residual=x, row_scale=keep[0])
         ln2 = (self.norm2.weight.detach(), self.norm2.bias.detach())
         st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm2.eps)
         F = self.ffn.feedforward_channels
         h = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln2), M, C, p["fc1"], shift=p["fc1_b"], act=ACT_GELU)
-        return gemm(_a(_lib.SWIN_A_ROWS, h, ldx=F), M, F, p["fc2"], shift=p["fc2_b"], residual=x)
+        return gemm(_a(_lib.SWIN_A_ROWS, h, ldx=F), M, F, p["fc2"], shift=p["fc2_b"], residual=x, row_scale=keep[1])
 
 
 class PatchEmbed(nn.Module):
@@ -308,11 +321,13 @@ class SwinTransformer(nn.Module):
         assert strides[0] == patch_size, "Use non-overlapping patch embed."
         self.out_indices = out_indices
         self.use_abs_pos_embed = use_abs_pos_embed
+        self.drop_rate, self.attn_drop_rate = drop_rate, attn_drop_rate
         self.patch_embed = PatchEmbed(in_channels, embed_dims, patch_size, strides[0],
                                       norm_cfg if patch_norm else None)
         self.drop_after_pos = nn.Dropout(p=drop_rate)
         total = sum(depths)
         dpr = [x.item() for x in torch.linspace(0, drop_path_rate, total)]
+        self.drop_path_rates = dpr          # per block, in block order
         self.stages = nn.ModuleList()
         c = embed_dims
         for i in range(len(depths)):
@@ -340,6 +355,40 @@ class SwinTransformer(nn.Module):
     def forward(self, x):
         if self.training:
             raise _training_error("SwinTransformer")
+        return self._run(x, None)
+
+    def drop_layers(self):
+        """DropPath rates of the layers that draw a mask, in mask-row order: by block, the attention branch before the
+        FFN; a block whose rate is 0 draws nothing (mmcv DropPath returns its input)"""
+        return [r for r in self.drop_path_rates if r > 0.0 for _ in range(2)]
+
+    @torch.no_grad()
+    def forward_train(self, x, drop_keep=None):
+        """Training-mode forward: forward()'s kernels with stochastic depth (mmcv DropPath: per image keep =
+        floor(keep_prob + U[0, 1)), branch output * keep / keep_prob).  No backward: the maps come back without a
+        gradient (the shipped config detaches them).  drop_keep: [len(drop_layers()), N] of 0 / 1, one row per drawing
+        layer in drop_layers() order; None draws every mask with ONE torch.rand call on the device (mmcv's random
+        stream is not reproduced draw for draw)."""
+        assert self.training, "call .train() first (forward() is the eval-mode forward)"
+        if self.drop_rate != 0.0 or self.attn_drop_rate != 0.0:
+            raise NotImplementedError(f"SwinTransformer.forward_train: drop_rate {self.drop_rate} / attn_drop_rate "
+                                      f"{self.attn_drop_rate} (only DropPath is built)")
+        _lib.require_cuda(x)
+        rates = self.drop_layers()
+        if not rates:
+            return self._run(x, None)
+        N = x.shape[0]
+        keep_prob = 1.0 - torch.tensor(rates, dtype=torch.float32, device=x.device)[:, None]
+        if drop_keep is None:
+            drop_keep = torch.floor(keep_prob + torch.rand(len(rates), N, device=x.device))
+        else:
+            _lib.require_cuda(drop_keep)
+            if tuple(drop_keep.shape) != (len(rates), N):
+                raise ValueError(f"drop_keep {tuple(drop_keep.shape)}: need {(len(rates), N)}")
+        return self._run(x, (drop_keep.to(torch.float32) / keep_prob).contiguous())
+
+    def _run(self, x, scales):
+        """scales: [len(drop_layers()), N] DropPath factors (keep / keep_prob) or None"""
         _lib.require_cuda(x)
         assert x.dim() == 4, x.shape
         x = x.float().contiguous()
@@ -347,9 +396,14 @@ class SwinTransformer(nn.Module):
         p = self._packed(x.device)
         t, (H, W) = self.patch_embed.run(p["patch"], x)
         outs = []
+        row = 0
         for i, stage in enumerate(self.stages):
             for blk, bp in zip(stage.blocks, p["blocks"][i]):
-                t = blk.run(bp, t, N, H, W)
+                keep = (None, None)
+                if scales is not None and blk.attn.drop_path_rate > 0.0:
+                    keep = (scales[row], scales[row + 1])
+                    row += 2
+                t = blk.run(bp, t, N, H, W, keep)
             if i in self.out_indices:
                 outs.append(layernorm(t, getattr(self, f"norm{i}"), out_nchw=(N, H, W)))
             if stage.downsample is not None:

@@ -6,6 +6,12 @@
   * ISFusionDetector.simple_test (images -> boxes) against ISFusionPtsPath.simple_test on precomputed camera features
 
     python tools/camera_bench.py [--steps 10] [--warmup 3] [--points 300000]
+    python tools/camera_bench.py --train [--steps 10] [--warmup 3] [--runs 3]
+
+--train: one camera training step instead -- SwinTransformer.forward_train (stochastic depth, no backward: detach=True)
++ GeneralizedLSSFPN.forward_train + the neck's backward from a gradient on the stride-16 output (what Point-to-Grid
+sends back), against the float32 stock-torch composition of tests/camera_train_common.py (same masks, autograd) on the
+same GPU, each measured --runs times; plus the single kernels of the lateral step's backward at the shipped level-1 size.
 
 Prints one JSON line per measurement (ms per call, mean over --steps)."""
 import argparse
@@ -37,13 +43,86 @@ def timed(fn, steps, warmup):
     return a.elapsed_time(b) / steps
 
 
+def train_bench(a, dev):
+    import camera_train_common as CT
+    from isfusion_amd import _lib, generalized_lss as gl
+    from isfusion_amd.generalized_lss import GeneralizedLSSFPN
+    from isfusion_amd.swin import SwinTransformer
+    bb, nk = SwinTransformer(**CC.BACKBONE), GeneralizedLSSFPN(**CC.NECK)
+    bb.load_state_dict(CC.seeded_module_state(bb, 4101))
+    nk.load_state_dict(CC.seeded_module_state(nk, 4202))
+    bb, nk = bb.to(dev).train(), nk.to(dev).train()
+    B, H, W = 2, 384, 1056
+    flat = CC.images(3, B * 6, H, W).to(dev)
+    keep = CT.fixed_drop_keep(9, B * 6).to(dev)
+    up = torch.randn(B * 6, 256, H // 16, W // 16, device=dev) * 1e-3
+
+    def hip_step():
+        for p in nk.parameters():
+            p.grad = None
+        outs = nk.forward_train(bb.forward_train(flat, drop_keep=keep))
+        outs[1].backward(up)
+
+    sd = CC.cast(bb.state_dict(), torch.float32, dev)
+    nd = CT.leaf_params(nk.state_dict(), torch.float32, dev)
+
+    def torch_step():
+        for v in nd.values():
+            v.grad = None
+        with torch.no_grad():
+            feats = CT.swin_forward_train(sd, flat, keep)
+        outs = CT.neck_forward_train(nd, feats)
+        outs[1].backward(up)
+
+    for run in range(a.runs):
+        ms = timed(hip_step, a.steps, a.warmup)
+        print(json.dumps(dict(what="camera_train_step", impl="hip", images=B * 6, hw=[H, W], run=run, ms=round(ms, 3))))
+        ms = timed(torch_step, a.steps, a.warmup)
+        print(json.dumps(dict(what="camera_train_step", impl="torch_fp32", images=B * 6, hw=[H, W], run=run,
+                              ms=round(ms, 3))))
+    ms = timed(lambda: bb.forward_train(flat, drop_keep=keep), a.steps, a.warmup)
+    print(json.dumps(dict(what="backbone_forward_train", impl="hip", images=B * 6, ms=round(ms, 3))))
+    with torch.no_grad():
+        ms = timed(lambda: CT.swin_forward_train(sd, flat, keep), a.steps, a.warmup)
+    print(json.dumps(dict(what="backbone_forward_train", impl="torch_fp32", images=B * 6, ms=round(ms, 3))))
+    feats = bb.forward_train(flat, drop_keep=keep)
+
+    def neck_hip():
+        for p in nk.parameters():
+            p.grad = None
+        nk.forward_train(feats)[1].backward(up)
+
+    def neck_torch():
+        for v in nd.values():
+            v.grad = None
+        CT.neck_forward_train(nd, feats)[1].backward(up)
+
+    print(json.dumps(dict(what="neck_forward_backward", impl="hip", ms=round(timed(neck_hip, a.steps, a.warmup), 3))))
+    print(json.dumps(dict(what="neck_forward_backward", impl="torch_fp32",
+                          ms=round(timed(neck_torch, a.steps, a.warmup), 3))))
+    # the lateral step's backward kernels at the shipped level-1 size: fine 24 x 66 x 384, coarse 12 x 33 x 768, N = 256
+    n, (h, w), (h2, w2) = B * 6, (H // 16, W // 16), (H // 32, W // 32)
+    g, sc = _lib.grad_rescale(up.permute(0, 2, 3, 1).reshape(n * h * w, 256).contiguous())
+    fine, coarse = feats[1], feats[2]
+    g2 = gl.upsample_rows_adjoint(g, n, h, w, h2, w2)
+    for what, fn in (("upsample_rows_adjoint", lambda: gl.upsample_rows_adjoint(g, n, h, w, h2, w2)),
+                     ("rows_weight_grad fine [R 19008, N 256, K 384]", lambda: gl.rows_weight_grad(g, fine, sc[1:])),
+                     ("rows_weight_grad coarse [R 4752, N 256, K 768]", lambda: gl.rows_weight_grad(g2, coarse, sc[1:])),
+                     ("torch fp32 g^T x fine (rows)", lambda: g.t().matmul(fine.permute(0, 2, 3, 1).reshape(-1, 384)))):
+        print(json.dumps(dict(what=what, ms=round(timed(fn, a.steps * 5, a.warmup), 4))))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--points", type=int, default=300000)
+    ap.add_argument("--train", action="store_true", help="time one camera training step (forward_train + neck backward)")
+    ap.add_argument("--runs", type=int, default=3, help="--train: repetitions of the headline measurement")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.train:
+        return train_bench(a, dev)
     det = ISFusionDetector(img_backbone=dict(type="SwinTransformer", **CC.BACKBONE),
                            img_neck=dict(type="GeneralizedLSSFPN", **CC.NECK), detach=True).eval()
     det._lidar.randomize_weights_(0).randomize_bn_(1)

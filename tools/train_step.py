@@ -2,7 +2,7 @@
 all-reduce over xGMI on the GRADIENTS only -- the forward has no collective):
 
     python tools/train_step.py --gpus N [--batch 2] [--points 60000] [--steps 3] [--bf16] [--autocast]
-                               [--optimizer sgd|config] [--max-iters M] [--gt-paste]
+                               [--optimizer sgd|config] [--max-iters M] [--gt-paste] [--camera]
 
 starts N ranks by itself (isfusion_amd.launch.self_launch: a re-exec under torch.distributed.run on 127.0.0.1; fewer
 than N visible GPUs is an error) -- the reference's tools/run-nus.sh:11-13; under a launcher it runs as the rank it is:
@@ -19,7 +19,13 @@ kernels) against the synthetic scenes' boxes (synthetic.scene_boxes).  Prints on
 --gt-paste (with --loss detection) puts ObjectSampleV2 in front of every step: a small database built from other
 synthetic scenes' boxes, one isfusion_amd.gt_paste plan per frame, and the points through
 MultiSweepPointLoader(paste=...) (isf_assemble_points_paste); the step then trains on the pasted points and the
-concatenated boxes.  Also runs on a single GPU without torchrun (world size 1)."""
+concatenated boxes.  --camera trains the whole ISFusionDetector from images (6 synthetic views per frame in the shape
+MultiViewImageLoader hands over, [B, 6, 3, 384, 1056] float32) instead of precomputed camera features: the Swin backbone's
+training-mode forward (stochastic depth, no backward: detach=True), the LSS-FPN neck with its backward, then the same
+point-cloud path; --loss detection goes through ISFusionDetector.forward_train.  The backbone and the neck's level-0
+convs receive no gradient (only the stride-16 map reaches Point-to-Grid), so --camera FREEZES those parameters
+(requires_grad False) rather than asking DistributedDataParallel for find_unused_parameters: no per-step graph search,
+and the optimizer skips them.  Also runs on a single GPU without torchrun (world size 1)."""
 import argparse
 import json
 import os
@@ -87,6 +93,10 @@ def main():
     ap.add_argument("--gt-paste", action="store_true",
                     help="ObjectSampleV2 in front of every step (needs --loss detection): a synthetic database, one "
                          "GT-paste plan per frame, points through isf_assemble_points_paste")
+    ap.add_argument("--camera", action="store_true",
+                    help="train ISFusionDetector from images (Swin forward_train + LSS-FPN forward_train / backward) instead "
+                         "of precomputed camera features; the parameters that get no gradient -- img_backbone.* and the "
+                         "neck's level-0 convs -- are frozen (requires_grad False), not left to find_unused_parameters")
     a = ap.parse_args()
     if a.gt_paste and a.loss != "detection":
         ap.error("--gt-paste pastes ground truth: it needs --loss detection")
@@ -105,7 +115,26 @@ def main():
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29540")
     dist.init_process_group(a.backend, rank=rank, world_size=world)  # "nccl" IS RCCL on ROCm
-    net = ISFusionPtsPath().train()
+    if a.camera:
+        from isfusion_amd.detector import ISFusionDetector
+        # img_backbone / img_neck / detach of configs/isfusion/isfusion_0075voxel.py:17-45
+        net = ISFusionDetector(
+            img_backbone=dict(type="SwinTransformer", embed_dims=96, depths=[2, 2, 6, 2], num_heads=[3, 6, 12, 24],
+                              window_size=7, mlp_ratio=4, qkv_bias=True, qk_scale=None, drop_rate=0.0, attn_drop_rate=0.0,
+                              drop_path_rate=0.2, patch_norm=True, out_indices=[1, 2, 3], with_cp=False,
+                              convert_weights=False),
+            img_neck=dict(type="GeneralizedLSSFPN", in_channels=[192, 384, 768], out_channels=256, start_level=0,
+                          num_outs=3), detach=True).train()
+        g = torch.Generator().manual_seed(4100)
+        with torch.no_grad():                                        # O(1) activations through the 12 blocks
+            for name, p in list(net.img_backbone.named_parameters()) + list(net.img_neck.named_parameters()):
+                if p.dim() > 1 and not name.endswith("relative_position_bias_table"):
+                    p.copy_(torch.randn(p.shape, generator=g) * (p[0].numel() ** -0.5))
+        for name, p in net.named_parameters():
+            if name.startswith(("img_backbone.", "img_neck.lateral_convs.0.", "img_neck.fpn_convs.0.")):
+                p.requires_grad_(False)                              # no gradient reaches them (module docstring)
+    else:
+        net = ISFusionPtsPath().train()
     net._lidar.randomize_weights_(0).randomize_bn_(1)
     for mod, seed in ((net.fusion_encoder, 100), (net.pts_backbone, 200), (net.pts_neck, 250)):
         mod.load_state_dict(seeded_state_dict(mod, seed))
@@ -125,6 +154,11 @@ def main():
             self.m = m
 
         def forward(self, pts, img, metas, kw, gt=None):
+            if a.camera and gt is not None:
+                return self.m.forward_train(points=pts, img_metas=metas, gt_bboxes_3d=gt[0], gt_labels_3d=gt[1],
+                                            img=img, **kw)
+            if a.camera:
+                img = self.m.extract_img_feat(img, metas)
             if gt is not None:
                 return self.m.forward_train(pts, img, metas, gt[0], gt[1], **kw)
             return self.m.forward_train_pts(pts, img, metas, **kw)
@@ -164,7 +198,11 @@ def main():
                                                   [torch.from_numpy(r["gt_labels_3d"]).to(dev) for r in results]),
                     sum(len(p.objects) for p in plans if p is not None))
     inp = synthetic.fusion_inputs(7 + rank, a.batch)
-    img = tuple(torch.from_numpy(x).to(dev).to(torch.bfloat16 if a.bf16 else torch.float32) for x in inp["img_feats"])
+    if a.camera:
+        h, w = inp["input_shape"]
+        img = torch.randn(a.batch, 6, 3, h, w, generator=torch.Generator().manual_seed(70 + rank)).to(dev)
+    else:
+        img = tuple(torch.from_numpy(x).to(dev).to(torch.bfloat16 if a.bf16 else torch.float32) for x in inp["img_feats"])
     kw = dict(lidar2img=torch.from_numpy(inp["lidar2img"]), img_aug_matrix=torch.from_numpy(inp["img_aug_matrix"]),
               lidar_aug_matrix=torch.from_numpy(inp["lidar_aug_matrix"]))
     metas = [dict(input_shape=inp["input_shape"]) for _ in range(a.batch)]
@@ -199,7 +237,7 @@ def main():
     dt = (time.perf_counter() - t0) / max(a.steps, 1)
     per_step = [round(marks[i].elapsed_time(marks[i + 1]), 1) for i in range(a.steps + 1)]   # [0] = the warm-up step
     if rank == 0:
-        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss,
+        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss, "camera": a.camera,
                           "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses],
                           "optimizer": a.optimizer, **({"grad_norm": [round(n, 6) for n in norms]} if recipe else {}),
                           **({"gt_paste_objects": pasted} if paste is not None else {})}))
