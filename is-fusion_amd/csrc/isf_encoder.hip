@@ -196,18 +196,9 @@ int sparse_to_dense_bev_impl(Arena& a, const void* feats, int fmt, const int32_t
   dim3 grid(ceil_div(W, kDenseX), H, B);
   ISF_REQUIRE(!skip_empty || (fmt == 1 && occ_in && (long long)H * W < (1ll << 30)), ISF_ERR_ARG,
               "dense: two passes need split rows + index");
-  if (fmt == 1 && skip_empty)
-    hipLaunchKernelGGL((dense_bev_kernel<1, true>), grid, dim3(256), 0, st, feats, C, D, H, W, occ.bits, occ.prefix,
-                       perm, out);
-  else if (fmt == 1)
-    hipLaunchKernelGGL(dense_bev_kernel<1>, grid, dim3(256), 0, st, feats, C, D, H, W, occ.bits, occ.prefix,
-                       perm, out);
-  else if (fmt == 2)
-    hipLaunchKernelGGL(dense_bev_kernel<2>, grid, dim3(256), 0, st, feats, C, D, H, W, occ.bits, occ.prefix,
-                       perm, out);
-  else
-    hipLaunchKernelGGL(dense_bev_kernel<0>, grid, dim3(256), 0, st, feats, C, D, H, W, occ.bits, occ.prefix,
-                       perm, out);
+  const auto kernel = fmt == 1 ? (skip_empty ? dense_bev_kernel<1, true> : dense_bev_kernel<1>)
+                                : (fmt == 2 ? dense_bev_kernel<2> : dense_bev_kernel<0>);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, feats, C, D, H, W, occ.bits, occ.prefix, perm, out);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
@@ -306,115 +297,34 @@ struct StageTables {
   int32_t* ucount = nullptr;
 };
 
-struct LevelState {
-  int shape[3];
-  int n;                  // active rows (host)
-  const int32_t* coors;   // [n,4] sorted
-  OccIndex occ;
-  bool has_occ;
-  // SubM rulebook cache for this level (all SubM convs of one level share the active set)
-  int cache_ks[3];
-  int32_t* cache_nbr;
-  int cache_stride;
-  long long cache_pairs;
-  StageTables cache_stage;   // staging tables of cache_nbr (slots == nullptr: not built)
-  const int32_t* cache_order;   // tile order / table of cache_nbr for a (cache_order_cin -> cache_order_cout) launch, or nullptr
-  int cache_order_cin, cache_order_cout;
-  int cache_order_kind;         // kOrderPerm | kOrderTable | kOrderParts
-  const uint32_t* cache_lmask;  // non-null: cache_nbr is LINE-COMPRESSED (lines [ks0 * ks1][stride]) with these tap masks
-  ConvCuPlan cache_cu;          // unit plan of cache_nbr for the one-workgroup-per-CU kernel (n_out == 0: not built)
-  const int32_t* cache_rowmap;  // ROW SORT of cache_nbr (conv_row_sort_impl): position -> row, or nullptr
-  const int32_t* cache_nbr_sorted;   // cache_nbr by position
-  const uint32_t* cache_lmask_sorted;   // cache_lmask by position (line-compressed tables)
-  int cache_sort_part_rows;     // the launch plan's rows per part the sort was cut for
+// ONE NEIGHBOUR TABLE and everything derived from it, all built behind it on the geometry stream.  The SubM convs of a
+// level with one kernel size share LevelState::subm, a strided conv has a table of its own; NbrTable{} is the reset.
+struct NbrTable {
+  int32_t* nbr = nullptr;   // [K][stride]
+  int stride = 0, rows = 0;
+  int ks[3] = {0, 0, 0};
+  const uint32_t* lmask = nullptr;   // non-null: nbr is LINE-COMPRESSED (lines [ks0 * ks1][stride]) with these tap masks
+  StageTables stage;                 // staging tables (slots == nullptr: not built)
+  const int32_t* order = nullptr;    // tile order / tile table / part table of an (order_cin -> order_cout) launch, or nullptr
+  int order_cin = 0, order_cout = 0;
+  int order_kind = kOrderPerm;       // kOrderPerm | kOrderTable | kOrderParts
+  ConvCuPlan cu;                     // unit plan for the one-workgroup-per-CU kernel (n_out == 0: not built)
+  const int32_t* rowmap = nullptr;   // ROW SORT (conv_row_sort_impl): position -> row, or nullptr
+  const int32_t* nbr_sorted = nullptr;      // nbr by position
+  const uint32_t* lmask_sorted = nullptr;   // lmask by position
+  int sort_part_rows = 0;            // the launch plan's rows per part the sort was cut for
+  int pair_slot = 0;                 // the table's pair total lives in pair_counts[pair_slot]
+  int K() const { return ks[0] * ks[1] * ks[2]; }
 };
 
-// unit plan of one neighbour table (isf_spconv_cu.hip), built behind it on the geometry stream
-static int build_cu_plan(Arena& a, const int32_t* nbr, int stride, int K, int n_out, ConvCuPlan* plan, hipStream_t sg,
-                         int cap = 16) {
-  int32_t* buf = nullptr;
-  ISF_TRY(a.alloc_n(&buf, conv_cu_plan_ints(n_out)));
-  return conv_cu_plan_impl(nbr, stride, K, n_out, buf, plan, sg, cap);
-}
-
-// tile order / tile table of one conv launch over a neighbour table, built behind the table on the geometry stream.  A
-// launch of the tile kernel that is resident in one round gets a TILE TABLE (conv16_table_part: the groups dealt to the
-// compute units by equal work; *kind = kOrderTable, run the conv with mode | kConvModeTileTable); the LDS-DMA kernel's launches keep the
-// permutation of uniform tiles (conv16_tile_order_impl).  A launch of SEVERAL ROUNDS (uniform tiles) gets a PART TABLE
-// (conv16_part_table_impl: equal-work XCD parts, heavy tiles first -- in tile order when !order_ok; *kind = kOrderParts, run
-// the conv with mode | kConvModePartTable) when parts_ok.  *order stays nullptr when none applies.
-static int build_tile_order(Arena& a, const isf_conv_layer& ly, int K, const int32_t* nbr, int stride, int n_out,
-                            int mode, bool dma, const int32_t** order, hipStream_t sg, const uint32_t* lmask = nullptr,
-                            int* kind = nullptr, bool tables = true,
-                            const int32_t* coors_out = nullptr /* [n_out][4] (b, z, y, x) of the output rows */, int band = 0,
-                            bool order_ok = true, bool parts_ok = false) {
-  *order = nullptr;
-  if (kind) *kind = kOrderPerm;
-  const ConvKernel kernel = dma ? kConvKernelDma : kConvKernelTile;
-  Conv16LaunchInfo info;
-  if (parts_ok && kind && n_out > 0) {   // the launch's uniform plan: several rounds?
-    ISF_TRY(conv16_launch_info(kernel, ly.c_in, ly.c_out, n_out, mode | ISF_CONV_MODE_UNIFORM_TILES, &info));
-    if (conv16_parts_apply(info)) {
-      const int parts = conv16_order_parts(info), T = conv16_parts_tiles(info.full, parts);
-      int32_t *work = nullptr, *table = nullptr;
-      ISF_TRY(a.alloc_n(&work, (size_t)2 * T));
-      ISF_TRY(a.alloc_n(&table, (size_t)conv16_part_table_ints(parts, conv16_parts_cap(T, parts))));
-      ISF_TRY(conv16_part_table_impl(nbr, lmask, stride, K, n_out, ly.c_in, ly.c_out, info, !order_ok, work, table, sg,
-                                     (mode & ISF_CONV_MODE_UNIFORM_TILES) != 0));
-      *order = table;
-      *kind = kOrderParts;
-      return ISF_OK;
-    }
-  }
-  if (!order_ok) return ISF_OK;
-  ISF_TRY(conv16_launch_info(kernel, ly.c_in, ly.c_out, n_out, mode, &info));
-  if (!dma && kind && tables && !lmask && conv16_table_applies(info) && n_out >= 16 * info.cus_per_xcd) {
-    const int ng = ceil_div(n_out, 16);
-    int32_t *masks = nullptr, *work = nullptr, *table = nullptr;
-    ISF_TRY(a.alloc_n(&masks, (size_t)ng));
-    ISF_TRY(a.alloc_n(&work, (size_t)ng));
-    ISF_TRY(a.alloc_n(&table, (size_t)conv16_table_ints(info)));
-    ISF_TRY(conv_group_masks_impl(nbr, stride, K, n_out, masks, work, sg));
-    ISF_TRY(conv16_tile_table_impl(work, n_out, info, table, sg));
-    *order = table;
-    *kind = kOrderTable;
-    return ISF_OK;
-  }
-  if (!conv16_order_applies(info)) {
-    // a launch of several rounds: its tiles band by band in y (conv16_band_order_kernel), so that the rows the dz = +-1
-    // taps gather are still in the XCD's L2
-    if (band > 0 && coors_out && conv16_band_order_applies(info)) {
-      int32_t* ord = nullptr;
-      ISF_TRY(a.alloc_n(&ord, (size_t)conv16_order_parts(info) * conv16_order_tiles(info)));
-      ISF_TRY(conv16_band_order_impl(coors_out, n_out, info, band, ord, sg));
-      *order = ord;
-    }
-    return ISF_OK;
-  }
-  const size_t n = (size_t)conv16_order_parts(info) * conv16_order_tiles(info);
-  int32_t *work = nullptr, *ord = nullptr;
-  ISF_TRY(a.alloc_n(&work, n));
-  ISF_TRY(a.alloc_n(&ord, n));
-  ISF_TRY(conv16_tile_order_impl(nbr, stride, K, n_out, info, work, ord, sg, lmask));
-  *order = ord;
-  return ISF_OK;
-}
-
-// staging tables of one neighbour table (isf_spconv_stage.hip), built behind it on the geometry stream
-static int build_stage_tables(Arena& a, const int32_t* nbr, int stride, int K, StageTables* t, hipStream_t sg) {
-  const int units = stride / isf_stage_unit_rows();
-  ISF_TRY(a.alloc_n(&t->slots, (size_t)K * stride));
-  ISF_TRY(a.alloc_n(&t->ulist, (size_t)units * isf_stage_unit_cap()));
-  ISF_TRY(a.alloc_n(&t->ucount, (size_t)units));
-  return stage_tables_impl(nbr, stride, K, t->slots, t->ulist, t->ucount, sg);
-}
-
-// LDS rows per 128-row tile a layer stages by default (0 = the gather kernel): measured choice per channel shape
-// (profiles/r03_*).
-static int default_stage_rows(const isf_conv_layer& ly) {
-  (void)ly;
-  return 0;
-}
+struct LevelState {
+  int shape[3] = {0, 0, 0};
+  int n = 0;                        // active rows (host)
+  const int32_t* coors = nullptr;   // [n,4] sorted
+  OccIndex occ;
+  bool has_occ = false;
+  NbrTable subm;                    // the level's shared SubM table (nbr == nullptr: none yet)
+};
 
 static int ensure_occ(Arena& a, LevelState& L, int B, hipStream_t st) {
   if (L.has_occ) return ISF_OK;
@@ -426,7 +336,7 @@ static int ensure_occ(Arena& a, LevelState& L, int B, hipStream_t st) {
 }
 
 // isf_encoder_options.diagnostic: what each bit selects, and what was measured with it, is recorded beside its ISF_ENC_DIAG_*
-// name in include/isf_hip.h.  sparse_encoder_forward_impl decodes it once, at its top.
+// name in include/isf_hip.h.  decode_encoder_options decodes it once per call.
 static constexpr int kKnockoutBits = ISF_ENC_DIAG_NO_GATHER | ISF_ENC_DIAG_NO_WEIGHTS | ISF_ENC_DIAG_NO_LOOP | ISF_ENC_DIAG_NO_SHARING;
 static constexpr int kDeepOptBits = ISF_CONV_MODE_STAGGER | ISF_CONV_MODE_R4_ISSUE | ISF_CONV_MODE_TWO_AHEAD | ISF_CONV_MODE_DEEP | kConvModeNarrowTiles;
 static constexpr struct { int diag, mode; } kDiagToConvMode[] = {
@@ -445,6 +355,364 @@ static constexpr int kEncDiagKnown =
     ISF_ENC_DIAG_DENSE_TABLES | ISF_ENC_DIAG_TILE_TABLES | ISF_ENC_DIAG_COUNTS_MEMCPY | ISF_ENC_DIAG_BAND_ORDER | ISF_ENC_DIAG_NO_ROW_SORT |
     ISF_ENC_DIAG_NARROW_ROW_SORT | ISF_ENC_DIAG_SORT_KEY_AB | ISF_ENC_DIAG_VFE_FP32_ROWS | ISF_ENC_DIAG_VOXELIZE_PER_FRAME |
     ISF_ENC_DIAG_BEV_ONE_PASS;
+static constexpr int kSortMinRows = 4096;   // (configs[2] at B = 2: 7.05 ms sorted from 4 096 rows up, 7.10 from 32 768, 7.10 unsorted)
+
+// f16x3 split MFMA when every layer was packed for it (and precision 1 does not override it), else fp32 MFMA
+static bool encoder_use16(const isf_conv_layer* layers, int num_layers, int precision) {
+  bool use16 = precision != 1;
+  for (int i = 0; i < num_layers; ++i)
+    use16 = use16 && layers[i].packed16 && sparse_conv_f16x3_supported(layers[i].c_in, layers[i].c_out);
+  return use16;
+}
+
+// isf_encoder_options, decoded and validated once per call
+struct EncoderKnobs {
+  int precision = 0;
+  int dg = 0;          // timing diagnostic of the conv kernels (they exist on the gather kernel only)
+  int conv_mode = 0;   // what every layer's launch starts from: a knock-out or f16 storage, | uniform tiles
+  int one_block = 0;   // for the 256-column layers
+  int deep_opts = 0;   // for 128 columns and more
+  bool chunk_split = false;
+  bool tile_order = true, dma_gather = true, line_tables = true, mailbox = true, row_sort = true;   // defaults a bit switches off
+  bool tile_tables = false, band_order = false, narrow_sort = false, cu_units = false;               // opt-ins
+  int sort_key = 1;    // conv_row_sort_impl: 1 = six coarse bits (one radix pass), 2 = coarse | in-plane taps
+  int cu_variant = 0, cu_cap = 16;   // isf_conv_cu_plan.variant and its unit shape
+  int stage_opt = 0;   // stage_rows: LDS rows a layer of stage_mask stages (0 and -1: the gather kernels)
+  unsigned stage_mask = 0;
+  int bev_format = 0;
+  bool use16 = false;          // encoder_use16
+  bool f16io = false;          // f16 rows between the layers
+  bool fp32_class = false;     // the split-precision kernels proper: the only ones the variants apply to
+  bool bev_two_pass = false;   // the fp32 BEV map of split rows in two passes (dense_bev_kernel): zeros early, on the geometry stream
+};
+
+static int decode_encoder_options(const isf_encoder_options* opt, const isf_conv_layer* layers, int num_layers, bool fp32_map,
+                                  EncoderKnobs* knobs) {
+  EncoderKnobs k;
+  const int diagnostic = opt ? opt->diagnostic : 0;
+  k.precision = opt ? opt->precision : 0;
+  k.dg = diagnostic & kKnockoutBits;
+  ISF_REQUIRE(k.precision >= 0 && k.precision <= 2 && diagnostic >= 0 && (diagnostic & ~kEncDiagKnown) == 0 &&
+                  (k.dg == 0 || conv_mode_is_knockout(k.dg) || k.dg == ISF_ENC_DIAG_NO_SHARING) && !(k.precision == 2 && k.dg != 0),
+              ISF_ERR_ARG, "sparse_encoder: options (precision %d, diagnostic %d)", k.precision, diagnostic);
+  int translated = 0;
+  for (const auto& t : kDiagToConvMode)
+    if (diagnostic & t.diag) translated |= t.mode;
+  k.f16io = k.precision == 2;
+  k.fp32_class = k.dg == 0 && !k.f16io;
+  k.conv_mode = (k.f16io ? ISF_CONV_MODE_F16_STORAGE : k.dg) | (translated & ISF_CONV_MODE_UNIFORM_TILES);
+  k.one_block = translated & (ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W);
+  k.deep_opts = translated & kDeepOptBits;
+  k.chunk_split = (translated & ISF_CONV_MODE_CHUNK_SPLIT) && k.fp32_class && k.one_block == 0 && k.deep_opts == 0;
+  auto on = [&](int bit) { return (diagnostic & bit) != 0; };
+  k.tile_order = !on(ISF_ENC_DIAG_LAUNCH_ORDER);
+  k.dma_gather = !on(ISF_ENC_DIAG_NARROW_GATHER);
+  k.line_tables = !on(ISF_ENC_DIAG_DENSE_TABLES);
+  k.mailbox = !on(ISF_ENC_DIAG_COUNTS_MEMCPY);
+  k.row_sort = !on(ISF_ENC_DIAG_NO_ROW_SORT);
+  k.tile_tables = on(ISF_ENC_DIAG_TILE_TABLES);
+  k.band_order = on(ISF_ENC_DIAG_BAND_ORDER);
+  k.narrow_sort = on(ISF_ENC_DIAG_NARROW_ROW_SORT);
+  k.cu_units = on(ISF_ENC_DIAG_CU_KERNEL);
+  k.sort_key = on(ISF_ENC_DIAG_SORT_KEY_AB) ? 2 : 1;
+  k.cu_variant = (diagnostic & ISF_ENC_DIAG_CU_VARIANT_MASK) >> ISF_ENC_DIAG_CU_VARIANT_SHIFT;
+  k.cu_cap = conv_cu_variant_cap(k.cu_variant);
+  k.stage_opt = opt ? opt->stage_rows : 0;
+  k.stage_mask = opt ? (unsigned)opt->stage_mask : 0u;
+  k.bev_format = opt ? opt->bev_format : 0;
+  ISF_REQUIRE(k.stage_opt >= -1, ISF_ERR_ARG, "sparse_encoder: stage_rows %d", k.stage_opt);
+  ISF_REQUIRE(num_layers > 0 && num_layers <= 32, ISF_ERR_ARG, "sparse_encoder: %d layers (1..32)", num_layers);
+  k.use16 = encoder_use16(layers, num_layers, k.precision);
+  k.bev_two_pass = !on(ISF_ENC_DIAG_BEV_ONE_PASS) && k.use16 && !k.f16io && k.bev_format == 0 && fp32_map;
+  *knobs = k;
+  return ISF_OK;
+}
+
+// what ONE LAYER runs on, decided on the host from the knobs, the layer list and the row count of the layer's table
+struct LayerPlan {
+  int K = 0, nx = 0;
+  int srows = 0;            // LDS rows this layer stages (0 = a gather kernel)
+  bool cu = false;          // 256-column layers: one workgroup per CU over units of equal work (isf_spconv_cu.hip)
+  bool dma = false;         // narrow layers: LDS-DMA gathers (isf_spconv_dma.hip)
+  int layer_mode = 0;       // the conv mode on the tile kernel, as the launch and everything planned for it see it
+  bool parts_ok = false;    // equal-work parts when the launch runs in several rounds
+  bool want_order = false;  // build_tile_order: a tile order / table, or a part table
+  bool lines = false;       // a table this layer builds is line-compressed
+  bool sort = false;        // ROW SORT (round 6): the rows are computed in the order of their tap masks
+  int sort_key = 1;
+  bool sort_full_key = false;   // a line-compressed table of the input level: all 27 mask bits decide
+  int part_rows = 0;        // sort: rows per part of this layer's launch plan
+};
+
+static int plan_layer(const EncoderKnobs& kn, const isf_conv_layer* layers, int i, int num_layers, int rows, LayerPlan* plan) {
+  const isf_conv_layer& ly = layers[i];
+  const bool subm = ly.conv_type == ISF_CONV_SUBM;
+  LayerPlan p;
+  p.K = ly.ksize[0] * ly.ksize[1] * ly.ksize[2];
+  p.nx = ly.ksize[2];
+  // the timing diagnostics and ISF_CONV_MODE_NO_SHARING exist on the gather kernel only: no staging, no LDS-DMA
+  if (kn.use16 && kn.fp32_class && kn.stage_opt > 0 && sparse_conv_f16x3_supported(ly.c_in, ly.c_out) &&
+      (kn.stage_mask == 0 || ((kn.stage_mask >> i) & 1u)))
+    p.srows = kn.stage_opt;
+  p.cu = kn.use16 && kn.cu_units && p.srows == 0 && kn.conv_mode == 0 && sparse_conv_cu_supported(ly.c_in, ly.c_out);
+  const bool plan_ok = kn.use16 && p.srows == 0 && !p.cu;   // the tile kernel or the LDS-DMA kernel
+  p.layer_mode = kn.conv_mode | (kn.fp32_class && ly.c_out >= 128 ? kn.deep_opts : 0) |
+                 (kn.chunk_split && plan_ok && ly.c_out == 256 && ly.c_in >= 128 ? ISF_CONV_MODE_CHUNK_SPLIT : 0);
+  p.dma = kn.use16 && kn.dma_gather && p.srows == 0 && kn.dg == 0 && sparse_conv_dma_supported(ly.c_in, ly.c_out);
+  // the uniform-tiles diagnostic keeps the equal-row parts (with the launch-order diagnostic: no table at all), and so do
+  // the opt-ins whose tables are cut for them (narrow row sort, band order)
+  p.parts_ok = plan_ok && kn.dg == 0 && !((kn.conv_mode & ISF_CONV_MODE_UNIFORM_TILES) && !kn.tile_order) && !kn.band_order &&
+               !(p.dma && kn.narrow_sort) && (p.dma || (p.layer_mode & (ISF_CONV_MODE_DEEP | ISF_CONV_MODE_CHUNK_SPLIT)) == 0);
+  p.want_order = (plan_ok && kn.tile_order) || p.parts_ok;
+  // a table may be line-compressed when every layer that reads it runs the LDS-DMA kernel: for a SubM table, all the SubM
+  // layers of this level with the same kernel (up to the next strided conv); for a strided conv, itself
+  p.lines = p.dma && kn.line_tables && kn.stage_opt <= 0 && (p.nx == 1 || p.nx == 3) && ly.ksize[0] * ly.ksize[1] <= 9;
+  for (int j = i; p.lines && subm && j < num_layers && layers[j].conv_type == ISF_CONV_SUBM; ++j) {
+    const isf_conv_layer& q = layers[j];
+    if (q.ksize[0] == ly.ksize[0] && q.ksize[1] == ly.ksize[1] && q.ksize[2] == ly.ksize[2] &&
+        !sparse_conv_dma_supported(q.c_in, q.c_out))
+      p.lines = false;
+  }
+  // row sort: deep layers on the tile kernel; SubM layers on the LDS-DMA kernel (full or line-compressed table) as an opt-in.
+  // (The f16-storage mode too: the sort only renames positions; its epilogue reads / writes through the row map.)  A strided
+  // conv sorts its own table (its rows want 10 of 27 taps, in many patterns: -12 % tile-taps, -26 % MFMA blocks at level 3
+  // on the benchmark geometry, profiles/r06_row_sort.txt) with the one-pass key.
+  const bool sort_mode_ok = kn.dg == 0 && kn.one_block == 0 && (kn.deep_opts & ~kConvModeNarrowTiles) == 0;
+  const bool sortable = kn.row_sort && plan_ok && p.K == 27 && sort_mode_ok && rows >= kSortMinRows;
+  p.sort = sortable && (subm ? (p.dma ? kn.narrow_sort : ly.c_out >= 128) : (!p.dma && ly.c_out >= 128));
+  p.sort_key = subm ? kn.sort_key : 1;
+  p.sort_full_key = true;   // the input level's rows have few, varied neighbours (6 of 27 on the benchmark geometry)
+  for (int j = 0; j < i; ++j) p.sort_full_key = p.sort_full_key && layers[j].conv_type == ISF_CONV_SUBM;
+  if (p.sort) {
+    Conv16LaunchInfo info;
+    ISF_TRY(conv16_launch_info(p.dma ? kConvKernelDma : kConvKernelTile, ly.c_in, ly.c_out, rows, p.dma ? kn.conv_mode : p.layer_mode,
+                               &info));
+    p.part_rows = info.part_rows;
+  }
+  *plan = p;
+  return ISF_OK;
+}
+
+// a level sorted for one launch plan serves only the layers whose plan is cut the same way; the others keep the plain table
+static bool sort_applies(const NbrTable& t, const LayerPlan& p) {
+  return p.sort && t.rowmap && p.part_rows == t.sort_part_rows;
+}
+
+// staging tables of a neighbour table (isf_spconv_stage.hip)
+static int build_stage_tables(Arena& a, NbrTable& t, hipStream_t sg) {
+  const int units = t.stride / isf_stage_unit_rows();
+  ISF_TRY(a.alloc_n(&t.stage.slots, (size_t)t.K() * t.stride));
+  ISF_TRY(a.alloc_n(&t.stage.ulist, (size_t)units * isf_stage_unit_cap()));
+  ISF_TRY(a.alloc_n(&t.stage.ucount, (size_t)units));
+  return stage_tables_impl(t.nbr, t.stride, t.K(), t.stage.slots, t.stage.ulist, t.stage.ucount, sg);
+}
+
+// row sort of a neighbour table for the launch plan of `p`; the plain table stays
+static int build_row_sort(Arena& a, NbrTable& t, const LayerPlan& p, hipStream_t sg) {
+  int32_t *rm = nullptr, *ns = nullptr;
+  ISF_TRY(a.alloc_n(&rm, (size_t)t.stride));
+  if (t.lmask) {
+    const int nl = t.ks[0] * t.ks[1];
+    uint32_t* lms = nullptr;
+    ISF_TRY(a.alloc_n(&ns, (size_t)nl * t.stride));
+    ISF_TRY(a.alloc_n(&lms, (size_t)t.stride));
+    ISF_TRY(conv_row_sort_lines_impl(a, t.nbr, t.lmask, t.stride, nl, t.rows, p.part_rows, p.sort_full_key, rm, ns, lms, sg));
+    t.lmask_sorted = lms;
+  } else {
+    ISF_TRY(a.alloc_n(&ns, (size_t)t.K() * t.stride));
+    ISF_TRY(conv_row_sort_impl(a, t.nbr, t.stride, t.K(), t.rows, p.part_rows, rm, ns, sg, p.sort_key));
+  }
+  t.rowmap = rm;
+  t.nbr_sorted = ns;
+  t.sort_part_rows = p.part_rows;
+  return ISF_OK;
+}
+
+// tile order / tile table of layer `ly`'s launch over a neighbour table (the sorted one when the sort applies).  A launch
+// of the tile kernel that is resident in one round gets a TILE TABLE (conv16_table_part: the groups dealt to the compute
+// units by equal work; kOrderTable, run the conv with mode | kConvModeTileTable); the LDS-DMA kernel's launches keep the
+// permutation of uniform tiles (conv16_tile_order_impl).  A launch of SEVERAL ROUNDS (uniform tiles) gets a PART TABLE
+// (conv16_part_table_impl: equal-work XCD parts, heavy tiles first -- in tile order without kn.tile_order; kOrderParts, run
+// the conv with mode | kConvModePartTable) when p.parts_ok.  t.order stays nullptr when none applies.
+static int build_tile_order(Arena& a, NbrTable& t, const LayerPlan& p, const EncoderKnobs& kn, const isf_conv_layer& ly,
+                            const LevelState& out /* the level of the table's rows */, hipStream_t sg) {
+  const bool sorted = sort_applies(t, p);
+  const int32_t* nbr = sorted ? t.nbr_sorted : t.nbr;
+  const uint32_t* lmask = sorted && t.lmask ? t.lmask_sorted : t.lmask;
+  const int K = t.K(), stride = t.stride, n_out = t.rows, mode = p.layer_mode;
+  t.order = nullptr;
+  t.order_kind = kOrderPerm;
+  t.order_cin = ly.c_in;
+  t.order_cout = ly.c_out;
+  const ConvKernel kernel = p.dma ? kConvKernelDma : kConvKernelTile;
+  Conv16LaunchInfo info;
+  if (p.parts_ok && n_out > 0) {   // the launch's uniform plan: several rounds?
+    ISF_TRY(conv16_launch_info(kernel, ly.c_in, ly.c_out, n_out, mode | ISF_CONV_MODE_UNIFORM_TILES, &info));
+    if (conv16_parts_apply(info)) {
+      const int parts = conv16_order_parts(info), T = conv16_parts_tiles(info.full, parts);
+      int32_t *work = nullptr, *table = nullptr;
+      ISF_TRY(a.alloc_n(&work, (size_t)2 * T));
+      ISF_TRY(a.alloc_n(&table, (size_t)conv16_part_table_ints(parts, conv16_parts_cap(T, parts))));
+      ISF_TRY(conv16_part_table_impl(nbr, lmask, stride, K, n_out, ly.c_in, ly.c_out, info, !kn.tile_order, work, table, sg,
+                                     (mode & ISF_CONV_MODE_UNIFORM_TILES) != 0));
+      t.order = table;
+      t.order_kind = kOrderParts;
+      return ISF_OK;
+    }
+  }
+  if (!kn.tile_order) return ISF_OK;
+  ISF_TRY(conv16_launch_info(kernel, ly.c_in, ly.c_out, n_out, mode, &info));
+  if (!p.dma && kn.tile_tables && !lmask && conv16_table_applies(info) && n_out >= 16 * info.cus_per_xcd) {
+    const int ng = ceil_div(n_out, 16);
+    int32_t *masks = nullptr, *work = nullptr, *table = nullptr;
+    ISF_TRY(a.alloc_n(&masks, (size_t)ng));
+    ISF_TRY(a.alloc_n(&work, (size_t)ng));
+    ISF_TRY(a.alloc_n(&table, (size_t)conv16_table_ints(info)));
+    ISF_TRY(conv_group_masks_impl(nbr, stride, K, n_out, masks, work, sg));
+    ISF_TRY(conv16_tile_table_impl(work, n_out, info, table, sg));
+    t.order = table;
+    t.order_kind = kOrderTable;
+    return ISF_OK;
+  }
+  if (!conv16_order_applies(info)) {
+    // a launch of several rounds: its tiles band by band in y (conv16_band_order_kernel), so that the rows the dz = +-1
+    // taps gather are still in the XCD's L2
+    if (kn.band_order && conv16_band_order_applies(info)) {
+      int32_t* ord = nullptr;
+      ISF_TRY(a.alloc_n(&ord, (size_t)conv16_order_parts(info) * conv16_order_tiles(info)));
+      ISF_TRY(conv16_band_order_impl(out.coors, n_out, info, std::max(8, out.shape[1] / 45), ord, sg));
+      t.order = ord;
+    }
+    return ISF_OK;
+  }
+  const size_t n = (size_t)conv16_order_parts(info) * conv16_order_tiles(info);
+  int32_t *work = nullptr, *ord = nullptr;
+  ISF_TRY(a.alloc_n(&work, n));
+  ISF_TRY(a.alloc_n(&ord, n));
+  ISF_TRY(conv16_tile_order_impl(nbr, stride, K, n_out, info, work, ord, sg, lmask));
+  t.order = ord;
+  return ISF_OK;
+}
+
+// unit plan of a neighbour table (isf_spconv_cu.hip)
+static int build_cu_plan(Arena& a, NbrTable& t, int cap, hipStream_t sg) {
+  int32_t* buf = nullptr;
+  ISF_TRY(a.alloc_n(&buf, conv_cu_plan_ints(t.rows)));
+  return conv_cu_plan_impl(t.nbr, t.stride, t.K(), t.rows, buf, &t.cu, sg, cap);
+}
+
+// the neighbour table of layer `ly`: rows of level `out` (SubM: out is in), neighbours in level `in`, whose index exists
+static int build_nbr_table(Arena& a, const LevelState& in, const LevelState& out, const isf_conv_layer& ly, bool lines,
+                           int pair_slot, unsigned long long* pair_count, hipStream_t sg, NbrTable* t) {
+  const bool subm = ly.conv_type == ISF_CONV_SUBM;
+  *t = NbrTable{};
+  t->stride = isf_nbr_stride(out.n);
+  t->rows = out.n;
+  for (int j = 0; j < 3; ++j) t->ks[j] = ly.ksize[j];
+  t->pair_slot = pair_slot;   // resolved after the final sync
+  if (lines) {
+    uint32_t* lm = nullptr;
+    ISF_TRY(a.alloc_n(&t->nbr, (size_t)ly.ksize[0] * ly.ksize[1] * t->stride));
+    ISF_TRY(a.alloc_n(&lm, (size_t)t->stride));
+    ISF_TRY(launch_nbr_lines(a, out.coors, out.n, in.shape, ly.ksize, ly.stride, ly.padding, subm, in.occ, t->nbr, lm, t->stride,
+                             pair_count, sg));
+    t->lmask = lm;
+  } else {
+    ISF_TRY(a.alloc_n(&t->nbr, (size_t)t->K() * t->stride));
+    ISF_TRY(launch_nbr(a, out.coors, out.n, in.shape, ly.ksize, ly.stride, ly.padding, subm, in.occ, nullptr, t->nbr, t->stride,
+                       pair_count, sg));
+  }
+  return ISF_OK;
+}
+
+// Build what the launch of `p` needs behind the table and does not have yet, on the geometry stream: staging tables, row
+// sort, tile order / table / part table (again when the launch shape changes), unit plan.  Everything is built on first
+// need: a later layer of the level may be the first to stage, to sort or to run the unit kernel.  *enqueued: anything?
+static int prepare_table(Arena& a, NbrTable& t, const LayerPlan& p, const EncoderKnobs& kn, const isf_conv_layer& ly,
+                         const LevelState& out, hipStream_t sg, bool* enqueued) {
+  *enqueued = false;
+  if (p.srows > 0 && !t.stage.slots) {
+    ISF_TRY(build_stage_tables(a, t, sg));
+    *enqueued = true;
+  }
+  if (p.sort && !t.rowmap) {   // (sorted for another plan already: this layer keeps the plain table)
+    ISF_TRY(build_row_sort(a, t, p, sg));
+    *enqueued = true;
+  }
+  if (p.want_order && (t.order_cin != ly.c_in || t.order_cout != ly.c_out)) {
+    ISF_TRY(build_tile_order(a, t, p, kn, ly, out, sg));
+    *enqueued = true;
+  }
+  if (p.cu && t.cu.n_out == 0 && t.rows > 0) {
+    ISF_TRY(build_cu_plan(a, t, kn.cu_cap, sg));
+    *enqueued = true;
+  }
+  return ISF_OK;
+}
+
+// the output level of the strided conv `ly` over level L: its index, its row count (a host wait) and its coordinates
+static int open_next_level(Arena& a, LevelState& L, const isf_conv_layer& ly, int i, int B, bool mailbox, hipStream_t sg,
+                           LevelState* next) {
+  LevelState Nx;
+  ISF_TRY(ensure_occ(a, L, B, sg));
+  ISF_TRY(isf_conv_out_shape(L.shape, ly.ksize, ly.stride, ly.padding, Nx.shape));
+  ISF_REQUIRE(Nx.shape[0] > 0 && Nx.shape[1] > 0 && Nx.shape[2] > 0, ISF_ERR_ARG, "sparse_encoder: layer %d output shape empty", i);
+  ISF_TRY(occ_create(a, &Nx.occ, B, Nx.shape[0], Nx.shape[1], Nx.shape[2], sg));
+  ISF_TRY(launch_mark_out(L.coors, L.n, L.shape, ly.ksize, ly.stride, ly.padding, Nx.occ, sg));
+  ISF_TRY(occ_scan(a, Nx.occ, sg));
+  if (mailbox) {                               // host wait without a copy command (post_int / wait_int)
+    unsigned ticket = 0;
+    ISF_TRY(post_int(a, Nx.occ.total, sg, &ticket));
+    ISF_TRY(wait_int(a, ticket, sg, &Nx.n));
+  } else {
+    ISF_TRY(read_int(Nx.occ.total, &Nx.n, sg));  // host sync: sizes the next level's buffers / grids
+  }
+  Nx.has_occ = true;
+  int32_t* nc = nullptr;
+  ISF_TRY(a.alloc_n(&nc, (size_t)std::max(Nx.n, 1) * 4));
+  if (Nx.n > 0) ISF_TRY(occ_compact_coords4(Nx.occ, nc, sg));
+  Nx.coors = nc;
+  *next = Nx;
+  return ISF_OK;
+}
+
+// layer i's convolution y = conv(x) on the kernel its plan names, over the table and what prepare_table built for it
+static int run_layer_conv(const EncoderKnobs& kn, const LayerPlan& p, const isf_conv_layer& ly, int i, const NbrTable& t,
+                          const void* x, int n_in, const void* res, void* y, hipStream_t st) {
+  const bool sorted = sort_applies(t, p);   // positions instead of rows: the sorted table + the row map
+  const uint32_t* lmask = sorted && t.lmask ? t.lmask_sorted : t.lmask;
+  ISF_REQUIRE(!lmask || p.dma, ISF_ERR_UNSUPPORTED, "sparse_encoder: layer %d cannot read a line-compressed table", i);
+  const int32_t* nbr = sorted ? t.nbr_sorted : t.nbr;
+  const int n_out = t.rows;
+  ConvCall call = conv_call(x, ly.c_in, ly.packed16, p.K, ly.c_out, nbr, t.stride, n_out, ly.scale, ly.shift, res, ly.relu, y,
+                            kn.conv_mode, st);
+  if (p.srows > 0) return sparse_conv_forward_staged_impl(call, t.stage.slots, t.stage.ulist, t.stage.ucount, p.srows);
+  if (p.cu && n_out > 0) {
+    ConvCuPlan units = t.cu;
+    units.variant = kn.cu_variant;
+    return sparse_conv_forward_cu_impl(call, units);
+  }
+  if (kn.use16) {   // the LDS-DMA kernel or the tile kernel, on the order / table and the row sort built for this launch
+    const int order_bit = order_mode_bit(p.want_order ? t.order_kind : kOrderPerm);
+    call.order = p.want_order ? t.order : nullptr;
+    call.rowmap = sorted ? t.rowmap : nullptr;
+    if (p.dma) {
+      call.mode = kn.conv_mode | order_bit;
+      call.lmask = lmask;
+      call.nx = p.nx;
+      return sparse_conv_forward_dma_impl(call);
+    }
+    call.mode = p.layer_mode | order_bit | (ly.c_out == 256 && kn.fp32_class ? kn.one_block : 0);
+    return sparse_conv_forward_f16x3_impl(call);
+  }
+  const float *xf = reinterpret_cast<const float*>(x), *rf = reinterpret_cast<const float*>(res);
+  float* yf = reinterpret_cast<float*>(y);
+  if (sparse_conv_mfma_supported(ly.c_in, ly.c_out))
+    return sparse_conv_forward_packed_impl(xf, n_in, ly.c_in, ly.packed, p.K, ly.c_out, nbr, t.stride, n_out, ly.scale, ly.shift, rf,
+                                           ly.relu, yf, st);
+  return sparse_conv_forward_generic_impl(xf, ly.c_in, ly.packed, p.K, ly.c_out, nbr, t.stride, n_out, ly.scale, ly.shift, rf,
+                                          ly.relu, yf, st);
+}
 
 int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0, int n0, int B,
                                 const int shape0[3], const OccIndex* occ0, const isf_conv_layer* layers,
@@ -452,39 +720,12 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
                                 isf_encoder_stats* stats, int time_layers, const isf_encoder_options* opt,
                                 hipStream_t st, hipEvent_t geometry_ready = nullptr,
                                 const void* x0_split = nullptr /* x0 already in the split format (DynamicVFE wrote it) */) {
-  const int precision = opt ? opt->precision : 0, diagnostic = opt ? opt->diagnostic : 0;
-  const int dg = diagnostic & kKnockoutBits;   // timing diagnostic of the conv kernels (they exist on the gather kernel only)
-  ISF_REQUIRE(precision >= 0 && precision <= 2 && diagnostic >= 0 && (diagnostic & ~kEncDiagKnown) == 0 &&
-                  (dg == 0 || conv_mode_is_knockout(dg) || dg == ISF_ENC_DIAG_NO_SHARING) && !(precision == 2 && dg != 0),
-              ISF_ERR_ARG, "sparse_encoder: options (precision %d, diagnostic %d)", precision, diagnostic);
-  int translated = 0;
-  for (const auto& t : kDiagToConvMode)
-    if (diagnostic & t.diag) translated |= t.mode;
-  const bool f16io = precision == 2;             // f16 rows between the layers
-  const bool fp32_class = dg == 0 && !f16io;     // the split-precision kernels proper: the only ones the variants below apply to
-  // what every layer's launch starts from: a knock-out or f16 storage, | uniform tiles
-  const int conv_mode = (f16io ? ISF_CONV_MODE_F16_STORAGE : dg) | (translated & ISF_CONV_MODE_UNIFORM_TILES);
-  const int one_block = translated & (ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W);   // for the 256-column layers
-  const int deep_opts = translated & kDeepOptBits;                                                // for 128 columns and more
-  const bool chunk_split = (translated & ISF_CONV_MODE_CHUNK_SPLIT) && fp32_class && one_block == 0 && deep_opts == 0;
-  auto on = [&](int bit) { return (diagnostic & bit) != 0; };
-  const bool tile_order = !on(ISF_ENC_DIAG_LAUNCH_ORDER), dma_gather = !on(ISF_ENC_DIAG_NARROW_GATHER);
-  const bool line_tables = !on(ISF_ENC_DIAG_DENSE_TABLES), mailbox = !on(ISF_ENC_DIAG_COUNTS_MEMCPY), row_sort = !on(ISF_ENC_DIAG_NO_ROW_SORT);
-  const bool tile_tables = on(ISF_ENC_DIAG_TILE_TABLES), band_order = on(ISF_ENC_DIAG_BAND_ORDER);            // opt-ins
-  const bool narrow_sort = on(ISF_ENC_DIAG_NARROW_ROW_SORT), cu_units = on(ISF_ENC_DIAG_CU_KERNEL);
-  const int sort_key = on(ISF_ENC_DIAG_SORT_KEY_AB) ? 2 : 1;   // conv_row_sort_impl: 1 = six coarse bits (one radix pass), 2 = coarse | in-plane taps
-  const int cu_variant = (diagnostic & ISF_ENC_DIAG_CU_VARIANT_MASK) >> ISF_ENC_DIAG_CU_VARIANT_SHIFT;   // isf_conv_cu_plan.variant
-  auto band_of = [&](const int shape[3]) -> int { return band_order ? std::max(8, shape[1] / 45) : 0; };
-  constexpr int sort_min_rows = 4096;   // (configs[2] at B = 2: 7.05 ms sorted from 4 096 rows up, 7.10 from 32 768, 7.10 unsorted)
-  const int cu_cap = conv_cu_variant_cap(cu_variant);   // unit shape of the requested kernel variant
-  const int stage_opt = opt ? opt->stage_rows : 0;
-  const unsigned stage_mask = opt ? (unsigned)opt->stage_mask : 0u;
-  ISF_REQUIRE(stage_opt >= -1, ISF_ERR_ARG, "sparse_encoder: stage_rows %d", stage_opt);
-  ISF_REQUIRE(num_layers > 0 && num_layers <= 32, ISF_ERR_ARG, "sparse_encoder: %d layers (1..32)", num_layers);
+  EncoderKnobs kn;
+  ISF_TRY(decode_encoder_options(opt, layers, num_layers, spatial_features != nullptr, &kn));
   // Geometry (occupancy indexes, output sets, neighbour tables: small integer kernels + the host syncs that size
   // the next level) runs on a side stream and overlaps the convolutions of the previous level on `st`; a
-  // convolution waits for the event recorded behind its level's table.  `sg` first waits for everything the
-  // caller enqueued on `st` -- or only for `geometry_ready`, the point where the VFE's coordinates are final.
+  // convolution waits for the event recorded behind what prepare_table built for it.  `sg` first waits for everything
+  // the caller enqueued on `st` -- or only for `geometry_ready`, the point where the VFE's coordinates are final.
   hipStream_t sg = nullptr;
   ISF_TRY(side_stream(a, &sg));
   if (geometry_ready) ISF_HIP_TRY(hipStreamWaitEvent(sg, geometry_ready, 0));   // coords final: overlap the VFE tail too
@@ -493,42 +734,22 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
   for (int j = 0; j < 3; ++j) L.shape[j] = shape0[j];
   L.n = n0;
   L.coors = coors0;
-  L.has_occ = false;
   if (occ0) { L.occ = *occ0; L.has_occ = true; }
-  L.cache_nbr = nullptr;
-  L.cache_order = nullptr;
-  L.cache_order_cin = L.cache_order_cout = 0;
-  L.cache_order_kind = kOrderPerm;
-  L.cache_cu = ConvCuPlan();
-  L.cache_lmask = nullptr;
-  L.cache_rowmap = L.cache_nbr_sorted = nullptr;
-  L.cache_lmask_sorted = nullptr;
-  L.cache_sort_part_rows = 0;
-  // precision: f16x3 split MFMA when every layer was packed for it (and not overridden), else fp32 MFMA
-  bool use16 = precision != 1;
-  for (int i = 0; i < num_layers; ++i)
-    use16 = use16 && layers[i].packed16 && sparse_conv_f16x3_supported(layers[i].c_in, layers[i].c_out);
-  // the fp32 BEV map of split rows in two passes (dense_bev_kernel): zeros early on the geometry stream, the occupied
-  // segments last
-  const bool bev_two_pass = !on(ISF_ENC_DIAG_BEV_ONE_PASS) && use16 && !f16io && (!opt || opt->bev_format == 0) &&
-                            spatial_features != nullptr;
   bool bev_zeroed = false;
   const void* outputs[32];
   int out_rows[32];
   const void* x = x0;
-  const void* x_in0 = x0;
-  ISF_REQUIRE(!x0_split || (use16 && !f16io), ISF_ERR_ARG, "sparse_encoder: split input without the split kernels");
+  ISF_REQUIRE(!x0_split || (kn.use16 && !kn.f16io), ISF_ERR_ARG, "sparse_encoder: split input without the split kernels");
   if (x0_split) {
     x = x0_split;
-    x_in0 = x0_split;
-  } else if (use16) {  // inter-layer activations live in the split (hi8|lo8 f16) format: same bytes as fp32
+  } else if (kn.use16) {  // inter-layer activations live in the split (hi8|lo8 f16) format: same bytes as fp32
     void* xs0 = nullptr;
     ISF_TRY(a.alloc(&xs0, (size_t)std::max(n0, 1) * layers[0].c_in * 4));
-    if (f16io) ISF_TRY(f32_to_half_impl(x0, (size_t)n0 * layers[0].c_in, xs0, st));
+    if (kn.f16io) ISF_TRY(f32_to_half_impl(x0, (size_t)n0 * layers[0].c_in, xs0, st));
     else ISF_TRY(f32_to_split_impl(x0, (size_t)n0 * layers[0].c_in, xs0, st));
     x = xs0;
-    x_in0 = xs0;
   }
+  const void* x_in0 = x;
   unsigned long long* pair_counts = nullptr;   // per-rulebook pair totals: statistics only (8 + 1 launches a caller without
   if (stats) {                                   // `stats` does not pay for)
     ISF_TRY(a.alloc_n(&pair_counts, 32));
@@ -545,246 +766,34 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
     const int K = ly.ksize[0] * ly.ksize[1] * ly.ksize[2];
     ISF_REQUIRE(K >= 1 && K <= 27, ISF_ERR_UNSUPPORTED, "sparse_encoder: layer %d has %d taps", i, K);
     ISF_REQUIRE(ly.c_in == c_last, ISF_ERR_ARG, "sparse_encoder: layer %d expects %d channels, got %d", i, ly.c_in, c_last);
-    int32_t* nbr = nullptr;
-    int stride = 0;
-    int n_out = L.n;
-    int n_in = L.n;
-    // LDS rows this layer stages (0 = gather kernel); the timing diagnostics exist on the gather kernel only
-    int srows = 0;
-    if (use16 && dg == 0 && !f16io && stage_opt >= 0 && sparse_conv_f16x3_supported(ly.c_in, ly.c_out))
-      srows = stage_opt == 0 ? default_stage_rows(ly)
-                             : ((stage_mask == 0 || ((stage_mask >> i) & 1u)) ? stage_opt : 0);
-    StageTables stg;
-    const int32_t* order = nullptr;
-    int order_kind = kOrderPerm;
-    // 256-column layers: one workgroup per CU over units of equal work (isf_spconv_cu.hip; fp32-class mode only)
-    const bool cu = use16 && cu_units && srows == 0 && conv_mode == 0 && sparse_conv_cu_supported(ly.c_in, ly.c_out);
-    ConvCuPlan cu_plan;
-    // equal-work parts for the launches of several rounds; the uniform-tiles diagnostic keeps the
-    // equal-row parts (with the launch-order diagnostic: no table at all), and so do the opt-ins whose tables are cut for
-    // them (narrow row sort, band order)
-    const bool plan_ok = use16 && srows == 0 && !cu;
-    const bool want_tile_order = plan_ok && tile_order;
-    // this layer's conv mode on the tile kernel, as the launch and everything planned for the launch (row sort, tile order) see it
-    const int layer_mode = conv_mode | (fp32_class && ly.c_out >= 128 ? deep_opts : 0) |
-                           (chunk_split && use16 && !cu && srows == 0 && ly.c_out == 256 && ly.c_in >= 128 ? ISF_CONV_MODE_CHUNK_SPLIT : 0);
-    // narrow layers: LDS-DMA gathers (isf_spconv_dma.hip); the timing diagnostics and ISF_CONV_MODE_NO_SHARING exist on the gather kernel
-    const bool dma = use16 && dma_gather && srows == 0 && dg == 0 && sparse_conv_dma_supported(ly.c_in, ly.c_out);
-    const bool parts_ok = plan_ok && dg == 0 && !((conv_mode & ISF_CONV_MODE_UNIFORM_TILES) && !tile_order) && !band_order && !(dma && narrow_sort) &&
-                          (dma || (layer_mode & (ISF_CONV_MODE_DEEP | ISF_CONV_MODE_CHUNK_SPLIT)) == 0);
-    const bool want_order = want_tile_order || parts_ok;   // build_tile_order: a tile order / table, or a part table
-    const uint32_t* lmask = nullptr;   // non-null: `nbr` is the line-compressed table of this layer
-    const int nx = ly.ksize[2];
-    // a rulebook may be line-compressed when every layer that reads it runs the LDS-DMA kernel: for a SubM table, all the
-    // SubM layers of this level with the same kernel (up to the next strided conv); for a strided conv, itself
-    auto lines_ok = [&](int first) -> bool {
-      if (!use16 || !dma_gather || !line_tables || dg != 0 || stage_opt > 0 || (nx != 1 && nx != 3) ||
-          ly.ksize[0] * ly.ksize[1] > 9)
-        return false;
-      for (int j = first; j < num_layers; ++j) {
-        const isf_conv_layer& q = layers[j];
-        if (q.conv_type != ISF_CONV_SUBM) break;
-        if (q.ksize[0] != ly.ksize[0] || q.ksize[1] != ly.ksize[1] || q.ksize[2] != ly.ksize[2]) continue;
-        if (!sparse_conv_dma_supported(q.c_in, q.c_out)) return false;
-      }
-      return true;
-    };
-    // ROW SORT (round 6): a SubM layer computes its rows in the order of their tap masks (deep layers on the tile kernel,
-    // narrow layers on the LDS-DMA kernel, full or line-compressed table)
-    // (the f16-storage mode too, round 6: the sort only renames positions; its epilogue reads / writes through the row map)
-    const bool sort_mode_ok = dg == 0 && one_block == 0 && (deep_opts & ~kConvModeNarrowTiles) == 0;
-    const bool sort_ok = row_sort && use16 && !cu && srows == 0 && ly.conv_type == ISF_CONV_SUBM && K == 27 &&
-                         sort_mode_ok && L.n >= sort_min_rows && (dma ? narrow_sort : ly.c_out >= 128);
-    const int32_t* rowmap = nullptr;
-    auto launch_info = [&](int rows, Conv16LaunchInfo* info) -> int {
-      return conv16_launch_info(dma ? kConvKernelDma : kConvKernelTile, ly.c_in, ly.c_out, rows, dma ? conv_mode : layer_mode, info);
-    };
-    auto ensure_row_sort = [&](const int32_t* table, int tstride, int rows, bool* built) -> int {
-      *built = false;
-      if (!sort_ok || L.cache_rowmap) return ISF_OK;   // (sorted for another plan: this layer keeps the plain table)
-      Conv16LaunchInfo info;
-      ISF_TRY(launch_info(rows, &info));
-      int32_t *rm = nullptr, *ns = nullptr;
-      ISF_TRY(a.alloc_n(&rm, (size_t)tstride));
-      if (L.cache_lmask) {
-        const int nl = ly.ksize[0] * ly.ksize[1];
-        uint32_t* lms = nullptr;
-        ISF_TRY(a.alloc_n(&ns, (size_t)nl * tstride));
-        ISF_TRY(a.alloc_n(&lms, (size_t)tstride));
-        // the input level's rows have few, varied neighbours (6 of 27 on the benchmark geometry): all 27 bits decide
-        ISF_TRY(conv_row_sort_lines_impl(a, table, L.cache_lmask, tstride, nl, rows, info.part_rows, L.coors == coors0, rm, ns,
-                                         lms, sg));
-        L.cache_lmask_sorted = lms;
-      } else {
-        ISF_TRY(a.alloc_n(&ns, (size_t)K * tstride));
-        ISF_TRY(conv_row_sort_impl(a, table, tstride, K, rows, info.part_rows, rm, ns, sg, sort_key));
-      }
-      L.cache_rowmap = rm;
-      L.cache_nbr_sorted = ns;
-      L.cache_sort_part_rows = info.part_rows;
-      *built = true;
-      return ISF_OK;
-    };
-    auto sort_applies = [&](const int32_t* table, int tstride, int rows) -> bool {   // this layer's plan == the sort's plan
-      if (!sort_ok || !L.cache_rowmap) return false;
-      Conv16LaunchInfo info;
-      if (launch_info(rows, &info) != ISF_OK) return false;
-      return info.part_rows == L.cache_sort_part_rows;
-    };
+    const int n_in = L.n;
+    unsigned long long* pair_count = stats ? pair_counts + i : nullptr;
+    // plan the layer and get its table: the level's shared SubM table (built on a miss), or a strided conv's own
+    LayerPlan p;
+    NbrTable own;
+    NbrTable* t = &L.subm;
+    bool fresh = true;
     if (ly.conv_type == ISF_CONV_SUBM) {
-      const bool hit = L.cache_nbr && L.cache_ks[0] == ly.ksize[0] && L.cache_ks[1] == ly.ksize[1] &&
-                       L.cache_ks[2] == ly.ksize[2];
-      if (!hit) {
+      ISF_TRY(plan_layer(kn, layers, i, num_layers, L.n, &p));
+      fresh = !(t->nbr && t->ks[0] == ly.ksize[0] && t->ks[1] == ly.ksize[1] && t->ks[2] == ly.ksize[2]);
+      if (fresh) {
         ISF_TRY(ensure_occ(a, L, B, sg));
-        stride = isf_nbr_stride(L.n);
-        L.cache_lmask = nullptr;
-        if (sparse_conv_dma_supported(ly.c_in, ly.c_out) && lines_ok(i)) {
-          const int nl = ly.ksize[0] * ly.ksize[1];
-          uint32_t* lm = nullptr;
-          ISF_TRY(a.alloc_n(&nbr, (size_t)nl * stride));
-          ISF_TRY(a.alloc_n(&lm, (size_t)stride));
-          ISF_TRY(launch_nbr_lines(a, L.coors, L.n, L.shape, ly.ksize, ly.stride, ly.padding, true, L.occ, nbr, lm, stride,
-                                   stats ? pair_counts + i : nullptr, sg));
-          L.cache_lmask = lm;
-        } else {
-          ISF_TRY(a.alloc_n(&nbr, (size_t)K * stride));
-          ISF_TRY(launch_nbr(a, L.coors, L.n, L.shape, ly.ksize, ly.stride, ly.padding, true, L.occ, nullptr, nbr,
-                             stride, stats ? pair_counts + i : nullptr, sg));
-        }
-        L.cache_nbr = nbr;
-        L.cache_stride = stride;
-        for (int j = 0; j < 3; ++j) L.cache_ks[j] = ly.ksize[j];
-        L.cache_pairs = -(long long)i - 1;  // pairs live in pair_counts[i]; resolved after the final sync
-        L.cache_stage = StageTables();
-        if (srows > 0) ISF_TRY(build_stage_tables(a, nbr, stride, K, &L.cache_stage, sg));
-        L.cache_order = nullptr;
-        L.cache_order_cin = L.cache_order_cout = 0;
-        L.cache_order_kind = kOrderPerm;
-        L.cache_cu = ConvCuPlan();
-        L.cache_rowmap = L.cache_nbr_sorted = nullptr;
-        L.cache_lmask_sorted = nullptr;
-        L.cache_sort_part_rows = 0;
-        {
-          bool built = false;
-          ISF_TRY(ensure_row_sort(nbr, stride, n_out, &built));
-        }
-        if (want_order) {
-          ISF_TRY(build_tile_order(a, ly, K, sort_applies(nbr, stride, n_out) ? L.cache_nbr_sorted : nbr, stride, n_out,
-                                   layer_mode, dma, &L.cache_order, sg,
-                                   (L.cache_lmask && sort_applies(nbr, stride, n_out)) ? L.cache_lmask_sorted : L.cache_lmask,
-                                   &L.cache_order_kind, tile_tables, L.coors, band_of(L.shape), tile_order, parts_ok));
-          L.cache_order_cin = ly.c_in;
-          L.cache_order_cout = ly.c_out;
-        }
-        if (cu) ISF_TRY(build_cu_plan(a, nbr, stride, K, n_out, &L.cache_cu, sg, cu_cap));
-        ISF_TRY(stream_wait_stream(a, st, sg));   // this level's convolutions wait for its table
-      } else {
-        nbr = L.cache_nbr;
-        stride = L.cache_stride;
-        if (srows > 0 && !L.cache_stage.slots) {   // an earlier layer of the level ran unstaged: build the tables now
-          ISF_TRY(build_stage_tables(a, nbr, stride, K, &L.cache_stage, sg));
-          ISF_TRY(stream_wait_stream(a, st, sg));
-        }
-        {   // an earlier layer of the level did not sort (another kernel): sort now
-          bool built = false;
-          ISF_TRY(ensure_row_sort(nbr, stride, n_out, &built));
-          if (built) ISF_TRY(stream_wait_stream(a, st, sg));
-        }
-        if (want_order && (L.cache_order_cin != ly.c_in || L.cache_order_cout != ly.c_out)) {   // another launch shape
-          ISF_TRY(build_tile_order(a, ly, K, sort_applies(nbr, stride, n_out) ? L.cache_nbr_sorted : nbr, stride, n_out,
-                                   layer_mode, dma, &L.cache_order, sg,
-                                   (L.cache_lmask && sort_applies(nbr, stride, n_out)) ? L.cache_lmask_sorted : L.cache_lmask,
-                                   &L.cache_order_kind, tile_tables, L.coors, band_of(L.shape), tile_order, parts_ok));
-          L.cache_order_cin = ly.c_in;
-          L.cache_order_cout = ly.c_out;
-          ISF_TRY(stream_wait_stream(a, st, sg));
-        }
-        if (cu && L.cache_cu.n_out == 0) {   // an earlier layer of the level did not need the unit plan
-          ISF_TRY(build_cu_plan(a, nbr, stride, K, n_out, &L.cache_cu, sg, cu_cap));
-          ISF_TRY(stream_wait_stream(a, st, sg));
-        }
+        ISF_TRY(build_nbr_table(a, L, L, ly, p.lines, i, pair_count, sg, t));
       }
-      cu_plan = L.cache_cu;
-      lmask = L.cache_lmask;
-      if (sort_applies(nbr, stride, n_out)) {   // positions instead of rows: the sorted table + the row map
-        nbr = const_cast<int32_t*>(L.cache_nbr_sorted);
-        if (lmask) lmask = L.cache_lmask_sorted;
-        rowmap = L.cache_rowmap;
-      }
-      ISF_REQUIRE(!lmask || dma, ISF_ERR_UNSUPPORTED, "sparse_encoder: layer %d cannot read a line-compressed table", i);
-      stg = L.cache_stage;
-      if (want_order) {
-        order = L.cache_order;
-        order_kind = L.cache_order_kind;
-      }
-      if (stats) stats->pairs[i] = hit ? L.cache_pairs : -(long long)i - 1;
     } else {
-      ISF_TRY(ensure_occ(a, L, B, sg));
       LevelState Nx;
-      ISF_TRY(isf_conv_out_shape(L.shape, ly.ksize, ly.stride, ly.padding, Nx.shape));
-      ISF_REQUIRE(Nx.shape[0] > 0 && Nx.shape[1] > 0 && Nx.shape[2] > 0, ISF_ERR_ARG,
-                  "sparse_encoder: layer %d output shape empty", i);
-      ISF_TRY(occ_create(a, &Nx.occ, B, Nx.shape[0], Nx.shape[1], Nx.shape[2], sg));
-      ISF_TRY(launch_mark_out(L.coors, L.n, L.shape, ly.ksize, ly.stride, ly.padding, Nx.occ, sg));
-      ISF_TRY(occ_scan(a, Nx.occ, sg));
-      if (mailbox) {                               // host wait without a copy command (post_int / wait_int)
-        unsigned ticket = 0;
-        ISF_TRY(post_int(a, Nx.occ.total, sg, &ticket));
-        ISF_TRY(wait_int(a, ticket, sg, &Nx.n));
-      } else {
-        ISF_TRY(read_int(Nx.occ.total, &Nx.n, sg));  // host sync: sizes the next level's buffers / grids
-      }
-      Nx.has_occ = true;
-      int32_t* nc = nullptr;
-      ISF_TRY(a.alloc_n(&nc, (size_t)std::max(Nx.n, 1) * 4));
-      if (Nx.n > 0) ISF_TRY(occ_compact_coords4(Nx.occ, nc, sg));
-      Nx.coors = nc;
-      stride = isf_nbr_stride(Nx.n);
-      if (dma && lines_ok(num_layers)) {     // a strided conv's table has one reader
-        uint32_t* lm = nullptr;
-        ISF_TRY(a.alloc_n(&nbr, (size_t)ly.ksize[0] * ly.ksize[1] * stride));
-        ISF_TRY(a.alloc_n(&lm, (size_t)stride));
-        ISF_TRY(launch_nbr_lines(a, Nx.coors, Nx.n, L.shape, ly.ksize, ly.stride, ly.padding, false, L.occ, nbr, lm, stride,
-                                 stats ? pair_counts + i : nullptr, sg));
-        lmask = lm;
-      } else {
-        ISF_TRY(a.alloc_n(&nbr, (size_t)K * stride));
-        ISF_TRY(launch_nbr(a, Nx.coors, Nx.n, L.shape, ly.ksize, ly.stride, ly.padding, false, L.occ, nullptr, nbr,
-                           stride, stats ? pair_counts + i : nullptr, sg));
-      }
-      if (srows > 0) ISF_TRY(build_stage_tables(a, nbr, stride, K, &stg, sg));
-      // ROW SORT of a deep strided convolution's own table (its rows want 10 of 27 taps, in many patterns: -12 % tile-taps,
-      // -26 % MFMA blocks at level 3 on the benchmark geometry, profiles/r06_row_sort.txt)
-      if (row_sort && use16 && !dma && !cu && srows == 0 && !lmask && ly.c_out >= 128 && K == 27 && sort_mode_ok &&
-          Nx.n >= sort_min_rows) {
-        Conv16LaunchInfo info;
-        ISF_TRY(conv16_launch_info(kConvKernelTile, ly.c_in, ly.c_out, Nx.n, layer_mode, &info));
-        int32_t *rm = nullptr, *ns = nullptr;
-        ISF_TRY(a.alloc_n(&rm, (size_t)stride));
-        ISF_TRY(a.alloc_n(&ns, (size_t)K * stride));
-        ISF_TRY(conv_row_sort_impl(a, nbr, stride, K, Nx.n, info.part_rows, rm, ns, sg, 1));
-        nbr = ns;
-        rowmap = rm;
-      }
-      if (want_order)
-        ISF_TRY(build_tile_order(a, ly, K, nbr, stride, Nx.n, layer_mode, dma, &order, sg, lmask, &order_kind, tile_tables,
-                                 Nx.coors, band_of(Nx.shape), tile_order, parts_ok));
-      if (cu && Nx.n > 0) ISF_TRY(build_cu_plan(a, nbr, stride, K, Nx.n, &cu_plan, sg, cu_cap));
-      if (stats) stats->pairs[i] = -(long long)i - 1;
-      Nx.cache_cu = ConvCuPlan();
-      Nx.cache_lmask = nullptr;
-      Nx.cache_rowmap = Nx.cache_nbr_sorted = nullptr;
-      Nx.cache_lmask_sorted = nullptr;
-      Nx.cache_sort_part_rows = 0;
-      Nx.cache_nbr = nullptr;
-      Nx.cache_order = nullptr;
-      Nx.cache_order_cin = Nx.cache_order_cout = 0;
-      Nx.cache_order_kind = kOrderPerm;
-      n_out = Nx.n;
+      ISF_TRY(open_next_level(a, L, ly, i, B, kn.mailbox, sg, &Nx));
+      ISF_TRY(plan_layer(kn, layers, i, num_layers, Nx.n, &p));
+      t = &own;
+      ISF_TRY(build_nbr_table(a, L, Nx, ly, p.lines, i, pair_count, sg, t));
       L = Nx;
-      ISF_TRY(stream_wait_stream(a, st, sg));
     }
-    if (bev_two_pass && i == num_layers - 1 && (long long)L.shape[1] * L.shape[2] < (1ll << 30)) {
+    bool enqueued = false;
+    ISF_TRY(prepare_table(a, *t, p, kn, ly, L, sg, &enqueued));
+    if (fresh || enqueued) ISF_TRY(stream_wait_stream(a, st, sg));   // the convolution waits for its table
+    if (stats) stats->pairs[i] = -(long long)t->pair_slot - 1;   // pairs live in pair_counts[pair_slot]
+    const int n_out = t->rows;
+    if (kn.bev_two_pass && i == num_layers - 1 && (long long)L.shape[1] * L.shape[2] < (1ll << 30)) {
       // L is the output level and the last convolution no longer waits for `sg`: the zero segments of the map are written
       // beside the convolutions still queued on `st` (a strided last layer has built the index above; the buffer is free:
       // `sg` started behind everything the caller had queued on `st`); the join before dense_bev_kernel covers this launch
@@ -802,34 +811,7 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
       res = outputs[ly.residual_from];
     }
     if (!ev.empty()) ISF_HIP_TRY(hipEventRecord(ev[2 * i], st));
-    ConvCall call = conv_call(x, ly.c_in, ly.packed16, K, ly.c_out, nbr, stride, n_out, ly.scale, ly.shift, res, ly.relu, y,
-                              conv_mode, st);
-    if (use16 && srows > 0)
-      ISF_TRY(sparse_conv_forward_staged_impl(call, stg.slots, stg.ulist, stg.ucount, srows));
-    else if (cu && n_out > 0 && ((cu_plan.variant = cu_variant), true))
-      ISF_TRY(sparse_conv_forward_cu_impl(call, cu_plan));
-    else if (use16) {   // the LDS-DMA kernel or the tile kernel, on the order / table and the row sort built for this launch
-      call.order = order;
-      call.rowmap = rowmap;
-      if (dma) {
-        call.mode = conv_mode | order_mode_bit(order_kind);
-        call.lmask = lmask;
-        call.nx = nx;
-        ISF_TRY(sparse_conv_forward_dma_impl(call));
-      } else {
-        call.mode = layer_mode | order_mode_bit(order_kind) | (ly.c_out == 256 && fp32_class ? one_block : 0);
-        ISF_TRY(sparse_conv_forward_f16x3_impl(call));
-      }
-    } else if (sparse_conv_mfma_supported(ly.c_in, ly.c_out))
-      ISF_TRY(sparse_conv_forward_packed_impl(reinterpret_cast<const float*>(x), n_in, ly.c_in, ly.packed, K,
-                                              ly.c_out, nbr, stride, n_out, ly.scale, ly.shift,
-                                              reinterpret_cast<const float*>(res), ly.relu,
-                                              reinterpret_cast<float*>(y), st));
-    else
-      ISF_TRY(sparse_conv_forward_generic_impl(reinterpret_cast<const float*>(x), ly.c_in, ly.packed, K, ly.c_out,
-                                               nbr, stride, n_out, ly.scale, ly.shift,
-                                               reinterpret_cast<const float*>(res), ly.relu,
-                                               reinterpret_cast<float*>(y), st));
+    ISF_TRY(run_layer_conv(kn, p, ly, i, *t, x, n_in, res, y, st));
     if (!ev.empty()) ISF_HIP_TRY(hipEventRecord(ev[2 * i + 1], st));
     outputs[i] = y;
     out_rows[i] = n_out;
@@ -840,16 +822,16 @@ int sparse_encoder_forward_impl(Arena& a, const float* x0, const int32_t* coors0
   // dense BEV of the last level
   ISF_TRY(ensure_occ(a, L, B, sg));
   ISF_TRY(stream_wait_stream(a, st, sg));
-  if (opt && opt->bev_format == 1) {   // split-format token matrices (same byte count as the fp32 map)
-    ISF_REQUIRE(use16 && !f16io, ISF_ERR_UNSUPPORTED, "sparse_encoder: bev_format 1 needs the split-precision path");
+  if (kn.bev_format == 1) {   // split-format token matrices (same byte count as the fp32 map)
+    ISF_REQUIRE(kn.use16 && !kn.f16io, ISF_ERR_UNSUPPORTED, "sparse_encoder: bev_format 1 needs the split-precision path");
     ISF_TRY(sparse_to_bev_split_impl(x, c_last, B, L.shape[0], L.shape[1], L.shape[2], L.occ, spatial_features, st));
   } else {
-    ISF_REQUIRE(!opt || opt->bev_format == 0, ISF_ERR_ARG, "sparse_encoder: bev_format %d (0 fp32 map, 1 split token matrices)",
-                opt->bev_format);
-    ISF_TRY(sparse_to_dense_bev_impl(a, x, use16 ? (f16io ? 2 : 1) : 0, L.coors, L.n, c_last, B, L.shape[0], L.shape[1],
+    ISF_REQUIRE(kn.bev_format == 0, ISF_ERR_ARG, "sparse_encoder: bev_format %d (0 fp32 map, 1 split token matrices)",
+                kn.bev_format);
+    ISF_TRY(sparse_to_dense_bev_impl(a, x, kn.use16 ? (kn.f16io ? 2 : 1) : 0, L.coors, L.n, c_last, B, L.shape[0], L.shape[1],
                                      L.shape[2], spatial_features, &L.occ, st, bev_zeroed));
   }
-  if (stats) stats->precision = use16 ? 1 : 0;
+  if (stats) stats->precision = kn.use16 ? 1 : 0;
   if (out_shape) { out_shape[0] = c_last * L.shape[0]; out_shape[1] = L.shape[1]; out_shape[2] = L.shape[2]; out_shape[3] = L.n; }
   if (stats) {
     unsigned long long h_pairs[32];
@@ -933,14 +915,6 @@ int isf_sparse_encoder_forward(const float* voxel_features, const int32_t* coors
                                      spatial_features, out_shape_host, stats_host, time_layers, options, st);
 }
 
-// does sparse_encoder_forward_impl run these layers on the split-format kernels (fp32-class f16x3 arithmetic)?
-static bool encoder_takes_split_input(const isf_conv_layer* layers, int num_layers, const isf_encoder_options* opt) {
-  if ((opt ? opt->precision : 0) != 0 || num_layers <= 0 || num_layers > 32) return false;
-  for (int i = 0; i < num_layers; ++i)
-    if (!layers[i].packed16 || !isf::sparse_conv_f16x3_supported(layers[i].c_in, layers[i].c_out)) return false;
-  return true;
-}
-
 // the LiDAR branch over B frames: one concatenated block (`points`) or one block per frame (`frame_points`, B <= kVoxMaxBatch)
 static int lidar_branch_impl(const float* points, const float* const* frame_points, const int64_t* point_offsets_host,
                              int batch_size, const isf_vfe_params* vfe_host, const int sparse_shape_host[3],
@@ -988,7 +962,9 @@ static int lidar_branch_impl(const float* points, const float* const* frame_poin
   // the voxel rows go straight into the split format the first convolution reads (whole rows from the VFE's segmented
   // max, the rows cut by a wave boundary from a fix-up pass): no [N, 64] fp32 -> split conversion pass in between
   void* vf_split = nullptr;
-  if (encoder_takes_split_input(layers_host, num_layers, options) && vfe_host->c2 == layers_host[0].c_in &&
+  const bool split_kernels = (options ? options->precision : 0) == 0 && num_layers > 0 && num_layers <= 32 &&
+                             encoder_use16(layers_host, num_layers, 0);   // fp32-class f16x3 arithmetic on split rows
+  if (split_kernels && vfe_host->c2 == layers_host[0].c_in &&
       !(options && (options->diagnostic & ISF_ENC_DIAG_VFE_FP32_ROWS)))   // fp32 rows + the conversion pass (same bits)
     ISF_TRY(a.alloc(&vf_split, (size_t)P * vfe_host->c2 * 4));
   ISF_TRY(dynamic_vfe_impl(a, nullptr, coors4, P, Cin, batch_size, vfe_host->voxel_size, vfe_host->coors_range,

@@ -559,6 +559,51 @@ def test_sparse_encoder_and_lidar_branch_vs_oracle(dev, oracle_mod):
     assert lb.last_stats.pairs[0] == pairs0 and lb.last_stats.pairs[1] == pairs0
 
 
+def test_sparse_encoder_one_table_shared_by_every_kernel_family(dev, oracle_mod):
+    """one level whose shared SubM table is read by the LDS-DMA kernel (2 x 64 -> 64), the tile kernel at two widths
+    (64 -> 128, 128 -> 256, 256 -> 256) and the unit-plan-capable shapes, then the 3-tap strided 256 -> 256: what the shipped
+    plan (one channel shape per level) never asks of the encoder's host side -- a row sort, a tile order for another launch
+    shape, a unit plan and staging tables that a LATER layer of the level is the first to need.  About 6 000 rows: above the
+    row-sort threshold of 4 096.  Reference: the scalar oracle, 1e-3 absolute (the BEV tolerance); every switch that only
+    changes tables / orders / kernels must keep the default's bits."""
+    import isfusion_amd as m
+    B, shape = 2, [5, 64, 64]
+    enc = m.SparseEncoder(in_channels=64, sparse_shape=shape, base_channels=64, output_channels=256,
+                          encoder_channels=((64, 128, 256, 256),), encoder_paddings=((1, 1, 1, 1),), block_type="conv_module")
+    m.LidarBranch.randomize_weights_(enc, 0)
+    m.LidarBranch.randomize_bn_(enc, 1)
+    enc = enc.eval().to(dev)
+    plan = enc.plan_to_numpy()
+    assert [(L["kind"], L["weight"].shape[-2], L["weight"].shape[-1]) for L in plan["layers"]] == [
+        ("subm", 64, 64), ("subm", 64, 64), ("subm", 64, 128), ("subm", 128, 256), ("subm", 256, 256), ("spconv", 256, 256)]
+    rng = np.random.default_rng(2610)
+    coors = _random_geometry(rng, B, shape, 6000)
+    feats = rng.normal(0, 1, (len(coors), 64)).astype(np.float32)
+    bev, _ = oracle_mod.sparse_encoder_forward(plan, feats, coors, B)
+    vf, vc = T(feats, dev), T(coors, dev)
+
+    def run(**kw):
+        return enc.forward_fused(vf, vc, B, **kw)
+
+    want = run()
+    got = want.cpu().numpy()
+    assert got.shape == bev.shape == (B, 512, 64, 64)
+    err = np.abs(got - bev).max()
+    print(f"max |encoder - oracle| = {err:.3e}, max |oracle| = {np.abs(bev).max():.3f}")
+    assert np.abs(bev).max() > 0.5 and (bev == 0).any()
+    assert err < 1e-3, err
+    assert np.array_equal(got != 0, bev != 0)
+    for diag in (_lib.ENC_DIAG_LAUNCH_ORDER, _lib.ENC_DIAG_NO_ROW_SORT, _lib.ENC_DIAG_DENSE_TABLES, _lib.ENC_DIAG_UNIFORM_TILES,
+                 _lib.ENC_DIAG_TILE_TABLES):
+        assert torch.equal(run(conv_diag=diag), want), diag
+    assert torch.equal(run(stage_rows=-1), want)
+    assert torch.equal(run(stage_rows=320, stage_mask=0b010100), want)      # staging tables built late, at layers 2 and 4
+    cu = run(conv_diag=_lib.ENC_DIAG_CU_KERNEL)                             # the unit plan built late, at layer 3
+    assert torch.equal(run(conv_diag=_lib.ENC_DIAG_CU_KERNEL), cu)
+    assert torch.equal(run(conv_diag=_lib.ENC_DIAG_CU_KERNEL | _lib.ENC_DIAG_LAUNCH_ORDER), cu)
+    assert torch.equal(run(precision=2, conv_diag=_lib.ENC_DIAG_NO_ROW_SORT), run(precision=2))
+
+
 def test_chunk_split_of_the_256_column_layers(dev, oracle_mod):
     """round 6 (opt-in: CONV_MODE_CHUNK_SPLIT / ENC_DIAG_CHUNK_SPLIT; measured slower): a tile of a 256-column layer is
     computed by two workgroups, each over half of the 32-channel chunks; the second to arrive adds the other's accumulator
