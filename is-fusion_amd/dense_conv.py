@@ -13,9 +13,7 @@ import torch
 
 from . import _lib
 from .norm import fold_bn
-from .spconv import pack_filters_f16x3
-
-SUPPORTED = (32, 64, 128, 256)
+from .spconv import F16X3_CHANNELS as SUPPORTED, Rulebook, _conv_args, pack_filters_f16x3
 
 
 class SplitMap:
@@ -56,19 +54,21 @@ class SplitMap:
 _grids = {}
 
 
-def grid_rulebook(device, B, H, W, stride=1, transpose=False):
-    """cached arithmetic neighbour table of a dense B x H x W grid for a 3x3 / pad 1 convolution"""
-    key = (str(device), B, H, W, stride, bool(transpose))
+def grid_rulebook(device, B, H, W, stride=1):
+    """spconv.Rulebook (out_shape = (oh, ow)) of a dense B x H x W grid under a 3x3 / pad 1 / `stride` convolution: the
+    arithmetic neighbour table, cached per geometry together with what the backward passes hang on it (transposed table,
+    pair lists).  The inference and the training path share it."""
+    key = (str(device), B, H, W, stride)
     if key not in _grids:
         lib = _lib.load()
         ohw = (ctypes.c_int * 2)()
-        _lib.check(lib.isf_dense_grid_rulebook(B, H, W, 3, 3, stride, 1, int(transpose), None, 0, ohw, None))
+        _lib.check(lib.isf_dense_grid_rulebook(B, H, W, 3, 3, stride, 1, 0, None, 0, ohw, None))
         n_out = B * ohw[0] * ohw[1]
         nstride = lib.isf_nbr_stride(n_out)
         nbr = torch.empty((9, nstride), dtype=torch.int32, device=device)
-        _lib.check(lib.isf_dense_grid_rulebook(B, H, W, 3, 3, stride, 1, int(transpose), _lib.ptr(nbr), nstride, ohw,
+        _lib.check(lib.isf_dense_grid_rulebook(B, H, W, 3, 3, stride, 1, 0, _lib.ptr(nbr), nstride, ohw,
                                                _lib.stream()), "isf_dense_grid_rulebook")
-        _grids[key] = (nbr, nstride, ohw[0], ohw[1])
+        _grids[key] = Rulebook(nbr, nstride, B * H * W, n_out, None, (ohw[0], ohw[1]))
     return _grids[key]
 
 
@@ -122,21 +122,19 @@ class PackedConvBN:
         maps = inputs if isinstance(inputs, (list, tuple)) else [inputs]
         assert len(maps) == len(self.groups), "one SplitMap per 256-channel group"
         m0 = maps[0]
-        nbr, nstride, oh, ow = grid_rulebook(m0.data.device, m0.B, m0.H, m0.W, self.stride, False)
-        n_out = m0.B * oh * ow
+        rb = grid_rulebook(m0.data.device, m0.B, m0.H, m0.W, self.stride)
         lib = _lib.load()
         acc = None
         for gi, (m, (off, c, pk, pkt)) in enumerate(zip(maps, self.groups)):
             assert m.C == c and (m.B, m.H, m.W) == (m0.B, m0.H, m0.W)
             last = gi == len(self.groups) - 1
-            out = torch.empty(n_out * self.c_out * 4, dtype=torch.uint8, device=m.data.device)
+            out = torch.empty(rb.num_out * self.c_out * 4, dtype=torch.uint8, device=m.data.device)
             _lib.check(lib.isf_sparse_conv_forward_f16x3(
-                _lib.ptr(m.data), m.num_tokens, c, _lib.ptr(pkt if transpose else pk), 9, self.c_out, _lib.ptr(nbr),
-                nstride, n_out, _lib.ptr(self.scale), _lib.ptr(self.shift if last else self.zero_shift),
-                _lib.ptr(acc) if acc is not None else None, int(self.relu and last), _lib.ptr(out), 0, _lib.stream()),
+                *_conv_args(m.data, pkt if transpose else pk, 9, c, self.c_out, rb, self.scale,
+                            self.shift if last else self.zero_shift, acc, self.relu and last, out), 0, _lib.stream()),
                 "isf_sparse_conv_forward_f16x3")
             acc = out
-        return SplitMap(acc, m0.B, self.c_out, oh, ow)
+        return SplitMap(acc, m0.B, self.c_out, *rb.out_shape)
 
 
 def pack_sequential(seq):

@@ -34,19 +34,6 @@ ENABLED = True        # False: every stack on the stock modules (the round-5 tra
 _amp_fwd = torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
 _amp_bwd = torch.amp.custom_bwd(device_type="cuda")
 
-_rulebooks = {}
-
-
-def dense_rulebook(device, B, H, W, stride):
-    """spconv.Rulebook of a dense B x H x W grid under a 3x3 / pad 1 / `stride` convolution, cached per geometry together
-    with what the backward passes hang on it (transposed table, pair lists)."""
-    key = (str(device), B, H, W, stride)
-    if key not in _rulebooks:
-        nbr, nstride, oh, ow = grid_rulebook(device, B, H, W, stride, False)
-        rb = sp.Rulebook(nbr, nstride, B * H * W, B * oh * ow, None, (oh, ow))
-        _rulebooks[key] = rb
-    return _rulebooks[key]
-
 
 def supported(conv):
     """can this nn.Conv2d run on the kernels?"""
@@ -55,7 +42,7 @@ def supported(conv):
             conv.padding_mode == "zeros" and conv.weight.is_cuda):
         return False
     cin, cout = conv.in_channels, conv.out_channels
-    return cout in (32, 64, 128, 256) and cin >= 32 and cin % 256 in (0, 32, 64, 128)   # <= 256-channel input groups
+    return cout in sp.F16X3_CHANNELS and cin >= 32 and cin % 256 in (0, 32, 64, 128)   # <= 256-channel input groups
 
 
 def _groups(weight, transpose):
@@ -114,20 +101,15 @@ class DenseConvFunction(torch.autograd.Function):
         groups = _groups(weight, transpose)
         gs, sc = sp.grad_to_split(grad_out)
         grad_rows = grad_w = None
-        if ctx.needs_input_grad[0]:
-            nbr_t, st = sp.transposed_nbr(rb)
-            rbt = rb.__dict__.get("_rbt")
-            if rbt is None:
-                rbt = rb._rbt = sp._TransposedRulebook(nbr_t, st, rb.num_out, rb.num_in)
-            parts = [sp.from_split_scaled(sp.sparse_conv_split(gs, pkt, 9, cout, c, rbt, ordered=False, mode=mode),
-                                          (rb.num_in, c), sc[1:]) for _, c, _, pkt in groups]
-            grad_rows = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
-        if ctx.needs_input_grad[1]:
-            # (WGRAD_FULL_TAPS: every tap list of a dense grid is full -- larger reduction chunks, a third of the partial-sum traffic)
-            parts = [sp.sparse_conv_backward_filter_f16x3(xs, c, gs, cout, rb, sc[1:], (1, 3, 3, c, cout),
-                                                          mode=(_lib.WGRAD_F16 if mode & _lib.CONV_MODE_F16 else 0) | _lib.WGRAD_FULL_TAPS)
-                     for xs, (_, c, _, _) in zip(ctx.saved_tensors, groups)]
-            g5 = (parts[0] if len(parts) == 1 else torch.cat(parts, 3)).view(3, 3, cin, cout)
+        want_dx, want_dw = ctx.needs_input_grad[:2]
+        # (WGRAD_FULL_TAPS: every tap list of a dense grid is full -- larger reduction chunks, a third of the partial-sum traffic)
+        parts = [sp.split_backward(xs, gs, sc, rb, pkt, 9, c, cout, bool(mode & _lib.CONV_MODE_F16), want_dx, want_dw,
+                                   (1, 3, 3, c, cout), _lib.WGRAD_FULL_TAPS)
+                 for xs, (_, c, _, pkt) in zip(ctx.saved_tensors, groups)]
+        if want_dx:
+            grad_rows = parts[0][0] if len(parts) == 1 else torch.cat([dx for dx, _ in parts], 1)
+        if want_dw:
+            g5 = (parts[0][1] if len(parts) == 1 else torch.cat([dw for _, dw in parts], 3)).view(3, 3, cin, cout)
             grad_w = (g5.permute(3, 2, 1, 0) if transpose else g5.permute(3, 2, 0, 1)).contiguous()
         return grad_rows, grad_w, None, None, None
 
@@ -192,7 +174,7 @@ def conv_stack(seq, x, transpose=False):
     with torch.autocast("cuda", enabled=False):
         rows = to_rows(x)
         for conv, bn, relu in layers:
-            rb = dense_rulebook(rows.device, B, H, W, conv.stride[0])
+            rb = grid_rulebook(rows.device, B, H, W, conv.stride[0])
             rows = DenseConvFunction.apply(rows, conv.weight, rb, transpose, half)
             H, W = rb.out_shape
             if conv.bias is not None:

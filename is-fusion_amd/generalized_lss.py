@@ -18,7 +18,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .dense_conv import PackedConvBN, SplitMap
+from .dense_conv import PackedConvBN, SplitMap, grid_rulebook
 from .fusion_ops import ACT_NONE, ACT_RELU, PackedLinear, _cache
 from .norm import fold_bn
 from .swin import _a, _training_error, gemm
@@ -207,7 +207,7 @@ class GeneralizedLSSFPN(nn.Module):
         variance and num_batches_tracked move as nn.BatchNorm2d's do), all levels computed as in forward().  inputs: the
         backbone's NCHW maps, without a gradient (the backbone has no backward).  Returns NCHW views of token rows."""
         from . import spconv as sp
-        from .dense_train import DenseConvFunction, dense_rulebook, from_rows, supported
+        from .dense_train import DenseConvFunction, from_rows, supported
         from .norm import bn1d_relu
         assert len(inputs) == len(self.in_channels)
         _lib.require_cuda(*inputs)
@@ -230,7 +230,7 @@ class GeneralizedLSSFPN(nn.Module):
                 lc, fc = self.lateral_convs[i], self.fpn_convs[i]
                 rows = LateralFunction.apply(fine, coarse, lc.conv.weight)
                 rows = bn1d_relu(lc.bn, rows, relu=lc.activate is not None)
-                rows = DenseConvFunction.apply(rows, fc.conv.weight, dense_rulebook(rows.device, B, H, W, 1), False, half)
+                rows = DenseConvFunction.apply(rows, fc.conv.weight, grid_rulebook(rows.device, B, H, W, 1), False, half)
                 rows = bn1d_relu(fc.bn, rows, relu=fc.activate is not None)
                 lat[i] = from_rows(rows, B, H, W)
         return tuple(lat[:len(lat) - 1])

@@ -87,12 +87,25 @@ class _SparseToDense(torch.autograd.Function):
 
 
 class Rulebook:
-    """Output-stationary neighbour table of one conv geometry on one active set."""
+    """Output-stationary neighbour table of one conv geometry on one active set, and `derived`: every table built from
+    it (tile orders and tables, line form, unit plans, stage tables, pair lists, the transposed view), by key."""
 
     def __init__(self, nbr, stride, num_in, num_out, out_indices, out_shape):
         self.nbr, self.stride = nbr, stride
         self.num_in, self.num_out = num_in, num_out
         self.out_indices, self.out_shape = out_indices, out_shape
+        self.derived = {}
+
+    def cached(self, key, build):
+        """derived[key], from build() on first use (a None result is kept like any other)"""
+        if key not in self.derived:
+            self.derived[key] = build()
+        return self.derived[key]
+
+    def transposed(self):
+        """the Rulebook the dX pass runs the forward kernels on (isf_transpose_rulebook): rows of the conv's OUTPUT feed
+        rows of its INPUT.  Cached, so what hangs on the view (tile orders) is built once per rulebook, not per layer."""
+        return self.cached("transposed", lambda: _transpose(self))
 
 
 def build_rulebook(indices, batch_size, spatial_shape, ksize, stride, padding, subm):
@@ -201,34 +214,43 @@ def _is_production_mode(mode):
     return (mode & ~_lib.CONV_MODE_UNIFORM_TILES) in (0, _lib.CONV_MODE_F16, _lib.CONV_MODE_F16_STORAGE)
 
 
-def tile_order(rb, c_in, c_out, mode=0, dma=False):
-    """int32 tile order of the launch sparse_conv_forward_f16x3 (dma=True: sparse_conv_forward_dma -- its launch plan
-    differs) makes for this rulebook and channel shape (isf_sparse_conv_tile_order), or None when the launch is not a
-    single resident round.  Cached on the rulebook per (shape, mode, kernel)."""
-    cache = rb.__dict__.setdefault("_tile_order", {})
+def _tile_order_and_work(rb, c_in, c_out, mode, dma):
+    """(order, work) of tile_order / tile_work, or None; cached on the rulebook per (shape, mode, kernel)"""
     mode = int(mode) | (_lib.CONV_MODE_DMA_PLAN if dma else 0)
-    key = (int(c_in), int(c_out), mode)
-    if key not in cache:
+
+    def build():
         lib = _lib.load()
         K = rb.nbr.numel() // rb.stride
         dev = rb.nbr.device
         work = torch.empty(8 * 255, dtype=torch.int32, device=dev)
         order = torch.empty(8 * 255, dtype=torch.int32, device=dev)
         n = ctypes.c_int(0)
-        _lib.check(lib.isf_sparse_conv_tile_order(_lib.ptr(rb.nbr), rb.stride, K, rb.num_out, c_in, c_out, int(mode),
+        _lib.check(lib.isf_sparse_conv_tile_order(_lib.ptr(rb.nbr), rb.stride, K, rb.num_out, c_in, c_out, mode,
                                                   _lib.ptr(work), _lib.ptr(order), ctypes.byref(n), _lib.stream()),
                    "isf_sparse_conv_tile_order")
-        cache[key] = (order[:n.value], work[:n.value]) if n.value else None
-    return cache[key][0] if cache[key] is not None else None
+        return (order[:n.value], work[:n.value]) if n.value else None
+    return rb.cached(("tile_order", int(c_in), int(c_out), mode), build)
+
+
+def tile_order(rb, c_in, c_out, mode=0, dma=False):
+    """int32 tile order of the launch sparse_conv_forward_f16x3 (dma=True: sparse_conv_forward_dma -- its launch plan
+    differs) makes for this rulebook and channel shape (isf_sparse_conv_tile_order), or None when the launch is not a
+    single resident round."""
+    pair = _tile_order_and_work(rb, c_in, c_out, mode, dma)
+    return pair[0] if pair is not None else None
+
+
+def tile_work(rb, c_in, c_out, mode=0, dma=False):
+    """int32 work (multiply steps) per tile of that launch, in launch order: what tile_order sorted; None like it."""
+    pair = _tile_order_and_work(rb, c_in, c_out, mode, dma)
+    return pair[1] if pair is not None else None
 
 
 def tile_table(rb, c_in, c_out, mode=0):
     """Equal-work tile table of the launch isf_sparse_conv_forward_f16x3 would make on this Rulebook for (c_in, c_out,
     mode) (isf_sparse_conv_tile_table), cached; None when the launch is not one resident round.  Opt-in: measured slower
     than uniform tiles + tile_order."""
-    cache = rb.__dict__.setdefault("_tile_tables", {})
-    key = (c_in, c_out, mode)
-    if key not in cache:
+    def build():
         lib = _lib.load()
         K = rb.nbr.numel() // rb.stride
         dev = rb.nbr.device
@@ -239,8 +261,8 @@ def tile_table(rb, c_in, c_out, mode=0):
         _lib.check(lib.isf_sparse_conv_tile_table(_lib.ptr(rb.nbr), rb.stride, K, rb.num_out, c_in, c_out, int(mode),
                                                   _lib.ptr(scratch), _lib.ptr(table), ctypes.byref(n), _lib.stream()),
                    "isf_sparse_conv_tile_table")
-        cache[key] = table[:n.value] if n.value else None
-    return cache[key]
+        return table[:n.value] if n.value else None
+    return rb.cached(("tile_table", c_in, c_out, mode), build)
 
 
 def tile_table_host(work, part_groups, parts, cus=32, wgs_per_cu=3, groups_per_tile=8):
@@ -254,18 +276,32 @@ def tile_table_host(work, part_groups, parts, cus=32, wgs_per_cu=3, groups_per_t
     return tiles, bool(fits.value)
 
 
+def _row_format(features, residual, rb, c_out, mode):
+    """The row format a conv mode exchanges, decided here only: f16 storage converts through half rows, everything else
+    through split rows -> (converted features, converted residual | None, raw output rows, the converter
+    back(rows, shape) to fp32)."""
+    to, back, width = (to_half, from_half, 2) if _is_f16_storage(mode) else (to_split, from_split, 4)
+    xs = to(features)
+    rs = None if residual is None else to(residual)
+    return xs, rs, torch.empty(rb.num_out * c_out * width, dtype=torch.uint8, device=features.device), back
+
+
+def _conv_args(xs, packed16, K, c_in, c_out, rb, scale, shift, residual, relu, ys):
+    """the 14 leading arguments the conv launch entries share, in C order (what isf::conv_call takes).  One Python call per
+    launch: the pointers are read here, not through _lib.ptr (the training step is paced by the host)."""
+    return (xs.data_ptr(), rb.num_in, c_in, None if packed16 is None else packed16.data_ptr(), K, c_out, rb.nbr.data_ptr(),
+            rb.stride, rb.num_out, None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(),
+            None if residual is None else residual.data_ptr(), int(bool(relu)), ys.data_ptr())
+
+
 def sparse_conv_forward_f16x3(features, packed16, K, c_in, c_out, rb, scale=None, shift=None, residual=None,
                               relu=False, mode=0, order=None, table=None):
     """fp32 in / fp32 out convenience wrapper around the split-precision kernel (converts at both ends); CONV_MODE_F16_STORAGE (f16
     storage) converts through f16 rows instead of split rows.  order: tile_order(rb, c_in, c_out, mode) or None."""
     _lib.require_cuda(features)
-    f16io = _is_f16_storage(mode)
-    xs = to_half(features) if f16io else to_split(features)
-    rs = None if residual is None else (to_half(residual) if f16io else to_split(residual))
-    ys = torch.empty(rb.num_out * c_out * (2 if f16io else 4), dtype=torch.uint8, device=features.device)
+    xs, rs, ys, back = _row_format(features, residual, rb, c_out, mode)
     lib = _lib.load()
-    args = (_lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, c_out, _lib.ptr(rb.nbr), rb.stride, rb.num_out,
-            _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(rs), int(bool(relu)), _lib.ptr(ys), int(mode))
+    args = _conv_args(xs, packed16, K, c_in, c_out, rb, scale, shift, rs, relu, ys) + (int(mode),)
     if table is not None:
         _lib.check(lib.isf_sparse_conv_forward_f16x3_tiled(*args, _lib.ptr(table), _lib.stream()),
                    "isf_sparse_conv_forward_f16x3_tiled")
@@ -274,7 +310,7 @@ def sparse_conv_forward_f16x3(features, packed16, K, c_in, c_out, rb, scale=None
     else:
         _lib.check(lib.isf_sparse_conv_forward_f16x3_ordered(*args, _lib.ptr(order), _lib.stream()),
                    "isf_sparse_conv_forward_f16x3_ordered")
-    return from_half(ys, (rb.num_out, c_out)) if f16io else from_split(ys, (rb.num_out, c_out))
+    return back(ys, (rb.num_out, c_out))
 
 
 def sparse_conv_forward_dma(features, packed16, K, c_in, c_out, rb, scale=None, shift=None, residual=None, relu=False,
@@ -282,21 +318,17 @@ def sparse_conv_forward_dma(features, packed16, K, c_in, c_out, rb, scale=None, 
     """sparse_conv_forward_f16x3 on the LDS-DMA gather kernel of the narrow layers (isf_sparse_conv_forward_dma:
     c_in, c_out in {32, 64}); bit-identical results."""
     _lib.require_cuda(features)
-    f16io = _is_f16_storage(mode)
-    xs = to_half(features) if f16io else to_split(features)
-    rs = None if residual is None else (to_half(residual) if f16io else to_split(residual))
-    ys = torch.empty(rb.num_out * c_out * (2 if f16io else 4), dtype=torch.uint8, device=features.device)
+    xs, rs, ys, back = _row_format(features, residual, rb, c_out, mode)
     _lib.check(_lib.load().isf_sparse_conv_forward_dma(
-        _lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, c_out, _lib.ptr(rb.nbr), rb.stride, rb.num_out,
-        _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(rs), int(bool(relu)), _lib.ptr(ys), int(mode), _lib.ptr(order),
+        *_conv_args(xs, packed16, K, c_in, c_out, rb, scale, shift, rs, relu, ys), int(mode), _lib.ptr(order),
         _lib.stream()), "isf_sparse_conv_forward_dma")
-    return from_half(ys, (rb.num_out, c_out)) if f16io else from_split(ys, (rb.num_out, c_out))
+    return back(ys, (rb.num_out, c_out))
 
 
 def rulebook_lines(rb, taps_per_line=3):
     """(lines int32 [K / tpl, stride], mask int32 [stride], flag int32 [1]) -- the LINE-COMPRESSED form of a Rulebook's
     neighbour table (isf_rulebook_to_lines), cached on it; flag != 0: the table is not in rank order and has no such form."""
-    if getattr(rb, "_lines", None) is None:
+    def build():
         K = rb.nbr.numel() // rb.stride
         dev = rb.nbr.device
         lines = torch.empty((K // taps_per_line, rb.stride), dtype=torch.int32, device=dev)
@@ -305,8 +337,8 @@ def rulebook_lines(rb, taps_per_line=3):
         _lib.check(_lib.load().isf_rulebook_to_lines(_lib.ptr(rb.nbr), rb.stride, K, taps_per_line, rb.num_out,
                                                      _lib.ptr(lines), _lib.ptr(mask), _lib.ptr(flag), _lib.stream()),
                    "isf_rulebook_to_lines")
-        rb._lines = (lines, mask, flag)
-    return rb._lines
+        return lines, mask, flag
+    return rb.cached("lines", build)
 
 
 def lines_to_nbr(lines, mask, K, taps_per_line=3):
@@ -322,16 +354,13 @@ def sparse_conv_forward_dma_lines(features, packed16, K, c_in, c_out, rb, scale=
                                   relu=False, mode=0, taps_per_line=3):
     """sparse_conv_forward_dma reading the line-compressed table (isf_sparse_conv_forward_dma_lines); bit-identical."""
     _lib.require_cuda(features)
-    f16io = _is_f16_storage(mode)
-    xs = to_half(features) if f16io else to_split(features)
-    rs = None if residual is None else (to_half(residual) if f16io else to_split(residual))
-    ys = torch.empty(rb.num_out * c_out * (2 if f16io else 4), dtype=torch.uint8, device=features.device)
+    xs, rs, ys, back = _row_format(features, residual, rb, c_out, mode)
     lines, mask, _flag = rulebook_lines(rb, taps_per_line)
     _lib.check(_lib.load().isf_sparse_conv_forward_dma_lines(
         _lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, taps_per_line, c_out, _lib.ptr(lines), _lib.ptr(mask),
         rb.stride, rb.num_out, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(rs), int(bool(relu)), _lib.ptr(ys), int(mode),
         _lib.stream()), "isf_sparse_conv_forward_dma_lines")
-    return from_half(ys, (rb.num_out, c_out)) if f16io else from_split(ys, (rb.num_out, c_out))
+    return back(ys, (rb.num_out, c_out))
 
 
 class PartTable:
@@ -371,10 +400,7 @@ def sparse_conv_forward_parts(features, packed16, K, c_in, c_out, rb, pt, scale=
     """the launch of sparse_conv_forward_dma (dma=True) / _dma_lines (lines) / _f16x3 on the part table `pt`
     (isf_sparse_conv_forward_parts); bit-identical to them.  split_out: the raw output rows (uint8) instead of fp32."""
     _lib.require_cuda(features)
-    f16io = _is_f16_storage(mode)
-    xs = to_half(features) if f16io else to_split(features)
-    rs = None if residual is None else (to_half(residual) if f16io else to_split(residual))
-    ys = torch.empty(rb.num_out * c_out * (2 if f16io else 4), dtype=torch.uint8, device=features.device)
+    xs, rs, ys, back = _row_format(features, residual, rb, c_out, mode)
     table_nbr, mask, nx = rb.nbr, None, 0
     if lines:
         table_nbr, mask, _flag = rulebook_lines(rb, 3)
@@ -385,7 +411,7 @@ def sparse_conv_forward_parts(features, packed16, K, c_in, c_out, rb, pt, scale=
         int(mode) | (_lib.CONV_MODE_DMA_PLAN if dma else 0), _lib.ptr(pt.table), _lib.stream()), "isf_sparse_conv_forward_parts")
     if split_out:
         return ys
-    return from_half(ys, (rb.num_out, c_out)) if f16io else from_split(ys, (rb.num_out, c_out))
+    return back(ys, (rb.num_out, c_out))
 
 
 CU_CAP8_VARIANTS = (9, 15)      # isf_conv_cu_plan.variant values that work on units of <= 8 groups
@@ -396,8 +422,8 @@ def cu_plan(rb, variant=0):
     (16 groups per unit; 8 for the two-workgroups-per-CU variants): (isf_conv_cu_plan struct, the int32 buffer it points
     into).  One plan serves every 256-column layer on the rulebook."""
     cap8 = int(variant) in CU_CAP8_VARIANTS
-    key = "_cu_plan8" if cap8 else "_cu_plan"
-    if getattr(rb, key, None) is None:
+
+    def build():
         lib = _lib.load()
         K = rb.nbr.numel() // rb.stride
         n = ctypes.c_size_t(0)
@@ -407,8 +433,8 @@ def cu_plan(rb, variant=0):
         plan.variant = 9 if cap8 else 0       # read by the planner: decides the unit shape
         _lib.check(lib.isf_sparse_conv_cu_plan(_lib.ptr(rb.nbr), rb.stride, K, rb.num_out, _lib.ptr(buf),
                                                ctypes.byref(plan), _lib.stream()), "isf_sparse_conv_cu_plan")
-        setattr(rb, key, (plan, buf))
-    return getattr(rb, key)
+        return plan, buf
+    return rb.cached(("cu_plan", 8 if cap8 else 16), build)
 
 
 def cu_plan_units(rb, variant=0):
@@ -424,7 +450,6 @@ def cu_plan_units(rb, variant=0):
 def cu_plan_host(work, cus=256):
     """isf_sparse_conv_cu_plan_host: the plan arithmetic on the CPU (no device work): work [groups] int32 -> units
     [num_units, 2]."""
-    import numpy as np
     lib = _lib.load()
     work = np.ascontiguousarray(work, dtype=np.int32)
     cap = lib.isf_sparse_conv_cu_max_units(len(work), cus)
@@ -447,16 +472,13 @@ def sparse_conv_forward_cu(features, packed16, K, c_in, c_out, rb, scale=None, s
     assembly multiply phase; 9 / 10 = two 4-wave workgroups per CU over units of <= 8 groups: valid results; 1 / 2 / 3,
     11-15 timing knock-outs)."""
     _lib.require_cuda(features)
-    xs = to_split(features)
-    rs = None if residual is None else to_split(residual)
-    ys = torch.empty(rb.num_out * c_out * 4, dtype=torch.uint8, device=features.device)
+    xs, rs, ys, back = _row_format(features, residual, rb, c_out, 0)      # split rows: the kernel has no other mode
     plan, _buf = cu_plan(rb, variant)
     plan = _lib.ConvCuPlan(plan.group_masks, plan.units, plan.num_units, plan.max_units, plan.num_out, int(variant), plan.cap)
     _lib.check(_lib.load().isf_sparse_conv_forward_cu(
-        _lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, c_out, _lib.ptr(rb.nbr), rb.stride, rb.num_out,
-        _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(rs), int(bool(relu)), _lib.ptr(ys), ctypes.byref(plan),
-        _lib.stream()), "isf_sparse_conv_forward_cu")
-    return from_split(ys, (rb.num_out, c_out))
+        *_conv_args(xs, packed16, K, c_in, c_out, rb, scale, shift, rs, relu, ys), ctypes.byref(plan), _lib.stream()),
+        "isf_sparse_conv_forward_cu")
+    return back(ys, (rb.num_out, c_out))
 
 
 def sparse_conv_forward_best(features, packed16, K, c_in, c_out, rb, scale=None, shift=None, residual=None, relu=False,
@@ -481,10 +503,9 @@ def sparse_conv_trace(xs, packed16, K, c_in, c_out, rb, scale=None, shift=None, 
     cap = 8 * 255
     trace = torch.zeros((cap * 8,), dtype=torch.int64, device=xs.device)
     n = ctypes.c_int(0)
-    _lib.check(lib.isf_sparse_conv_trace(_lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, c_out, _lib.ptr(rb.nbr),
-                                         rb.stride, rb.num_out, _lib.ptr(scale), _lib.ptr(shift),
-                                         _lib.ptr(residual_split), int(bool(relu)), _lib.ptr(ys), _lib.ptr(order),
-                                         _lib.ptr(trace), cap, ctypes.byref(n), _lib.stream()), "isf_sparse_conv_trace")
+    _lib.check(lib.isf_sparse_conv_trace(*_conv_args(xs, packed16, K, c_in, c_out, rb, scale, shift, residual_split, relu, ys),
+                                         _lib.ptr(order), _lib.ptr(trace), cap, ctypes.byref(n), _lib.stream()),
+               "isf_sparse_conv_trace")
     return ys, trace[:n.value * 8].view(n.value, 8)
 
 
@@ -499,25 +520,21 @@ def sparse_conv_dma_trace(xs, packed16, K, c_in, c_out, rb, scale=None, shift=No
     ys = torch.empty(rb.num_out * c_out * 4, dtype=torch.uint8, device=xs.device)
     table, mask, stride, nx = rb.nbr, None, rb.stride, 0
     if lines:
-        lt = rulebook_lines(rb, 3)
-        if lt is not None:
-            table, mask, nx = lt[0], lt[1], 3
+        (table, mask, _flag), nx = rulebook_lines(rb, 3), 3
     cap = 8 * 1024
     trace = torch.zeros((cap * 16,), dtype=torch.int64, device=xs.device)
     n = ctypes.c_int(0)
     if part_table is not None:     # the launch on its equal-work parts (part_table(rb, c_in, c_out, lines=lines))
         _lib.check(lib.isf_sparse_conv_dma_trace_parts(
-            _lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, nx, c_out, _lib.ptr(table),
-            _lib.ptr(mask) if mask is not None else None, stride, rb.num_out, _lib.ptr(scale), _lib.ptr(shift),
-            _lib.ptr(residual_split), int(bool(relu)), _lib.ptr(ys), _lib.ptr(part_table.table), _lib.ptr(trace), cap,
-            ctypes.byref(n), _lib.stream()), "isf_sparse_conv_dma_trace_parts")
+            _lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, nx, c_out, _lib.ptr(table), _lib.ptr(mask), stride,
+            rb.num_out, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual_split), int(bool(relu)), _lib.ptr(ys),
+            _lib.ptr(part_table.table), _lib.ptr(trace), cap, ctypes.byref(n), _lib.stream()),
+            "isf_sparse_conv_dma_trace_parts")
         return ys, trace[:n.value * 16].view(n.value, 16)
-    n = ctypes.c_int(0)
     _lib.check(lib.isf_sparse_conv_dma_trace(_lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, nx, c_out, _lib.ptr(table),
-                                             _lib.ptr(mask) if mask is not None else None, stride, rb.num_out,
-                                             _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual_split), int(bool(relu)),
-                                             _lib.ptr(ys), _lib.ptr(trace), cap, ctypes.byref(n), _lib.stream()),
-               "isf_sparse_conv_dma_trace")
+                                             _lib.ptr(mask), stride, rb.num_out, _lib.ptr(scale), _lib.ptr(shift),
+                                             _lib.ptr(residual_split), int(bool(relu)), _lib.ptr(ys), _lib.ptr(trace), cap,
+                                             ctypes.byref(n), _lib.stream()), "isf_sparse_conv_dma_trace")
     return ys, trace[:n.value * 16].view(n.value, 16)
 
 
@@ -534,8 +551,7 @@ def sparse_conv_phase_trace(xs, packed16, K, c_in, c_out, rb, scale=None, shift=
     trace = torch.zeros((nbytes // 8,), dtype=torch.int64, device=xs.device)
     n, nw, dpw = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
     _lib.check(lib.isf_sparse_conv_phase_trace(
-        _lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, c_out, _lib.ptr(rb.nbr), rb.stride, rb.num_out,
-        _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual_split), int(bool(relu)), _lib.ptr(ys), _lib.ptr(order),
+        *_conv_args(xs, packed16, K, c_in, c_out, rb, scale, shift, residual_split, relu, ys), _lib.ptr(order),
         _lib.ptr(trace), nbytes, ctypes.byref(n), ctypes.byref(nw), ctypes.byref(dpw), _lib.stream()),
         "isf_sparse_conv_phase_trace")
     wg = trace[:n.value * 8].view(n.value, 8)
@@ -547,7 +563,7 @@ def stage_tables(rb):
     """(slots uint16 [K, stride], ulist int32 [stride / 64, cap], ucount int32 [stride / 64]) of a Rulebook
     (isf_rulebook_stage_tables), cached on it: the distinct input rows of every 64-row unit and where each table entry
     sits in that list -- what the LDS-staged conv kernel copies once per tile."""
-    if getattr(rb, "_stage", None) is None:
+    def build():
         lib = _lib.load()
         K = rb.nbr.numel() // rb.stride
         units = rb.stride // lib.isf_stage_unit_rows()
@@ -557,24 +573,22 @@ def stage_tables(rb):
         ucount = torch.empty((units,), dtype=torch.int32, device=dev)
         _lib.check(lib.isf_rulebook_stage_tables(_lib.ptr(rb.nbr), rb.stride, K, _lib.ptr(slots), _lib.ptr(ulist),
                                                  _lib.ptr(ucount), _lib.stream()), "isf_rulebook_stage_tables")
-        rb._stage = (slots, ulist, ucount)
-    return rb._stage
+        return slots, ulist, ucount
+    return rb.cached("stage", build)
 
 
 def sparse_conv_forward_staged(features, packed16, K, c_in, c_out, rb, scale=None, shift=None, residual=None,
                                relu=False, stage_rows=512, mode=0):
     """sparse_conv_forward_f16x3 with the tile's input rows staged in LDS (isf_sparse_conv_forward_staged)."""
     _lib.require_cuda(features)
-    xs = to_split(features)
-    rs = to_split(residual) if residual is not None else None
-    ys = torch.empty(rb.num_out * c_out * 4, dtype=torch.uint8, device=features.device)
+    xs, rs, ys, back = _row_format(features, residual, rb, c_out, 0)      # split rows whatever the mode
     slots, ulist, ucount = stage_tables(rb)
     lib = _lib.load()
     _lib.check(lib.isf_sparse_conv_forward_staged(
         _lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, c_out, _lib.ptr(slots), rb.stride, _lib.ptr(ulist),
         _lib.ptr(ucount), rb.num_out, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(rs), int(bool(relu)), _lib.ptr(ys),
         int(stage_rows), int(mode), _lib.stream()), "isf_sparse_conv_forward_staged")
-    return from_split(ys, (rb.num_out, c_out))
+    return back(ys, (rb.num_out, c_out))
 
 
 def sparse_conv_forward(features, packed, K, c_in, c_out, rb, scale=None, shift=None, residual=None, relu=False):
@@ -583,9 +597,8 @@ def sparse_conv_forward(features, packed, K, c_in, c_out, rb, scale=None, shift=
     out = torch.empty((rb.num_out, c_out), dtype=torch.float32, device=features.device)
     lib = _lib.load()
     _lib.check(lib.isf_sparse_conv_forward_packed(
-        _lib.ptr(features), rb.num_in, c_in, _lib.ptr(packed), K, c_out, _lib.ptr(rb.nbr), rb.stride,
-        rb.num_out, _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), int(bool(relu)), _lib.ptr(out),
-        _lib.stream()), "isf_sparse_conv_forward_packed")
+        *_conv_args(features, packed, K, c_in, c_out, rb, scale, shift, residual, relu, out), _lib.stream()),
+        "isf_sparse_conv_forward_packed")
     return out
 
 
@@ -594,37 +607,26 @@ def sparse_conv_split(xs, packed16, K, c_in, c_out, rb, ordered=True, mode=0):
     sparse_conv_forward_best -- LDS-DMA gathers for the narrow shapes, tile-order table for one-round launches
     (ordered=False: tiles in launch order; the training path rebuilds its rulebooks every step and the three kernels that
     build a table -- 0.6 ms per step over the encoder -- cost more than the 2 % an ordered launch gains)."""
-    lib = _lib.load()
-    if not ordered:
-        ys = torch.empty(rb.num_out * c_out * 4, dtype=torch.uint8, device=xs.device)
-        args = (_lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, c_out, _lib.ptr(rb.nbr), rb.stride, rb.num_out,
-                None, None, None, 0, _lib.ptr(ys), int(mode))   # CONV_MODE_F16: single-pass f16 (hi halves only)
-        if c_in <= 64 and c_out <= 64:
-            _lib.check(lib.isf_sparse_conv_forward_dma(*args, None, _lib.stream()), "isf_sparse_conv_forward_dma")
-        else:
-            _lib.check(lib.isf_sparse_conv_forward_f16x3(*args, _lib.stream()), "isf_sparse_conv_forward_f16x3")
-        return ys
-    assert mode == 0, "ordered launches: fp32-class mode only (the training path passes ordered=False)"
+    assert not ordered or mode == 0, "ordered launches: fp32-class mode only (the training path passes ordered=False)"
+    narrow = c_in <= 64 and c_out <= 64
     ys = torch.empty(rb.num_out * c_out * 4, dtype=torch.uint8, device=xs.device)
-    args = (_lib.ptr(xs), rb.num_in, c_in, _lib.ptr(packed16), K, c_out, _lib.ptr(rb.nbr), rb.stride, rb.num_out,
-            None, None, None, 0, _lib.ptr(ys), 0)
-    if c_in <= 64 and c_out <= 64:
-        _lib.check(lib.isf_sparse_conv_forward_dma(*args, _lib.ptr(tile_order(rb, c_in, c_out, 0, dma=True)),
-                                                   _lib.stream()), "isf_sparse_conv_forward_dma")
+    order = tile_order(rb, c_in, c_out, 0, dma=narrow) if ordered else None
+    # (mode CONV_MODE_F16: single-pass f16, hi halves only)
+    args = _conv_args(xs, packed16, K, c_in, c_out, rb, None, None, None, False, ys) + (int(mode),)
+    if narrow:
+        name, args = "isf_sparse_conv_forward_dma", args + (_lib.ptr(order),)
+    elif order is None:
+        name = "isf_sparse_conv_forward_f16x3"
     else:
-        order = tile_order(rb, c_in, c_out, 0)
-        if order is None:
-            _lib.check(lib.isf_sparse_conv_forward_f16x3(*args, _lib.stream()), "isf_sparse_conv_forward_f16x3")
-        else:
-            _lib.check(lib.isf_sparse_conv_forward_f16x3_ordered(*args, _lib.ptr(order), _lib.stream()),
-                       "isf_sparse_conv_forward_f16x3_ordered")
+        name, args = "isf_sparse_conv_forward_f16x3_ordered", args + (_lib.ptr(order),)
+    _lib.check(getattr(_lib.load(), name)(*args, _lib.stream()), name)
     return ys
 
 
 def pair_lists(rb):
     """(indice_pairs int32 [K, 2, cap], indice_num int32 [K], cap) of a Rulebook (isf_rulebook_pair_lists): the spconv-1
     interchange format the reference's backward walks, cached on the rulebook (every layer of a level shares it)."""
-    if getattr(rb, "_pairs", None) is None:
+    def build():
         lib = _lib.load()
         K = rb.nbr.numel() // rb.stride
         cap = lib.isf_pair_list_capacity(rb.num_in, rb.num_out)
@@ -632,8 +634,8 @@ def pair_lists(rb):
         num = torch.empty((K,), dtype=torch.int32, device=rb.nbr.device)
         _lib.check(lib.isf_rulebook_pair_lists(_lib.ptr(rb.nbr), rb.stride, rb.num_out, K, cap, _lib.ptr(pairs),
                                                _lib.ptr(num), _lib.stream()), "isf_rulebook_pair_lists")
-        rb._pairs = (pairs, num, cap)
-    return rb._pairs
+        return pairs, num, cap
+    return rb.cached("pairs", build)
 
 
 def grad_to_split(g):
@@ -682,28 +684,21 @@ WGRAD_F16X3 = True
 TRAINING_KERNELS = True
 
 
+def _transpose(rb):
+    """Rulebook.transposed(), uncached: nbr_t [K, stride_t] (input row -> output row per tap), num_in / num_out swapped"""
+    lib = _lib.load()
+    K = rb.nbr.numel() // rb.stride
+    st = lib.isf_nbr_stride(max(rb.num_in, 1))
+    nbr_t = torch.empty((K, st), dtype=torch.int32, device=rb.nbr.device)
+    _lib.check(lib.isf_transpose_rulebook(_lib.ptr(rb.nbr), rb.stride, rb.num_out, K, rb.num_in, _lib.ptr(nbr_t),
+                                          st, _lib.stream()), "isf_transpose_rulebook")
+    return Rulebook(nbr_t, st, rb.num_out, rb.num_in, None, None)
+
+
 def transposed_nbr(rb):
-    """nbr_t [K, stride_t] of a Rulebook (isf_transpose_rulebook), cached on it: input row -> output row per tap."""
-    if getattr(rb, "nbr_t", None) is None:
-        lib = _lib.load()
-        K = rb.nbr.numel() // rb.stride
-        st = lib.isf_nbr_stride(max(rb.num_in, 1))
-        nbr_t = torch.empty((K, st), dtype=torch.int32, device=rb.nbr.device)
-        _lib.check(lib.isf_transpose_rulebook(_lib.ptr(rb.nbr), rb.stride, rb.num_out, K, rb.num_in, _lib.ptr(nbr_t),
-                                              st, _lib.stream()), "isf_transpose_rulebook")
-        rb.nbr_t, rb.stride_t = nbr_t, st
-    return rb.nbr_t, rb.stride_t
-
-
-def _f16x3_shape(c_in, c_out):
-    return c_in in (32, 64, 128, 256) and c_out in (32, 64, 128, 256)
-
-
-class _TransposedRulebook:
-    """the view of a Rulebook the dX pass needs: rows of the conv's OUTPUT feed rows of its INPUT"""
-
-    def __init__(self, nbr_t, stride_t, num_out, num_in):
-        self.nbr, self.stride, self.num_in, self.num_out = nbr_t, stride_t, num_out, num_in
+    """(nbr_t [K, stride_t], stride_t) of a Rulebook: the table of its cached transposed view."""
+    rbt = rb.transposed()
+    return rbt.nbr, rbt.stride
 
 
 # Packed copies follow derived.py's rule: they are keyed on the parameter's version counter and address.  torch.optim
@@ -726,6 +721,21 @@ def _packed_pair(weight, w, K, c_in, c_out):
     return s["pair"]
 
 
+def split_backward(xs, gs, sc, rb, packed_t, K, c_in, c_out, half, want_dx, want_dw, wshape, wgrad_flags=0):
+    """(dX, dW) of a conv whose forward saved its split input rows `xs`.  gs, sc = grad_to_split(grad_out): one scaled
+    split of the gradient serves dX (the forward kernel over the transposed rulebook with the per-tap transposed filters
+    `packed_t`) and dW (isf_spconv_wgrad16.hip, [*wshape]); the scale is a device scalar, undone in either's last pass.
+    half: single-pass f16 arithmetic; wgrad_flags: further WGRAD_* bits (a dense grid's WGRAD_FULL_TAPS)."""
+    grad_in = grad_w = None
+    if want_dx:
+        grad_in = from_split_scaled(sparse_conv_split(gs, packed_t, K, c_out, c_in, rb.transposed(), ordered=False,
+                                                      mode=_lib.CONV_MODE_F16 if half else 0), (rb.num_in, c_in), sc[1:])
+    if want_dw:
+        grad_w = sparse_conv_backward_filter_f16x3(xs, c_in, gs, c_out, rb, sc[1:], wshape,
+                                                   mode=(_lib.WGRAD_F16 if half else 0) | wgrad_flags)
+    return grad_in, grad_w
+
+
 class SparseConvFunction(torch.autograd.Function):
     """SparseConvFunction / SubMConvFunction of the reference (ops/spconv/functional.py:22-97): forward =
     indice_conv, backward = indice_conv_backward -> (input_bp, filters_bp), on the HIP kernels.  `weight` is the
@@ -744,18 +754,18 @@ class SparseConvFunction(torch.autograd.Function):
         w = weight.detach().float().contiguous()
         features = features.detach().float().contiguous()
         xs = None
-        if _f16x3_shape(c_in, c_out) and WGRAD_F16X3 and rb.num_out > 0 and rb.num_in > 0:
+        if f16x3_supported(c_in, c_out) and WGRAD_F16X3 and rb.num_out > 0 and rb.num_in > 0:
             # split rows once: the conv reads them, and so will dW in the backward pass (saved INSTEAD of the fp32 rows)
             xs = to_split(features)
             out = from_split(sparse_conv_split(xs, _packed_pair(weight, w, K, c_in, c_out)[0], K, c_in, c_out, rb, ordered=False,
                                                mode=_lib.CONV_MODE_F16 if half else 0), (rb.num_out, c_out))
-        elif _f16x3_shape(c_in, c_out):    # the inference kernel (f16x3 split MFMA): 3-4x the fp32-MFMA kernel's rate
+        elif f16x3_supported(c_in, c_out):    # the inference kernel (f16x3 split MFMA): 3-4x the fp32-MFMA kernel's rate
             out = sparse_conv_forward_best(features, pack_filters_f16x3(w), K, c_in, c_out, rb)
         else:
             out = torch.empty((rb.num_out, c_out), dtype=torch.float32, device=features.device)
             _lib.check(_lib.load().isf_sparse_conv_forward(
-                _lib.ptr(features), rb.num_in, c_in, _lib.ptr(w), K, c_out, _lib.ptr(rb.nbr), rb.stride, rb.num_out,
-                None, None, None, 0, _lib.ptr(out), _lib.stream()), "isf_sparse_conv_forward")
+                *_conv_args(features, w, K, c_in, c_out, rb, None, None, None, False, out), _lib.stream()),
+                "isf_sparse_conv_forward")
         ctx.split_saved = xs is not None
         ctx.half = bool(half) and xs is not None
         ctx.packed_t = _packed_pair(weight, w, K, c_in, c_out)[1] if xs is not None else None   # dX's filters
@@ -773,35 +783,22 @@ class SparseConvFunction(torch.autograd.Function):
         lib = _lib.load()
         grad_in = grad_w = None
         if ctx.split_saved:
-            # one scaled split of the gradient serves dX (the forward kernel over the transposed rulebook with the
-            # transposed filters) and dW (isf_spconv_wgrad16.hip); the scale is a device scalar, undone in the last pass
             gs, sc = grad_to_split(g)
-            if ctx.needs_input_grad[0]:
-                nbr_t, st = transposed_nbr(rb)
-                rbt = rb.__dict__.get("_rbt")
-                if rbt is None:      # cached: its tile-order tables are built once per rulebook, not once per layer
-                    rbt = rb._rbt = _TransposedRulebook(nbr_t, st, rb.num_out, rb.num_in)
-                grad_in = from_split_scaled(sparse_conv_split(gs, ctx.packed_t, K, c_out, c_in, rbt, ordered=False,
-                                                              mode=_lib.CONV_MODE_F16 if ctx.half else 0),
-                                            (rb.num_in, c_in), sc[1:])
-            if ctx.needs_input_grad[1]:
-                grad_w = sparse_conv_backward_filter_f16x3(features, c_in, gs, c_out, rb, sc[1:], ctx.wshape,
-                                                           mode=_lib.WGRAD_F16 if ctx.half else 0)
-            return grad_in, grad_w, None, None
+            return (*split_backward(features, gs, sc, rb, ctx.packed_t, K, c_in, c_out, ctx.half, ctx.needs_input_grad[0],
+                                    ctx.needs_input_grad[1], ctx.wshape), None, None)
         if ctx.needs_input_grad[0]:
-            nbr_t, st = transposed_nbr(rb)
-            if _f16x3_shape(c_out, c_in):
+            rbt = rb.transposed()
+            if f16x3_supported(c_out, c_in):
                 # dX[i] = sum_k g[nbr_t[k][i]] W_k^T: the forward kernel over the transposed rulebook with the
                 # per-tap transposed filters.  Its operands travel as f16 hi + lo halves, so the gradient is brought
                 # into f16's normal range by a power of two first (exact; see _lib.pow2_rescale) and scaled back
                 gs, sc = _lib.pow2_rescale(g)
                 wt = w.view(K, c_in, c_out).transpose(1, 2).contiguous().view(*ctx.wshape[:-2], c_out, c_in)
-                rbt = _TransposedRulebook(nbr_t, st, rb.num_out, rb.num_in)
                 grad_in = sparse_conv_forward_best(gs, pack_filters_f16x3(wt), K, c_out, c_in, rbt) / sc
             else:   # fp32-MFMA kernel: no f16 halves, gradients of any magnitude are safe
                 grad_in = torch.empty((rb.num_in, c_in), dtype=torch.float32, device=g.device)
                 _lib.check(lib.isf_sparse_conv_backward_input(_lib.ptr(g), rb.num_out, c_out, _lib.ptr(w), K, c_in,
-                                                              _lib.ptr(nbr_t), st, rb.num_in, _lib.ptr(grad_in),
+                                                              _lib.ptr(rbt.nbr), rbt.stride, rb.num_in, _lib.ptr(grad_in),
                                                               _lib.stream()), "isf_sparse_conv_backward_input")
         if ctx.needs_input_grad[1]:
             grad_w = torch.empty(ctx.wshape, dtype=torch.float32, device=g.device)

@@ -26,7 +26,7 @@ from . import head_loss
 from ._lib import require_cuda as _lib_require_cuda
 from .dense_conv import PackedConvBN, SplitMap
 from .fusion_modules import PositionEmbeddingLearned, _SelfAttn
-from .spconv import from_split
+from .spconv import F16X3_CHANNELS, from_split
 
 
 class _ConvModule1d(nn.Sequential):
@@ -176,7 +176,7 @@ class TransFusionHeadV2(nn.Module):
             if len(seq) != 2 or not isinstance(seq[0], _ConvModule1d) or not isinstance(seq[1], nn.Conv1d):
                 return None
             conv, bn, last = seq[0].conv, seq[0].bn, seq[1]
-            if conv.weight.shape[0] != 64 or conv.weight.shape[1] not in (32, 64, 128, 256):
+            if conv.weight.shape[0] != 64 or conv.weight.shape[1] not in F16X3_CHANNELS:
                 return None
             scale = (bn.weight / torch.sqrt(bn.running_var + bn.eps)).detach().float()
             heads.append((name, conv.weight.detach().float()[:, :, 0] * scale[:, None],

@@ -251,7 +251,7 @@ def test_packed_weight_caches_follow_the_fused_step(dev):
     from isfusion_amd import dense_train, optim, spconv
     net = build_path().to(dev).train()
     sw = next(m.weight for m in net.pts_middle_encoder.modules()
-              if isinstance(m, spconv.SubMConv3d) and spconv._f16x3_shape(m.weight.shape[-2], m.weight.shape[-1]))
+              if isinstance(m, spconv.SubMConv3d) and spconv.f16x3_supported(m.weight.shape[-2], m.weight.shape[-1]))
     dw = next(m.weight for m in net.modules() if dense_train.supported(m))
 
     def spack():

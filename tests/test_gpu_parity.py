@@ -807,7 +807,7 @@ def test_conv_tile_order_is_a_per_part_permutation_and_keeps_the_bits(dev):
             continue
         parts = 4 if cout == 256 else 8
         o = order.cpu().numpy().reshape(parts, -1)
-        work = rb._tile_order[(cin, cout, 0)][1].cpu().numpy().reshape(parts, -1)
+        work = sp.tile_work(rb, cin, cout).cpu().numpy().reshape(parts, -1)
         tiles = o.shape[1]
         assert tiles > 32
         for q in range(parts):

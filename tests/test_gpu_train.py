@@ -519,7 +519,7 @@ def _stack_case(name):
 
 @pytest.mark.parametrize("transpose", [False, True])
 @pytest.mark.parametrize("name", ["convmodule_768", "second_block", "narrow", "single_bias"])
-def test_dense_conv_stack_training_matches_float64_stock_modules(dev, name, transpose):
+def test_dense_conv_stack_training_matches_float64_stock_modules(dev, name, transpose, monkeypatch):
     """dense_train.conv_stack (sparse-conv kernels over the dense grid: forward, dX over the transposed rulebook, dW on the
     f16 matrix cores, fused BatchNorm on token rows) against the same nn modules in float64 on the CPU: output, input
     gradient, every parameter gradient, BatchNorm running statistics.  transpose: the stack applied to the spatially
@@ -545,6 +545,26 @@ def test_dense_conv_stack_training_matches_float64_stock_modules(dev, name, tran
         assert rel_err(p.grad, q.grad.float()) < 2e-4, n
     for (n, b), (_, c) in zip(net.named_buffers(), ref.named_buffers()):
         assert rel_err(b.float(), c.float()) < 1e-5, n
+    if name == "narrow":      # one Rulebook per grid geometry: the inference PackedConvBN and conv_stack get the same object
+        from isfusion_amd import dense_conv as dc
+        seen = []
+
+        def recording(*a, _grid=dc.grid_rulebook):
+            seen.append(_grid(*a))
+            return seen[-1]
+        monkeypatch.setattr(dc, "grid_rulebook", recording)
+        monkeypatch.setattr(dt, "grid_rulebook", recording)
+        B, _, H, W = x.shape
+        for stride in (1, 2):
+            conv = torch.nn.Conv2d(128, 64, 3, stride=stride, padding=1, bias=False).to(dev)
+            with torch.no_grad():
+                out = dc.PackedConvBN(conv, None, False)(dc.SplitMap.from_nchw(xg.detach()), transpose)
+            dt.conv_stack(conv, xg, transpose)
+            rb = recording(xg.device, B, H, W, stride)
+            assert len(seen) == 3 * stride and all(r is rb for r in seen[-3:])
+            assert rb.out_shape == (out.H, out.W) == ((H - 1) // stride + 1, (W - 1) // stride + 1)
+            assert (rb.num_in, rb.num_out) == (B * H * W, B * out.H * out.W)
+        assert seen[0] is not seen[-1]
 
 
 def test_dense_conv_stack_under_autocast_and_fallbacks(dev):

@@ -466,7 +466,8 @@ def test_sparse_conv_modules_use_the_half_kernels_under_autocast_only(dev):
 
 def test_training_path_without_the_f16_wgrad_still_works(dev):
     """spconv.WGRAD_F16X3 = False restores the round-2 backward (fp32-MFMA dW, torch-op gradient scaling); both paths
-    agree to fp32 rounding"""
+    agree to fp32 rounding.  Its dX runs on the rulebook's cached transposed view: a second call reuses the view and the
+    tile order built on it, and gives the same bits."""
     from isfusion_amd import spconv
     rng = np.random.default_rng(3)
     B, shape, n, cin, cout = 2, [9, 24, 24], 1500, 64, 128
@@ -478,17 +479,22 @@ def test_training_path_without_the_f16_wgrad_still_works(dev):
     gout = torch.randn(n, cout, device=dev) * 1e-6
     res = []
     try:
-        for flag in (True, False):
+        for flag in (True, False, False):
             spconv.WGRAD_F16X3 = flag
             x, wt = feats.clone().requires_grad_(), w.clone().requires_grad_()
             out = spconv.SparseConvFunction.apply(x, wt, rb)
             out.backward(gout)
-            res.append((out.detach(), x.grad, wt.grad))
+            res.append((out.detach(), x.grad, wt.grad, rb.transposed(), dict(rb.transposed().derived)))
     finally:
         spconv.WGRAD_F16X3 = True
     assert torch.equal(res[0][0], res[1][0])
-    for a, b in zip(res[0][1:], res[1][1:]):
+    for a, b in zip(res[0][1:3], res[1][1:3]):
         assert float((a - b).abs().max()) < 1e-4 * float(b.abs().max())
+    assert res[0][3] is res[1][3] is res[2][3] and (res[0][3].num_in, res[0][3].num_out) == (rb.num_out, rb.num_in)
+    # the split path launches in launch order and builds nothing; the cross-check's dX builds one tile order (128 -> 64), once
+    assert res[0][4] == {} and list(res[1][4]) == [("tile_order", cout, cin, 0)] and res[2][4].keys() == res[1][4].keys()
+    assert all(res[2][4][k] is v for k, v in res[1][4].items())
+    assert all(torch.equal(a, b) for a, b in zip(res[1][:3], res[2][:3]))
 
 
 def test_sparse_encoder_training_step_matches_torch_dense_autograd(dev):
@@ -537,6 +543,42 @@ def test_sparse_encoder_training_step_matches_torch_dense_autograd(dev):
     assert (x.grad - xr.grad).abs().max().item() < 1e-4 * max(1.0, xr.grad.abs().max().item())
     for conv, w in zip(convs, grads_ref):
         assert (conv.weight.grad - w.grad).abs().max().item() < 1e-4 * max(1.0, w.grad.abs().max().item())
+
+
+def test_sparse_encoder_training_step_shares_one_transposed_view_and_pair_list_per_rulebook(dev, monkeypatch):
+    """two SubM 32 -> 32 layers on one indice_key + one strided 32 -> 64 conv, one forward and backward: both SubM layers'
+    dX runs on the SAME Rulebook.transposed() object, the level's rulebook caches exactly one transposed table and one
+    pair list, and the strided layer's rulebook holds its own pair of them"""
+    import isfusion_amd as m
+    from isfusion_amd import spconv
+    rng = np.random.default_rng(18)
+    B, shape, n = 1, [8, 16, 16], 300
+    cells = np.sort(rng.choice(B * int(np.prod(shape)), n, replace=False))
+    idx = np.stack(np.unravel_index(cells, (B, *shape)), 1).astype(np.int32)
+    convs = [m.SubMConv3d(32, 32, 3, padding=1, bias=False, indice_key="subm1").to(dev),
+             m.SubMConv3d(32, 32, 3, padding=1, bias=False, indice_key="subm1").to(dev),
+             m.SparseConv3d(32, 64, 3, stride=2, padding=1, bias=False, indice_key="down").to(dev)]
+    seen = []
+
+    def recording(xs, packed16, K, c_in, c_out, rb, *a, _split=spconv.sparse_conv_split, **k):
+        seen.append(rb)
+        return _split(xs, packed16, K, c_in, c_out, rb, *a, **k)
+    monkeypatch.setattr(spconv, "sparse_conv_split", recording)
+    x = _T(rng.normal(size=(n, 32)).astype(np.float32), dev).requires_grad_()
+    t = m.SparseConvTensor(x, _T(idx, dev), shape, B)
+    for conv in convs:
+        t = conv(t)
+    t.features.square().mean().backward()
+    level, down = t.indice_dict["subm1"], t.indice_dict["down"]
+    assert level is not down and down.num_out == t.features.shape[0] > 0
+    assert len(seen) == 6 and all(a is b for a, b in zip(seen, (level, level, down, down.transposed(), level.transposed(),
+                                                                level.transposed())))
+    for rb in (level, down):
+        assert set(rb.derived) == {"transposed", "pairs"}
+        assert rb.transposed().nbr is spconv.transposed_nbr(rb)[0] and rb.transposed().derived == {}
+        assert (rb.transposed().num_in, rb.transposed().num_out) == (rb.num_out, rb.num_in)
+    assert level.transposed() is not down.transposed() and level.derived["pairs"] is not down.derived["pairs"]
+    assert float(x.grad.abs().max()) > 0 and all(float(c.weight.grad.abs().max()) > 0 for c in convs)
 
 
 # ------------------------------------------------------------------------------------------- MSDA backward (8f #2)

@@ -43,6 +43,35 @@ def test_ops_refuse_cpu_tensors():
         m.DynamicScatter([1, 1, 1], [0, 0, 0, 1, 1, 1], True)(torch.rand(4, 3), torch.zeros(4, 3, dtype=torch.int32))
 
 
+def test_rulebook_cache_builds_once_per_key_and_travels_with_the_active_set():
+    """Rulebook.cached(key, build) runs build once per key (a None result counts) and hands the same object back;
+    replace_feature and a SubM layer's output share the tensor's rulebook dict, so what is cached on a rulebook serves every
+    layer on that active set.  No library call: CPU tensors."""
+    from isfusion_amd import spconv
+    rb = spconv.Rulebook(torch.zeros((27, 128), dtype=torch.int32), 128, 5, 5, torch.zeros((5, 4), dtype=torch.int32), [4, 4, 4])
+    assert rb.derived == {}
+    calls = []
+
+    def build(value):
+        calls.append(value)
+        return value
+    table = object()
+    assert rb.cached("a", lambda: build(table)) is table and rb.cached("a", lambda: build(object())) is table
+    assert rb.cached(("b", 32, 64), lambda: build(None)) is None and rb.cached(("b", 32, 64), lambda: build(1)) is None
+    assert calls == [table, None] and set(rb.derived) == {"a", ("b", 32, 64)}
+    view = spconv.Rulebook(rb.nbr, rb.stride, rb.num_out, rb.num_in, None, None)
+    rb.derived["transposed"] = view
+    assert rb.transposed() is view and spconv.transposed_nbr(rb) == (view.nbr, view.stride)
+    x = spconv.SparseConvTensor(torch.zeros(5, 16), rb.out_indices, [4, 4, 4], 1)
+    x._rulebooks["subm", (3, 3, 3), (4, 4, 4)] = rb
+    conv = spconv.SubMConv3d(16, 32, 3, padding=1, bias=False, indice_key="k")
+    assert conv.rulebook_for(x) is rb
+    for y in (x.replace_feature(torch.ones(5, 16)), conv._wrap(x, torch.zeros(5, 32), rb)):
+        assert y._rulebooks is x._rulebooks and conv.rulebook_for(y).derived["a"] is table
+    down = spconv.SparseConv3d(16, 32, 3, stride=2, padding=1, bias=False)
+    assert down._wrap(x, torch.zeros(5, 32), rb)._rulebooks is not x._rulebooks      # another active set
+
+
 def test_state_dict_keys_match_reference_layout():
     import isfusion_amd as m
     lb = m.LidarBranch()

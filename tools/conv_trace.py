@@ -184,7 +184,7 @@ def main():
     order = spconv.tile_order(rb, C, C)
     print(f"level {args.level}: {rb.num_out} rows, {C} -> {C}; tile order {'built' if order is not None else 'not applicable'}")
     if order is not None:
-        work = rb._tile_order[(C, C, 0)][1].cpu().numpy()
+        work = spconv.tile_work(rb, C, C).cpu().numpy()
         print(f"   tile work (row group, tap) pairs: mean {work.mean():.0f} min {work.min()} max {work.max()}")
     out = {}
     for name, o in (("launch order", None), ("tile order", order)):

@@ -73,7 +73,7 @@ def main():
             return t0.elapsed_time(t1) / n
 
         def build_pairs():
-            rb._pairs = None
+            rb.derived.pop("pairs", None)
             sp.pair_lists(rb)
         ms_pairs = timed(build_pairs)
         ms_split = timed(lambda: sp.grad_to_split(g))
