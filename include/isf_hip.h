@@ -1293,6 +1293,32 @@ int isf_swin_window_attention(const float* qkv, const float* qkv_bias, const flo
                               int width, int channels, int heads, int window, int shift, float scale, float* out,
                               isf_stream_t stream);
 
+/* f16 inference mode of the Swin-T backbone (isf_swin.hip, isf_swin_f16.hip) -----------------------------------
+ * What the reference computes for SwinTransformer under mmcv's fp16 machinery (auto_fp16 / torch.autocast(float16):
+ * half nn.Linear / Conv2d / matmul, swin.py:20-368, utils/transformer.py:134-400), with the residual stream, LayerNorm
+ * statistics, softmax, GELU, accumulation and the epilogue arithmetic in fp32.  Every store to an f16 tensor
+ * saturates at +-65504 instead of producing inf.
+ * isf_pack_linear_f16 replaces weight.half(): weight [out, in] (torch layout, fp32) -> one plane of f16 MFMA
+ *   fragments, isf_packed_linear_f16_bytes(out, in) bytes, 16-byte aligned.  out % 16 == 0, in % 32 == 0.
+ * isf_swin_gemm_f16 replaces the half nn.Linear / Conv2d of the mode: isf_swin_gemm with ONE matrix instruction per
+ *   product.  Same loader, epilogue and argument meanings; packed_weight_f16 from isf_pack_linear_f16.  ROWS, PATCH and
+ *   MERGE loaders (no UPCAT), y_hw == 0.  a_is_f16 != 0: a->x (declared const float*) points to _Float16 rows
+ *   [num_rows, a->ldx] with a->ldx counted in f16 ELEMENTS (>= k, % 8 == 0, x 16-byte aligned), ROWS loader without
+ *   the LayerNorm prologue; else the loader's fp32 values are rounded to f16 after the prologue.  y_is_f16 != 0: y is
+ *   f16 rows [num_rows, ldy] (ldy in f16 elements, ROWS loader only), else fp32 rows.
+ * isf_swin_window_attention_f16 replaces ShiftWindowMSA + WindowMSA after the half qkv Linear: isf_swin_window_attention
+ *   on f16 qkv rows [batch*height*width, 3 channels] -> f16 out rows [batch*height*width, channels], on the matrix
+ *   cores.  qkv_bias (fp32, NULL = none) and rel_bias (fp32 [heads, 49, 49]) as there; scores and softmax in fp32, the
+ *   probabilities rounded to f16 for the second product.  qkv and qkv_bias 16-byte aligned. */
+size_t isf_packed_linear_f16_bytes(int out_features, int in_features);
+int isf_pack_linear_f16(const float* weight, int out_features, int in_features, void* packed, isf_stream_t stream);
+int isf_swin_gemm_f16(const isf_swin_a* a, int a_is_f16, int num_rows, int k, const void* packed_weight_f16,
+                      int out_features, const float* scale, const float* shift, int activation, const float* residual,
+                      void* y, int y_is_f16, int ldy, int y_hw, isf_stream_t stream);
+int isf_swin_window_attention_f16(const void* qkv, const float* qkv_bias, const float* rel_bias, int batch, int height,
+                                  int width, int channels, int heads, int window, int shift, float scale, void* out,
+                                  isf_stream_t stream);
+
 /* Backward of the neck's top-down step (isf_swin_train.hip) --------------------------------------------------
  * The 1x1 lateral conv over cat([fine, F.interpolate(coarse, bilinear, align_corners=True)]) (generalized_lss.py:83-100)
  * under autograd: upsample_bilinear2d_backward + cat backward + the conv's wgrad / dgrad.  With output-gradient token

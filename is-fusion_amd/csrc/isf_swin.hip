@@ -17,6 +17,12 @@
 //                        product, fp32 accumulate (as isf_linear.hip); weights packed by isf_pack_linear.
 //                        tiling: workgroup 128 rows x 64 columns, 4 waves of 32 x 64; A (split into hi / lo halves by
 //                        the loader) and B staged through a double-buffered LDS ring, one 32-deep K step per stage.
+//   isf_swin_gemm_f16    the same kernel template in the f16 inference mode (SwinTransformer.set_precision("f16")): ONE
+//                        v_mfma_f32_16x16x32_f16 per product.  The loader converts its fp32 rows (after the LayerNorm
+//                        prologue) to f16, or reads f16 rows as they are; the weight is one f16 plane
+//                        (isf_pack_linear_f16); accumulation and the epilogue stay fp32; the output rows are fp32 (into
+//                        the residual stream) or f16 (qkv, the FFN hidden).  Every store to an f16 tensor saturates at
+//                        +-65504 instead of producing inf.  Window attention of this mode: isf_swin_f16.hip.
 //   isf_swin_row_stats   mean / rstd of the loader's rows (one wave per row, two passes in fp32)
 //   isf_swin_layernorm   LayerNorm of token rows, stored as rows or NCHW (patch_norm, the out_indices norms)
 //   isf_swin_window_attention  (shifted) window attention on the token-major qkv: padding, cyclic shift, window
@@ -26,6 +32,7 @@
 #include <stdlib.h>
 
 #include "isf_common.h"
+#include "isf_f16.h"
 
 namespace isf {
 
@@ -113,12 +120,21 @@ __device__ __forceinline__ void swin_a_slot(int t, int i, int& rl, int& kg) {
   else { rl = t & 127; kg = ((t >> 7) << 1) + i; }
 }
 
-template <int MODE, bool LN, bool RS = false>
+// Operand precision of swin_gemm_kernel.  X3: f16 hi / lo split of both operands, three products (the default mode).
+// F16 / F16_ROWS (isf_swin_gemm_f16, the f16 inference mode): one product -- the loader delivers only the hi half of the
+// fp32 source (F16), or a.x points to f16 rows [M, ldx] that are staged as they are, 8 elements per 16-byte load
+// (F16_ROWS); the weight is one f16 plane (isf_pack_linear_f16, no scale), the LDS ring holds half the bytes per K step.
+// Y16: the output rows are f16, stored saturating (sat_f16).  Accumulation and the epilogue arithmetic stay fp32.
+enum { SWIN_PREC_X3 = 0, SWIN_PREC_F16 = 1, SWIN_PREC_F16_ROWS = 2 };
+
+template <int MODE, bool LN, bool RS = false, int PREC = SWIN_PREC_X3, bool Y16 = false>
 __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int K, const uint4* __restrict__ wp,
                                                          const float* __restrict__ w_inv_scale, int N, SwinEpi ep,
                                                          float* __restrict__ y) {
-  __shared__ uint4 as_[2][2][4][SW_BM];   // [buf][hi|lo][k group][row]
-  __shared__ uint4 bs_[2][4][128];        // [buf][column tile][hi 0..63 | lo 64..127]
+  constexpr int NP = PREC == SWIN_PREC_X3 ? 2 : 1;   // operand planes (hi | lo, or hi alone)
+  constexpr int TS = 64 * NP;                        // uint4 per packed column tile and K step
+  __shared__ uint4 as_[2][NP][4][SW_BM];  // [buf][hi|lo][k group][row]
+  __shared__ uint4 bs_[2][4][TS];         // [buf][column tile][hi 0..63 | lo 64..127]
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int ntiles = N >> 4;
   const int nt0 = blockIdx.x * 4;
@@ -133,33 +149,68 @@ __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int
     if (LN && rr[i] < M) { mean[i] = a.ln_stats[2 * rr[i]]; rstd[i] = a.ln_stats[2 * rr[i] + 1]; }
   }
   sf8 av[2];
-  uint4 bv[2];
+  uint4 a16[2];   // F16_ROWS: the staged f16 row pieces
+  uint4 bv[NP];
   auto fetch = [&](int ks) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int k0 = ks * 32 + kg[i] * 8;
-      av[i] = rr[i] < M ? swin_load_a<MODE>(a, rr[i], k0) : sf8{0, 0, 0, 0, 0, 0, 0, 0};
-      if (LN && rr[i] < M) {
-        const sf8 g = ld8(a.ln_gamma + k0), be = ld8(a.ln_beta + k0);
-        av[i] = (av[i] - mean[i]) * rstd[i] * g + be;
+      if constexpr (PREC == SWIN_PREC_F16_ROWS) {
+        a16[i] = rr[i] < M ? *reinterpret_cast<const uint4*>(reinterpret_cast<const _Float16*>(a.x) +
+                                                             (size_t)rr[i] * a.ldx + k0)
+                           : make_uint4(0, 0, 0, 0);
+      } else {
+        av[i] = rr[i] < M ? swin_load_a<MODE>(a, rr[i], k0) : sf8{0, 0, 0, 0, 0, 0, 0, 0};
+        if constexpr (LN && PREC != SWIN_PREC_X3) {
+          // The same LayerNorm arithmetic, element by element.  Written as the vector expression below, the compiler
+          // emits v_pk_mul_f32 (op_sel:[0,1]) feeding v_pk_fma_f32, and in these instantiations that pair returned
+          // gamma * 0 + beta in the low half for lanes 48..63 of about 1 % of the rows once a compute unit ran its
+          // second round of workgroups (x, mean, rstd, gamma, beta were read back correct from the same registers;
+          // DESIGN 4.0c has the ISA).  The empty asm statements keep the elements out of packed instructions.
+          // Seen with hipcc of ROCm 7.2 (AMD clang 22.0.0git) on gfx950; guarded by tests/test_gpu_camera_f16.py::
+          // test_layernorm_prologue_f16_is_exact_in_every_round_of_workgroups -- run it after a compiler change.
+          if (rr[i] < M) {
+            const sf8 g = ld8(a.ln_gamma + k0), be = ld8(a.ln_beta + k0);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              float tn = (av[i][j] - mean[i]) * rstd[i];
+              asm volatile("" : "+v"(tn));
+              float r = tn * g[j] + be[j];
+              asm volatile("" : "+v"(r));
+              av[i][j] = r;
+            }
+          }
+        } else if (LN && rr[i] < M) {
+          const sf8 g = ld8(a.ln_gamma + k0), be = ld8(a.ln_beta + k0);
+          av[i] = (av[i] - mean[i]) * rstd[i] * g + be;
+        }
       }
     }
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; i < NP; ++i) {
       const int idx = t + 256 * i;
-      const int tile = idx >> 7;
-      bv[i] = nt0 + tile < ntiles ? wp[((size_t)ks * ntiles + nt0) * 128 + idx] : make_uint4(0, 0, 0, 0);
+      const int tile = idx / TS;
+      bv[i] = nt0 + tile < ntiles ? wp[((size_t)ks * ntiles + nt0) * TS + idx] : make_uint4(0, 0, 0, 0);
     }
   };
   auto commit = [&](int buf) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      sh8 hi, lo;
-      swin_split8(av[i], hi, lo);
-      as_[buf][0][kg[i]][rl[i]] = *reinterpret_cast<const uint4*>(&hi);
-      as_[buf][1][kg[i]][rl[i]] = *reinterpret_cast<const uint4*>(&lo);
-      const int idx = t + 256 * i;
-      bs_[buf][idx >> 7][idx & 127] = bv[i];
+      if constexpr (PREC == SWIN_PREC_X3) {
+        sh8 hi, lo;
+        swin_split8(av[i], hi, lo);
+        as_[buf][0][kg[i]][rl[i]] = *reinterpret_cast<const uint4*>(&hi);
+        as_[buf][1][kg[i]][rl[i]] = *reinterpret_cast<const uint4*>(&lo);
+      } else if constexpr (PREC == SWIN_PREC_F16) {
+        const sh8 hi = __builtin_convertvector(av[i], sh8);
+        as_[buf][0][kg[i]][rl[i]] = *reinterpret_cast<const uint4*>(&hi);
+      } else {
+        as_[buf][0][kg[i]][rl[i]] = a16[i];
+      }
+      if (i < NP) {
+        const int idx = t + 256 * i;
+        bs_[buf][idx / TS][idx % TS] = bv[i];
+      }
     }
   };
   sf4 acc[2][4];
@@ -179,20 +230,24 @@ __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       const int row = wave * 32 + g * 16 + (lane & 15);
-      const uint4 h = as_[buf][0][lane >> 4][row], l = as_[buf][1][lane >> 4][row];
+      const uint4 h = as_[buf][0][lane >> 4][row], l = as_[buf][NP - 1][lane >> 4][row];
       ah[g] = *reinterpret_cast<const sh8*>(&h);
       al[g] = *reinterpret_cast<const sh8*>(&l);
     }
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-      if (nt < ntv) {
-        const uint4 bhu = bs_[buf][nt][lane], blu = bs_[buf][nt][64 + lane];
+      // single-pass modes multiply every column tile: the tiles past N are zeros in LDS, and straight-line MFMAs keep
+      // the accumulators where they are
+      if (PREC != SWIN_PREC_X3 || nt < ntv) {
+        const uint4 bhu = bs_[buf][nt][lane], blu = bs_[buf][nt][TS - 64 + lane];
         const sh8 bh = *reinterpret_cast<const sh8*>(&bhu);
         const sh8 bl = *reinterpret_cast<const sh8*>(&blu);
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-          acc[g][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[g], bh, acc[g][nt], 0, 0, 0);
-          acc[g][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[g], bl, acc[g][nt], 0, 0, 0);
+          if constexpr (PREC == SWIN_PREC_X3) {
+            acc[g][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[g], bh, acc[g][nt], 0, 0, 0);
+            acc[g][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[g], bl, acc[g][nt], 0, 0, 0);
+          }
           acc[g][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[g], bh, acc[g][nt], 0, 0, 0);
         }
       }
@@ -201,7 +256,7 @@ __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int
     __syncthreads();
   }
   // C/D layout: lane holds rows 16 g + 4 (lane >> 4) + j of the wave's 32, column 16 nt + (lane & 15)
-  const float winv = *w_inv_scale;
+  const float winv = PREC == SWIN_PREC_X3 ? *w_inv_scale : 1.f;   // the single f16 plane carries no scale
 #pragma unroll
   for (int nt = 0; nt < 4; ++nt) {
     if (nt >= ntv) continue;
@@ -214,12 +269,14 @@ __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int
       for (int j = 0; j < 4; ++j) {
         const int r = R0 + wave * 32 + g * 16 + 4 * (lane >> 4) + j;
         if (r >= M) continue;
-        float z = acc[g][nt][j] * winv * sc + sh;
+        float z = (PREC == SWIN_PREC_X3 ? acc[g][nt][j] * winv : acc[g][nt][j]) * sc + sh;
         if (ep.act == 1) z = fmaxf(z, 0.f);
         else if (ep.act == 2) z = 0.5f * z * (1.f + erff(z * 0.70710678118654752440f));
         if (RS) z *= ep.row_scale[r / ep.rows_per_sample];
         if (ep.residual) z += ep.residual[(size_t)r * N + n];
-        if (ep.y_hw) {
+        if constexpr (Y16) {
+          reinterpret_cast<_Float16*>(y)[(size_t)r * ep.ldy + n] = sat_f16(z);
+        } else if (ep.y_hw) {
           const int b = r / ep.y_hw, pos = r - b * ep.y_hw;
           y[((size_t)b * N + n) * ep.y_hw + pos] = z;
         } else {
@@ -396,7 +453,8 @@ static int swin_check_a(const isf_swin_a* a, int M, int K, bool gemm) {
   switch (a->mode) {
     case ISF_SWIN_A_ROWS:
       ISF_REQUIRE(a->ldx >= K && a->ldx % 4 == 0 && ((uintptr_t)a->x & 15) == 0, ISF_ERR_ARG,
-                  "swin: rows need ldx >= K, ldx %% 4 == 0, 16-byte aligned x");
+                  "swin: rows need ldx >= K, ldx %% 4 == 0 (%% 8 for f16 rows, ldx in elements of the row type), "
+                  "16-byte aligned x");
       break;
     case ISF_SWIN_A_MERGE:
       ISF_REQUIRE(a->c % 8 == 0 && K == 4 * a->c && ((uintptr_t)a->x & 15) == 0, ISF_ERR_ARG,
@@ -420,7 +478,7 @@ extern "C" {
 static int swin_gemm_launch(const isf_swin_a* a, int num_rows, int k, const void* packed_weight, int out_features,
                             const float* scale, const float* shift, int activation, const float* residual,
                             const float* row_scale, int rows_per_sample, float* y, int ldy, int y_hw,
-                            isf_stream_t stream) {
+                            isf_stream_t stream, int prec = isf::SWIN_PREC_X3, bool y16 = false) {
   using namespace isf;
   ISF_REQUIRE(num_rows >= 0 && out_features > 0 && out_features % 16 == 0, ISF_ERR_ARG,
               "swin_gemm: bad sizes (rows %d, out %d)", num_rows, out_features);
@@ -437,13 +495,41 @@ static int swin_gemm_launch(const isf_swin_a* a, int num_rows, int k, const void
               ISF_ERR_ARG, "swin_gemm_rowscale: rows mode without LayerNorm, rows %d a multiple of rows_per_sample %d",
               num_rows, rows_per_sample);
   const uint4* wp = reinterpret_cast<const uint4*>(packed_weight);
-  const float* winv =
+  const float* winv = prec != SWIN_PREC_X3 ? nullptr :
       reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed_weight) + (size_t)out_features * k * 4);
   SwinEpi ep{scale, shift, residual, activation, ldy, y_hw, row_scale, rows_per_sample};
   hipStream_t st = as_stream(stream);
   const dim3 grid(ceil_div(out_features / 16, 4), ceil_div(num_rows, SW_BM)), block(256);
 #define ISF_SWIN_GEMM(MODE_, ...) \
   hipLaunchKernelGGL((swin_gemm_kernel<MODE_, __VA_ARGS__>), grid, block, 0, st, *a, num_rows, k, wp, winv, out_features, ep, y)
+  if (prec != SWIN_PREC_X3) {
+    // the f16 inference mode: the forms SwinTransformer's forward is made of (no DropPath, no NCHW store, no UPCAT)
+    ISF_REQUIRE(!row_scale && y_hw == 0 && a->mode != ISF_SWIN_A_UPCAT, ISF_ERR_UNSUPPORTED,
+                "swin_gemm_f16: rows / patch / merge loaders, row-major output, no row scale");
+    ISF_REQUIRE(prec == SWIN_PREC_F16 || (a->mode == ISF_SWIN_A_ROWS && !ln && a->ldx % 8 == 0), ISF_ERR_ARG,
+                "swin_gemm_f16: f16 A rows need the rows loader without LayerNorm and ldx %% 8 == 0 (f16 elements)");
+    ISF_REQUIRE(!y16 || a->mode == ISF_SWIN_A_ROWS, ISF_ERR_UNSUPPORTED, "swin_gemm_f16: f16 output needs the rows loader");
+#define ISF_SWIN_GEMM16(MODE_, LN_, PREC_)                                              \
+  do {                                                                                  \
+    if (y16) ISF_SWIN_GEMM(MODE_, LN_, false, PREC_, true);                             \
+    else ISF_SWIN_GEMM(MODE_, LN_, false, PREC_, false);                                \
+  } while (0)
+    switch (a->mode) {
+      case ISF_SWIN_A_ROWS:
+        if (prec == SWIN_PREC_F16_ROWS) ISF_SWIN_GEMM16(ISF_SWIN_A_ROWS, false, SWIN_PREC_F16_ROWS);
+        else if (ln) ISF_SWIN_GEMM16(ISF_SWIN_A_ROWS, true, SWIN_PREC_F16);
+        else ISF_SWIN_GEMM16(ISF_SWIN_A_ROWS, false, SWIN_PREC_F16);
+        break;
+      case ISF_SWIN_A_MERGE:
+        if (ln) ISF_SWIN_GEMM(ISF_SWIN_A_MERGE, true, false, SWIN_PREC_F16, false);
+        else ISF_SWIN_GEMM(ISF_SWIN_A_MERGE, false, false, SWIN_PREC_F16, false);
+        break;
+      case ISF_SWIN_A_PATCH: ISF_SWIN_GEMM(ISF_SWIN_A_PATCH, false, false, SWIN_PREC_F16, false); break;
+    }
+#undef ISF_SWIN_GEMM16
+    ISF_LAUNCH_CHECK();
+    return ISF_OK;
+  }
   switch (a->mode) {
     case ISF_SWIN_A_ROWS:
       if (row_scale) ISF_SWIN_GEMM(ISF_SWIN_A_ROWS, false, true);
@@ -473,6 +559,14 @@ int isf_swin_gemm_rowscale(const isf_swin_a* a, int num_rows, int k, const void*
   ISF_REQUIRE(row_scale, ISF_ERR_ARG, "swin_gemm_rowscale: null row_scale");
   return swin_gemm_launch(a, num_rows, k, packed_weight, out_features, scale, shift, activation, residual, row_scale,
                           rows_per_sample, y, ldy, y_hw, stream);
+}
+
+int isf_swin_gemm_f16(const isf_swin_a* a, int a_is_f16, int num_rows, int k, const void* packed_weight_f16,
+                      int out_features, const float* scale, const float* shift, int activation, const float* residual,
+                      void* y, int y_is_f16, int ldy, int y_hw, isf_stream_t stream) {
+  return swin_gemm_launch(a, num_rows, k, packed_weight_f16, out_features, scale, shift, activation, residual, nullptr, 0,
+                          reinterpret_cast<float*>(y), ldy, y_hw, stream,
+                          a_is_f16 ? isf::SWIN_PREC_F16_ROWS : isf::SWIN_PREC_F16, y_is_f16 != 0);
 }
 
 int isf_swin_row_stats(const isf_swin_a* a, int num_rows, int k, float eps, float* stats, isf_stream_t stream) {

@@ -449,6 +449,16 @@ class ISFusionDetector(ISFusionPtsPath):
     def with_img_neck(self):
         return self.img_neck is not None
 
+    @property
+    def camera_precision(self):
+        """"f32" (default) or "f16": the precision mode of the camera backbone (SwinTransformer.set_precision); the neck
+        takes the backbone's fp32 maps in either mode"""
+        return self.img_backbone.precision
+
+    @camera_precision.setter
+    def camera_precision(self, mode):
+        self.img_backbone.set_precision(mode)
+
     def extract_img_feat(self, img, img_metas):
         """isfusion.py:54-81: img [B, num_cams, 3, H, W] (normalised) -> the neck's tuple of [B*num_cams, C, h, w].
         Cameras listed in a meta's img_mask_idx are zeroed in `img` (in place, as the reference does); every meta gets

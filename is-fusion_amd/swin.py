@@ -13,6 +13,13 @@ with ``strict=True`` (187 entries for configs/isfusion/isfusion_0075voxel.py, mm
 PatchEmbed is one GEMM whose loader gathers the 4 x 4 x 3 patches from the NCHW image (+ a LayerNorm pass), PatchMerging
 one GEMM whose loader gathers the 2 x 2 neighbourhood (+ its LayerNorm prologue), the out_indices norms one LayerNorm
 pass that stores NCHW.  Packed weights are derived once per parameter version (fusion_ops._cache).
+
+``set_precision("f16")`` switches the eval-mode forward to the f16 inference mode (isf_swin_gemm_f16,
+isf_swin_window_attention_f16): one matrix instruction per product instead of three, and the branch intermediates --
+qkv [M, 3C], the attention output [M, C], the FFN hidden [M, 4C] -- are f16 rows.  The residual stream, LayerNorm
+statistics, softmax, GELU and every accumulation stay fp32, PatchEmbed / PatchMerging write fp32 rows, and the
+out_indices maps are the same fp32 NCHW tensors.  The mode's packed weights live in the same per-module cache, next to
+the default mode's.  ``precision`` is a plain attribute: no parameter, no buffer, no constructor argument.
 """
 import ctypes
 
@@ -62,6 +69,45 @@ def gemm(a, rows, k, pl, *, scale=None, shift=None, act=ACT_NONE, residual=None,
                                          _lib.ptr(shift), act, _lib.ptr(residual), _lib.ptr(y), ldy, y_hw,
                                          _lib.stream()), "isf_swin_gemm")
     return y
+
+
+class PackedLinearF16:
+    """nn.Linear weights as one plane of f16 MFMA fragments (isf_pack_linear_f16), for the f16 inference mode"""
+
+    def __init__(self, weight):
+        _lib.require_cuda(weight)
+        w = weight.detach().float().contiguous()
+        self.out_features, self.in_features = w.shape
+        lib = _lib.load()
+        self.packed = torch.empty(lib.isf_packed_linear_f16_bytes(self.out_features, self.in_features),
+                                  dtype=torch.uint8, device=w.device)
+        _lib.check(lib.isf_pack_linear_f16(_lib.ptr(w), self.out_features, self.in_features, _lib.ptr(self.packed),
+                                           _lib.stream()), "isf_pack_linear_f16")
+
+
+def gemm_f16(a, rows, k, pl, *, shift=None, act=ACT_NONE, residual=None, out_f16=False):
+    """isf_swin_gemm_f16: act(A W^T + shift) + residual -> [rows, N] fp32, or f16 rows for out_f16.  A comes from the
+    loader `a`; when its x is an f16 tensor, the rows are read as they are (ROWS loader)."""
+    s, keep = a
+    N = pl.out_features
+    x = keep[0]
+    y = torch.empty((rows, N), dtype=torch.float16 if out_f16 else torch.float32, device=x.device)
+    if residual is not None:
+        assert residual.dtype == torch.float32 and residual.is_contiguous() and tuple(residual.shape) == (rows, N)
+    _lib.check(_lib.load().isf_swin_gemm_f16(ctypes.byref(s), int(x.dtype == torch.float16), rows, k,
+                                             _lib.ptr(pl.packed), N, None, _lib.ptr(shift), act, _lib.ptr(residual),
+                                             _lib.ptr(y), int(out_f16), N, 0, _lib.stream()), "isf_swin_gemm_f16")
+    return y
+
+
+def window_attention_f16(qkv, qkv_bias, rel_bias, B, H, W, C, heads, window, shift, scale):
+    """isf_swin_window_attention_f16: f16 qkv rows [B*H*W, 3C] -> f16 attention output rows [B*H*W, C] (before proj)"""
+    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and tuple(qkv.shape) == (B * H * W, 3 * C)
+    out = torch.empty((B * H * W, C), dtype=torch.float16, device=qkv.device)
+    _lib.check(_lib.load().isf_swin_window_attention_f16(_lib.ptr(qkv), _lib.ptr(qkv_bias), _lib.ptr(rel_bias), B, H,
+                                                         W, C, heads, window, shift, float(scale), _lib.ptr(out),
+                                                         _lib.stream()), "isf_swin_window_attention_f16")
+    return out
 
 
 def row_stats(a, rows, k, eps):
@@ -192,6 +238,33 @@ class SwinBlock(nn.Module):
                     fc1=PackedLinear(l1.weight), fc1_b=l1.bias.detach(), fc2=PackedLinear(l2.weight),
                     fc2_b=l2.bias.detach())
 
+    def pack_f16(self):
+        m = self.attn.w_msa
+        l1, l2 = self.ffn.layers[0][0], self.ffn.layers[1]
+        return dict(qkv=PackedLinearF16(m.qkv.weight), qkv_b=None if m.qkv.bias is None else m.qkv.bias.detach(),
+                    proj=PackedLinearF16(m.proj.weight), proj_b=m.proj.bias.detach(), rel=m.relative_bias(),
+                    fc1=PackedLinearF16(l1.weight), fc1_b=l1.bias.detach(), fc2=PackedLinearF16(l2.weight),
+                    fc2_b=l2.bias.detach())
+
+    def run_f16(self, p, x, B, H, W):
+        """run() in the f16 inference mode: x and the result are the fp32 residual rows; qkv, the attention output
+        and the FFN hidden are f16 rows"""
+        M, C = x.shape
+        m = self.attn.w_msa
+        ln1 = (self.norm1.weight.detach(), self.norm1.bias.detach())
+        st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm1.eps)
+        qkv = gemm_f16(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln1), M, C, p["qkv"], shift=p["qkv_b"],
+                       out_f16=True)
+        att = window_attention_f16(qkv, p["qkv_b"], p["rel"], B, H, W, C, m.num_heads, self.attn.window_size,
+                                   self.attn.shift_size, m.scale)
+        x = gemm_f16(_a(_lib.SWIN_A_ROWS, att, ldx=C), M, C, p["proj"], shift=p["proj_b"], residual=x)
+        ln2 = (self.norm2.weight.detach(), self.norm2.bias.detach())
+        st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm2.eps)
+        F = self.ffn.feedforward_channels
+        h = gemm_f16(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln2), M, C, p["fc1"], shift=p["fc1_b"], act=ACT_GELU,
+                     out_f16=True)
+        return gemm_f16(_a(_lib.SWIN_A_ROWS, h, ldx=F), M, F, p["fc2"], shift=p["fc2_b"], residual=x)
+
     def run(self, p, x, B, H, W, keep=(None, None)):
         """x: token rows [B*H*W, C] -> the block's output rows.  keep: per-image DropPath factors [B] (keep / keep_prob)
         of the attention and the FFN branch, or None: the branch output is multiplied by them after window reverse /
@@ -226,17 +299,19 @@ class PatchEmbed(nn.Module):
         else:
             self.norm = None
 
-    def pack(self):
+    def pack(self, linear=PackedLinear):
+        """linear: PackedLinear (default mode) or PackedLinearF16 (f16 inference mode)"""
         w = self.projection.weight.detach().float().flatten(1)           # [C, cin*16], k = ci*16 + ky*4 + kx
         k = (w.shape[1] + 31) // 32 * 32
         wp = torch.cat([w, w.new_zeros(w.shape[0], k - w.shape[1])], 1)
-        return dict(w=PackedLinear(wp), b=self.projection.bias.detach().float().contiguous(), k=k)
+        return dict(w=linear(wp), b=self.projection.bias.detach().float().contiguous(), k=k)
 
     def run(self, p, img):
         N, C, H, W = img.shape
         Ho, Wo = (H + 3) // 4, (W + 3) // 4
         M = N * Ho * Wo
-        x = gemm(_a(_lib.SWIN_A_PATCH, img, n=N, c=C, h=H, w=W), M, p["k"], p["w"], shift=p["b"])
+        mm = gemm_f16 if isinstance(p["w"], PackedLinearF16) else gemm
+        x = mm(_a(_lib.SWIN_A_PATCH, img, n=N, c=C, h=H, w=W), M, p["k"], p["w"], shift=p["b"])
         if self.norm is not None:
             x = layernorm(x, self.norm)
         return x, (Ho, Wo)
@@ -258,12 +333,13 @@ class PatchMerging(nn.Module):
             self.norm = None
         self.reduction = nn.Linear(4 * in_channels, out_channels, bias=False)
 
-    def pack(self):
+    def pack(self, linear=PackedLinear):
+        """linear: PackedLinear (default mode) or PackedLinearF16 (f16 inference mode)"""
         # nn.Unfold orders the merged vector c*4 + q (q = kh*2 + kw); the loader reads q*C + c (contiguous channels)
         C = self.in_channels
         w = self.reduction.weight.detach().float()
         wl = w.view(-1, C, 4).permute(0, 2, 1).reshape(w.shape[0], 4 * C)
-        p = dict(w=PackedLinear(wl))
+        p = dict(w=linear(wl))
         if self.norm is not None:
             p["g"] = self.norm.weight.detach().float().view(C, 4).t().contiguous().view(-1)
             p["b"] = self.norm.bias.detach().float().view(C, 4).t().contiguous().view(-1)
@@ -279,7 +355,8 @@ class PatchMerging(nn.Module):
             a = _a(_lib.SWIN_A_MERGE, x, stats=st, ln=(p["g"], p["b"]), **geo)
         else:
             a = _a(_lib.SWIN_A_MERGE, x, **geo)
-        return gemm(a, M, 4 * C, p["w"]), (Ho, Wo)
+        mm = gemm_f16 if isinstance(p["w"], PackedLinearF16) else gemm
+        return mm(a, M, 4 * C, p["w"]), (Ho, Wo)
 
 
 class SwinBlockSequence(nn.Module):
@@ -342,8 +419,30 @@ class SwinTransformer(nn.Module):
         for i in out_indices:
             self.add_module(f"norm{i}", nn.LayerNorm(self.num_features[i]))
 
+    PRECISIONS = ("f32", "f16")
+    precision = "f32"       # a plain attribute (set_precision): not a parameter, buffer or constructor argument
+
+    def set_precision(self, mode):
+        """"f32": the default f16x3 kernels (fp32-class accuracy).  "f16": the f16 inference mode -- single-pass
+        products, f16 branch intermediates, fp32 residual stream; eval-mode forward only."""
+        if mode not in self.PRECISIONS:
+            raise ValueError(f"SwinTransformer.set_precision: {mode!r} (one of {self.PRECISIONS})")
+        self.precision = mode
+        return self
+
     def _packed(self, dev):
+        """the packed weights of the current mode; both modes' copies share the module's one derived-weight store, so a
+        parameter change drops both and each is derived again on its next use"""
         c = _cache(self, dev)
+        if self.precision == "f16":
+            if "f16" not in c:
+                with torch.no_grad():
+                    c["f16"] = dict(
+                        patch=self.patch_embed.pack(PackedLinearF16),
+                        blocks=[[blk.pack_f16() for blk in st.blocks] for st in self.stages],
+                        merge=[st.downsample.pack(PackedLinearF16) if st.downsample is not None else None
+                               for st in self.stages])
+            return c["f16"]
         if "patch" not in c:
             with torch.no_grad():
                 c["patch"] = self.patch_embed.pack()
@@ -370,6 +469,9 @@ class SwinTransformer(nn.Module):
         layer in drop_layers() order; None draws every mask with ONE torch.rand call on the device (mmcv's random
         stream is not reproduced draw for draw)."""
         assert self.training, "call .train() first (forward() is the eval-mode forward)"
+        if self.precision != "f32":
+            raise NotImplementedError(f"SwinTransformer.forward_train: precision {self.precision!r} is an inference "
+                                      'mode (train with set_precision("f32"))')
         if self.drop_rate != 0.0 or self.attn_drop_rate != 0.0:
             raise NotImplementedError(f"SwinTransformer.forward_train: drop_rate {self.drop_rate} / attn_drop_rate "
                                       f"{self.attn_drop_rate} (only DropPath is built)")
@@ -393,6 +495,8 @@ class SwinTransformer(nn.Module):
         assert x.dim() == 4, x.shape
         x = x.float().contiguous()
         N = x.shape[0]
+        f16 = self.precision == "f16"
+        assert not (f16 and scales is not None)
         p = self._packed(x.device)
         t, (H, W) = self.patch_embed.run(p["patch"], x)
         outs = []
@@ -403,7 +507,7 @@ class SwinTransformer(nn.Module):
                 if scales is not None and blk.attn.drop_path_rate > 0.0:
                     keep = (scales[row], scales[row + 1])
                     row += 2
-                t = blk.run(bp, t, N, H, W, keep)
+                t = blk.run_f16(bp, t, N, H, W) if f16 else blk.run(bp, t, N, H, W, keep)
             if i in self.out_indices:
                 outs.append(layernorm(t, getattr(self, f"norm{i}"), out_nchw=(N, H, W)))
             if stage.downsample is not None:

@@ -7,6 +7,12 @@
 
     python tools/camera_bench.py [--steps 10] [--warmup 3] [--points 300000]
     python tools/camera_bench.py --train [--steps 10] [--warmup 3] [--runs 3]
+    python tools/camera_bench.py --precision both [--steps 10] [--warmup 3] [--runs 3]
+
+--precision f32 (default) is the run above.  f16 / both: the backbone's precision modes (SwinTransformer.set_precision)
+in ONE process on the same weights and images -- per run and mode the backbone, extract_img_feat and
+ISFusionDetector.simple_test times, and once per mode the error of the three backbone maps against the float64
+restatement at the bench size.
 
 --train: one camera training step instead -- SwinTransformer.forward_train (stochastic depth, no backward: detach=True)
 + GeneralizedLSSFPN.forward_train + the neck's backward from a gradient on the stride-16 output (what Point-to-Grid
@@ -112,17 +118,7 @@ def train_bench(a, dev):
         print(json.dumps(dict(what=what, ms=round(timed(fn, a.steps * 5, a.warmup), 4))))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--points", type=int, default=300000)
-    ap.add_argument("--train", action="store_true", help="time one camera training step (forward_train + neck backward)")
-    ap.add_argument("--runs", type=int, default=3, help="--train: repetitions of the headline measurement")
-    a = ap.parse_args()
-    dev = torch.device("cuda:0")
-    if a.train:
-        return train_bench(a, dev)
+def build_detector(dev):
     det = ISFusionDetector(img_backbone=dict(type="SwinTransformer", **CC.BACKBONE),
                            img_neck=dict(type="GeneralizedLSSFPN", **CC.NECK), detach=True).eval()
     det._lidar.randomize_weights_(0).randomize_bn_(1)
@@ -132,6 +128,72 @@ def main():
     det.img_neck.load_state_dict(CC.seeded_module_state(det.img_neck, 4202))
     det = det.to(dev)
     det.freeze()
+    return det
+
+
+def precision_bench(a, dev):
+    modes = ["f32", "f16"] if a.precision == "both" else [a.precision]
+    det = build_detector(dev)
+    B, H, W = 2, 384, 1056
+    img = CC.images(3, B * 6, H, W).to(dev).view(B, 6, 3, H, W)
+    flat = img.view(B * 6, 3, H, W)
+    bb = det.img_backbone
+    pts = [torch.from_numpy(p).to(dev) for p in synthetic.batch(2, B, a.points)]
+    inp = synthetic.fusion_inputs(5, B)
+    kw = dict(lidar2img=torch.from_numpy(inp["lidar2img"]), img_aug_matrix=torch.from_numpy(inp["img_aug_matrix"]),
+              lidar_aug_matrix=torch.from_numpy(inp["lidar_aug_matrix"]))
+    metas = [dict(input_shape=inp["input_shape"]) for _ in range(B)]
+    with torch.no_grad():
+        ref = CC.swin_forward(CC.cast(bb.state_dict(), torch.float64, dev), flat.double())
+    for mode in modes:
+        det.camera_precision = mode
+        got = bb(flat)
+        print(json.dumps(dict(what="backbone_error_vs_float64", precision=mode, images=B * 6, hw=[H, W],
+                              max_abs_err=[float((x.double() - r).abs().max()) for x, r in zip(got, ref)],
+                              max_abs_ref=[float(r.abs().max()) for r in ref])))
+    del ref
+    for run in range(a.runs):
+        for mode in modes:
+            det.camera_precision = mode
+            row = dict(precision=mode, run=run, images=B * 6)
+            print(json.dumps(dict(what="backbone", ms=round(timed(lambda: bb(flat), a.steps, a.warmup), 3), **row)))
+            print(json.dumps(dict(what="extract_img_feat",
+                                  ms=round(timed(lambda: det.extract_img_feat(img, metas), a.steps, a.warmup), 3), **row)))
+            print(json.dumps(dict(what="simple_test", input="images", batch=B,
+                                  ms=round(timed(lambda: det.simple_test(pts, metas, img=img, **kw), a.steps, a.warmup), 3),
+                                  **row)))
+    det.camera_precision = "f32"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--points", type=int, default=300000)
+    ap.add_argument("--train", action="store_true", help="time one camera training step (forward_train + neck backward)")
+    ap.add_argument("--runs", type=int, default=3, help="--train / --precision f16|both: repetitions of the measurement")
+    ap.add_argument("--precision", choices=("f32", "f16", "both"), default="f32",
+                    help="f16 / both: time the backbone's precision modes in one process (default: the f32 run)")
+    ap.add_argument("--profile-forward", action="store_true",
+                    help="run the backbone forward of --precision (f32 or f16) --steps times and exit: the process to "
+                         "put under a kernel trace (profiles/camera_f16_kernels.txt)")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    if a.train:
+        return train_bench(a, dev)
+    if a.profile_forward:
+        if a.precision == "both":
+            ap.error("--profile-forward traces one mode: --precision f32 or f16")
+        det = build_detector(dev)
+        det.camera_precision = a.precision
+        flat = CC.images(3, 12, 384, 1056).to(dev)
+        for _ in range(a.warmup + a.steps):
+            det.img_backbone(flat)
+        torch.cuda.synchronize()
+        return None
+    if a.precision != "f32":
+        return precision_bench(a, dev)
+    det = build_detector(dev)
     B, H, W = 2, 384, 1056
     img = CC.images(3, B * 6, H, W).to(dev).view(B, 6, 3, H, W)
     flat = img.view(B * 6, 3, H, W)
