@@ -23,6 +23,8 @@
 //                        (isf_pack_linear_f16); accumulation and the epilogue stay fp32; the output rows are fp32 (into
 //                        the residual stream) or f16 (qkv, the FFN hidden).  Every store to an f16 tensor saturates at
 //                        +-65504 instead of producing inf.  Window attention of this mode: isf_swin_f16.hip.
+//                        All three GEMM entries (swin.gemm in Python) end in swin_gemm_launch; swin_gemm_forms is the one
+//                        statement of which (loader, LayerNorm, row scale, precision, f16 output) forms are built.
 //   isf_swin_row_stats   mean / rstd of the loader's rows (one wave per row, two passes in fp32)
 //   isf_swin_layernorm   LayerNorm of token rows, stored as rows or NCHW (patch_norm, the out_indices norms)
 //   isf_swin_window_attention  (shifted) window attention on the token-major qkv: padding, cyclic shift, window
@@ -36,14 +38,13 @@
 
 namespace isf {
 
-typedef _Float16 sh8 __attribute__((ext_vector_type(8)));
 typedef float sf4 __attribute__((ext_vector_type(4)));
 typedef float sf8 __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ void swin_split8(const sf8 v, sh8& hi, sh8& lo) {
-  hi = __builtin_convertvector(v, sh8);
+__device__ __forceinline__ void swin_split8(const sf8 v, fh8& hi, fh8& lo) {
+  hi = __builtin_convertvector(v, fh8);
   const sf8 r = v - __builtin_convertvector(hi, sf8);
-  lo = __builtin_convertvector(r, sh8);
+  lo = __builtin_convertvector(r, fh8);
 }
 
 __device__ __forceinline__ sf8 ld8(const float* p) {
@@ -197,12 +198,12 @@ __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       if constexpr (PREC == SWIN_PREC_X3) {
-        sh8 hi, lo;
+        fh8 hi, lo;
         swin_split8(av[i], hi, lo);
         as_[buf][0][kg[i]][rl[i]] = *reinterpret_cast<const uint4*>(&hi);
         as_[buf][1][kg[i]][rl[i]] = *reinterpret_cast<const uint4*>(&lo);
       } else if constexpr (PREC == SWIN_PREC_F16) {
-        const sh8 hi = __builtin_convertvector(av[i], sh8);
+        const fh8 hi = __builtin_convertvector(av[i], fh8);
         as_[buf][0][kg[i]][rl[i]] = *reinterpret_cast<const uint4*>(&hi);
       } else {
         as_[buf][0][kg[i]][rl[i]] = a16[i];
@@ -226,13 +227,13 @@ __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int
     const int buf = ks & 1;
     const bool more = ks + 1 < ksteps;
     if (more) fetch(ks + 1);
-    sh8 ah[2], al[2];
+    fh8 ah[2], al[2];
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       const int row = wave * 32 + g * 16 + (lane & 15);
       const uint4 h = as_[buf][0][lane >> 4][row], l = as_[buf][NP - 1][lane >> 4][row];
-      ah[g] = *reinterpret_cast<const sh8*>(&h);
-      al[g] = *reinterpret_cast<const sh8*>(&l);
+      ah[g] = *reinterpret_cast<const fh8*>(&h);
+      al[g] = *reinterpret_cast<const fh8*>(&l);
     }
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
@@ -240,8 +241,8 @@ __global__ __launch_bounds__(256) void swin_gemm_kernel(isf_swin_a a, int M, int
       // the accumulators where they are
       if (PREC != SWIN_PREC_X3 || nt < ntv) {
         const uint4 bhu = bs_[buf][nt][lane], blu = bs_[buf][nt][TS - 64 + lane];
-        const sh8 bh = *reinterpret_cast<const sh8*>(&bhu);
-        const sh8 bl = *reinterpret_cast<const sh8*>(&blu);
+        const fh8 bh = *reinterpret_cast<const fh8*>(&bhu);
+        const fh8 bl = *reinterpret_cast<const fh8*>(&blu);
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
           if constexpr (PREC == SWIN_PREC_X3) {
@@ -471,6 +472,34 @@ static int swin_check_a(const isf_swin_a* a, int M, int K, bool gemm) {
   return ISF_OK;
 }
 
+// The swin_gemm_kernel instantiations that are built, one row each: swin_gemm_launch looks the call's form up here, and a
+// form without a row is ISF_ERR_UNSUPPORTED.  Default mode (X3): ROWS plain / LayerNorm / row scale, MERGE plain /
+// LayerNorm, PATCH, UPCAT.  f16 inference mode: ROWS {fp32 rows plain, fp32 rows LayerNorm, f16 rows} x {fp32, f16 out},
+// MERGE plain / LayerNorm, PATCH -- the forms SwinTransformer's forward is made of (no DropPath, no UPCAT).
+// The kernels stand in the code object in row order.
+using SwinGemmKernel = void (*)(isf_swin_a, int, int, const uint4*, const float*, int, SwinEpi, float*);
+struct SwinGemmForm { int mode; bool ln, rs; int prec; bool y16; SwinGemmKernel kernel; };
+template <int MODE, bool LN, bool RS = false, int PREC = SWIN_PREC_X3, bool Y16 = false>
+constexpr SwinGemmForm swin_gemm_form() { return {MODE, LN, RS, PREC, Y16, swin_gemm_kernel<MODE, LN, RS, PREC, Y16>}; }
+static const SwinGemmForm swin_gemm_forms[] = {
+    swin_gemm_form<ISF_SWIN_A_ROWS, false, false, SWIN_PREC_F16_ROWS, true>(),
+    swin_gemm_form<ISF_SWIN_A_ROWS, false, false, SWIN_PREC_F16_ROWS, false>(),
+    swin_gemm_form<ISF_SWIN_A_ROWS, true, false, SWIN_PREC_F16, true>(),
+    swin_gemm_form<ISF_SWIN_A_ROWS, true, false, SWIN_PREC_F16, false>(),
+    swin_gemm_form<ISF_SWIN_A_ROWS, false, false, SWIN_PREC_F16, true>(),
+    swin_gemm_form<ISF_SWIN_A_ROWS, false, false, SWIN_PREC_F16, false>(),
+    swin_gemm_form<ISF_SWIN_A_MERGE, true, false, SWIN_PREC_F16, false>(),
+    swin_gemm_form<ISF_SWIN_A_MERGE, false, false, SWIN_PREC_F16, false>(),
+    swin_gemm_form<ISF_SWIN_A_PATCH, false, false, SWIN_PREC_F16, false>(),
+    swin_gemm_form<ISF_SWIN_A_ROWS, false, true>(),
+    swin_gemm_form<ISF_SWIN_A_ROWS, true>(),
+    swin_gemm_form<ISF_SWIN_A_ROWS, false>(),
+    swin_gemm_form<ISF_SWIN_A_MERGE, true>(),
+    swin_gemm_form<ISF_SWIN_A_MERGE, false>(),
+    swin_gemm_form<ISF_SWIN_A_PATCH, false>(),
+    swin_gemm_form<ISF_SWIN_A_UPCAT, false>(),
+};
+
 }  // namespace isf
 
 extern "C" {
@@ -486,61 +515,27 @@ static int swin_gemm_launch(const isf_swin_a* a, int num_rows, int k, const void
   ISF_TRY(swin_check_a(a, num_rows, k, true));
   ISF_REQUIRE(packed_weight && y, ISF_ERR_ARG, "swin_gemm: null pointer");
   const bool ln = a->ln_stats != nullptr;
-  ISF_REQUIRE(!ln || ((a->mode == ISF_SWIN_A_ROWS || a->mode == ISF_SWIN_A_MERGE) && a->ln_gamma && a->ln_beta),
-              ISF_ERR_ARG, "swin_gemm: LayerNorm prologue needs rows / merge mode and gamma, beta");
+  ISF_REQUIRE(!ln || (a->ln_gamma && a->ln_beta), ISF_ERR_ARG, "swin_gemm: LayerNorm prologue needs gamma, beta");
   ISF_REQUIRE(y_hw > 0 ? num_rows % y_hw == 0 : ldy >= out_features, ISF_ERR_ARG, "swin_gemm: bad output layout");
   ISF_REQUIRE(activation >= 0 && activation <= 2, ISF_ERR_ARG, "swin_gemm: activation %d", activation);
-  ISF_REQUIRE(!row_scale || (a->mode == ISF_SWIN_A_ROWS && !ln && rows_per_sample > 0 &&
-                             num_rows % rows_per_sample == 0),
-              ISF_ERR_ARG, "swin_gemm_rowscale: rows mode without LayerNorm, rows %d a multiple of rows_per_sample %d",
-              num_rows, rows_per_sample);
+  ISF_REQUIRE(!row_scale || (rows_per_sample > 0 && num_rows % rows_per_sample == 0), ISF_ERR_ARG,
+              "swin_gemm_rowscale: rows %d a multiple of rows_per_sample %d", num_rows, rows_per_sample);
+  // the f16 output store knows rows only, and the mode is built for row-major outputs
+  ISF_REQUIRE(prec == SWIN_PREC_X3 || y_hw == 0, ISF_ERR_UNSUPPORTED, "swin_gemm_f16: row-major output only");
+  ISF_REQUIRE(prec != SWIN_PREC_F16_ROWS || a->ldx % 8 == 0, ISF_ERR_ARG,
+              "swin_gemm_f16: f16 A rows need ldx %% 8 == 0 (f16 elements)");
+  const SwinGemmForm* form = nullptr;
+  for (const SwinGemmForm& f : swin_gemm_forms)
+    if (f.mode == a->mode && f.ln == ln && f.rs == (row_scale != nullptr) && f.prec == prec && f.y16 == y16) form = &f;
+  ISF_REQUIRE(form, ISF_ERR_UNSUPPORTED,
+              "swin_gemm: form not built (loader %d, LayerNorm prologue %d, row scale %d, operand precision %d, f16 "
+              "output %d)", a->mode, (int)ln, (int)(row_scale != nullptr), prec, (int)y16);
   const uint4* wp = reinterpret_cast<const uint4*>(packed_weight);
   const float* winv = prec != SWIN_PREC_X3 ? nullptr :
       reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed_weight) + (size_t)out_features * k * 4);
   SwinEpi ep{scale, shift, residual, activation, ldy, y_hw, row_scale, rows_per_sample};
-  hipStream_t st = as_stream(stream);
   const dim3 grid(ceil_div(out_features / 16, 4), ceil_div(num_rows, SW_BM)), block(256);
-#define ISF_SWIN_GEMM(MODE_, ...) \
-  hipLaunchKernelGGL((swin_gemm_kernel<MODE_, __VA_ARGS__>), grid, block, 0, st, *a, num_rows, k, wp, winv, out_features, ep, y)
-  if (prec != SWIN_PREC_X3) {
-    // the f16 inference mode: the forms SwinTransformer's forward is made of (no DropPath, no NCHW store, no UPCAT)
-    ISF_REQUIRE(!row_scale && y_hw == 0 && a->mode != ISF_SWIN_A_UPCAT, ISF_ERR_UNSUPPORTED,
-                "swin_gemm_f16: rows / patch / merge loaders, row-major output, no row scale");
-    ISF_REQUIRE(prec == SWIN_PREC_F16 || (a->mode == ISF_SWIN_A_ROWS && !ln && a->ldx % 8 == 0), ISF_ERR_ARG,
-                "swin_gemm_f16: f16 A rows need the rows loader without LayerNorm and ldx %% 8 == 0 (f16 elements)");
-    ISF_REQUIRE(!y16 || a->mode == ISF_SWIN_A_ROWS, ISF_ERR_UNSUPPORTED, "swin_gemm_f16: f16 output needs the rows loader");
-#define ISF_SWIN_GEMM16(MODE_, LN_, PREC_)                                              \
-  do {                                                                                  \
-    if (y16) ISF_SWIN_GEMM(MODE_, LN_, false, PREC_, true);                             \
-    else ISF_SWIN_GEMM(MODE_, LN_, false, PREC_, false);                                \
-  } while (0)
-    switch (a->mode) {
-      case ISF_SWIN_A_ROWS:
-        if (prec == SWIN_PREC_F16_ROWS) ISF_SWIN_GEMM16(ISF_SWIN_A_ROWS, false, SWIN_PREC_F16_ROWS);
-        else if (ln) ISF_SWIN_GEMM16(ISF_SWIN_A_ROWS, true, SWIN_PREC_F16);
-        else ISF_SWIN_GEMM16(ISF_SWIN_A_ROWS, false, SWIN_PREC_F16);
-        break;
-      case ISF_SWIN_A_MERGE:
-        if (ln) ISF_SWIN_GEMM(ISF_SWIN_A_MERGE, true, false, SWIN_PREC_F16, false);
-        else ISF_SWIN_GEMM(ISF_SWIN_A_MERGE, false, false, SWIN_PREC_F16, false);
-        break;
-      case ISF_SWIN_A_PATCH: ISF_SWIN_GEMM(ISF_SWIN_A_PATCH, false, false, SWIN_PREC_F16, false); break;
-    }
-#undef ISF_SWIN_GEMM16
-    ISF_LAUNCH_CHECK();
-    return ISF_OK;
-  }
-  switch (a->mode) {
-    case ISF_SWIN_A_ROWS:
-      if (row_scale) ISF_SWIN_GEMM(ISF_SWIN_A_ROWS, false, true);
-      else if (ln) ISF_SWIN_GEMM(ISF_SWIN_A_ROWS, true);
-      else ISF_SWIN_GEMM(ISF_SWIN_A_ROWS, false);
-      break;
-    case ISF_SWIN_A_MERGE: if (ln) ISF_SWIN_GEMM(ISF_SWIN_A_MERGE, true); else ISF_SWIN_GEMM(ISF_SWIN_A_MERGE, false); break;
-    case ISF_SWIN_A_PATCH: ISF_SWIN_GEMM(ISF_SWIN_A_PATCH, false); break;
-    case ISF_SWIN_A_UPCAT: ISF_SWIN_GEMM(ISF_SWIN_A_UPCAT, false); break;
-  }
-#undef ISF_SWIN_GEMM
+  hipLaunchKernelGGL(form->kernel, grid, block, 0, as_stream(stream), *a, num_rows, k, wp, winv, out_features, ep, y);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }

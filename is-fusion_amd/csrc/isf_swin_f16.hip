@@ -1,10 +1,12 @@
 // isf_swin_f16.hip -- the f16 inference mode of the Swin-T backbone (SwinTransformer.set_precision("f16")): what is not
-// the GEMM (isf_swin_gemm_f16 is swin_gemm_kernel of isf_swin.hip, instantiated for single-pass products).
+// the GEMM (isf_swin_gemm_f16 is swin_gemm_kernel of isf_swin.hip, instantiated for single-pass products; swin.gemm in
+// Python).  swin.window_attention picks this file's attention entry when the qkv rows are f16.
 //
 // Reference: mmdet3d/models/backbones/swin.py (WindowMSA / ShiftWindowMSA) under mmcv's fp16 machinery (auto_fp16 /
 // torch.autocast): half qkv, half matmuls, softmax, half attention output.  Here:
 //   isf_swin_window_attention_f16  (shifted) window attention on f16 token-major qkv rows, on the matrix cores.  One wave
-//                        per (window, image, head).  Index arithmetic is swin_window_attn_kernel's: zero padding to
+//                        per (window, image, head).  The index arithmetic restates swin_window_attn_kernel's (isf_swin.hip;
+//                        a shared inline helper changed the machine code of both kernels): zero padding to
 //                        multiples of 7, cyclic shift, partition / reverse, a padded cell's q / k / v = the qkv bias (and
 //                        the cell IS attended to), -100 between shift regions, relative position bias [heads, 49, 49].
 //                        The 49 tokens are padded to 64 = 4 tiles of 16; head dim 32 = one K step of

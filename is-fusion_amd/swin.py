@@ -18,8 +18,10 @@ pass that stores NCHW.  Packed weights are derived once per parameter version (f
 isf_swin_window_attention_f16): one matrix instruction per product instead of three, and the branch intermediates --
 qkv [M, 3C], the attention output [M, C], the FFN hidden [M, 4C] -- are f16 rows.  The residual stream, LayerNorm
 statistics, softmax, GELU and every accumulation stay fp32, PatchEmbed / PatchMerging write fp32 rows, and the
-out_indices maps are the same fp32 NCHW tensors.  The mode's packed weights live in the same per-module cache, next to
-the default mode's.  ``precision`` is a plain attribute: no parameter, no buffer, no constructor argument.
+out_indices maps are the same fp32 NCHW tensors.  Both modes run the one schedule above through ``gemm`` and
+``window_attention``: the precision is carried by the packed weight (PackedLinear / PackedLinearF16) and by the dtype of
+the qkv rows, nothing else.  Each mode's packed weights live under its name in the same per-module cache.
+``precision`` is a plain attribute: no parameter, no buffer, no constructor argument.
 """
 import ctypes
 
@@ -42,35 +44,6 @@ def _a(mode, x, *, ldx=0, n=0, c=0, h=0, w=0, x2=None, c2=0, h2=0, w2=0, stats=N
     return s, (x, x2, stats, g, b)
 
 
-def gemm(a, rows, k, pl, *, scale=None, shift=None, act=ACT_NONE, residual=None, out_nchw=None, row_scale=None):
-    """isf_swin_gemm: act((A W^T) * scale + shift) + residual -> [rows, N], or [B, N, H, W] for out_nchw=(B, H, W).
-    row_scale [samples] (isf_swin_gemm_rowscale): the branch output of sample r // (rows // samples) is multiplied by
-    row_scale[sample] before the residual is added (DropPath)."""
-    s, keep = a
-    N = pl.out_features
-    dev = keep[0].device
-    if out_nchw is not None:
-        B, H, W = out_nchw
-        y = torch.empty((B, N, H, W), dtype=torch.float32, device=dev)
-        ldy, y_hw = 0, H * W
-    else:
-        y = torch.empty((rows, N), dtype=torch.float32, device=dev)
-        ldy, y_hw = N, 0
-    if residual is not None:
-        assert residual.is_contiguous() and tuple(residual.shape) == (rows, N)
-    if row_scale is not None:
-        assert row_scale.dtype == torch.float32 and row_scale.is_contiguous() and rows % row_scale.numel() == 0
-        _lib.check(_lib.load().isf_swin_gemm_rowscale(ctypes.byref(s), rows, k, _lib.ptr(pl.packed), N, _lib.ptr(scale),
-                                                      _lib.ptr(shift), act, _lib.ptr(residual), _lib.ptr(row_scale),
-                                                      rows // row_scale.numel(), _lib.ptr(y), ldy, y_hw,
-                                                      _lib.stream()), "isf_swin_gemm_rowscale")
-        return y
-    _lib.check(_lib.load().isf_swin_gemm(ctypes.byref(s), rows, k, _lib.ptr(pl.packed), N, _lib.ptr(scale),
-                                         _lib.ptr(shift), act, _lib.ptr(residual), _lib.ptr(y), ldy, y_hw,
-                                         _lib.stream()), "isf_swin_gemm")
-    return y
-
-
 class PackedLinearF16:
     """nn.Linear weights as one plane of f16 MFMA fragments (isf_pack_linear_f16), for the f16 inference mode"""
 
@@ -85,29 +58,44 @@ class PackedLinearF16:
                                            _lib.stream()), "isf_pack_linear_f16")
 
 
-def gemm_f16(a, rows, k, pl, *, shift=None, act=ACT_NONE, residual=None, out_f16=False):
-    """isf_swin_gemm_f16: act(A W^T + shift) + residual -> [rows, N] fp32, or f16 rows for out_f16.  A comes from the
-    loader `a`; when its x is an f16 tensor, the rows are read as they are (ROWS loader)."""
+def gemm(a, rows, k, pl, *, scale=None, shift=None, act=ACT_NONE, residual=None, out_nchw=None, row_scale=None,
+         out_f16=False):
+    """act((A W^T) * scale + shift) + residual -> [rows, N], or [B, N, H, W] for out_nchw=(B, H, W).  A comes from the
+    loader `a`.  The packed weight carries the precision: a PackedLinear goes to isf_swin_gemm (f16x3 products), a
+    PackedLinearF16 to isf_swin_gemm_f16 (single-pass products; when the loader's x is an f16 tensor its rows are read
+    as they are, and out_f16 stores f16 rows).
+    row_scale [samples] (isf_swin_gemm_rowscale): the branch output of sample r // (rows // samples) is multiplied by
+    row_scale[sample] before the residual is added (DropPath)."""
     s, keep = a
     N = pl.out_features
     x = keep[0]
-    y = torch.empty((rows, N), dtype=torch.float16 if out_f16 else torch.float32, device=x.device)
+    f16 = isinstance(pl, PackedLinearF16)
+    if f16 and row_scale is not None:
+        raise NotImplementedError("swin.gemm: row_scale with a PackedLinearF16 (isf_swin_gemm_f16 has no row scale)")
+    if out_f16 and not f16:
+        raise NotImplementedError("swin.gemm: out_f16 with an f16x3 PackedLinear (isf_swin_gemm stores fp32)")
+    if out_nchw is not None:
+        B, H, W = out_nchw
+        shape, ldy, y_hw = (B, N, H, W), 0, H * W
+    else:
+        shape, ldy, y_hw = (rows, N), N, 0
+    y = torch.empty(shape, dtype=torch.float16 if out_f16 else torch.float32, device=x.device)
     if residual is not None:
         assert residual.dtype == torch.float32 and residual.is_contiguous() and tuple(residual.shape) == (rows, N)
-    _lib.check(_lib.load().isf_swin_gemm_f16(ctypes.byref(s), int(x.dtype == torch.float16), rows, k,
-                                             _lib.ptr(pl.packed), N, None, _lib.ptr(shift), act, _lib.ptr(residual),
-                                             _lib.ptr(y), int(out_f16), N, 0, _lib.stream()), "isf_swin_gemm_f16")
+    lib = _lib.load()
+    # what the three entries share: the operands before y, and y's layout after it
+    ops = (rows, k, _lib.ptr(pl.packed), N, _lib.ptr(scale), _lib.ptr(shift), act, _lib.ptr(residual))
+    lay = (ldy, y_hw, _lib.stream())
+    if f16:
+        _lib.check(lib.isf_swin_gemm_f16(ctypes.byref(s), int(x.dtype == torch.float16), *ops, _lib.ptr(y),
+                                         int(out_f16), *lay), "isf_swin_gemm_f16")
+    elif row_scale is not None:
+        assert row_scale.dtype == torch.float32 and row_scale.is_contiguous() and rows % row_scale.numel() == 0
+        _lib.check(lib.isf_swin_gemm_rowscale(ctypes.byref(s), *ops, _lib.ptr(row_scale), rows // row_scale.numel(),
+                                              _lib.ptr(y), *lay), "isf_swin_gemm_rowscale")
+    else:
+        _lib.check(lib.isf_swin_gemm(ctypes.byref(s), *ops, _lib.ptr(y), *lay), "isf_swin_gemm")
     return y
-
-
-def window_attention_f16(qkv, qkv_bias, rel_bias, B, H, W, C, heads, window, shift, scale):
-    """isf_swin_window_attention_f16: f16 qkv rows [B*H*W, 3C] -> f16 attention output rows [B*H*W, C] (before proj)"""
-    assert qkv.dtype == torch.float16 and qkv.is_contiguous() and tuple(qkv.shape) == (B * H * W, 3 * C)
-    out = torch.empty((B * H * W, C), dtype=torch.float16, device=qkv.device)
-    _lib.check(_lib.load().isf_swin_window_attention_f16(_lib.ptr(qkv), _lib.ptr(qkv_bias), _lib.ptr(rel_bias), B, H,
-                                                         W, C, heads, window, shift, float(scale), _lib.ptr(out),
-                                                         _lib.stream()), "isf_swin_window_attention_f16")
-    return out
 
 
 def row_stats(a, rows, k, eps):
@@ -135,11 +123,13 @@ def layernorm(x, norm, out_nchw=None):
 
 
 def window_attention(qkv, qkv_bias, rel_bias, B, H, W, C, heads, window, shift, scale):
-    """isf_swin_window_attention: qkv rows [B*H*W, 3C] -> attention output rows [B*H*W, C] (before proj)"""
-    out = torch.empty((B * H * W, C), dtype=torch.float32, device=qkv.device)
-    _lib.check(_lib.load().isf_swin_window_attention(_lib.ptr(qkv), _lib.ptr(qkv_bias), _lib.ptr(rel_bias), B, H, W,
-                                                     C, heads, window, shift, float(scale), _lib.ptr(out),
-                                                     _lib.stream()), "isf_swin_window_attention")
+    """qkv rows [B*H*W, 3C] -> attention output rows [B*H*W, C] (before proj) of qkv's dtype: fp32 rows go to
+    isf_swin_window_attention, f16 rows to isf_swin_window_attention_f16"""
+    entry = {torch.float32: "isf_swin_window_attention", torch.float16: "isf_swin_window_attention_f16"}[qkv.dtype]
+    assert qkv.is_contiguous() and tuple(qkv.shape) == (B * H * W, 3 * C)
+    out = torch.empty((B * H * W, C), dtype=qkv.dtype, device=qkv.device)
+    _lib.check(getattr(_lib.load(), entry)(_lib.ptr(qkv), _lib.ptr(qkv_bias), _lib.ptr(rel_bias), B, H, W, C, heads,
+                                           window, shift, float(scale), _lib.ptr(out), _lib.stream()), entry)
     return out
 
 
@@ -230,57 +220,34 @@ class SwinBlock(nn.Module):
         self.norm2 = nn.LayerNorm(embed_dims)
         self.ffn = FFN(embed_dims, feedforward_channels, drop_rate, drop_path_rate)
 
-    def pack(self):
+    def pack(self, linear=PackedLinear):
+        """linear: PackedLinear (default mode) or PackedLinearF16 (f16 inference mode)"""
         m = self.attn.w_msa
         l1, l2 = self.ffn.layers[0][0], self.ffn.layers[1]
-        return dict(qkv=PackedLinear(m.qkv.weight), qkv_b=None if m.qkv.bias is None else m.qkv.bias.detach(),
-                    proj=PackedLinear(m.proj.weight), proj_b=m.proj.bias.detach(), rel=m.relative_bias(),
-                    fc1=PackedLinear(l1.weight), fc1_b=l1.bias.detach(), fc2=PackedLinear(l2.weight),
-                    fc2_b=l2.bias.detach())
-
-    def pack_f16(self):
-        m = self.attn.w_msa
-        l1, l2 = self.ffn.layers[0][0], self.ffn.layers[1]
-        return dict(qkv=PackedLinearF16(m.qkv.weight), qkv_b=None if m.qkv.bias is None else m.qkv.bias.detach(),
-                    proj=PackedLinearF16(m.proj.weight), proj_b=m.proj.bias.detach(), rel=m.relative_bias(),
-                    fc1=PackedLinearF16(l1.weight), fc1_b=l1.bias.detach(), fc2=PackedLinearF16(l2.weight),
-                    fc2_b=l2.bias.detach())
-
-    def run_f16(self, p, x, B, H, W):
-        """run() in the f16 inference mode: x and the result are the fp32 residual rows; qkv, the attention output
-        and the FFN hidden are f16 rows"""
-        M, C = x.shape
-        m = self.attn.w_msa
-        ln1 = (self.norm1.weight.detach(), self.norm1.bias.detach())
-        st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm1.eps)
-        qkv = gemm_f16(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln1), M, C, p["qkv"], shift=p["qkv_b"],
-                       out_f16=True)
-        att = window_attention_f16(qkv, p["qkv_b"], p["rel"], B, H, W, C, m.num_heads, self.attn.window_size,
-                                   self.attn.shift_size, m.scale)
-        x = gemm_f16(_a(_lib.SWIN_A_ROWS, att, ldx=C), M, C, p["proj"], shift=p["proj_b"], residual=x)
-        ln2 = (self.norm2.weight.detach(), self.norm2.bias.detach())
-        st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm2.eps)
-        F = self.ffn.feedforward_channels
-        h = gemm_f16(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln2), M, C, p["fc1"], shift=p["fc1_b"], act=ACT_GELU,
-                     out_f16=True)
-        return gemm_f16(_a(_lib.SWIN_A_ROWS, h, ldx=F), M, F, p["fc2"], shift=p["fc2_b"], residual=x)
+        return dict(qkv=linear(m.qkv.weight), qkv_b=None if m.qkv.bias is None else m.qkv.bias.detach(),
+                    proj=linear(m.proj.weight), proj_b=m.proj.bias.detach(), rel=m.relative_bias(),
+                    fc1=linear(l1.weight), fc1_b=l1.bias.detach(), fc2=linear(l2.weight), fc2_b=l2.bias.detach())
 
     def run(self, p, x, B, H, W, keep=(None, None)):
-        """x: token rows [B*H*W, C] -> the block's output rows.  keep: per-image DropPath factors [B] (keep / keep_prob)
-        of the attention and the FFN branch, or None: the branch output is multiplied by them after window reverse /
-        un-shift and before the identity is added (swin.py:251, mmcv FFN)."""
+        """x: token rows [B*H*W, C] -> the block's output rows; x and the result are the fp32 residual rows.  With the
+        f16 pack (pack(PackedLinearF16)) qkv, the attention output and the FFN hidden are f16 rows.  keep: per-image
+        DropPath factors [B] (keep / keep_prob) of the attention and the FFN branch, or None: the branch output is
+        multiplied by them after window reverse / un-shift and before the identity is added (swin.py:251, mmcv FFN);
+        gemm refuses them with the f16 pack."""
         M, C = x.shape
         m = self.attn.w_msa
+        h16 = isinstance(p["qkv"], PackedLinearF16)
         ln1 = (self.norm1.weight.detach(), self.norm1.bias.detach())
         st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm1.eps)
-        qkv = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln1), M, C, p["qkv"], shift=p["qkv_b"])
+        qkv = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln1), M, C, p["qkv"], shift=p["qkv_b"], out_f16=h16)
         att = window_attention(qkv, p["qkv_b"], p["rel"], B, H, W, C, m.num_heads, self.attn.window_size,
                                self.attn.shift_size, m.scale)
         x = gemm(_a(_lib.SWIN_A_ROWS, att, ldx=C), M, C, p["proj"], shift=p["proj_b"], residual=x, row_scale=keep[0])
         ln2 = (self.norm2.weight.detach(), self.norm2.bias.detach())
         st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm2.eps)
         F = self.ffn.feedforward_channels
-        h = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln2), M, C, p["fc1"], shift=p["fc1_b"], act=ACT_GELU)
+        h = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln2), M, C, p["fc1"], shift=p["fc1_b"], act=ACT_GELU,
+                 out_f16=h16)
         return gemm(_a(_lib.SWIN_A_ROWS, h, ldx=F), M, F, p["fc2"], shift=p["fc2_b"], residual=x, row_scale=keep[1])
 
 
@@ -310,8 +277,7 @@ class PatchEmbed(nn.Module):
         N, C, H, W = img.shape
         Ho, Wo = (H + 3) // 4, (W + 3) // 4
         M = N * Ho * Wo
-        mm = gemm_f16 if isinstance(p["w"], PackedLinearF16) else gemm
-        x = mm(_a(_lib.SWIN_A_PATCH, img, n=N, c=C, h=H, w=W), M, p["k"], p["w"], shift=p["b"])
+        x = gemm(_a(_lib.SWIN_A_PATCH, img, n=N, c=C, h=H, w=W), M, p["k"], p["w"], shift=p["b"])
         if self.norm is not None:
             x = layernorm(x, self.norm)
         return x, (Ho, Wo)
@@ -355,8 +321,7 @@ class PatchMerging(nn.Module):
             a = _a(_lib.SWIN_A_MERGE, x, stats=st, ln=(p["g"], p["b"]), **geo)
         else:
             a = _a(_lib.SWIN_A_MERGE, x, **geo)
-        mm = gemm_f16 if isinstance(p["w"], PackedLinearF16) else gemm
-        return mm(a, M, 4 * C, p["w"]), (Ho, Wo)
+        return gemm(a,M, 4 * C, p["w"]), (Ho, Wo)
 
 
 class SwinBlockSequence(nn.Module):
@@ -434,21 +399,14 @@ class SwinTransformer(nn.Module):
         """the packed weights of the current mode; both modes' copies share the module's one derived-weight store, so a
         parameter change drops both and each is derived again on its next use"""
         c = _cache(self, dev)
-        if self.precision == "f16":
-            if "f16" not in c:
-                with torch.no_grad():
-                    c["f16"] = dict(
-                        patch=self.patch_embed.pack(PackedLinearF16),
-                        blocks=[[blk.pack_f16() for blk in st.blocks] for st in self.stages],
-                        merge=[st.downsample.pack(PackedLinearF16) if st.downsample is not None else None
-                               for st in self.stages])
-            return c["f16"]
-        if "patch" not in c:
+        if self.precision not in c:
+            linear = {"f32": PackedLinear, "f16": PackedLinearF16}[self.precision]
             with torch.no_grad():
-                c["patch"] = self.patch_embed.pack()
-                c["blocks"] = [[blk.pack() for blk in st.blocks] for st in self.stages]
-                c["merge"] = [st.downsample.pack() if st.downsample is not None else None for st in self.stages]
-        return c
+                c[self.precision] = dict(
+                    patch=self.patch_embed.pack(linear),
+                    blocks=[[blk.pack(linear) for blk in st.blocks] for st in self.stages],
+                    merge=[st.downsample.pack(linear) if st.downsample is not None else None for st in self.stages])
+        return c[self.precision]
 
     @torch.no_grad()
     def forward(self, x):
@@ -495,8 +453,7 @@ class SwinTransformer(nn.Module):
         assert x.dim() == 4, x.shape
         x = x.float().contiguous()
         N = x.shape[0]
-        f16 = self.precision == "f16"
-        assert not (f16 and scales is not None)
+        assert scales is None or self.precision == "f32"      # DropPath is not built for the f16 inference mode
         p = self._packed(x.device)
         t, (H, W) = self.patch_embed.run(p["patch"], x)
         outs = []
@@ -507,7 +464,7 @@ class SwinTransformer(nn.Module):
                 if scales is not None and blk.attn.drop_path_rate > 0.0:
                     keep = (scales[row], scales[row + 1])
                     row += 2
-                t = blk.run_f16(bp, t, N, H, W) if f16 else blk.run(bp, t, N, H, W, keep)
+                t = blk.run(bp, t, N, H, W, keep)
             if i in self.out_indices:
                 outs.append(layernorm(t, getattr(self, f"norm{i}"), out_nchw=(N, H, W)))
             if stage.downsample is not None:

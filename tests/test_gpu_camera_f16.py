@@ -87,7 +87,7 @@ def _attention_case(C, heads, H, W, shift, with_bias, seed):
     qkv16 = r(B * H * W, 3 * C).half()
     bias = r(3 * C, s=0.5).float() if with_bias else None
     table = r(heads, 49, 49, s=0.5).float()
-    got = swin.window_attention_f16(qkv16, bias, table, B, H, W, C, heads, 7, shift, 32 ** -0.5)
+    got = swin.window_attention(qkv16, bias, table, B, H, W, C, heads, 7, shift, 32 ** -0.5)
     assert got.dtype == torch.float16 and tuple(got.shape) == (B * H * W, C)
     b64 = None if bias is None else bias.half().double()          # a padded cell holds the bias as the qkv GEMM stores it
     ref = _attention_ref(qkv16.double(), b64, table.double(), B, H, W, C, heads, shift)
@@ -134,8 +134,8 @@ def test_rows_layernorm_gelu_f16_out_equals_float64(shape):
     x, g, b = (r(M, K, s=3.0) + 0.5).float(), (1 + r(K, s=0.1)).float(), r(K, s=0.1).float()
     w, bias = r(N, K, s=K ** -0.5).float(), r(N, s=0.1).float()
     st = swin.row_stats(swin._a(_lib.SWIN_A_ROWS, x, ldx=K), M, K, 1e-5)
-    got = swin.gemm_f16(swin._a(_lib.SWIN_A_ROWS, x, ldx=K, stats=st, ln=(g, b)), M, K, swin.PackedLinearF16(w),
-                        shift=bias, act=ACT_GELU, out_f16=True)
+    got = swin.gemm(swin._a(_lib.SWIN_A_ROWS, x, ldx=K, stats=st, ln=(g, b)), M, K, swin.PackedLinearF16(w),
+                    shift=bias, act=ACT_GELU, out_f16=True)
     assert got.dtype == torch.float16
     a16 = F.layer_norm(x.double(), (K,), g.double(), b.double(), 1e-5).half().double()
     w16 = w.half().double()
@@ -152,7 +152,7 @@ def test_rows_f16_in_fp32_out_bias_residual_equals_float64():
     r = _gen(31)
     h16 = r(M, K).half()
     w, bias, res = r(N, K, s=K ** -0.5).float(), r(N, s=0.1).float(), r(M, N).float()
-    got = swin.gemm_f16(swin._a(_lib.SWIN_A_ROWS, h16, ldx=K), M, K, swin.PackedLinearF16(w), shift=bias, residual=res)
+    got = swin.gemm(swin._a(_lib.SWIN_A_ROWS, h16, ldx=K), M, K, swin.PackedLinearF16(w), shift=bias, residual=res)
     assert got.dtype == torch.float32
     w16 = w.half().double()
     ref = h16.double() @ w16.t() + bias.double() + res.double()
@@ -203,7 +203,7 @@ def test_patch_gemm_f16_equals_float64(hw):
     img = r(2, 3, H, W).float()
     p = m.pack(swin.PackedLinearF16)
     Ho, Wo = (H + 3) // 4, (W + 3) // 4
-    got = swin.gemm_f16(swin._a(_lib.SWIN_A_PATCH, img, n=2, c=3, h=H, w=W), 2 * Ho * Wo, p["k"], p["w"], shift=p["b"])
+    got = swin.gemm(swin._a(_lib.SWIN_A_PATCH, img, n=2, c=3, h=H, w=W), 2 * Ho * Wo, p["k"], p["w"], shift=p["b"])
     i16 = F.pad(img.half().double(), (0, (-W) % 4, 0, (-H) % 4))
     w16 = m.projection.weight.detach().half().double()
     ref = F.conv2d(i16, w16, m.projection.bias.double(), stride=4).flatten(2).transpose(1, 2).reshape(-1, 96)
@@ -235,7 +235,7 @@ def test_layernorm_prologue_f16_is_exact_in_every_round_of_workgroups():
     w = r(N, C, s=C ** -0.5).float()
     pl = PackedLinearF16(w)
     st = swin.row_stats(swin._a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, 1e-5)
-    runs = [swin.gemm_f16(swin._a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=(g, b)), M, C, pl) for _ in range(2)]
+    runs = [swin.gemm(swin._a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=(g, b)), M, C, pl) for _ in range(2)]
     a16 = F.layer_norm(x.double(), (C,), g.double(), b.double(), 1e-5).half().double()
     w16 = w.half().double()
     ref = a16 @ w16.t()
@@ -261,13 +261,13 @@ def test_layernorm_prologue_f16_is_exact_in_every_round_of_workgroups():
 
 def test_block_f16_is_bit_identical_run_to_run_at_full_size():
     """one stage-0 block at 12 x 96 x 264 tokens (2376 row tiles: several rounds of workgroups per compute unit)"""
-    from isfusion_amd.swin import SwinBlock
+    from isfusion_amd.swin import PackedLinearF16, SwinBlock
     blk = SwinBlock(96, 3, 384, shift=True).to(DEV).eval()
     blk.load_state_dict(CC.seeded_module_state(blk, 21))
     B, H, W = 12, 96, 264
     x = _gen(8)(B * H * W, 96).float()
-    p = blk.pack_f16()
-    a, b = blk.run_f16(p, x, B, H, W), blk.run_f16(p, x, B, H, W)
+    p = blk.pack(PackedLinearF16)
+    a, b = blk.run(p, x, B, H, W), blk.run(p, x, B, H, W)
     assert torch.equal(a, b) and bool(torch.isfinite(a).all())
     sd64 = CC.cast({"b." + k: v for k, v in blk.state_dict().items()}, torch.float64, DEV)
     sd32 = CC.cast({"b." + k: v for k, v in blk.state_dict().items()}, torch.float32, DEV)
@@ -276,6 +276,54 @@ def test_block_f16_is_bit_identical_run_to_run_at_full_size():
         with torch.autocast("cuda", dtype=torch.float16):
             ac = CC.swin_block(sd32, "b.", x.view(B, H * W, 96), (H, W), 3, 7, 3).reshape(-1, 96)
     _rule("stage-0 block at 12 x 96 x 264", a, ref, ac)
+
+
+def test_gemm_forms_that_are_not_built_are_refused_before_a_launch():
+    """the launcher's table of built forms (swin_gemm_forms): every combination outside it, and a null row_scale, comes
+    back with a code and a message, and y keeps its fill.  Arguments are valid otherwise, so the loader checks pass."""
+    import ctypes
+    from isfusion_amd import _lib, swin
+    from isfusion_amd.fusion_ops import PackedLinear
+    lib = _lib.load()
+    M, K, N = 16, 32, 16
+    r = _gen(41)
+    w = r(N, K).float()
+    x3, f16 = PackedLinear(w), swin.PackedLinearF16(w)
+    x, g, b = r(M, K).float(), r(K).float(), r(K).float()
+    st = swin.row_stats(swin._a(_lib.SWIN_A_ROWS, x, ldx=K), M, K, 1e-5)
+    rows = swin._a(_lib.SWIN_A_ROWS, x, ldx=K)
+    rows_ln = swin._a(_lib.SWIN_A_ROWS, x, ldx=K, stats=st, ln=(g, b))
+    rows16_ln = swin._a(_lib.SWIN_A_ROWS, x.half(), ldx=K, stats=st, ln=(g, b))
+    merge = swin._a(_lib.SWIN_A_MERGE, r(64, 8).float(), n=1, c=8, h=8, w=8)
+    upcat = swin._a(_lib.SWIN_A_UPCAT, r(1, 16, 4, 4).float(), n=1, c=16, h=4, w=4, x2=r(1, 16, 2, 2).float(), c2=16,
+                    h2=2, w2=2)
+    keep = torch.ones(1, dtype=torch.float32, device=DEV)
+    y = torch.full((M, N), 7.0, dtype=torch.float32, device=DEV)
+    yp, stream = _lib.ptr(y), _lib.stream()
+
+    def gemm_f16(a, a16, pl, y16, y_hw):
+        return lib.isf_swin_gemm_f16(ctypes.byref(a[0]), a16, M, K, _lib.ptr(pl.packed), N, None, None, 0, None, yp, y16,
+                                     0 if y_hw else N, y_hw, stream)
+
+    def gemm_rowscale(a, row_scale):
+        return lib.isf_swin_gemm_rowscale(ctypes.byref(a[0]), M, K, _lib.ptr(x3.packed), N, None, None, 0, None,
+                                          _lib.ptr(row_scale), M, yp, N, 0, stream)
+
+    cases = {"f16 mode, UPCAT loader": lambda: gemm_f16(upcat, 0, f16, 0, 0),
+             "f16 mode, y_hw > 0": lambda: gemm_f16(rows, 0, f16, 0, M),
+             "f16 A rows, LayerNorm prologue": lambda: gemm_f16(rows16_ln, 1, f16, 0, 0),
+             "f16 output, MERGE loader": lambda: gemm_f16(merge, 0, f16, 1, 0),
+             "row scale, LayerNorm prologue": lambda: gemm_rowscale(rows_ln, keep),
+             "isf_swin_gemm_rowscale, null row_scale": lambda: gemm_rowscale(rows, None)}
+    for what, call in cases.items():
+        rc = call()
+        msg = lib.isf_last_error().decode()
+        print(f"{what}: code {rc}, {msg!r}")
+        assert rc != _lib.ISF_OK and msg.startswith("swin_gemm"), (what, rc, msg)
+    assert bool((y == 7.0).all())
+    with pytest.raises(NotImplementedError, match="row_scale"):
+        swin.gemm(rows, M, K, f16, row_scale=keep)
+    assert gemm_f16(rows, 0, f16, 0, 0) == _lib.ISF_OK and not bool((y == 7.0).any())     # the calls above were valid
 
 
 # --------------------------------------------------------------------------------------------------- backbone
@@ -334,7 +382,7 @@ def test_modes_do_not_leak():
 def test_f16_stores_saturate():
     """one C = 96 block whose fc1 weights are scaled until the FFN hidden passes the f16 range: stored as +-65504, not
     inf, so every output stays finite"""
-    from isfusion_amd.swin import SwinBlock
+    from isfusion_amd.swin import PackedLinearF16, SwinBlock
     r = _gen(3)
     blk = SwinBlock(96, 3, 384).to(DEV).eval()
     sd = CC.seeded_module_state(blk, 12)
@@ -342,7 +390,7 @@ def test_f16_stores_saturate():
     blk.load_state_dict(sd)
     B, H, W = 2, 9, 10
     x = r(B * H * W, 96).float()
-    y = blk.run_f16(blk.pack_f16(), x, B, H, W)
+    y = blk.run(blk.pack(PackedLinearF16), x, B, H, W)
     # the premise, in float64: the hidden does leave the f16 range
     sd64 = CC.cast({"b." + k: v for k, v in blk.state_dict().items()}, torch.float64, DEV)
     x64 = x.double().view(B, H * W, 96)
