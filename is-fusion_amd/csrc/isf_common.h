@@ -50,6 +50,11 @@ void set_error(const char* fmt, ...);
 struct ByteMaps {
   unsigned char* fine = nullptr;
   unsigned char* coarse = nullptr;
+  // the level-0 index itself lives here too, so that a call writes only the words that are, or were, non-zero:
+  // BETWEEN CALLS every word of `bits0` whose `dirty` byte is 0 is zero (prefix0 is defined only behind a non-zero word)
+  unsigned long long* bits0 = nullptr;   // [words]
+  uint32_t* prefix0 = nullptr;           // [words]
+  unsigned char* dirty = nullptr;        // [words], the shape of `coarse`: 1 = bits0[w] != 0
   size_t words = 0;
 };
 
@@ -104,15 +109,24 @@ struct OccIndex {
   int* total;                // device scalar: number of set bits
 };
 
-int occ_create(Arena& a, OccIndex* occ, int B, int D, int H, int W, hipStream_t st, bool zero = true);
+// bits / prefix: the caller's arrays (round_up(nwords, 1024) entries each) instead of arena memory; only with zero = false
+int occ_create(Arena& a, OccIndex* occ, int B, int D, int H, int W, hipStream_t st, bool zero = true,
+               unsigned long long* bits = nullptr, uint32_t* prefix = nullptr);
 size_t occ_bits_bytes(const OccIndex& occ);   // bytes occ_create(zero = true) clears
-// atomic-free marking through persistent byte maps (writes EVERY bitmap word: create with zero = false)
+// the level-0 index of the byte-map marking below: bits / prefix are the workspace's persistent arrays (ByteMaps), which the
+// marking keeps up to date by writing only the words that are, or were, non-zero.  prefix[w] is defined only where
+// bits[w] != 0 (occ_lookup and every other reader look at the word first); one such index per workspace at a time.
+int occ_create_bytemap(Arena& a, OccIndex* occ, int B, int D, int H, int W, hipStream_t st);
+// atomic-free marking through persistent byte maps; `occ` comes from occ_create_bytemap
 int occ_mark_coords4_bytemap(Arena& a, const OccIndex& occ, const int32_t* coors4, int n, hipStream_t st,
                              uint32_t* block_sums = nullptr /* occ_scan_block_sums: the pack pass leaves the blocks' popcounts */);
 int scan_u32_exclusive(Arena& a, const uint32_t* in, uint32_t* out, size_t n, hipStream_t st);
 // prefix + total.  block_sums: the blocks' popcounts are there already (the byte-map pack pass wrote them: no count launch);
-// clear: counters [0, total] are zeroed in the prefix launch (one per rank + one; at least total + 1 allocated)
-int occ_scan(Arena& a, const OccIndex& occ, hipStream_t st, uint32_t* block_sums = nullptr, uint32_t* clear = nullptr);
+// clear: counters [0, total] are zeroed in the prefix launch (one per rank + one; at least total + 1 allocated);
+// ticket: the total goes to the host mailbox as post_int(occ.total) would send it (wait_int(*ticket) receives it) -- from
+// inside the prefix launch where that launch forms the total itself, by a post_int behind it otherwise
+int occ_scan(Arena& a, const OccIndex& occ, hipStream_t st, uint32_t* block_sums = nullptr, uint32_t* clear = nullptr,
+             unsigned* ticket = nullptr);
 int occ_scan_block_sums(Arena& a, const OccIndex& occ, uint32_t** sums);   // the buffer `block_sums` of occ_scan
 int occ_mark_coords4(const OccIndex& occ, const int32_t* coors4, int n, hipStream_t st);
 // coords of all set bits in rank order -> out [total,4]

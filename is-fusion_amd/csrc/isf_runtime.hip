@@ -64,16 +64,21 @@ int Arena::alloc(void** out, size_t bytes) {
   return ISF_OK;
 }
 
+static void bytemaps_free(ByteMaps& bm) {   // (a partly allocated set too: hipFree(nullptr) is a no-op)
+  (void)hipFree(bm.fine);
+  (void)hipFree(bm.coarse);
+  (void)hipFree(bm.bits0);
+  (void)hipFree(bm.prefix0);
+  (void)hipFree(bm.dirty);
+  bm = ByteMaps();
+}
+
 int Arena::release() {
   if (!blocks_.empty() || bytemaps.fine || side || mailbox_host || zero_pool || ks_scratch || ks_count)
     ISF_HIP_TRY(hipDeviceSynchronize());
   for (auto& b : blocks_) ISF_HIP_TRY(hipFree(b.base));
   blocks_.clear();
-  if (bytemaps.fine) {
-    (void)hipFree(bytemaps.fine);
-    (void)hipFree(bytemaps.coarse);
-    bytemaps = ByteMaps();
-  }
+  bytemaps_free(bytemaps);
   for (auto e : events) (void)hipEventDestroy(e);
   events.clear();
   next_event = 0;
@@ -108,6 +113,12 @@ int Arena::list_blocks(unsigned long long* base_cap, int max_pairs, int* num_pai
     if (n < max_pairs) { base_cap[2 * n] = (unsigned long long)(size_t)bytemaps.fine; base_cap[2 * n + 1] = bytemaps.words * 64; }
     ++n;
     if (n < max_pairs) { base_cap[2 * n] = (unsigned long long)(size_t)bytemaps.coarse; base_cap[2 * n + 1] = bytemaps.words; }
+    ++n;
+    if (n < max_pairs) { base_cap[2 * n] = (unsigned long long)(size_t)bytemaps.bits0; base_cap[2 * n + 1] = bytemaps.words * 8; }
+    ++n;
+    if (n < max_pairs) { base_cap[2 * n] = (unsigned long long)(size_t)bytemaps.prefix0; base_cap[2 * n + 1] = bytemaps.words * 4; }
+    ++n;
+    if (n < max_pairs) { base_cap[2 * n] = (unsigned long long)(size_t)bytemaps.dirty; base_cap[2 * n + 1] = bytemaps.words; }
     ++n;
   }
   *num_pairs = n;
@@ -207,7 +218,8 @@ __global__ void publish_int_kernel(const int* __restrict__ src, volatile int* bo
   __threadfence_system();
 }
 
-int post_int(Arena& a, const int* dev, hipStream_t st, unsigned* ticket) {
+// the next ticket and its slot (device address): whoever writes (value, ticket) there, value first, posts the int
+static int mailbox_reserve(Arena& a, unsigned* ticket, int** box) {
   if (!a.mailbox_host) {
     void* h = nullptr;
     // coherent (fine-grained) explicitly: the host polls this memory while the kernel that writes it may still be
@@ -221,10 +233,16 @@ int post_int(Arena& a, const int* dev, hipStream_t st, unsigned* ticket) {
     a.mailbox_seq = 0;
   }
   const unsigned t = ++a.mailbox_seq;          // tickets start at 1: a zeroed slot never matches
-  const unsigned slot = t % kMailboxSlots;
-  hipLaunchKernelGGL(publish_int_kernel, dim3(1), dim3(1), 0, st, dev, a.mailbox_dev + 2 * slot, (int)t);
-  ISF_LAUNCH_CHECK();
+  *box = a.mailbox_dev + 2 * (t % kMailboxSlots);
   *ticket = t;
+  return ISF_OK;
+}
+
+int post_int(Arena& a, const int* dev, hipStream_t st, unsigned* ticket) {
+  int* box = nullptr;
+  ISF_TRY(mailbox_reserve(a, ticket, &box));
+  hipLaunchKernelGGL(publish_int_kernel, dim3(1), dim3(1), 0, st, dev, box, (int)*ticket);
+  ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
 
@@ -342,8 +360,10 @@ __global__ __launch_bounds__(1024) void occ_scan_sums_kernel(uint32_t* __restric
 
 // Offset of a block = sum of the totals of the blocks before it.  Up to kLookBehindBlocks blocks every block adds them up
 // itself (SUMS = true: `block_sums` holds raw totals; the last block also writes the grand total) -- the single-workgroup scan
-// in between is one launch more than the few KiB of L2 reads it saves; larger grids (level 0: 5 000 blocks) keep it.
-static constexpr int kLookBehindBlocks = 2048;
+// in between is one launch (13 us of latency at level 0) more than the L2 reads it saves: 20 KiB for the last of the 5 200
+// blocks of the 0.075 m level-0 grid at B = 4; larger grids (0.05 m voxels: 11 700 blocks) keep it.  Blocks without a set
+// bit have total 0 and are added like any other.
+static constexpr int kLookBehindBlocks = 8192;
 __device__ __forceinline__ uint32_t scan_look_behind(const uint32_t* __restrict__ block_sums, uint32_t* lds) {
   uint32_t s = 0;
   for (int i = threadIdx.x; i < (int)blockIdx.x; i += kScanThreads) s += block_sums[i];
@@ -363,21 +383,38 @@ template <bool SUMS>
 __global__ __launch_bounds__(kScanThreads) void occ_write_prefix_kernel(
     const unsigned long long* __restrict__ bits, size_t nwords,
     const uint32_t* __restrict__ block_offsets, uint32_t* __restrict__ prefix, int* __restrict__ total,
-    uint32_t* __restrict__ clear /* or nullptr: one counter per rank + one; a block zeroes those of its own ranks */) {
+    uint32_t* __restrict__ clear /* or nullptr: one counter per rank + one; a block zeroes those of its own ranks */,
+    const unsigned char* __restrict__ word_mask /* or nullptr: one byte per word (round_up(nwords, 1024) of them), 0 = the
+                                                   word is zero; a thread whose four words are reads no bitmap word and
+                                                   writes no prefix (nobody asks for the prefix of an empty word) */,
+    volatile int* box /* SUMS only, or nullptr: the host mailbox slot that receives (total, ticket) */, int ticket) {
+  static_assert(kWordsPerThread == 4, "one 4-byte load of the word mask per thread");
   __shared__ uint32_t lds[kScanThreads / 64];
   const size_t w0 = (size_t)blockIdx.x * kWordsPerBlock + (size_t)threadIdx.x * kWordsPerThread;
-  uint32_t pc[kWordsPerThread];
+  const bool live = !word_mask || *reinterpret_cast<const unsigned int*>(word_mask + w0) != 0u;
+  uint32_t pc[kWordsPerThread] = {0u, 0u, 0u, 0u};
+  if (live) {
 #pragma unroll
-  for (int i = 0; i < kWordsPerThread; ++i) pc[i] = (w0 + i < nwords) ? __popcll(bits[w0 + i]) : 0;
+    for (int i = 0; i < kWordsPerThread; ++i) pc[i] = (w0 + i < nwords) ? __popcll(bits[w0 + i]) : 0;
+  }
   uint32_t c = pc[0] + pc[1] + pc[2] + pc[3];
   uint32_t tot;
   const uint32_t base = SUMS ? scan_look_behind(block_offsets, lds) : block_offsets[blockIdx.x];
   uint32_t ex = block_exclusive_scan(c, lds, &tot) + base;
-  if (SUMS && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *total = (int)(base + tot);
+  if (SUMS && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    *total = (int)(base + tot);
+    if (box) {   // what publish_int_kernel does, without its launch: the value, then the ticket, each pushed to the host
+      box[0] = (int)(base + tot);
+      __threadfence_system();
+      box[1] = ticket;
+      __threadfence_system();
+    }
+  }
   if (clear) {   // ranks [base, base + tot) are this block's; the last block adds counter [total]
     const uint32_t n = tot + (blockIdx.x == gridDim.x - 1 ? 1u : 0u);
     for (uint32_t i = threadIdx.x; i < n; i += kScanThreads) clear[base + i] = 0u;
   }
+  if (!live) return;   // (behind the last barrier)
 #pragma unroll
   for (int i = 0; i < kWordsPerThread; ++i) {
     if (w0 + i < nwords) prefix[w0 + i] = ex;
@@ -389,14 +426,21 @@ size_t occ_bits_bytes(const OccIndex& occ) {   // what occ_create's zero fill co
   return round_up(occ.nwords, kWordsPerBlock) * sizeof(unsigned long long);
 }
 
-int occ_create(Arena& a, OccIndex* occ, int B, int D, int H, int W, hipStream_t st, bool zero) {
+int occ_create(Arena& a, OccIndex* occ, int B, int D, int H, int W, hipStream_t st, bool zero,
+               unsigned long long* bits, uint32_t* prefix) {
+  ISF_REQUIRE((bits != nullptr) == (prefix != nullptr) && !(bits && zero), ISF_ERR_ARG,
+              "occ_create: the caller's arrays come as a pair and are not cleared here");
   occ->B = B; occ->D = D; occ->H = H; occ->W = W;
   occ->ncells = (unsigned long long)B * D * H * W;
   occ->nwords = (size_t)((occ->ncells + 63) / 64);
   // pad the word count to a multiple of kWordsPerThread so vector loads stay in bounds
   const size_t alloc_words = round_up(occ->nwords, kWordsPerBlock);
-  ISF_TRY(a.alloc_n(&occ->bits, alloc_words));
-  ISF_TRY(a.alloc_n(&occ->prefix, alloc_words));
+  occ->bits = bits;
+  occ->prefix = prefix;
+  if (!bits) {
+    ISF_TRY(a.alloc_n(&occ->bits, alloc_words));
+    ISF_TRY(a.alloc_n(&occ->prefix, alloc_words));
+  }
   ISF_TRY(a.alloc_n(&occ->total, 64));
   if (zero) ISF_HIP_TRY(hipMemsetAsync(occ->bits, 0, alloc_words * sizeof(unsigned long long), st));
   return ISF_OK;
@@ -407,9 +451,14 @@ int occ_create(Arena& a, OccIndex* occ, int B, int D, int H, int W, hipStream_t 
 // for 1.2 M points.  Instead: two persistent all-zero byte maps, `fine` (1 byte per cell) and `coarse`
 // (1 byte per 64-cell word).  Pass A: every point stores 1 into both (idempotent plain stores: racing
 // writers write the same value).  Pass B: one thread per word; touched words gather their 64 fine bytes into
-// the bitmap word and zero what they read, so both maps are clean again for the next frame; untouched words
-// write 0 (which also replaces the bitmap memset).  HBM traffic per frame: nwords (coarse) + 64 B per touched
-// word, instead of ~1.2 M fabric atomics.
+// the bitmap word and zero what they read, so both maps are clean again for the next frame.  The bitmap and its
+// prefix array are persistent too (ByteMaps::bits0 / prefix0), with a third byte map `dirty` (1 byte per word,
+// 1 = the word is non-zero): an untouched word that was zero after the previous call is not written at all -- at
+// level 0 at most 358 k of 5.3 M words are ever non-zero, and the pack pass wrote all 42 MB of them every frame.
+// INVARIANT between calls: dirty[w] == 0 implies bits0[w] == 0.  The thread that stores a word stores its dirty
+// byte, and no other kernel writes either array, so a later launch of the call that fails (or a call that returns
+// early) cannot break it; a pack launch that itself fails has written nothing.  HBM traffic per frame: 2 x nwords
+// (coarse, dirty) + 64 B per touched word, instead of ~1.2 M fabric atomics.
 
 __global__ void occ_bytemap_mark_kernel(const int32_t* __restrict__ coors4, int n, int B, int D, int H, int W,
                                         unsigned char* __restrict__ fine, unsigned char* __restrict__ coarse) {
@@ -426,6 +475,7 @@ __global__ __launch_bounds__(256) void occ_bytemap_pack_kernel(unsigned char* __
                                                                unsigned char* __restrict__ coarse,
                                                                size_t nwords_alloc,
                                                                unsigned long long* __restrict__ bits,
+                                                               unsigned char* __restrict__ dirty,
                                                                uint32_t* __restrict__ block_sums) {
   // thread -> 4 consecutive words (one 4-byte load of the coarse map); a workgroup covers the kWordsPerBlock words of one
   // block of occ_scan and, with `block_sums`, leaves their popcount there: what occ_block_count_kernel would re-read the
@@ -434,6 +484,7 @@ __global__ __launch_bounds__(256) void occ_bytemap_pack_kernel(unsigned char* __
   __shared__ uint32_t wave_sums[4];
   const size_t w0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const unsigned int c4 = *reinterpret_cast<const unsigned int*>(coarse + w0);
+  const unsigned int d4 = *reinterpret_cast<const unsigned int*>(dirty + w0);   // words the previous call left non-zero
   unsigned long long out[4] = {0ull, 0ull, 0ull, 0ull};
   if (c4) {
 #pragma unroll
@@ -456,8 +507,12 @@ __global__ __launch_bounds__(256) void occ_bytemap_pack_kernel(unsigned char* __
     }
     *reinterpret_cast<unsigned int*>(coarse + w0) = 0u;
   }
-  reinterpret_cast<ulonglong2*>(bits + w0)[0] = make_ulonglong2(out[0], out[1]);
-  reinterpret_cast<ulonglong2*>(bits + w0)[1] = make_ulonglong2(out[2], out[3]);
+  if (c4 | d4) {   // else: the four words are zero and stay zero
+    reinterpret_cast<ulonglong2*>(bits + w0)[0] = make_ulonglong2(out[0], out[1]);
+    reinterpret_cast<ulonglong2*>(bits + w0)[1] = make_ulonglong2(out[2], out[3]);
+    *reinterpret_cast<unsigned int*>(dirty + w0) = (out[0] ? 1u : 0u) | (out[1] ? 1u << 8 : 0u) | (out[2] ? 1u << 16 : 0u) |
+                                                   (out[3] ? 1u << 24 : 0u);
+  }
   if (block_sums) {
     uint32_t c = __popcll(out[0]) + __popcll(out[1]) + __popcll(out[2]) + __popcll(out[3]);
 #pragma unroll
@@ -488,63 +543,71 @@ __global__ __launch_bounds__(256) void occ_voxelize_mark_kernel(int P, int C, Vo
   }
 }
 
-static int occ_bytemaps_ensure(Arena& a, const OccIndex& occ, hipStream_t st, size_t* alloc_words_out) {
+static int occ_bytemaps_ensure(Arena& a, size_t nwords, hipStream_t st, size_t* alloc_words_out) {
   ByteMaps& bm = a.bytemaps;
-  const size_t alloc_words = round_up(occ.nwords, kWordsPerBlock);
+  const size_t alloc_words = round_up(nwords, kWordsPerBlock);
   *alloc_words_out = alloc_words;
-  if (bm.words < alloc_words) {  // (re)allocate the persistent maps; zeroed once, kept zero by the pack pass
+  if (bm.words < alloc_words) {  // (re)allocate the persistent maps; zeroed once, kept as the invariant says by the pack pass
     ISF_HIP_TRY(hipStreamSynchronize(st));
-    if (bm.fine) { ISF_HIP_TRY(hipFree(bm.fine)); ISF_HIP_TRY(hipFree(bm.coarse)); bm = ByteMaps(); }
-    if (hipMalloc(&bm.fine, alloc_words * 64) != hipSuccess || hipMalloc(&bm.coarse, alloc_words) != hipSuccess) {
+    bytemaps_free(bm);
+    if (hipMalloc(&bm.fine, alloc_words * 64) != hipSuccess || hipMalloc(&bm.coarse, alloc_words) != hipSuccess ||
+        hipMalloc(&bm.bits0, alloc_words * sizeof(unsigned long long)) != hipSuccess ||
+        hipMalloc(&bm.prefix0, alloc_words * sizeof(uint32_t)) != hipSuccess ||
+        hipMalloc(&bm.dirty, alloc_words) != hipSuccess) {
       (void)hipGetLastError();
-      set_error("occupancy byte maps: hipMalloc(%zu) failed", alloc_words * 65);
+      bytemaps_free(bm);
+      set_error("occupancy byte maps: hipMalloc(%zu) failed", alloc_words * 78);
       return ISF_ERR_NOMEM;
     }
+    bm.words = alloc_words;   // (before the fills: a failed fill leaves maps that release() frees)
     ISF_HIP_TRY(hipMemsetAsync(bm.fine, 0, alloc_words * 64, st));
     ISF_HIP_TRY(hipMemsetAsync(bm.coarse, 0, alloc_words, st));
-    bm.words = alloc_words;
+    ISF_HIP_TRY(hipMemsetAsync(bm.bits0, 0, alloc_words * sizeof(unsigned long long), st));
+    ISF_HIP_TRY(hipMemsetAsync(bm.prefix0, 0, alloc_words * sizeof(uint32_t), st));
+    ISF_HIP_TRY(hipMemsetAsync(bm.dirty, 0, alloc_words, st));
   }
   return ISF_OK;
 }
+
+int occ_create_bytemap(Arena& a, OccIndex* occ, int B, int D, int H, int W, hipStream_t st) {
+  size_t alloc_words = 0;
+  ISF_TRY(occ_bytemaps_ensure(a, (size_t)(((unsigned long long)B * D * H * W + 63) / 64), st, &alloc_words));
+  return occ_create(a, occ, B, D, H, W, st, false, a.bytemaps.bits0, a.bytemaps.prefix0);
+}
+
+// the pack pass skips words by the dirty map, which describes bits0 and nothing else
+#define ISF_REQUIRE_BYTEMAP_INDEX(a, occ, what)                                                                    \
+  ISF_REQUIRE((a).bytemaps.bits0 && (occ).bits == (a).bytemaps.bits0 && (occ).prefix == (a).bytemaps.prefix0 &&   \
+                  round_up((occ).nwords, kWordsPerBlock) <= (a).bytemaps.words,                                    \
+              ISF_ERR_ARG, what ": the index does not come from occ_create_bytemap")
 
 int occ_voxelize_mark_bytemap(Arena& a, const OccIndex& occ, int P, int C, const VoxGeom& g, const VoxBatch& vb,
                               int32_t* coors4, hipStream_t st, uint32_t* block_sums) {
   ISF_REQUIRE(vb.B >= 1 && vb.B <= kVoxMaxBatch && vb.B == occ.B && g.gy == occ.H && g.gx == occ.W && g.gz <= occ.D,
               ISF_ERR_ARG, "voxelize + mark: %d frames, grid %d x %d x %d vs index %d x %d x %d", vb.B, g.gz, g.gy, g.gx,
               occ.D, occ.H, occ.W);
-  size_t alloc_words = 0;
-  ISF_TRY(occ_bytemaps_ensure(a, occ, st, &alloc_words));
+  ISF_REQUIRE_BYTEMAP_INDEX(a, occ, "voxelize + mark");
+  const size_t alloc_words = round_up(occ.nwords, kWordsPerBlock);
   ByteMaps& bm = a.bytemaps;
   if (P > 0)
     hipLaunchKernelGGL(occ_voxelize_mark_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, P, C, g, vb, occ.D, coors4, bm.fine,
                        bm.coarse);
   hipLaunchKernelGGL(occ_bytemap_pack_kernel, dim3(ceil_div((long long)(alloc_words / 4), 256)), dim3(256), 0, st,
-                     bm.fine, bm.coarse, alloc_words, occ.bits, block_sums);
+                     bm.fine, bm.coarse, alloc_words, bm.bits0, bm.dirty, block_sums);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
 
 int occ_mark_coords4_bytemap(Arena& a, const OccIndex& occ, const int32_t* coors4, int n, hipStream_t st,
                              uint32_t* block_sums) {
-  ByteMaps& bm = a.bytemaps;
+  ISF_REQUIRE_BYTEMAP_INDEX(a, occ, "mark coords");
   const size_t alloc_words = round_up(occ.nwords, kWordsPerBlock);
-  if (bm.words < alloc_words) {  // (re)allocate the persistent maps; zeroed once, kept zero by the pack pass
-    ISF_HIP_TRY(hipStreamSynchronize(st));
-    if (bm.fine) { ISF_HIP_TRY(hipFree(bm.fine)); ISF_HIP_TRY(hipFree(bm.coarse)); bm = ByteMaps(); }
-    if (hipMalloc(&bm.fine, alloc_words * 64) != hipSuccess || hipMalloc(&bm.coarse, alloc_words) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("occupancy byte maps: hipMalloc(%zu) failed", alloc_words * 65);
-      return ISF_ERR_NOMEM;
-    }
-    ISF_HIP_TRY(hipMemsetAsync(bm.fine, 0, alloc_words * 64, st));
-    ISF_HIP_TRY(hipMemsetAsync(bm.coarse, 0, alloc_words, st));
-    bm.words = alloc_words;
-  }
+  ByteMaps& bm = a.bytemaps;
   if (n > 0)
     hipLaunchKernelGGL(occ_bytemap_mark_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, st, coors4, n, occ.B, occ.D,
                        occ.H, occ.W, bm.fine, bm.coarse);
   hipLaunchKernelGGL(occ_bytemap_pack_kernel, dim3(ceil_div((long long)(alloc_words / 4), 256)), dim3(256), 0, st,
-                     bm.fine, bm.coarse, alloc_words, occ.bits, block_sums);
+                     bm.fine, bm.coarse, alloc_words, bm.bits0, bm.dirty, block_sums);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
@@ -591,7 +654,7 @@ int occ_scan_block_sums(Arena& a, const OccIndex& occ, uint32_t** sums) {
   return a.alloc_n(sums, (size_t)ceil_div((long long)occ.nwords, kWordsPerBlock) + 1);
 }
 
-int occ_scan(Arena& a, const OccIndex& occ, hipStream_t st, uint32_t* block_sums, uint32_t* clear) {
+int occ_scan(Arena& a, const OccIndex& occ, hipStream_t st, uint32_t* block_sums, uint32_t* clear, unsigned* ticket) {
   const int nblocks = ceil_div((long long)occ.nwords, kWordsPerBlock);
   uint32_t* sums = block_sums;
   if (!sums) {
@@ -599,13 +662,21 @@ int occ_scan(Arena& a, const OccIndex& occ, hipStream_t st, uint32_t* block_sums
     hipLaunchKernelGGL(occ_block_count_kernel, dim3(nblocks), dim3(kScanThreads), 0, st, occ.bits,
                        occ.nwords, sums);
   }
+  // the persistent level-0 index: the dirty map, as the pack pass has just rewritten it, says which words are non-zero
+  const unsigned char* mask = occ.bits == a.bytemaps.bits0 ? a.bytemaps.dirty : nullptr;
   if (nblocks <= kLookBehindBlocks) {
+    int* box = nullptr;
+    if (ticket) ISF_TRY(mailbox_reserve(a, ticket, &box));
     hipLaunchKernelGGL(occ_write_prefix_kernel<true>, dim3(nblocks), dim3(kScanThreads), 0, st, occ.bits, occ.nwords, sums,
-                       occ.prefix, occ.total, clear);
+                       occ.prefix, occ.total, clear, mask, box, ticket ? (int)*ticket : 0);
   } else {
     hipLaunchKernelGGL(occ_scan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, nblocks, occ.total);
     hipLaunchKernelGGL(occ_write_prefix_kernel<false>, dim3(nblocks), dim3(kScanThreads), 0, st, occ.bits, occ.nwords, sums,
-                       occ.prefix, occ.total, clear);
+                       occ.prefix, occ.total, clear, mask, (int*)nullptr, 0);
+    if (ticket) {
+      ISF_LAUNCH_CHECK();
+      ISF_TRY(post_int(a, occ.total, st, ticket));
+    }
   }
   ISF_LAUNCH_CHECK();
   return ISF_OK;
@@ -693,7 +764,7 @@ __global__ void occ_compact_coords4_kernel(const unsigned long long* __restrict_
   const size_t w = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (w >= nwords) return;
   unsigned long long word = bits[w];
-  if (!word) return;
+  if (!word) return;   // (before the prefix: that of an empty word of the persistent level-0 index is undefined)
   uint32_t r = prefix[w];
   // decode the word's first cell once (the only divisions), then walk the set bits with carries
   unsigned long long cell = (unsigned long long)w << 6;
@@ -757,7 +828,7 @@ int isf_release_workspace(void) {
 }
 
 // DIAGNOSTIC: every device allocation behind the workspaces of the current device: (stream handle, base, bytes) triples,
-// per workspace its blocks, then its two byte maps -- tools/graph_fault.py maps a GPU fault address onto them
+// per workspace its blocks, then its byte maps and the level-0 index arrays -- tools/graph_fault.py maps a GPU fault address onto them
 int isf_debug_workspace_blocks(unsigned long long* stream_base_bytes, int max_triples, int* num_triples) {
   if (!stream_base_bytes || !num_triples || max_triples < 0) return ISF_ERR_ARG;
   int cur = 0;

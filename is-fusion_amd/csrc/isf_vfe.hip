@@ -186,7 +186,8 @@ __global__ __launch_bounds__(256) void vfe_order_kernel(VoxBatch frames /* where
 template <int CIN>
 __global__ __launch_bounds__(256) void vfe_mean_kernel(const float* __restrict__ recs,
                                                        const uint32_t* __restrict__ start, int N,
-                                                       float4* __restrict__ mean4) {
+                                                       float4* __restrict__ mean4, float* __restrict__ cut_a,
+                                                       float* __restrict__ cut_b) {
   const int lane = threadIdx.x & 63;
   const long long j0 = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;
   const long long nv = start[N];   // number of in-range points = records
@@ -223,6 +224,15 @@ __global__ __launch_bounds__(256) void vfe_mean_kernel(const float* __restrict__
     }
   }
   const int v0 = __builtin_amdgcn_readlane(v, 0), v63 = __builtin_amdgcn_readlane(v, 63);
+  // The segmented max of the layer kernels writes a voxel's row with ONE store when the voxel's run of records lies inside
+  // a wave, and with atomicMax when a wave boundary (every 64 records) cuts it -- which needs a zero row to start from.
+  // Only those rows are zeroed, here: this wave sees the boundary at its first record, and clears the row of the voxel
+  // that straddles it in both destination buffers (at most P / 64 rows; a voxel cut by several boundaries is cleared
+  // several times; the layer kernels are later launches of the same stream)
+  if (v0 >= 0 && vprev == v0) {   // wave-uniform (record j0 exists: j0 < nv)
+    cut_a[(size_t)v0 * kC + lane] = 0.f;
+    cut_b[(size_t)v0 * kC + lane] = 0.f;
+  }
   const int vn = __shfl_down(v, 1, 64);
   const bool end = v >= 0 && (lane == 63 || vn != v);
   const bool owned = !(v == v0 && vprev == v0);          // the run began in this wave
@@ -398,7 +408,7 @@ __device__ __forceinline__ void vfe_segmented_max(int myvox, int vprev, int vnex
   // invalid points (voxel -1) only follow the last valid one: they never end a run and what they add to m is dropped
   const unsigned long long ends = __ballot(myvox >= 0 && (lane == 63 || nxt != myvox));
   const int v0 = __builtin_amdgcn_readlane(myvox, 0), v63 = __builtin_amdgcn_readlane(myvox, 63);
-  // runs cut by the wave's boundaries accumulate with atomicMax (on rows zeroed by vfe_zero_cut_rows_kernel)
+  // runs cut by the wave's boundaries accumulate with atomicMax (on rows zeroed by vfe_mean_kernel)
   unsigned long long cut = 0;
   if (v0 >= 0 && vprev == v0) cut |= ends & (0ull - ends);   // the first run's end
   if (v63 >= 0 && vnext == v63) cut |= 1ull << 63;
@@ -433,24 +443,8 @@ __device__ __forceinline__ void vfe_segmented_max(int myvox, int vprev, int vnex
   }
 }
 
-// The segmented max writes a voxel's row with ONE store when the voxel's run of records lies inside a wave, and with
-// atomicMax when a wave boundary (every 64 records) cuts it -- which needs a zero row to start from.  Only those rows are
-// zeroed: one wave per boundary clears the rows of the voxel that straddles it, in both destination buffers (at most
-// P / 64 rows; round 2 zero-filled both [N, 64] buffers: two 92-MB fills per forward).
-__global__ __launch_bounds__(256) void vfe_zero_cut_rows_kernel(const float* __restrict__ recs,
-                                                                const int* __restrict__ n_valid,
-                                                                float* __restrict__ a, float* __restrict__ b) {
-  const int lane = threadIdx.x & 63;
-  const long long k = (long long)blockIdx.x * 4 + (threadIdx.x >> 6) + 1;   // boundary between records 64k - 1 and 64k
-  const long long j = k * 64;
-  const long long nv = *n_valid;
-  if (j >= nv) return;
-  const int v0 = __float_as_int(recs[(size_t)(j - 1) * 8 + 7]), v1 = __float_as_int(recs[(size_t)j * 8 + 7]);
-  if (v0 != v1 || v0 < 0) return;
-  a[(size_t)v0 * 64 + lane] = 0.f;
-  b[(size_t)v0 * 64 + lane] = 0.f;
-}
-
+// (The rows of the voxels cut by a wave boundary are zeroed by vfe_mean_kernel, one wave per boundary; round 2 zero-filled
+// both [N, 64] buffers: two 92-MB fills per forward.)
 // split output: the rows of the voxels cut by a wave boundary are final in the fp32 buffer only when layer 2 has
 // finished; one wave per boundary converts the row of the voxel that straddles it (a voxel cut by several boundaries is
 // converted several times, to the same bits)
@@ -710,10 +704,12 @@ static int vfe_run(Arena& a, const float* points, const int32_t* coors4, int P, 
   const VoxBatch frames = frames_in ? *frames_in : (voxelize ? *voxelize : vox_one_block(points, P));
   OccIndex occ;
   // d_alloc > grid z lets the sparse encoder (sparse_shape[0] = grid z + 1) reuse this index for level 0
-  ISF_TRY(occ_create(a, &occ, B, d_alloc > grid[2] ? d_alloc : grid[2], grid[1], grid[0], st, false));
-  // the pack pass of the marking leaves the scan's block popcounts (no count launch over the 42 MB bitmap it just wrote),
+  // (the workspace's persistent index arrays: the marking writes only the words that are, or were, non-zero)
+  ISF_TRY(occ_create_bytemap(a, &occ, B, d_alloc > grid[2] ? d_alloc : grid[2], grid[1], grid[0], st));
+  // the pack pass of the marking leaves the scan's block popcounts (no count launch over the bitmap),
   // and the scan's prefix launch zeroes the N + 1 per-voxel point counters that are used (N is known on the device only:
-  // a fill from the host had to cover the worst case of one voxel per point, P + 1)
+  // a fill from the host had to cover the worst case of one voxel per point, P + 1) and, where it forms the total itself,
+  // sends N to the host mailbox (no launch for that either)
   uint32_t *occ_sums = nullptr, *cnt = nullptr;
   ISF_TRY(occ_scan_block_sums(a, occ, &occ_sums));
   ISF_TRY(a.alloc_n(&cnt, (size_t)P + 1));
@@ -721,7 +717,8 @@ static int vfe_run(Arena& a, const float* points, const int32_t* coors4, int P, 
     ISF_TRY(occ_voxelize_mark_bytemap(a, occ, P, CIN, *vgeom, *voxelize, const_cast<int32_t*>(coors4), st, occ_sums));
   else
     ISF_TRY(occ_mark_coords4_bytemap(a, occ, coors4, P, st, occ_sums));
-  ISF_TRY(occ_scan(a, occ, st, occ_sums, cnt));
+  unsigned n_ticket = 0;
+  ISF_TRY(occ_scan(a, occ, st, occ_sums, cnt, &n_ticket));   // N = (value, ticket) into pinned host memory: no copy command
   float *sc1, *sc2;
   uint2* w1p;
   uint4* w2p;
@@ -744,8 +741,6 @@ static int vfe_run(Arena& a, const float* points, const int32_t* coors4, int P, 
   // waits, so the GPU keeps working while the host wakes up and launches the rest (the plain hipStreamSynchronize left
   // it idle for ~50 us per forward: profiles/r02_call22_timeline_gaps.txt).
   int N = 0;
-  unsigned n_ticket = 0;
-  ISF_TRY(post_int(a, occ.total, st, &n_ticket));   // (value, ticket) into pinned host memory: no copy command
   int32_t* pt2vox = pt2vox_out;
   if (!pt2vox) ISF_TRY(a.alloc_n(&pt2vox, (size_t)P));
   int32_t* slot;
@@ -773,12 +768,12 @@ static int vfe_run(Arena& a, const float* points, const int32_t* coors4, int P, 
   ISF_TRY(scan_u32_exclusive(a, cnt, start, (size_t)N, st));  // start[N] = number of in-range points
   hipLaunchKernelGGL(vfe_order_kernel<CIN>, dim3(ceil_div(P, 256)), dim3(256), 0, st, frames, pt2vox, slot, P, start,
                      recs);
-  hipLaunchKernelGGL(vfe_mean_kernel<CIN>, dim3(ceil_div(P, 256)), dim3(256), 0, st, recs, start, N, mean4);
-  const int* n_valid = reinterpret_cast<const int*>(start + N);
-  // rows of the voxels cut by a 64-record boundary start from zero (atomicMax), every other row is stored whole
-  static_assert(kRec == 8 && kC == 64, "vfe_zero_cut_rows_kernel indexes records / rows with these sizes");
-  hipLaunchKernelGGL(vfe_zero_cut_rows_kernel, dim3(ceil_div(ceil_div(P, 64), 4)), dim3(256), 0, st, recs, n_valid, vmax1,
+  // rows of the voxels cut by a 64-record boundary start from zero (atomicMax), every other row is stored whole: the mean
+  // kernel, one wave per 64 records like the layer kernels, zeroes them in both destination buffers
+  static_assert(kC == 64, "vfe_mean_kernel zeroes a row with one store per lane");
+  hipLaunchKernelGGL(vfe_mean_kernel<CIN>, dim3(ceil_div(P, 256)), dim3(256), 0, st, recs, start, N, mean4, vmax1,
                      voxel_feats);
+  const int* n_valid = reinterpret_cast<const int*>(start + N);
   hipLaunchKernelGGL(vfe_layer1_kernel<CIN>, dim3(ceil_div(P, kL1Threads)), dim3(kL1Threads), 0, st, recs,
                      voxel_coors, n_valid, mean4, g, w1p, sc1, shift1, vmax1);
   {
