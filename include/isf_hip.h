@@ -1370,6 +1370,58 @@ int isf_optim_adamw(const int64_t* tensors, const int32_t* chunks, int num_chunk
                     const isf_adamw_hp* hp_device, const double* partials, float max_norm, float* norm_out, int mode,
                     isf_stream_t stream);
 
+/* nuScenes detection evaluation: mAP / NDS on the device (isf_eval.hip) ----------------------------------------
+ * Together the four stages replace NuScenesDataset._evaluate_single (mmdet3d/datasets/nuscenes_dataset.py:421-476: the
+ *   JSON round trip and the nuScenes devkit's DetectionEval on the host) for boxes that are already on the device; the
+ *   protocol as built, the frame, the tie rule and the statement on devkit parity are DESIGN.md section 4.0f.  All arithmetic
+ *   is fp64 on the fp32 rows.  No stage syncs or copies to the host.
+ * isf_eval_attributes replaces the attribute heuristic of _format_bbox (nuscenes_dataset.py:378-397): attrs[i] =
+ *   hypot(boxes[i][7], boxes[i][8]) > 0.2 ? moving_attr[label] : still_attr[label] (HOST tables of num_classes attribute
+ *   ids, -1 = none); -1 for labels outside [0, num_classes).
+ * isf_eval_match replaces the range filter of lidar_nusc_box_to_global (nuscenes_dataset.py:690-697) and the devkit's
+ *   greedy matching (accumulate).  Sample s owns prediction rows [pred_off[s], pred_off[s + 1]) (<= max_pred <=
+ *   ISF_EVAL_MAX_PRED each) and ground-truth rows [gt_off[s], gt_off[s + 1]) (<= max_gt <= ISF_EVAL_MAX_GT each); the
+ *   offsets are DEVICE int32 [num_samples + 1].  Boxes are [rows, 9] (x, y, z_bottom, dx, dy, dz, yaw, vx, vy).  A row
+ *   is dropped when pred_valid is 0, its label is outside [0, num_classes), its score is NaN, gt_num_pts (NULL = all
+ *   kept) is <= 0, or |(M c)_xy| > class_range[label] with M = lidar2ego[s] (fp64 [4, 4], row major) and c the gravity
+ *   centre.  Per sample the kept predictions are ordered by descending score, equal scores by ascending row, and walked
+ *   once per distance threshold (HOST dist_ths, num_ths <= ISF_EVAL_MAX_THS): a prediction takes the nearest not yet
+ *   taken box of its class (xy centre distance, the lowest row on a tie) when that distance is < the threshold.
+ *   Outputs BY POSITION q = pred_off[s] + rank in that order (dropped rows fill the tail of the sample): keys (a uint32
+ *   whose ascending order is descending score), cls (the label; num_classes for a dropped row), tp_mask (bit t: TP at
+ *   threshold t), conf (the score) and, where bit tp_index is set, errs [rows, 5] = trans, scale, orient (period pi where
+ *   half_period[label]), vel, attr (NaN when the box's gt_attrs is < 0 or gt_attrs is NULL).  tp_mask_rows is the mask
+ *   by input row.  counts (DEVICE int32 [2 * num_classes], zeroed here) = kept boxes, then kept predictions, per class.
+ * isf_eval_order replaces the devkit's sort of a class's predictions by confidence: order [rows] = the positions in the
+ *   stable order of (cls, keys), i.e. class by class, descending score, ties by (sample, row).
+ * isf_eval_curves replaces the rest of accumulate: per (class, threshold) cumulative TP / FP over the class's segment and
+ *   np.interp onto recall_points (DEVICE fp64 [ISF_EVAL_POINTS], computed by the host); at tp_index the cumulative means
+ *   of the five errors over the matches and their interpolation onto the confidence curve.  curves [num_classes,
+ *   2 * num_ths + 5, ISF_EVAL_POINTS]: precision per threshold, confidence per threshold, the five TP curves.
+ * isf_eval_scalars replaces calc_ap, calc_tp, the per-class NaN rules (HOST nan_mask [num_classes], bit m = metric m is
+ *   NaN) and DetectionMetrics.serialize's aggregates.  result (fp64): ap [num_classes, num_ths], tp [num_classes, 5],
+ *   mean_dist_aps [num_classes], max_recall_ind [num_classes], tp_errors [5], tp_scores [5], mean_ap, nd_score. */
+#define ISF_EVAL_MAX_CLASSES 31
+#define ISF_EVAL_MAX_PRED 500
+#define ISF_EVAL_MAX_GT 1024
+#define ISF_EVAL_MAX_THS 4
+#define ISF_EVAL_NUM_ERRS 5
+#define ISF_EVAL_POINTS 101
+int isf_eval_attributes(const int32_t* labels, const float* boxes, int box_ld, long long rows, int num_classes,
+                        const int* moving_attr, const int* still_attr, int32_t* attrs, isf_stream_t stream);
+int isf_eval_match(const float* pred_boxes, const float* pred_scores, const int32_t* pred_labels, const uint8_t* pred_valid,
+                   const int32_t* pred_attrs, const int32_t* pred_off, int max_pred, const float* gt_boxes,
+                   const int32_t* gt_labels, const int32_t* gt_attrs, const int32_t* gt_num_pts, const int32_t* gt_off,
+                   int max_gt, const double* lidar2ego, int num_samples, int num_classes, const float* class_range,
+                   const int* half_period, const double* dist_ths, int num_ths, int tp_index, uint32_t* keys, int32_t* cls,
+                   uint8_t* tp_mask, uint8_t* tp_mask_rows, double* conf, double* errs, int32_t* counts, isf_stream_t stream);
+int isf_eval_order(const uint32_t* keys, const int32_t* cls, int rows, int num_classes, int32_t* order, isf_stream_t stream);
+int isf_eval_curves(const int32_t* order, const uint8_t* tp_mask, const double* conf, const double* errs, const int32_t* counts,
+                    const double* recall_points, int rows, int num_classes, int num_ths, int tp_index, double* curves,
+                    isf_stream_t stream);
+int isf_eval_scalars(const double* curves, int num_classes, int num_ths, int tp_index, const int* nan_mask, double min_recall,
+                     double min_precision, double mean_ap_weight, double* result, isf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -410,6 +410,14 @@ SIGNATURES = {
     "isf_optim_grad_sumsq": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "isf_optim_adamw": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(AdamWHp), c_int, c_void_p, c_void_p,
                                 ctypes.c_float, c_void_p, c_int, c_void_p]),
+    "isf_eval_attributes": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_int_p, c_int_p, c_void_p,
+                                    c_void_p]),
+    "isf_eval_match": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int, c_int, c_float_p, c_int_p,
+                               ctypes.POINTER(ctypes.c_double), c_int, c_int] + [c_void_p] * 8),
+    "isf_eval_order": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "isf_eval_curves": (c_int, [c_void_p] * 6 + [c_int] * 4 + [c_void_p, c_void_p]),
+    "isf_eval_scalars": (c_int, [c_void_p, c_int, c_int, c_int, c_int_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                 c_void_p, c_void_p]),
 }
 
 _lib = None
