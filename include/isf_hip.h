@@ -124,6 +124,30 @@ int isf_dynamic_point_to_voxel_forward(const float* feats, const int32_t* coors,
                                        int32_t* reduce_count, int* num_voxels_host,
                                        isf_stream_t stream);
 
+/* DETERMINISTIC ENTRIES (isf_*_det) ---------------------------------------------------------------------------------
+ * The library accumulates floats with atomics in four places; an fp32 atomic add rounds per add, so those results depend
+ * on the order in which the contributions arrive and differ run to run.  Each of the four has a sibling entry with the
+ * SAME ARGUMENT LIST that accumulates exactly, in 64-bit fixed point, and is therefore independent of the arrival order:
+ * bit-identical run to run and under any permutation of the contributions.  The mode is a different entry, not an option.
+ *   A = a bound of |contribution| from an absmax pass over the call's inputs, A < 2^ex;
+ *   N = a bound of the contributions per destination from the call's sizes;
+ *   e = 62 - ceil(log2 N) - ex, formed on the device (no host sync);
+ *   every contribution c is added as llrint(c * 2^e) (the scaling is exact) with a 64-bit integer atomic add into
+ *   accumulators in the library's workspace; a second pass writes float(ldexp(double(S), -e)).
+ * Resolution: 2^-(62 - ceil(log2 N)) of 2^ex -- finer than an fp32 sum for every N < 2^38.
+ * A == 0 gives zeros.  A NON-FINITE (an inf or a NaN among the inputs A is taken from) makes EVERY ELEMENT of every
+ * floating-point output of the call NaN.
+ *
+ * isf_dynamic_point_to_voxel_forward_det: isf_dynamic_point_to_voxel_forward (voxelization.h:108-121,
+ *   scatter_points_cuda.cu:183-239) with exact sums for reduce sum / mean: A = absmax(feats) (all rows), N = num_points;
+ *   the mean is __fdiv_rn(sum, count) as in the default.  reduce max takes the default's path (already order-free).
+ *   out_coors, coors_map and reduce_count are the default's. */
+int isf_dynamic_point_to_voxel_forward_det(const float* feats, const int32_t* coors, int num_points,
+                                           int num_feats, int reduce_type, float* reduced_feats,
+                                           int32_t* out_coors, int32_t* coors_map,
+                                           int32_t* reduce_count, int* num_voxels_host,
+                                           isf_stream_t stream);
+
 /* replaces voxel_layer.dynamic_point_to_voxel_backward(grad_feats, grad_reduced_feats, feats,
  *   reduced_feats, coors_idx, reduce_count, reduce_type)   voxelization.h:123-140,
  *   scatter_points_cuda.cu:241-308.  grad_feats [P,C] is fully overwritten.  Asynchronous. */
@@ -788,6 +812,18 @@ int isf_ms_deform_attn_backward(const float* value, const int64_t* spatial_shape
                                 int num_levels, int num_points, float* grad_value, float* grad_sampling_loc,
                                 float* grad_attn_weight, isf_stream_t stream);
 
+/* isf_ms_deform_attn_backward with exact accumulation (DETERMINISTIC ENTRIES above; same reference interface,
+ * multi_scale_deformable_attn_function.py:150-160).  grad_value: A = absmax(grad_output) * max(1, absmax(attn_weight)),
+ * N = num_queries * num_points.  A power-of-two head_dim <= 64 adds each grad_sampling_loc / grad_attn_weight element
+ * once (order-free as it is); any other head_dim accumulates them in fixed point too: A = 2 * num_keys *
+ * absmax(grad_output) * absmax(value) * max(1, absmax(attn_weight)), N = head_dim.  The three gradients are still
+ * ZEROED BY THE CALLER and added to (one fp32 add per element). */
+int isf_ms_deform_attn_backward_det(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                    const float* sampling_loc, const float* attn_weight, const float* grad_output,
+                                    int batch_size, int num_keys, int num_heads, int head_dim, int num_queries,
+                                    int num_levels, int num_points, float* grad_value, float* grad_sampling_loc,
+                                    float* grad_attn_weight, isf_stream_t stream);
+
 /* A10  in-group (in-window) indices -------------------------------------------------------------------------
  * replaces TorchEx ingroup_indices.forward(group_inds, out_inds)
  *   (mmdet3d/ops/TorchEx/torchex/src/ingroup_inds/ingroup_inds.cpp:24-54, ingroup_inds_kernel.cu:17-31; called by
@@ -1076,6 +1112,22 @@ int isf_p2g_backward(const float* pillars, int pillar_ld, int slots, const int32
                      int input_h, int input_w, int bev_size, const float* grad_out, float* grad_img_nhwc,
                      isf_stream_t stream);
 
+/* isf_p2g_backward with exact accumulation (DETERMINISTIC ENTRIES; same reference interface, fusion_encoder.py:989-1056):
+ * A = absmax(grad_out) (bilinear weights <= 1), N = num_pillars * slots. */
+int isf_p2g_backward_det(const float* pillars, int pillar_ld, int slots, const int32_t* pillar_coors, int num_pillars,
+                         int batch_size, int num_cam, int feat_h, int feat_w, int channels, const float* cam_params,
+                         int input_h, int input_w, int bev_size, const float* grad_out, float* grad_img_nhwc,
+                         isf_stream_t stream);
+
+/* Backward of a cell gather, deterministic (used under isfusion_amd.deterministic() in place of autograd's scatter_add):
+ * replaces autograd through x_scene.gather(2, top_idx) of get_instance_feat (fusion_encoder.py:1133-1141) and through the
+ * proposal-feature gather of TransFusionHeadV2.forward_single (transfusion_head_v2.py:799-803).  index [B, K] int32 cells
+ * (a cell may occur more than once: its gradients are summed in ascending entry order, no atomics); channels_last 0:
+ * grad_out [B, E, K] -> grad_x [B, E, num_cells]; channels_last 1: grad_out [B, K, E] -> grad_x [B, num_cells, E].
+ * grad_x is written completely.  Entries outside [0, num_cells) are ignored.  Asynchronous. */
+int isf_gather_cells_backward(const float* grad_out, const int32_t* index, int batch_size, int num_index, int channels,
+                              int num_cells, int channels_last, float* grad_x, isf_stream_t stream);
+
 /* 8f #2  multi-scale deformable attention backward (one level) --------------------------------------------------
  * replaces MultiScaleDeformableAttnFunction.backward -> ms_deform_attn_backward (ops/src/cuda/ms_deform_attn_cuda.cu,
  * ms_deform_im2col_cuda.cuh:301-920) plus the backward of the softmax / location arithmetic isf_msda_forward folds in.
@@ -1086,6 +1138,14 @@ int isf_msda_backward(const float* value, const float* sampling_offsets, const f
                       const float* reference_points, const float* grad_out, int batch_size, int num_queries,
                       int num_heads, int head_dim, int num_points, int height, int width, float* grad_value,
                       float* grad_offsets, float* grad_logits, isf_stream_t stream);
+
+/* isf_msda_backward with exact accumulation of grad_value (DETERMINISTIC ENTRIES; same reference interface,
+ * ms_deform_im2col_cuda.cuh:301-920): A = absmax(grad_out) (softmax and bilinear weights <= 1), N = num_queries *
+ * num_points.  grad_offsets / grad_logits are written once, as in the default. */
+int isf_msda_backward_det(const float* value, const float* sampling_offsets, const float* attention_logits,
+                          const float* reference_points, const float* grad_out, int batch_size, int num_queries,
+                          int num_heads, int head_dim, int num_points, int height, int width, float* grad_value,
+                          float* grad_offsets, float* grad_logits, isf_stream_t stream);
 
 /* 8f #2  attention backward ------------------------------------------------------------------------------------
  * replaces autograd through nn.MultiheadAttention's softmax(q k^T / sqrt(hd)) v core (sst_basic_block_v2.py:41-75,

@@ -187,6 +187,8 @@ SIGNATURES = {
                                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "isf_dynamic_point_to_voxel_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                                    c_void_p, c_void_p, c_void_p, c_int_p, c_void_p]),
+    "isf_dynamic_point_to_voxel_forward_det": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_int_p, c_void_p]),
     "isf_dynamic_point_to_voxel_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                     c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "isf_dynamic_vfe_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, _F3, _F6, c_void_p,
@@ -259,12 +261,16 @@ SIGNATURES = {
                                            c_int, c_int, c_int, c_void_p, c_void_p]),
     "isf_ms_deform_attn_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                             c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isf_ms_deform_attn_backward_det": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                            c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "isf_ingroup_indices": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "isf_packed_window_block_bytes": (ctypes.c_size_t, [c_int]),
     "isf_pack_window_block": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "isf_window_block_forward": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_void_p]),
     "isf_p2g_backward": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                 c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "isf_p2g_backward_det": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                  c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "isf_sparse_to_dense_bev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                         c_void_p, c_void_p]),
@@ -355,6 +361,8 @@ SIGNATURES = {
     "isf_sparse_conv_backward_filter_f16x3": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                       c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "isf_msda_backward": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p] * 4),
+    "isf_gather_cells_backward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "isf_msda_backward_det": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p] * 4),
     "isf_attention_backward": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                        c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                        c_void_p]),

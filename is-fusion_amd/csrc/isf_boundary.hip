@@ -8,6 +8,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "isf_common.h"
+#include "isf_fixed.h"
 
 namespace isf {
 
@@ -74,12 +75,17 @@ __global__ __launch_bounds__(256) void ms_deform_attn_kernel(
 // channel); the bilinear taps scatter into grad_value with atomics (a value cell is hit by many queries), the location
 // and weight gradients of a (query, head, level, point) are first summed over the head's channels inside the wave
 // (channels are consecutive lanes: a power-of-two head_dim <= 64 is one shuffle tree) and added once.
-template <bool TREE>
+// AccV / AccW: where grad_value and (without the tree) grad_weight / grad_loc accumulate -- AccF32 = the caller's arrays,
+// AccFixed = isf_ms_deform_attn_backward_det's fixed-point accumulators (isf_fixed.h).  With the tree a weight / location
+// gradient receives ONE add onto the caller's zero, which no order can change, so AccW stays AccF32 there.  Bounds of that
+// call: grad_value: A = absmax(grad_output) * max(1, absmax(attn_weight)) (the weights are an input here, not a softmax
+// of ours), N = Q * P per level; grad_weight / grad_loc without the tree: A = 2 * num_keys (no level side is longer) *
+// absmax(grad_output) * absmax(value) * max(1, absmax(attn_weight)), N = head_dim.  Resolution 2^-(62 - ceil(log2 N)) of the power of two above A.
+template <bool TREE, class AccV, class AccW>
 __global__ __launch_bounds__(256) void ms_deform_attn_backward_kernel(
     const float* __restrict__ value, const int64_t* __restrict__ spatial_shapes, const int64_t* __restrict__ level_start,
     const float* __restrict__ loc, const float* __restrict__ weight, const float* __restrict__ grad_out, int B, int S,
-    int M, int D, int Q, int L, int P, float* __restrict__ grad_value, float* __restrict__ grad_loc,
-    float* __restrict__ grad_weight) {
+    int M, int D, int Q, int L, int P, AccV grad_value, AccW grad_loc, AccW grad_weight) {
   const long long tid = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long total = (long long)B * Q * M * D;
   const bool live = tid < total;
@@ -110,22 +116,22 @@ __global__ __launch_bounds__(256) void ms_deform_attn_backward_kernel(
         if (h0 >= 0 && w0 >= 0) {
           const size_t o = vo + ((size_t)h0 * W + w0) * vstride;
           v1 = value[o];
-          if (live) atomicAdd(grad_value + o, hh * hw * tg);
+          if (live) grad_value.add(o, hh * hw * tg);
         }
         if (h0 >= 0 && w0 + 1 <= W - 1) {
           const size_t o = vo + ((size_t)h0 * W + w0 + 1) * vstride;
           v2 = value[o];
-          if (live) atomicAdd(grad_value + o, hh * lw * tg);
+          if (live) grad_value.add(o, hh * lw * tg);
         }
         if (h0 + 1 <= H - 1 && w0 >= 0) {
           const size_t o = vo + ((size_t)(h0 + 1) * W + w0) * vstride;
           v3 = value[o];
-          if (live) atomicAdd(grad_value + o, lh * hw * tg);
+          if (live) grad_value.add(o, lh * hw * tg);
         }
         if (h0 + 1 <= H - 1 && w0 + 1 <= W - 1) {
           const size_t o = vo + ((size_t)(h0 + 1) * W + w0 + 1) * vstride;
           v4 = value[o];
-          if (live) atomicAdd(grad_value + o, lh * lw * tg);
+          if (live) grad_value.add(o, lh * lw * tg);
         }
         g_w = go * (hh * hw * v1 + hh * lw * v2 + lh * hw * v3 + lh * lw * v4);
         g_x = (float)W * tg * (-hh * v1 + hh * v2 - lh * v3 + lh * v4);
@@ -138,14 +144,14 @@ __global__ __launch_bounds__(256) void ms_deform_attn_backward_kernel(
           g_y += __shfl_xor(g_y, s, 64);
         }
         if (live && d == 0) {
-          atomicAdd(grad_weight + qm * (long long)L * P + l * P + p, g_w);
-          atomicAdd(grad_loc + (qm * (long long)L * P + l * P + p) * 2, g_x);
-          atomicAdd(grad_loc + (qm * (long long)L * P + l * P + p) * 2 + 1, g_y);
+          grad_weight.add(qm * (long long)L * P + l * P + p, g_w);
+          grad_loc.add((qm * (long long)L * P + l * P + p) * 2, g_x);
+          grad_loc.add((qm * (long long)L * P + l * P + p) * 2 + 1, g_y);
         }
       } else if (live) {
-        atomicAdd(grad_weight + qm * (long long)L * P + l * P + p, g_w);
-        atomicAdd(grad_loc + (qm * (long long)L * P + l * P + p) * 2, g_x);
-        atomicAdd(grad_loc + (qm * (long long)L * P + l * P + p) * 2 + 1, g_y);
+        grad_weight.add(qm * (long long)L * P + l * P + p, g_w);
+        grad_loc.add((qm * (long long)L * P + l * P + p) * 2, g_x);
+        grad_loc.add((qm * (long long)L * P + l * P + p) * 2 + 1, g_y);
       }
     }
   }
@@ -220,17 +226,72 @@ int isf_ms_deform_attn_backward(const float* value, const int64_t* spatial_shape
   const long long total = (long long)batch_size * num_queries * num_heads * head_dim;
   const bool tree = head_dim <= 64 && (head_dim & (head_dim - 1)) == 0;
   if (tree)
-    hipLaunchKernelGGL(ms_deform_attn_backward_kernel<true>, dim3(ceil_div(total, 256)), dim3(256), 0,
+    hipLaunchKernelGGL((ms_deform_attn_backward_kernel<true, AccF32, AccF32>), dim3(ceil_div(total, 256)), dim3(256), 0,
                        as_stream(stream), value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                        grad_output, batch_size, num_keys, num_heads, head_dim, num_queries, num_levels, num_points,
-                       grad_value, grad_sampling_loc, grad_attn_weight);
+                       AccF32{grad_value}, AccF32{grad_sampling_loc}, AccF32{grad_attn_weight});
   else
-    hipLaunchKernelGGL(ms_deform_attn_backward_kernel<false>, dim3(ceil_div(total, 256)), dim3(256), 0,
+    hipLaunchKernelGGL((ms_deform_attn_backward_kernel<false, AccF32, AccF32>), dim3(ceil_div(total, 256)), dim3(256), 0,
                        as_stream(stream), value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                        grad_output, batch_size, num_keys, num_heads, head_dim, num_queries, num_levels, num_points,
-                       grad_value, grad_sampling_loc, grad_attn_weight);
+                       AccF32{grad_value}, AccF32{grad_sampling_loc}, AccF32{grad_attn_weight});
   ISF_LAUNCH_CHECK();
   return ISF_OK;
+}
+
+int isf_ms_deform_attn_backward_det(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index,
+                                    const float* sampling_loc, const float* attn_weight, const float* grad_output,
+                                    int batch_size, int num_keys, int num_heads, int head_dim, int num_queries,
+                                    int num_levels, int num_points, float* grad_value, float* grad_sampling_loc,
+                                    float* grad_attn_weight, isf_stream_t stream) {
+  using namespace isf;
+  ISF_REQUIRE(batch_size >= 0 && num_keys >= 0 && num_heads > 0 && head_dim > 0 && num_queries >= 0 &&
+                  num_levels > 0 && num_points > 0, ISF_ERR_ARG, "ms_deform_attn_backward_det: bad sizes");
+  if (batch_size == 0 || num_queries == 0) return ISF_OK;
+  ISF_REQUIRE(value && spatial_shapes && level_start_index && sampling_loc && attn_weight && grad_output &&
+                  grad_value && grad_sampling_loc && grad_attn_weight, ISF_ERR_ARG,
+              "ms_deform_attn_backward_det: null pointer");
+  hipStream_t st = as_stream(stream);
+  const long long total = (long long)batch_size * num_queries * num_heads * head_dim;
+  const bool tree = head_dim <= 64 && (head_dim & (head_dim - 1)) == 0;
+  const size_t nv = (size_t)batch_size * num_keys * num_heads * head_dim;
+  const size_t nw = (size_t)batch_size * num_queries * num_heads * num_levels * num_points;
+  Arena& a = arena_for_stream(st);
+  ISF_TRY(a.reset());
+  unsigned* bits = nullptr;   // [0] grad_output, [1] attn_weight, [2] value
+  FixedCtl* ctl = nullptr;    // [0] grad_value, [1] grad_weight / grad_loc
+  unsigned long long *accv = nullptr, *accw = nullptr;
+  ISF_TRY(fixed_ctl_begin(a, &bits, &ctl, 2, st));
+  const size_t nacc = nv + (tree ? 0 : 3 * nw);
+  ISF_TRY(a.alloc_n(&accv, nacc));
+  accw = accv + nv;
+  ISF_HIP_TRY(hipMemsetAsync(accv, 0, nacc * sizeof(unsigned long long), st));
+  ISF_TRY(fixed_absmax(grad_output, (size_t)total, bits + 0, st));
+  ISF_TRY(fixed_absmax(attn_weight, nw, bits + 1, st));
+  ISF_TRY(fixed_ctl(bits, 2, 2u, 0, ceil_log2((long long)num_queries * num_points), ctl, st));
+  if (tree) {
+    hipLaunchKernelGGL((ms_deform_attn_backward_kernel<true, AccFixed, AccF32>), dim3(ceil_div(total, 256)), dim3(256), 0, st,
+                       value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, batch_size, num_keys,
+                       num_heads, head_dim, num_queries, num_levels, num_points, AccFixed{accv, ctl},
+                       AccF32{grad_sampling_loc}, AccF32{grad_attn_weight});
+  } else {
+    // the largest level side bounds the location gradients' factor W (H); it is an input on the device, so the bound takes
+    // the largest side the key count allows: H, W <= num_keys
+    ISF_TRY(fixed_absmax(value, nv, bits + 2, st));
+    ISF_TRY(fixed_ctl(bits, 3, 2u, 1 + ceil_log2(num_keys > 1 ? num_keys : 1) + 1, ceil_log2(head_dim), ctl + 1, st));
+    hipLaunchKernelGGL((ms_deform_attn_backward_kernel<false, AccFixed, AccFixed>), dim3(ceil_div(total, 256)), dim3(256), 0,
+                       st, value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, batch_size,
+                       num_keys, num_heads, head_dim, num_queries, num_levels, num_points, AccFixed{accv, ctl},
+                       AccFixed{accw + nw, ctl + 1}, AccFixed{accw, ctl + 1});
+  }
+  ISF_LAUNCH_CHECK();
+  ISF_TRY(fixed_finish(accv, ctl, nv, grad_value, true, nullptr, 1, st));
+  if (tree) {
+    ISF_TRY(fixed_poison(grad_attn_weight, nw, ctl, st));
+    return fixed_poison(grad_sampling_loc, nw * 2, ctl, st);
+  }
+  ISF_TRY(fixed_finish(accw, ctl + 1, nw, grad_attn_weight, true, nullptr, 1, st));
+  return fixed_finish(accw + nw, ctl + 1, nw * 2, grad_sampling_loc, true, nullptr, 1, st);
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "isf_common.h"
+#include "isf_fixed.h"
 
 namespace isf {
 
@@ -105,12 +106,16 @@ __global__ __launch_bounds__(256) void p2g_kernel(const float* __restrict__ pill
 // (slot, camera) pair, in-view pairs visited wave-uniformly); each bilinear tap scatters weight * grad_canvas[cell]
 // into the NHWC gradient map with hardware fp32 atomics (the reference's F.grid_sample backward does the same).  The
 // sample positions do not depend on trainable tensors (points and calibration), so there is no gradient towards them.
-template <int CPL>
+// Acc: AccF32 = the gradient map itself; AccFixed = isf_p2g_backward_det's fixed-point accumulators (isf_fixed.h).  Bound
+// of that call: A = absmax of grad_out (the bilinear weights are <= 1), N = num_pillars * slots (a (pillar, slot) pair
+// reaches a cell of one camera's map through one tap at most): resolution 2^-(62 - ceil(log2(pillars * slots))) of
+// 2^ex >= A (30 k pillars x 20 slots: 2^-42).
+template <int CPL, class Acc>
 __global__ __launch_bounds__(256) void p2g_backward_kernel(const float* __restrict__ pillars, int pillar_ld, int T,
                                                            const int32_t* __restrict__ coors, int M, int num_cam,
                                                            int H, int W, int C, const float* __restrict__ cam, float in_h,
                                                            float in_w, int bev, const float* __restrict__ grad_out,
-                                                           float* __restrict__ grad_img /* [B*cam, H, W, C], zeroed */) {
+                                                           Acc grad_img /* [B*cam, H, W, C], zeroed */) {
   const int lane = threadIdx.x & 63;
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= M) return;
@@ -154,15 +159,15 @@ __global__ __launch_bounds__(256) void p2g_backward_kernel(const float* __restri
       const float fx = floorf(sx), fy = floorf(sy);
       const int x0 = (int)fx, y0 = (int)fy;
       const float lx = sx - fx, ly = sy - fy;
-      float* base = grad_img + (size_t)(b * num_cam + sk) * H * W * C + c0;
+      const size_t base = (size_t)(b * num_cam + sk) * H * W * C + c0;
 #pragma unroll
       for (int tap = 0; tap < 4; ++tap) {
         const int xx = x0 + (tap & 1), yy = y0 + (tap >> 1);
         if (xx < 0 || xx >= W || yy < 0 || yy >= H) continue;
         const float wgt = ((tap & 1) ? lx : 1.f - lx) * ((tap >> 1) ? ly : 1.f - ly);
-        float* dst = base + ((size_t)yy * W + xx) * C;
+        const size_t dst = base + ((size_t)yy * W + xx) * C;
 #pragma unroll
-        for (int c = 0; c < CPL; ++c) atomicAdd(dst + c, wgt * g[c]);
+        for (int c = 0; c < CPL; ++c) grad_img.add(dst + c, wgt * g[c]);
       }
     }
   }
@@ -473,11 +478,14 @@ __global__ __launch_bounds__(256) void msda_kernel(const float* __restrict__ val
 // channels, so the tap geometry is computed once per group and the channel reductions for d(attention) and d(location)
 // are four xor-shuffles inside the group.  grad_value is accumulated with hardware fp32 atomics (the reference does
 // the same, atomicAdd at :128-150), everything else is written once.
-template <int D, int P>
+// Acc: AccF32 = grad_value itself; AccFixed = isf_msda_backward_det's fixed-point accumulators (isf_fixed.h).  Bound of that
+// call: A = absmax of grad_out (softmax and bilinear weights are <= 1), N = Q * P (a sampling point reaches a value cell
+// through one tap at most): resolution 2^-(62 - ceil(log2(Q * P))) of 2^ex >= A (200 queries x 16 points: 2^-50).
+template <int D, int P, class Acc>
 __global__ __launch_bounds__(256) void msda_backward_kernel(
     const float* __restrict__ value, const float* __restrict__ offsets, const float* __restrict__ logits,
     const float* __restrict__ ref, const float* __restrict__ grad_out, int B, int Q, int heads, int H, int W,
-    float* __restrict__ grad_value, float* __restrict__ grad_offsets, float* __restrict__ grad_logits) {
+    Acc grad_value, float* __restrict__ grad_offsets, float* __restrict__ grad_logits) {
   static_assert(D == 16 && P == 16, "one 16-lane group per head: lanes = channels, and lane p stores point p");
   const long long tid = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long total = (long long)B * Q * heads * D;
@@ -516,22 +524,22 @@ __global__ __launch_bounds__(256) void msda_backward_kernel(
       if (h0 >= 0 && w0 >= 0) {
         const size_t at = vbase + ((size_t)h0 * W + w0) * vstride;
         v00 = value[at];
-        if (live) atomicAdd(grad_value + at, (1.f - lh) * (1.f - lw) * gv);
+        if (live) grad_value.add(at, (1.f - lh) * (1.f - lw) * gv);
       }
       if (h0 >= 0 && w0 + 1 <= W - 1) {
         const size_t at = vbase + ((size_t)h0 * W + w0 + 1) * vstride;
         v01 = value[at];
-        if (live) atomicAdd(grad_value + at, (1.f - lh) * lw * gv);
+        if (live) grad_value.add(at, (1.f - lh) * lw * gv);
       }
       if (h0 + 1 <= H - 1 && w0 >= 0) {
         const size_t at = vbase + ((size_t)(h0 + 1) * W + w0) * vstride;
         v10 = value[at];
-        if (live) atomicAdd(grad_value + at, lh * (1.f - lw) * gv);
+        if (live) grad_value.add(at, lh * (1.f - lw) * gv);
       }
       if (h0 + 1 <= H - 1 && w0 + 1 <= W - 1) {
         const size_t at = vbase + ((size_t)(h0 + 1) * W + w0 + 1) * vstride;
         v11 = value[at];
-        if (live) atomicAdd(grad_value + at, lh * lw * gv);
+        if (live) grad_value.add(at, lh * lw * gv);
       }
       s = (1.f - lh) * (1.f - lw) * v00 + (1.f - lh) * lw * v01 + lh * (1.f - lw) * v10 + lh * lw * v11;
       dsw = (1.f - lh) * (v01 - v00) + lh * (v11 - v10);      // d s / d w_im
@@ -561,6 +569,54 @@ __global__ __launch_bounds__(256) void msda_backward_kernel(
     go_off[0] = my_gx;
     go_off[1] = my_gy;
   }
+}
+
+// Backward of gathering K cells' feature vectors out of a map (x.gather(dim, index) in torch; the mined instance cells and
+// the head's proposal cells, which CAN name one cell twice: top index modulo H*W over all classes).  torch's backward is
+// a scatter_add with fp32 atomics, so two entries of one cell add in arrival order.  Here the FIRST entry of a cell (no
+// equal index before it) owns the cell: it sums its own and every later equal entry's gradient in ascending entry order and
+// stores once -- no atomics, the same bits every run.  grad_x is zeroed by the caller of the kernel.  One thread per
+// (b, k, e), e fastest; K is a few hundred, so the two scans of the index row cost nothing next to the step.
+__global__ __launch_bounds__(256) void gather_cells_backward_kernel(const float* __restrict__ g, const int32_t* __restrict__ index,
+                                                                    int B, int K, int E, int cells, long long g_k, long long g_e,
+                                                                    long long x_c, long long x_e, float* __restrict__ grad_x) {
+  const long long tid = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (tid >= (long long)B * K * E) return;
+  const int e = (int)(tid % E);
+  const int k = (int)((tid / E) % K);
+  const int b = (int)(tid / ((long long)E * K));
+  const int32_t* row = index + (size_t)b * K;
+  const int cell = row[k];
+  if (cell < 0 || cell >= cells) return;
+  for (int j = 0; j < k; ++j)
+    if (row[j] == cell) return;            // an earlier entry owns this cell
+  const float* gb = g + (size_t)b * K * E + (size_t)e * g_e;
+  float s = gb[(size_t)k * g_k];
+  for (int j = k + 1; j < K; ++j)
+    if (row[j] == cell) s += gb[(size_t)j * g_k];
+  grad_x[(size_t)b * cells * E + (size_t)cell * x_c + (size_t)e * x_e] = s;
+}
+
+// the channel dispatch of isf_p2g_backward and isf_p2g_backward_det
+template <class Acc>
+static int p2g_backward_launch(const float* pillars, int pillar_ld, int slots, const int32_t* pillar_coors, int num_pillars,
+                               int num_cam, int feat_h, int feat_w, int channels, const float* cam_params, int input_h,
+                               int input_w, int bev_size, const float* grad_out, Acc grad_img, hipStream_t st) {
+  const dim3 grid(ceil_div(num_pillars, 4)), block(256);
+#define ISF_P2GB(CPL)                                                                                                     \
+  hipLaunchKernelGGL((p2g_backward_kernel<CPL, Acc>), grid, block, 0, st, pillars, pillar_ld, slots, pillar_coors,        \
+                     num_pillars, num_cam, feat_h, feat_w, channels, cam_params, (float)input_h, (float)input_w, bev_size, \
+                     grad_out, grad_img)
+  switch (channels / 64) {
+    case 1: ISF_P2GB(1); break;
+    case 2: ISF_P2GB(2); break;
+    case 4: ISF_P2GB(4); break;
+    case 8: ISF_P2GB(8); break;
+    default: set_error("p2g_backward: channels %d not built (64, 128, 256, 512)", channels); return ISF_ERR_UNSUPPORTED;
+  }
+#undef ISF_P2GB
+  ISF_LAUNCH_CHECK();
+  return ISF_OK;
 }
 
 }  // namespace isf
@@ -629,21 +685,39 @@ int isf_p2g_backward(const float* pillars, int pillar_ld, int slots, const int32
   ISF_REQUIRE(pillars && pillar_coors && cam_params && grad_out, ISF_ERR_ARG, "p2g_backward: null pointer");
   ISF_REQUIRE(channels % 64 == 0 && channels <= 512 && pillar_ld >= 3, ISF_ERR_UNSUPPORTED,
               "p2g_backward: channels %d (need %%64 == 0, <= 512)", channels);
-  const dim3 grid(ceil_div(num_pillars, 4)), block(256);
-#define ISF_P2GB(CPL)                                                                                                     \
-  hipLaunchKernelGGL((p2g_backward_kernel<CPL>), grid, block, 0, st, pillars, pillar_ld, slots, pillar_coors, num_pillars, \
-                     num_cam, feat_h, feat_w, channels, cam_params, (float)input_h, (float)input_w, bev_size, grad_out,    \
-                     grad_img_nhwc)
-  switch (channels / 64) {
-    case 1: ISF_P2GB(1); break;
-    case 2: ISF_P2GB(2); break;
-    case 4: ISF_P2GB(4); break;
-    case 8: ISF_P2GB(8); break;
-    default: set_error("p2g_backward: channels %d not built (64, 128, 256, 512)", channels); return ISF_ERR_UNSUPPORTED;
+  return p2g_backward_launch(pillars, pillar_ld, slots, pillar_coors, num_pillars, num_cam, feat_h, feat_w, channels,
+                             cam_params, input_h, input_w, bev_size, grad_out, AccF32{grad_img_nhwc}, st);
+}
+
+int isf_p2g_backward_det(const float* pillars, int pillar_ld, int slots, const int32_t* pillar_coors, int num_pillars,
+                         int batch_size, int num_cam, int feat_h, int feat_w, int channels, const float* cam_params,
+                         int input_h, int input_w, int bev_size, const float* grad_out, float* grad_img_nhwc,
+                         isf_stream_t stream) {
+  using namespace isf;
+  ISF_REQUIRE(num_pillars >= 0 && batch_size > 0 && num_cam > 0 && feat_h > 0 && feat_w > 0 && bev_size > 0 && slots > 0 &&
+                  grad_img_nhwc, ISF_ERR_ARG, "p2g_backward_det: bad arguments");
+  hipStream_t st = as_stream(stream);
+  const size_t n = (size_t)batch_size * num_cam * feat_h * feat_w * channels;
+  if (num_pillars == 0) {
+    ISF_HIP_TRY(hipMemsetAsync(grad_img_nhwc, 0, sizeof(float) * n, st));
+    return ISF_OK;
   }
-#undef ISF_P2GB
-  ISF_LAUNCH_CHECK();
-  return ISF_OK;
+  ISF_REQUIRE(pillars && pillar_coors && cam_params && grad_out, ISF_ERR_ARG, "p2g_backward_det: null pointer");
+  ISF_REQUIRE(channels % 64 == 0 && channels <= 512 && pillar_ld >= 3, ISF_ERR_UNSUPPORTED,
+              "p2g_backward_det: channels %d (need %%64 == 0, <= 512)", channels);
+  Arena& a = arena_for_stream(st);
+  ISF_TRY(a.reset());
+  unsigned* bits = nullptr;
+  FixedCtl* ctl = nullptr;
+  unsigned long long* acc = nullptr;
+  ISF_TRY(fixed_ctl_begin(a, &bits, &ctl, 1, st));
+  ISF_TRY(a.alloc_n(&acc, n));
+  ISF_HIP_TRY(hipMemsetAsync(acc, 0, n * sizeof(unsigned long long), st));
+  ISF_TRY(fixed_absmax(grad_out, (size_t)batch_size * channels * bev_size * bev_size, bits, st));
+  ISF_TRY(fixed_ctl(bits, 1, 0, 0, ceil_log2((long long)num_pillars * slots), ctl, st));
+  ISF_TRY(p2g_backward_launch(pillars, pillar_ld, slots, pillar_coors, num_pillars, num_cam, feat_h, feat_w, channels,
+                              cam_params, input_h, input_w, bev_size, grad_out, AccFixed{acc, ctl}, st));
+  return fixed_finish(acc, ctl, n, grad_img_nhwc, false, nullptr, 1, st);
 }
 
 int isf_instance_topk(const float* heatmap, int batch_size, int num_classes, int height, int width, int k,
@@ -682,6 +756,26 @@ int isf_instance_topk(const float* heatmap, int batch_size, int num_classes, int
   return ISF_OK;
 }
 
+int isf_gather_cells_backward(const float* grad_out, const int32_t* index, int batch_size, int num_index, int channels,
+                              int num_cells, int channels_last, float* grad_x, isf_stream_t stream) {
+  using namespace isf;
+  ISF_REQUIRE(batch_size >= 0 && num_index >= 0 && channels > 0 && num_cells > 0, ISF_ERR_ARG,
+              "gather_cells_backward: bad sizes");
+  if (batch_size == 0) return ISF_OK;
+  ISF_REQUIRE(grad_x && (num_index == 0 || (grad_out && index)), ISF_ERR_ARG, "gather_cells_backward: null pointer");
+  hipStream_t st = as_stream(stream);
+  ISF_HIP_TRY(hipMemsetAsync(grad_x, 0, sizeof(float) * (size_t)batch_size * num_cells * channels, st));
+  if (num_index == 0) return ISF_OK;
+  const long long total = (long long)batch_size * num_index * channels;
+  // channels_last: grad_out [B, K, E], grad_x [B, cells, E]; else grad_out [B, E, K], grad_x [B, E, cells]
+  const long long g_k = channels_last ? channels : 1, g_e = channels_last ? 1 : num_index;
+  const long long x_c = channels_last ? channels : 1, x_e = channels_last ? 1 : num_cells;
+  hipLaunchKernelGGL(gather_cells_backward_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, grad_out, index, batch_size,
+                     num_index, channels, num_cells, g_k, g_e, x_c, x_e, grad_x);
+  ISF_LAUNCH_CHECK();
+  return ISF_OK;
+}
+
 int isf_msda_forward(const float* value, const float* sampling_offsets, const float* attention_logits,
                      const float* reference_points, int batch_size, int num_queries, int num_heads, int head_dim,
                      int num_points, int height, int width, float* out, isf_stream_t stream) {
@@ -716,11 +810,50 @@ int isf_msda_backward(const float* value, const float* sampling_offsets, const f
   ISF_REQUIRE(head_dim == 16 && num_points == 16, ISF_ERR_UNSUPPORTED,
               "msda_backward: built for head_dim 16, 16 points, one level (got %d, %d)", head_dim, num_points);
   const long long total = (long long)batch_size * num_queries * num_heads * head_dim;
-  hipLaunchKernelGGL((msda_backward_kernel<16, 16>), dim3(ceil_div(total, 256)), dim3(256), 0, st, value,
+  hipLaunchKernelGGL((msda_backward_kernel<16, 16, AccF32>), dim3(ceil_div(total, 256)), dim3(256), 0, st, value,
                      sampling_offsets, attention_logits, reference_points, grad_out, batch_size, num_queries, num_heads,
-                     height, width, grad_value, grad_offsets, grad_logits);
+                     height, width, AccF32{grad_value}, grad_offsets, grad_logits);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
+}
+
+int isf_msda_backward_det(const float* value, const float* sampling_offsets, const float* attention_logits,
+                          const float* reference_points, const float* grad_out, int batch_size, int num_queries,
+                          int num_heads, int head_dim, int num_points, int height, int width, float* grad_value,
+                          float* grad_offsets, float* grad_logits, isf_stream_t stream) {
+  using namespace isf;
+  ISF_REQUIRE(batch_size >= 0 && num_queries >= 0 && height > 0 && width > 0 && num_heads > 0, ISF_ERR_ARG,
+              "msda_backward_det: bad sizes");
+  ISF_REQUIRE(grad_value, ISF_ERR_ARG, "msda_backward_det: null grad_value");
+  hipStream_t st = as_stream(stream);
+  const size_t n = (size_t)batch_size * height * width * num_heads * head_dim;
+  if (batch_size == 0 || num_queries == 0) {
+    ISF_HIP_TRY(hipMemsetAsync(grad_value, 0, sizeof(float) * n, st));
+    return ISF_OK;
+  }
+  ISF_REQUIRE(value && sampling_offsets && attention_logits && reference_points && grad_out && grad_offsets &&
+                  grad_logits, ISF_ERR_ARG, "msda_backward_det: null pointer");
+  ISF_REQUIRE(head_dim == 16 && num_points == 16, ISF_ERR_UNSUPPORTED,
+              "msda_backward_det: built for head_dim 16, 16 points, one level (got %d, %d)", head_dim, num_points);
+  const long long total = (long long)batch_size * num_queries * num_heads * head_dim;
+  Arena& a = arena_for_stream(st);
+  ISF_TRY(a.reset());
+  unsigned* bits = nullptr;
+  FixedCtl* ctl = nullptr;
+  unsigned long long* acc = nullptr;
+  ISF_TRY(fixed_ctl_begin(a, &bits, &ctl, 1, st));
+  ISF_TRY(a.alloc_n(&acc, n));
+  ISF_HIP_TRY(hipMemsetAsync(acc, 0, n * sizeof(unsigned long long), st));
+  ISF_TRY(fixed_absmax(grad_out, (size_t)total, bits, st));
+  ISF_TRY(fixed_ctl(bits, 1, 0, 0, ceil_log2((long long)num_queries * num_points), ctl, st));
+  hipLaunchKernelGGL((msda_backward_kernel<16, 16, AccFixed>), dim3(ceil_div(total, 256)), dim3(256), 0, st, value,
+                     sampling_offsets, attention_logits, reference_points, grad_out, batch_size, num_queries, num_heads,
+                     height, width, AccFixed{acc, ctl}, grad_offsets, grad_logits);
+  ISF_LAUNCH_CHECK();
+  ISF_TRY(fixed_finish(acc, ctl, n, grad_value, false, nullptr, 1, st));
+  const size_t nl = (size_t)batch_size * num_queries * num_heads * num_points;
+  ISF_TRY(fixed_poison(grad_offsets, nl * 2, ctl, st));
+  return fixed_poison(grad_logits, nl, ctl, st);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "isf_common.h"
+#include "isf_fixed.h"
 
 namespace isf {
 
@@ -81,18 +82,23 @@ __global__ void sc_map_count_kernel(const int32_t* __restrict__ coors, int P, in
   cmap[i] = v;
 }
 
-// one wave handles 64 (point, channel) items laid out channel-fastest, so lanes of one point hit one row
+// one wave handles 64 (point, channel) items laid out channel-fastest, so lanes of one point hit one row.
+// Acc: where sum / mean accumulate -- AccF32 = `out` itself (fp32 atomics: the sum depends on the arrival order), AccFixed
+// = the 64-bit fixed-point accumulators of isf_dynamic_point_to_voxel_forward_det (exact, order-free; isf_fixed.h).
+// Bound of that call: A = absmax of feats, N = P rows per voxel at most: resolution 2^-(62 - ceil(log2 P)) of 2^ex >= A
+// (P = 2^21 points: 2^-41, against the 2^-24 of one fp32 add).  max is order-free as it is and takes the same path in both.
+template <class Acc>
 __global__ void sc_reduce_kernel(const float* __restrict__ feats, const int32_t* __restrict__ cmap,
-                                 long long total, int C, int reduce, float* __restrict__ out) {
+                                 long long total, int C, int reduce, float* __restrict__ out, Acc acc) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
   const int i = (int)(t / C), k = (int)(t % C);
   const int v = cmap[i];
   if (v < 0) return;
   const float f = feats[t];
-  float* o = out + (size_t)v * C + k;
-  if (reduce == ISF_REDUCE_MAX) atomic_max_f32(o, f);
-  else atomicAdd(o, f);
+  const size_t o = (size_t)v * C + k;
+  if (reduce == ISF_REDUCE_MAX) atomic_max_f32(out + o, f);
+  else acc.add(o, f);
 }
 
 __global__ void sc_mean_div_kernel(float* __restrict__ out, const int32_t* __restrict__ count,
@@ -104,7 +110,7 @@ __global__ void sc_mean_div_kernel(float* __restrict__ out, const int32_t* __res
 
 int dynamic_scatter_forward_impl(Arena& a, const float* feats, const int32_t* coors, int P, int C,
                                  int reduce, float* reduced, int32_t* out_coors, int32_t* cmap,
-                                 int32_t* count, int* M_host, hipStream_t st) {
+                                 int32_t* count, int* M_host, hipStream_t st, bool det = false) {
   *M_host = 0;
   if (P <= 0) return ISF_OK;
   int* ext = nullptr;
@@ -137,6 +143,24 @@ int dynamic_scatter_forward_impl(Arena& a, const float* feats, const int32_t* co
   hipLaunchKernelGGL(sc_coors_out_kernel, dim3(ceil_div(M, 256)), dim3(256), 0, st, c4, occ.total,
                      out_coors);
   const size_t n_out = (size_t)M * C;
+  const long long total = (long long)P * C;
+  if (det && reduce != ISF_REDUCE_MAX) {   // exact sums in fixed point, then one conversion (and the mean's division)
+    unsigned* bits = nullptr;
+    FixedCtl* ctl = nullptr;
+    unsigned long long* acc = nullptr;
+    ISF_TRY(fixed_ctl_begin(a, &bits, &ctl, 1, st));
+    ISF_TRY(a.alloc_n(&acc, n_out));
+    ISF_HIP_TRY(hipMemsetAsync(acc, 0, n_out * sizeof(unsigned long long), st));
+    ISF_TRY(fixed_absmax(feats, (size_t)total, bits, st));
+    ISF_TRY(fixed_ctl(bits, 1, 0, 0, ceil_log2(P), ctl, st));
+    ISF_HIP_TRY(hipMemsetAsync(count, 0, (size_t)M * sizeof(int32_t), st));
+    hipLaunchKernelGGL(sc_map_count_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, coors, P, (int)H,
+                       (int)W, occ.bits, occ.prefix, cmap, count);
+    hipLaunchKernelGGL(sc_reduce_kernel<AccFixed>, dim3(ceil_div(total, 256)), dim3(256), 0, st, feats, cmap, total,
+                       C, reduce, reduced, AccFixed{acc, ctl});
+    ISF_LAUNCH_CHECK();
+    return fixed_finish(acc, ctl, n_out, reduced, false, reduce == ISF_REDUCE_MEAN ? count : nullptr, C, st);
+  }
   if (reduce == ISF_REDUCE_MAX)
     hipLaunchKernelGGL(sc_fill_kernel, dim3(ceil_div((long long)n_out, 256)), dim3(256), 0, st, reduced,
                        n_out, -INFINITY);
@@ -145,9 +169,8 @@ int dynamic_scatter_forward_impl(Arena& a, const float* feats, const int32_t* co
   ISF_HIP_TRY(hipMemsetAsync(count, 0, (size_t)M * sizeof(int32_t), st));
   hipLaunchKernelGGL(sc_map_count_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, coors, P, (int)H,
                      (int)W, occ.bits, occ.prefix, cmap, count);
-  const long long total = (long long)P * C;
-  hipLaunchKernelGGL(sc_reduce_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, feats, cmap, total,
-                     C, reduce, reduced);
+  hipLaunchKernelGGL(sc_reduce_kernel<AccF32>, dim3(ceil_div(total, 256)), dim3(256), 0, st, feats, cmap, total,
+                     C, reduce, reduced, AccF32{reduced});
   if (reduce == ISF_REDUCE_MEAN)
     hipLaunchKernelGGL(sc_mean_div_kernel, dim3(ceil_div((long long)n_out, 256)), dim3(256), 0, st,
                        reduced, count, (long long)n_out, C);
@@ -249,6 +272,21 @@ int isf_dynamic_point_to_voxel_forward(const float* feats, const int32_t* coors,
   return isf::dynamic_scatter_forward_impl(a, feats, coors, num_points, num_feats, reduce_type,
                                            reduced_feats, out_coors, coors_map, reduce_count,
                                            num_voxels_host, isf::as_stream(stream));
+}
+
+int isf_dynamic_point_to_voxel_forward_det(const float* feats, const int32_t* coors, int num_points,
+                                           int num_feats, int reduce_type, float* reduced_feats,
+                                           int32_t* out_coors, int32_t* coors_map, int32_t* reduce_count,
+                                           int* num_voxels_host, isf_stream_t stream) {
+  ISF_REQUIRE(num_points >= 0 && num_feats > 0 && num_voxels_host && reduce_type >= 0 && reduce_type <= 2,
+              ISF_ERR_ARG, "dynamic_point_to_voxel_forward_det: bad arguments");
+  ISF_REQUIRE(num_points == 0 || (feats && coors && reduced_feats && out_coors && coors_map && reduce_count),
+              ISF_ERR_ARG, "dynamic_point_to_voxel_forward_det: null pointer");
+  isf::Arena& a = isf::arena_for_stream(isf::as_stream(stream));
+  ISF_TRY(a.reset());
+  return isf::dynamic_scatter_forward_impl(a, feats, coors, num_points, num_feats, reduce_type,
+                                           reduced_feats, out_coors, coors_map, reduce_count,
+                                           num_voxels_host, isf::as_stream(stream), true);
 }
 
 int isf_dynamic_point_to_voxel_backward(float* grad_feats, const float* grad_reduced_feats,

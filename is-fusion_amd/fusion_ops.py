@@ -9,7 +9,7 @@ import ctypes
 
 import torch
 
-from . import _lib
+from . import _lib, determinism
 # derived state (packed weights, tables, plans) follows one policy, derived.py; the names callers know stay here
 from .derived import drop as drop_caches, freeze, frozen, param_key, store as _cache  # noqa: F401
 
@@ -398,11 +398,47 @@ def decode_boxes(heatmap, query_score, query_labels, center, height, dim, rot, v
     return boxes, scores, labels, counts
 
 
+class _GatherCellsDet(torch.autograd.Function):
+    """gather_cells with the backward on isf_gather_cells_backward: a cell that the index names twice gets its two
+    gradients in a fixed order instead of autograd's scatter_add (fp32 atomics, arrival order)."""
+
+    @staticmethod
+    def forward(ctx, x, index, channels_last):
+        ctx.save_for_backward(index)
+        ctx.geom = (channels_last, tuple(x.shape), x.dtype)
+        dim = 1 if channels_last else 2
+        return x.gather(dim, index.unsqueeze(3 - dim).expand(-1, *((-1, x.size(2)) if channels_last else (x.size(1), -1))))
+
+    @staticmethod
+    def backward(ctx, g):
+        index, = ctx.saved_tensors
+        channels_last, shape, dtype = ctx.geom
+        B, K = index.shape
+        cells, E = (shape[1], shape[2]) if channels_last else (shape[2], shape[1])
+        go, idx = g.float().contiguous(), index.int().contiguous()
+        gx = torch.empty(shape, dtype=torch.float32, device=g.device)
+        _lib.check(_lib.load().isf_gather_cells_backward(_lib.ptr(go), _lib.ptr(idx), B, K, E, cells, int(channels_last),
+                                                         _lib.ptr(gx), _lib.stream()), "isf_gather_cells_backward")
+        return gx.to(dtype), None, None
+
+
+def gather_cells(x, index, channels_last=False):
+    """The feature vectors of the cells index [B, K] names: x [B, E, N] -> [B, E, K], or with channels_last x [B, N, E] ->
+    [B, K, E].  Under isfusion_amd.deterministic() the gradient towards x is order-independent (isf_gather_cells_backward);
+    by default it is autograd's own."""
+    if determinism.is_deterministic() and torch.is_grad_enabled() and x.requires_grad:
+        _lib.require_cuda(x, index)
+        return _GatherCellsDet.apply(x, index, channels_last)
+    if channels_last:
+        return x.gather(1, index[:, :, None].expand(-1, -1, x.size(2)))
+    return x.gather(2, index[:, None, :].expand(-1, x.size(1), -1))
+
+
 def gather_instances(x_scene, top_idx, bev_size):
     """x_ins [B, E, Q] and the (x, y) query positions of fusion_encoder.py:1133-1141 (create_2D_grid cell centres,
     axes swapped)."""
     B, E = x_scene.shape[:2]
-    x_ins = x_scene.reshape(B, E, -1).gather(2, top_idx[:, None, :].expand(-1, E, -1))
+    x_ins = gather_cells(x_scene.reshape(B, E, -1), top_idx)
     qx = (top_idx % bev_size).float() + 0.5
     qy = torch.div(top_idx, bev_size, rounding_mode="floor").float() + 0.5
     return x_ins, torch.stack([qx, qy], dim=-1)
@@ -445,6 +481,7 @@ class MultiScaleDeformableAttnFunction(torch.autograd.Function):
                                                           _lib.ptr(aw), B, S, M, D, Q, L, P, _lib.ptr(out),
                                                           _lib.stream()), "isf_ms_deform_attn_forward")
         ctx.save_for_backward(v, ss, ls, loc, aw)
+        ctx.entry = determinism.entry("isf_ms_deform_attn_backward")   # the backward matches the forward's mode
         return out
 
     @staticmethod
@@ -455,10 +492,9 @@ class MultiScaleDeformableAttnFunction(torch.autograd.Function):
         Q, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
         go = grad_output.float().contiguous()
         gv, gl, gw = torch.zeros_like(v), torch.zeros_like(loc), torch.zeros_like(aw)
-        _lib.check(_lib.load().isf_ms_deform_attn_backward(_lib.ptr(v), _lib.ptr(ss), _lib.ptr(ls), _lib.ptr(loc),
-                                                           _lib.ptr(aw), _lib.ptr(go), B, S, M, D, Q, L, P, _lib.ptr(gv),
-                                                           _lib.ptr(gl), _lib.ptr(gw), _lib.stream()),
-                   "isf_ms_deform_attn_backward")
+        _lib.check(getattr(_lib.load(), ctx.entry)(_lib.ptr(v), _lib.ptr(ss), _lib.ptr(ls), _lib.ptr(loc), _lib.ptr(aw),
+                                                   _lib.ptr(go), B, S, M, D, Q, L, P, _lib.ptr(gv), _lib.ptr(gl),
+                                                   _lib.ptr(gw), _lib.stream()), ctx.entry)
         return gv, None, None, gl, gw
 
 
@@ -494,6 +530,7 @@ class MSDAFunction(torch.autograd.Function):
         args = [t.detach().float().contiguous() for t in (value, offsets, logits, ref)]
         ctx.save_for_backward(*args)
         ctx.dims = (B, Q, nhead, hd, npts, H, W)
+        ctx.entry = determinism.entry("isf_msda_backward")   # the backward matches the forward's mode
         return msda(*args, B, Q, nhead, hd, npts, H, W)
 
     @staticmethod
@@ -503,9 +540,9 @@ class MSDAFunction(torch.autograd.Function):
         B, Q, nhead, hd, npts, H, W = ctx.dims
         g = grad_out.contiguous().float()
         gv, goff, glog = torch.empty_like(value), torch.empty_like(offsets), torch.empty_like(logits)
-        _lib.check(_lib.load().isf_msda_backward(_lib.ptr(value), _lib.ptr(offsets), _lib.ptr(logits), _lib.ptr(ref),
-                                                 _lib.ptr(g), B, Q, nhead, hd, npts, H, W, _lib.ptr(gv), _lib.ptr(goff),
-                                                 _lib.ptr(glog), _lib.stream()), "isf_msda_backward")
+        _lib.check(getattr(_lib.load(), ctx.entry)(_lib.ptr(value), _lib.ptr(offsets), _lib.ptr(logits), _lib.ptr(ref),
+                                                   _lib.ptr(g), B, Q, nhead, hd, npts, H, W, _lib.ptr(gv), _lib.ptr(goff),
+                                                   _lib.ptr(glog), _lib.stream()), ctx.entry)
         return (gv, goff, glog) + (None,) * 8
 
 

@@ -26,7 +26,7 @@ No CPU fallback: tensors must live on a GPU."""
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, determinism
 from . import fusion_ops as ops
 
 # the HIP kernels compute in fp32: under torch.autocast (the reference trains with mixed precision) inputs are cast
@@ -186,6 +186,7 @@ class P2GFunction(torch.autograd.Function):
         ctx.save_for_backward(pil, coors, cam)
         ctx.dims = (bs, num_cam, H, W, C, int(input_shape[0]), int(input_shape[1]), bev)
         ctx.in_dtype = img_feat.dtype
+        ctx.entry = determinism.entry("isf_p2g_backward")    # the backward matches the forward's mode wherever it runs
         return out
 
     @staticmethod
@@ -195,9 +196,9 @@ class P2GFunction(torch.autograd.Function):
         bs, num_cam, H, W, C, ih, iw, bev = ctx.dims
         go = g.contiguous().float()
         gi = torch.empty((bs * num_cam, H, W, C), dtype=torch.float32, device=go.device)
-        _lib.check(_lib.load().isf_p2g_backward(_lib.ptr(pil), pil.size(2), pil.size(1), _lib.ptr(coors), pil.size(0), bs,
-                                                num_cam, H, W, C, _lib.ptr(cam), ih, iw, bev, _lib.ptr(go), _lib.ptr(gi),
-                                                _lib.stream()), "isf_p2g_backward")
+        _lib.check(getattr(_lib.load(), ctx.entry)(_lib.ptr(pil), pil.size(2), pil.size(1), _lib.ptr(coors), pil.size(0), bs,
+                                                   num_cam, H, W, C, _lib.ptr(cam), ih, iw, bev, _lib.ptr(go), _lib.ptr(gi),
+                                                   _lib.stream()), ctx.entry)
         return (gi.permute(0, 3, 1, 2).to(ctx.in_dtype),) + (None,) * 7
 
 

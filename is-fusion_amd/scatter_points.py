@@ -9,7 +9,7 @@ import torch
 from torch import nn
 from torch.autograd import Function
 
-from . import _lib
+from . import _lib, determinism
 
 # the HIP kernels compute in fp32: under torch.autocast (the reference trains with mixed precision) inputs are cast
 # to fp32 on the way in and autocast is off inside forward / backward
@@ -18,7 +18,8 @@ _amp_bwd = torch.amp.custom_bwd(device_type="cuda")
 
 
 def dynamic_point_to_voxel_forward(feats, coors, reduce_type):
-    """-> [reduced_feats, out_coors, coors_map int32, reduce_count int32] (voxelization.h:108-121)."""
+    """-> [reduced_feats, out_coors, coors_map int32, reduce_count int32] (voxelization.h:108-121).
+    Under isfusion_amd.deterministic() the sums of "sum" / "mean" are exact (isf_dynamic_point_to_voxel_forward_det)."""
     _lib.require_cuda(feats, coors)
     if reduce_type not in _lib.REDUCE:
         raise RuntimeError("do not support reduce type " + str(reduce_type))
@@ -33,11 +34,10 @@ def dynamic_point_to_voxel_forward(feats, coors, reduce_type):
     cmap = torch.empty((P,), dtype=torch.int32, device=feats.device)
     cnt = torch.empty((P,), dtype=torch.int32, device=feats.device)
     m = ctypes.c_int(0)
-    lib = _lib.load()
-    _lib.check(lib.isf_dynamic_point_to_voxel_forward(
+    entry = determinism.entry("isf_dynamic_point_to_voxel_forward")
+    _lib.check(getattr(_lib.load(), entry)(
         _lib.ptr(feats_c), _lib.ptr(coors_c), P, C, _lib.REDUCE[reduce_type], _lib.ptr(red),
-        _lib.ptr(out_coors), _lib.ptr(cmap), _lib.ptr(cnt), ctypes.byref(m), _lib.stream()),
-        "isf_dynamic_point_to_voxel_forward")
+        _lib.ptr(out_coors), _lib.ptr(cmap), _lib.ptr(cnt), ctypes.byref(m), _lib.stream()), entry)
     M = m.value
     return [red[:M], out_coors[:M], cmap, cnt[:M]]
 

@@ -346,7 +346,7 @@ class TransFusionHeadV2(nn.Module):
         self.query_labels = labels
         self.last_top_index = cell
         rows = dense_train.to_rows(feat)                                                   # [B*HW, E], row b*HW + cell
-        query = rows.view(B, HW, E).gather(1, cell[:, :, None].expand(-1, -1, E))          # [B, P, E]
+        query = ops.gather_cells(rows.view(B, HW, E), cell, channels_last=True)             # [B, P, E]
         one_hot = torch.nn.functional.one_hot(labels, C).float()                          # class_encoding (Conv1d, k=1)
         query = (query + torch.nn.functional.linear(one_hot, self.class_encoding.weight[:, :, 0],
                                                     self.class_encoding.bias)).reshape(B * P, E)

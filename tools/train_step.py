@@ -2,7 +2,7 @@
 all-reduce over xGMI on the GRADIENTS only -- the forward has no collective):
 
     python tools/train_step.py --gpus N [--batch 2] [--points 60000] [--steps 3] [--bf16] [--autocast]
-                               [--optimizer sgd|config] [--max-iters M] [--gt-paste] [--camera]
+                               [--optimizer sgd|config] [--max-iters M] [--gt-paste] [--camera] [--deterministic]
 
 starts N ranks by itself (isfusion_amd.launch.self_launch: a re-exec under torch.distributed.run on 127.0.0.1; fewer
 than N visible GPUs is an error) -- the reference's tools/run-nus.sh:11-13; under a launcher it runs as the rank it is:
@@ -25,7 +25,10 @@ training-mode forward (stochastic depth, no backward: detach=True), the LSS-FPN 
 point-cloud path; --loss detection goes through ISFusionDetector.forward_train.  The backbone and the neck's level-0
 convs receive no gradient (only the stride-16 map reaches Point-to-Grid), so --camera FREEZES those parameters
 (requires_grad False) rather than asking DistributedDataParallel for find_unused_parameters: no per-step graph search,
-and the optimizer skips them.  Also runs on a single GPU without torchrun (world size 1)."""
+and the optimizer skips them.  --deterministic runs every step under isfusion_amd.set_deterministic(True) (exact,
+order-independent accumulation in the four scattering kernels; any --loss / --camera / --optimizer / --gt-paste); on one
+rank the steps are then bit-identical run to run -- the mode makes no claim about RCCL's reduction order across ranks.
+Also runs on a single GPU without torchrun (world size 1)."""
 import argparse
 import json
 import os
@@ -97,10 +100,15 @@ def main():
                     help="train ISFusionDetector from images (Swin forward_train + LSS-FPN forward_train / backward) instead "
                          "of precomputed camera features; the parameters that get no gradient -- img_backbone.* and the "
                          "neck's level-0 convs -- are frozen (requires_grad False), not left to find_unused_parameters")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="isfusion_amd.set_deterministic(True): the isf_*_det entries (fixed-point accumulation) in "
+                         "DynamicScatter, Point-to-Grid backward and both MSDA backwards")
     a = ap.parse_args()
     if a.gt_paste and a.loss != "detection":
         ap.error("--gt-paste pastes ground truth: it needs --loss detection")
+    import isfusion_amd
     from isfusion_amd import launch, synthetic
+    isfusion_amd.set_deterministic(a.deterministic)
     if a.stock_dense:
         from isfusion_amd import dense_train
         dense_train.ENABLED = False
@@ -237,7 +245,7 @@ def main():
     dt = (time.perf_counter() - t0) / max(a.steps, 1)
     per_step = [round(marks[i].elapsed_time(marks[i + 1]), 1) for i in range(a.steps + 1)]   # [0] = the warm-up step
     if rank == 0:
-        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss, "camera": a.camera,
+        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss, "camera": a.camera, "deterministic": a.deterministic,
                           "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses],
                           "optimizer": a.optimizer, **({"grad_norm": [round(n, 6) for n in norms]} if recipe else {}),
                           **({"gt_paste_objects": pasted} if paste is not None else {})}))
