@@ -171,8 +171,8 @@ __host__ __device__ __forceinline__ int wg16_addr(int c, int kg) {   // byte off
 // the two LDS base addresses its eight ds_write_b64 per item go to (immediate offsets from there).  The loads of a step
 // are UNCONDITIONAL 32-bit-offset loads (an `if (row >= 0) load` form compiled to a branch and an s_waitcnt vmcnt(0) per
 // load -- sixteen serialised memory round trips per step: 0.09 of the roofline, profiles/r05_wgrad16.txt); positions past
-// the wave's pair range load a valid row (index clamped to 0 / the next wave's pairs) and are zeroed on the x side in the
-// one step that can contain them.
+// the wave's pair range load a valid row (index clamped to 0 / the next wave's pairs) and are zeroed on both sides in the
+// one step that can contain them (both: the loaded dY row may be non-finite, and 0 * inf = NaN).
 template <int BC>
 struct Wg16Lane {
   unsigned piece_off[BC / 32];   // byte offset of this lane's piece inside a row, per item (hi / lo)
@@ -309,12 +309,18 @@ __global__ __launch_bounds__(256, 2) void wgrad16_kernel(const uint4* __restrict
     wg16_load<BM, HALF>(xb, x_row, LX, ix, rx);
     wg16_load<BN, HALF>(gb, g_row, LG, ig, rg);
     for (int p0 = my_begin; p0 < my_end; p0 += 32) {
-      if (p0 + 32 > my_end) {                            // the one step with positions past the range: zero their x rows
+      if (p0 + 32 > my_end) {                            // the one step with positions past the range: zero their rows on
+        // BOTH sides.  Zero x rows alone are not enough: the dY row loaded there (row 0 for the list's padding) may hold
+        // an inf / NaN, and 0 * inf = NaN would enter a tap that never pairs that row.
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           if (p0 + 4 * qx + j >= my_end) {
 #pragma unroll
             for (int it = 0; it < BM / 32; ++it) rx[it][j] = make_uint4(0, 0, 0, 0);
+          }
+          if (p0 + 4 * qg + j >= my_end) {
+#pragma unroll
+            for (int it = 0; it < BN / 32; ++it) rg[it][j] = make_uint4(0, 0, 0, 0);
           }
         }
       }

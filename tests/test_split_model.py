@@ -254,3 +254,217 @@ def test_vfe_offsets_only_bound_sees_a_flush():
         print(f"\nDynamicVFE, {'offset features only' if offsets_only else 'seeded weights'}: flushed layer-1 operands "
               f"x{r1:.2f}, flushed layer-2 operands x{r2:.2f} of the bound")
         assert (r1 > 5.0 and r2 > 5.0) if offsets_only else (r1 < 1.0 and r2 < 1.0)
+
+
+# ------------------------------------------------------------------------------------------------ the backward
+# tests/test_gpu_split_backward.py judges dX and dW per element by  3 n 2^-24 S / s  (+ the split store for dX).  Here, on
+# that file's own inputs (tests/split_backward_cases.py; the rulebooks restated in numpy), each of those bounds is shown
+# to be MET by an fp32 evaluation of the same halves (BLAS sgemm per product and tap, summed in fp32: one of the orders a
+# kernel may use) and LEFT by each of seven defects:
+#   1 the gradient halves flush f16 subnormals      2 the x halves do (dW only: dX reads no activations)
+#   3-5 one of the three products is missing        6 the scale comes from the wrong element
+#   7 the inverse scale is not applied to one chunk
+# A ratio is max |defect - model| / bound over the elements the model keeps finite; a defect that makes such an element
+# non-finite counts as infinitely far out.  Where a class cannot see a defect the ratio is printed and the reason given.
+def _f32(h):
+    return h.astype(np.float32)
+
+
+def _three32(ah, al, wh, wl):
+    return _f32(al) @ _f32(wh) + _f32(ah) @ _f32(wl) + _f32(ah) @ _f32(wh)
+
+
+def _wgrad32(x, g, pin, pout, counts):
+    s = sm.grad_scale(g)
+    (xh, xl), (gh, gl) = sm.split(x), sm.split(sm.scaled(g, s))
+    out = np.zeros((len(counts), x.shape[1], g.shape[1]), np.float32)
+    for k in range(len(counts)):
+        i, o = pin[k, :counts[k]], pout[k, :counts[k]]
+        for c in range(0, counts[k], 256):               # pair chunks of 256, partial blocks added in order
+            out[k] += _three32(xh[i[c:c + 256]].T, xl[i[c:c + 256]].T, gh[o[c:c + 256]], gl[o[c:c + 256]])
+    return out * np.float32(1.0 / s)
+
+
+def _dgrad32(g, w, nbr_t, num_in):
+    s = sm.grad_scale(g)
+    gh, gl = sm.split(sm.scaled(g, s))
+    wh, wl, sw = sm.split_weight(np.ascontiguousarray(w.transpose(0, 2, 1)))
+    y = np.zeros((num_in, w.shape[1]), np.float32)
+    for k in range(w.shape[0]):
+        m = nbr_t[k] >= 0
+        if m.any():
+            y[m] += _three32(gh[nbr_t[k, m]], gl[nbr_t[k, m]], wh[k], wl[k])
+    return sm.store_split(np.ldexp(y, -sw)) * np.float32(1.0 / s)
+
+
+def _ratio(defect, model, bound):
+    ok = np.isfinite(model)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        err = np.abs(defect - model)[ok]
+        r = np.where(err == 0, 0.0, err / bound[ok])
+    return float("inf") if not np.isfinite(r).all() else float(r.max())
+
+
+def _conv_case(cin, cout, geo):
+    import split_backward_cases as sc
+    rows = sc.conv_rows(cin, cout)
+    nbr, num_out = sc.cpu_nbr(sc.geometry(cin + cout, rows), sc.GRID, geo)
+    sc.check_rulebook(nbr, 4, chunks3=geo[0])
+    return rows, num_out, sm.transpose_nbr(nbr, rows), sm.pairs_from_nbr(nbr), sc.conv_weight(27, cin, cout, cin + 2 * cout)
+
+
+BWD_CONV_CASES = [(32, 32, "subm"), (64, 64, "subm"), (64, 64, "stride2")]
+
+
+@pytest.mark.parametrize("cin,cout,geo", BWD_CONV_CASES)
+def test_backward_conv_bounds_hold_for_an_fp32_evaluation_and_see_the_seven_defects(cin, cout, geo):
+    """dX and dW of the sparse conv on the GPU tier's rulebooks, gradient and activation classes.  Every defect must leave
+    its bound for at least one class (asserted); measured at 64 -> 64 (printed for each case):
+      * flushed gradient halves: dX x1600 (Grow), x2000 (Gspike), x2.6 (Gelem); dW x1e4 (Gspike x D), x6 (Gelem), x2 (Grow x
+        E_row).  Guni and Gedge cannot see them: Guni's rows are O(max), its lo halves normal f16 numbers, and Gedge's few
+        subnormal values drown in sums carried by its values of order one (x0.8 / x0.02);
+      * flushed x halves (dW): x1e4 with x at class A, x900 at B, x3.5 at C; D and the E classes are inside (nothing
+        subnormal at D; at E the large rows carry the sums);
+      * a missing lo product: dX x13 .. x42, dW x3 .. x15 -- except where the operand has no lo half: Gspike for g_lo (600 and
+        values of one or two bits), class A for x_lo (x0); a missing hi*hi product x1e4 everywhere;
+      * a scale taken from the finite 3.2e38 of the non-finite test's gradient (s = 2^-118) zeroes every finite row (x6e4,
+        x1e4); one taken from the tensor's smallest element overflows the large rows (non-finite: counted as infinite);
+      * an inverse scale that skips one chunk cannot be seen at s = 1 (the classes as built: x0, asserted) and is x6e16 /
+        x6e4 outside on the scale-equivariance inputs (the gradient times 2^-40 / 2^30)."""
+    import split_backward_cases as sc
+    rows, num_out, nbr_t, lists, w = _conv_case(cin, cout, sc.SUBM if geo == "subm" else sc.STRIDED)
+    pin, pout, counts = lists
+    big = int(np.argmax(counts))
+    seen = {}
+    note = lambda d, cls, r: seen.setdefault(d, {}).__setitem__(cls, r)
+    for gcls, xcls in sc.PAIRS:
+        g, x = sm.make_grad(gcls, (num_out, cout), 13), sm.make_class(xcls, (rows, cin), 31)
+        y, bx = sm.dgrad_model(g, w, nbr_t, rows)
+        m, S, n = sm.wgrad_model(x, g, *lists)
+        bw = sm.wgrad_bound(S, n)
+        assert _ratio(_dgrad32(g, w, nbr_t, rows).astype(np.float64), y, bx) <= 1.0, (gcls, "dX fp32")
+        assert _ratio(_wgrad32(x, g, *lists).astype(np.float64), m, bw) <= 1.0, (gcls, xcls, "dW fp32")
+        cls = f"{gcls} x {xcls}"
+        note("dX flushed g", cls, _ratio(sm.dgrad_model(g, w, nbr_t, rows, flush=True)[0], y, bx))
+        note("dW flushed g", cls, _ratio(sm.wgrad_model(x, g, *lists, flush="g")[0], m, bw))
+        note("dW flushed x", cls, _ratio(sm.wgrad_model(x, g, *lists, flush="x")[0], m, bw))
+        for i, name in enumerate(("lo*hi", "hi*lo", "hi*hi")):
+            terms = tuple(int(j != i) for j in range(3))
+            note(f"dX without g_{name.replace('*', '*w_')}", cls, _ratio(sm.dgrad_model(g, w, nbr_t, rows, terms=terms)[0], y, bx))
+            note(f"dW without x_{name.replace('*', '*g_')}", cls, _ratio(sm.wgrad_model(x, g, *lists, terms=terms)[0], m, bw))
+        tiny = float(np.abs(g[g != 0]).min())
+        s_bad = sm.grad_scale(np.array([tiny], np.float32))
+        note("dX scale from the smallest element", cls, _ratio(sm.dgrad_model(g, w, nbr_t, rows, s=s_bad)[0], y, bx))
+        note("dW scale from the smallest element", cls, _ratio(sm.wgrad_model(x, g, *lists, s=s_bad)[0], m, bw))
+        for f in (1.0,) + (sc.FACTORS if gcls in ("Guni", "Grow") else ()):
+            gf = sc.factor(g, f)
+            s = sm.grad_scale(gf)
+            yf, bxf = sm.dgrad_model(gf, w, nbr_t, rows)
+            mf, Sf, nf = sm.wgrad_model(x, gf, *lists)
+            skipped = yf.copy()
+            skipped[256:512] *= s                                    # rows 256 .. 511 never multiplied by 1 / s
+            chunk = sm.wgrad_model(x, gf, pin[:, :256], pout[:, :256], np.minimum(counts, 256))[0][big]
+            part = mf.copy()
+            part[big] += chunk * (s - 1.0)                           # the first chunk of the longest tap likewise
+            tag = cls if f == 1.0 else f"{cls} x 2^{int(np.log2(f))}"
+            note("dX inverse scale skips a chunk", tag, _ratio(skipped, yf, bxf))
+            note("dW inverse scale skips a chunk", tag, _ratio(part, mf, sm.wgrad_bound(Sf, nf)))
+    g, planted = sc.poisoned_grad((num_out, cout), cin + cout)
+    x = sm.make_class("C", (rows, cin), 31)
+    y, bx = sm.dgrad_model(g, w, nbr_t, rows)
+    m, S, n = sm.wgrad_model(x, g, *lists)
+    s_bad = 2.0 ** (10 - int(np.frexp(np.float32(3.2e38))[1]))
+    note("dX scale from the 3.2e38 entry", "non-finite", _ratio(sm.dgrad_model(g, w, nbr_t, rows, s=s_bad)[0], y, bx))
+    note("dW scale from the 3.2e38 entry", "non-finite", _ratio(sm.wgrad_model(x, g, *lists, s=s_bad)[0], m, sm.wgrad_bound(S, n)))
+    print()
+    for d, per in seen.items():
+        print(f"conv {cin}->{cout} {geo}, {d}: " + ", ".join(f"{c} x{r:.3g}" for c, r in per.items()))
+        assert max(per.values()) > 2.0, (d, per)
+    inside = lambda d, c: seen[d][c] <= 1.0
+    assert inside("dX flushed g", "Guni x C") and inside("dW flushed x", "Guni x C") and inside("dW flushed x", "Gspike x D")
+    assert all(inside(f"{t} inverse scale skips a chunk", f"{c[0]} x {c[1]}") for t in ("dX", "dW") for c in sc.PAIRS)
+
+
+def test_backward_gemm_bounds_hold_for_an_fp32_evaluation_and_see_the_seven_defects():
+    """the dense-GEMM forms on the GPU tier's shapes: LinearFunction's dX (700 x 256 -> 256) and isf_rows_weight_grad
+    (R = 130, 64 x 96), same defects (for dX a flush of the x halves does not exist: the weight is the other operand and
+    is packed at 2^12, nothing of it is subnormal).  The dX bound is the one that counts subnormal halves as 2^-14
+    (split_model.linear_dgrad_model): every defect still leaves it -- flushed gradient halves by x2900 (Grow) and x3400
+    (Gspike), a missing product by x2 .. x20 (the two lo products) and x1e4 (hi*hi); Guni and Gelem cannot see a flush."""
+    import split_backward_cases as sc
+    M, N, K = sc.LINEAR_SHAPES[0]                                    # gradient [M, N], weight [N, K]
+    w = sc.linear_weight(K, N, M + K + N)
+    R, (N2, K2) = 130, sc.ROWS_WGRAD_SHAPES[0]
+    seen = {}
+    note = lambda d, cls, r: seen.setdefault(d, {}).__setitem__(cls, r)
+    for gcls, xcls in sc.PAIRS:
+        g = sm.make_grad(gcls, (M, N), 43)
+        y, by = sm.linear_dgrad_model(g, w)
+        gh, gl = sm.split(g)
+        wh, wl, sw = sm.split_weight(w)
+        assert sm.grad_scale(g) == 1.0 and _ratio(np.ldexp(_three32(gh, gl, wh, wl), -sw).astype(np.float64), y, by) <= 1.0
+        g2, x2 = sm.make_grad(gcls, (R, N2), 47), sm.make_class(xcls, (R, K2), 53)
+        m, bm = sm.rows_wgrad_model(g2, x2)
+        g2h, g2l = sm.split(g2)
+        x2h, x2l = sm.split(x2)
+        fp32 = np.zeros(m.shape, np.float32)
+        for c in range(0, R, 32):                                    # row chunks, partial blocks added in order
+            fp32 += _three32(g2h[c:c + 32].T, g2l[c:c + 32].T, x2h[c:c + 32], x2l[c:c + 32])
+        assert _ratio(fp32.astype(np.float64), m, bm) <= 1.0
+        cls = f"{gcls} x {xcls}"
+        note("linear dX flushed g", gcls, _ratio(sm.linear_dgrad_model(g, w, flush=True)[0], y, by))
+        note("rows dW flushed g", cls, _ratio(sm.rows_wgrad_model(g2, x2, flush="g")[0], m, bm))
+        note("rows dW flushed x", cls, _ratio(sm.rows_wgrad_model(g2, x2, flush="x")[0], m, bm))
+        for i, name in enumerate(("lo*hi", "hi*lo", "hi*hi")):
+            terms = tuple(int(j != i) for j in range(3))
+            note(f"linear dX without g_{name.replace('*', '*w_')}", gcls, _ratio(sm.linear_dgrad_model(g, w, terms=terms)[0], y, by))
+            note(f"rows dW without g_{name.replace('*', '*x_')}", cls, _ratio(sm.rows_wgrad_model(g2, x2, terms=terms)[0], m, bm))
+        for gg, d, fn in ((g, "linear dX", lambda s: sm.linear_dgrad_model(g, w, s=s)[0]),
+                          (g2, "rows dW", lambda s: sm.rows_wgrad_model(g2, x2, s=s)[0])):
+            for what, el in (("smallest element", float(np.abs(gg[gg != 0]).min())), ("a 3.2e38 entry", 3.2e38)):
+                ref, b = (y, by) if d == "linear dX" else (m, bm)
+                note(f"{d} scale from {what}", cls, _ratio(fn(2.0 ** min(10 - int(np.frexp(np.float32(el))[1]), 126)), ref, b))
+        for f in (1.0,) + (sc.FACTORS if gcls in ("Guni", "Grow") else ()):
+            tag = cls if f == 1.0 else f"{cls} x 2^{int(np.log2(f))}"
+            gf, g2f = sc.factor(g, f), sc.factor(g2, f)
+            s = sm.grad_scale(gf)
+            yf, bf = sm.linear_dgrad_model(gf, w)
+            skipped = yf.copy()
+            skipped[256:512] *= s
+            note("linear dX inverse scale skips a chunk", tag, _ratio(skipped, yf, bf))
+            mf, bmf = sm.rows_wgrad_model(g2f, x2)
+            part = sm.rows_wgrad_model(g2f[:32], x2[:32], s=s)[0]
+            note("rows dW inverse scale skips a chunk", tag, _ratio(mf + part * (s - 1.0), mf, bmf))
+    print()
+    for d, per in seen.items():
+        print(f"{d}: " + ", ".join(f"{c} x{r:.3g}" for c, r in per.items()))
+        assert max(per.values()) > 2.0, (d, per)
+
+
+def test_grad_scale_rule():
+    """s = 2^(10 - e): the largest entry lands in [2^9, 2^10); clamped to 2^126 for a denormal maximum; 1 for zeros; inf,
+    NaN and finite entries above 3.0e38 do not set it"""
+    rng = np.random.default_rng(9)
+    for mag in (1e-30, 3e-9, 1e-6, 0.4999, 0.5, 1.0, 511.9, 512.0, 1023.9, 1024.0, 1e20, 2.9e38):
+        g = (rng.uniform(-1, 1, 100) * mag).astype(np.float32)
+        assert 2.0 ** 9 <= float(np.abs(g).max()) * sm.grad_scale(g) < 2.0 ** 10, mag
+    assert sm.grad_scale(np.zeros(8, np.float32)) == 1.0
+    assert sm.grad_scale(np.array([1e-40, -3e-41], np.float32)) == 2.0 ** 126
+    assert sm.grad_scale(np.array([np.inf, -np.inf, np.nan, 3.2e38, 600.0], np.float32)) == 1.0
+    assert sm.grad_scale(np.array([np.inf, np.nan], np.float32)) == 1.0
+    for cls in sm.GRAD_CLASSES:
+        assert sm.grad_scale(sm.make_grad(cls, (130, 64), 1)) == 1.0
+
+
+def test_backward_accuracy_table():
+    """relative error of a gradient row's dX and dW contribution against the row's magnitude relative to the tensor's
+    maximum: fp32 class down to 2^-12, 2^-25 absolute per element below (lo subnormal), half the bits gone at 2^-24, the
+    row lost from 2^-34 on (|g s| < 2^-25 rounds to zero)"""
+    table = sm.backward_accuracy_table()
+    print("\n  row / max   rel. error of dX    of dW   (f16x3 model against exact float64, 256-term Linear)")
+    for k, ex, ew in table:
+        print(f"  2^-{k:<8d}  {ex:.2g}          {ew:.2g}")
+    err = {k: (ex, ew) for k, ex, ew in table}
+    assert max(err[0]) < 3e-7 and max(err[12]) < 1e-6
+    assert all(err[b][i] > err[a][i] for a, b in ((13, 16), (16, 20), (20, 24), (24, 28), (28, 32)) for i in (0, 1))
+    assert min(err[24]) > 5e-4 and err[35] == (1.0, 1.0) and err[40] == (1.0, 1.0)
