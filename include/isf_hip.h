@@ -137,6 +137,8 @@ int isf_dynamic_point_to_voxel_forward(const float* feats, const int32_t* coors,
  * Resolution: 2^-(62 - ceil(log2 N)) of 2^ex -- finer than an fp32 sum for every N < 2^38.
  * A == 0 gives zeros.  A NON-FINITE (an inf or a NaN among the inputs A is taken from) makes EVERY ELEMENT of every
  * floating-point output of the call NaN.
+ * The float sums that cross RANKS (gradient all-reduce, naiveSyncBN statistics) are made exact the same way, with N = the
+ * world size and an integer collective between the passes: "Exact cross-rank sums" (isf_fixed_*_tensors, isf_fixed_sum_rows).
  *
  * isf_dynamic_point_to_voxel_forward_det: isf_dynamic_point_to_voxel_forward (voxelization.h:108-121,
  *   scatter_points_cuda.cu:183-239) with exact sums for reduce sum / mean: A = absmax(feats) (all rows), N = num_points;
@@ -1429,6 +1431,39 @@ int isf_optim_grad_sumsq(const int64_t* tensors, const int32_t* chunks, int num_
 int isf_optim_adamw(const int64_t* tensors, const int32_t* chunks, int num_chunks, const isf_adamw_hp* hp, int num_hp,
                     const isf_adamw_hp* hp_device, const double* partials, float max_norm, float* norm_out, int mode,
                     isf_stream_t stream);
+
+/* Exact cross-rank sums (isf_fixed_reduce.hip) -----------------------------------------------------------------
+ * The fixed-point sum of the DETERMINISTIC ENTRIES carried across the ranks of a data-parallel job.  A float all-reduce
+ *   (DistributedDataParallel's gradient buckets, mmdet3d/apis/train.py:82-86; the [2C] statistic vectors of naiveSyncBN,
+ *   mmdet3d/ops/norm.py:12-24,186) rounds after every add, so its bits depend on the collective's algorithm and on the
+ *   order of the ranks.  Here each rank turns its contribution into 64-bit integers, the COLLECTIVE SUMS INTEGERS, and
+ *   the sum is converted back: the result is a function of the multiset of the ranks' contributions only, whatever the
+ *   backend, the algorithm or the rank order.  isf_fixed_absmax_tensors / isf_fixed_pack_tensors /
+ *   isf_fixed_finish_tensors are the passes around two integer all-reduces, one launch each for any number of tensors;
+ *   isf_fixed_sum_rows is the whole sum for W gathered copies of one short vector.
+ *   tensors: DEVICE int64 [T, 3] = address of contiguous fp32 storage (any 4-byte alignment), numel, offset of the
+ *   tensor's first element in q.  chunks: DEVICE int32 [num_chunks, 2] = tensor, chunk k = elements
+ *   [k * ISF_OPTIM_CHUNK, min((k + 1) * ISF_OPTIM_CHUNK, numel)); one workgroup per chunk.  No host sync, no float atomic.
+ * isf_fixed_absmax_tensors: bits [num_tensors] is zeroed, then bits[t] = the largest bit pattern of |x| in tensor t
+ *   (integer max: order-free; an inf or a NaN shows as bits[t] >= 0x7f800000).  The caller takes the integer MAX of bits
+ *   over the ranks before the next two passes.
+ * isf_fixed_pack_tensors: per tensor A = the bound bits[t], A < 2^ex (frexp's exponent), e = 62 - log2_world - ex with
+ *   log2_world = ceil(log2(world size)) in [0, 10]; q[offset_t + i] = llrint(ldexp((double)x_i, e)) (int64; the scaling
+ *   is exact, |q| <= 2^(62 - log2_world), so the sum over the ranks stays below 2^62).  A == 0 and a non-finite bound
+ *   give zeros.  The caller takes the int64 SUM of q over the ranks.
+ * isf_fixed_finish_tensors: x_i = (float)(ldexp((double)q[offset_t + i], -e) / divisor), divisor in [1, 1024] (the world
+ *   size for a mean, 1 for a sum); EVERY element of a tensor whose bound is not finite becomes NaN.
+ * isf_fixed_sum_rows: out[c] = the exact sum over r < W of rows[r * n + c], divided by divisor, W <= ISF_FIXED_MAX_ROWS:
+ *   per column the bound over the W values, e = 62 - ceil(log2 W) - ex, the integer sum and the same finish.  A column
+ *   that holds a non-finite value gives NaN in that column only.  Independent of the order of the rows. */
+#define ISF_FIXED_MAX_ROWS 64
+int isf_fixed_absmax_tensors(const int64_t* tensors, const int32_t* chunks, int num_chunks, int num_tensors, uint32_t* bits,
+                             isf_stream_t stream);
+int isf_fixed_pack_tensors(const int64_t* tensors, const int32_t* chunks, int num_chunks, const uint32_t* bits,
+                           int log2_world, int64_t* q, isf_stream_t stream);
+int isf_fixed_finish_tensors(const int64_t* tensors, const int32_t* chunks, int num_chunks, const uint32_t* bits,
+                             int log2_world, const int64_t* q, double divisor, isf_stream_t stream);
+int isf_fixed_sum_rows(const float* rows, int W, int n, double divisor, float* out, isf_stream_t stream);
 
 /* nuScenes detection evaluation: mAP / NDS on the device (isf_eval.hip) ----------------------------------------
  * Together the four stages replace NuScenesDataset._evaluate_single (mmdet3d/datasets/nuscenes_dataset.py:421-476: the

@@ -143,6 +143,7 @@ class AdamWHp(ctypes.Structure):
 
 OPTIM_CHUNK, OPTIM_MAX_HP_ARGS = 32768, 16
 OPTIM_NO_CLIP, OPTIM_CLIP, OPTIM_SCALE_GRADS = 0, 1, 2
+FIXED_MAX_ROWS = 64         # ISF_FIXED_MAX_ROWS: rows isf_fixed_sum_rows adds
 
 # ISF_CONV_MODE_*: bits of the sparse convolutions' `mode` (include/isf_hip.h, isf_sparse_conv_forward_f16x3)
 CONV_MODE_F16, CONV_MODE_NO_GATHER, CONV_MODE_NO_WEIGHTS, CONV_MODE_NO_LOOP, CONV_MODE_NO_SHARING = 1, 2, 4, 8, 16
@@ -418,6 +419,10 @@ SIGNATURES = {
     "isf_optim_grad_sumsq": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "isf_optim_adamw": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(AdamWHp), c_int, c_void_p, c_void_p,
                                 ctypes.c_float, c_void_p, c_int, c_void_p]),
+    "isf_fixed_absmax_tensors": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "isf_fixed_pack_tensors": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "isf_fixed_finish_tensors": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, ctypes.c_double, c_void_p]),
+    "isf_fixed_sum_rows": (c_int, [c_void_p, c_int, c_int, ctypes.c_double, c_void_p, c_void_p]),
     "isf_eval_attributes": (c_int, [c_void_p, c_void_p, c_int, ctypes.c_longlong, c_int, c_int_p, c_int_p, c_void_p,
                                     c_void_p]),
     "isf_eval_match": (c_int, [c_void_p] * 6 + [c_int] + [c_void_p] * 5 + [c_int, c_void_p, c_int, c_int, c_float_p, c_int_p,

@@ -10,21 +10,21 @@ import torch.distributed as dist
 from torch import nn
 from torch.autograd import Function
 
+from .collectives import all_reduce_sum_
+from .determinism import is_deterministic
+
 
 class _AllReduceSum(Function):
     """Differentiable sum-all-reduce: backward all-reduces the gradient (norm.py:21-24)."""
 
     @staticmethod
     def forward(ctx, x):
-        y = x.clone()
-        dist.all_reduce(y, op=dist.ReduceOp.SUM)
-        return y
+        ctx.exact = is_deterministic()         # read in forward, kept for backward (DESIGN.md 4.0g)
+        return all_reduce_sum_(x.clone(), ctx.exact)
 
     @staticmethod
     def backward(ctx, g):
-        g = g.clone()
-        dist.all_reduce(g, op=dist.ReduceOp.SUM)
-        return g
+        return all_reduce_sum_(g.clone(), ctx.exact)
 
 
 def _sync_bn(mod, x, reduce_dims):
@@ -67,12 +67,13 @@ class _BN1dReLUFunction(Function):
         _lib.check(lib.isf_bn1d_stats_pivot(_lib.ptr(x), n, c, _lib.ptr(pivot), _lib.ptr(stats), _lib.stream()),
                    "isf_bn1d_stats_pivot")
         count, bwd_count = float(n), float(n)
+        exact = sync and is_deterministic()     # deterministic mode: the cross-rank sums are exact (collectives.py)
         if sync:
             # the reference averages the per-rank mean / mean-of-squares with EQUAL weights (ops/norm.py:186-190), whatever
             # the ranks' row counts: (sum / n_r) summed over ranks with count = world size is exactly that
             world = dist.get_world_size()
             stats.mul_(1.0 / n)
-            dist.all_reduce(stats, op=dist.ReduceOp.SUM)
+            all_reduce_sum_(stats, exact)
             count, bwd_count = float(world), float(world) * n
         y = torch.empty_like(x)
         saved = torch.empty(2 * c, dtype=torch.float32, device=x.device)
@@ -89,7 +90,7 @@ class _BN1dReLUFunction(Function):
         if nbt is not None and not counted:
             nbt.add_(1)
         ctx.save_for_backward(x, y if relu else None, gamma, saved)
-        ctx.geom = (n, c, bwd_count, bool(relu), residual is not None, sync)
+        ctx.geom = (n, c, bwd_count, bool(relu), residual is not None, sync, exact)
         return y
 
     @staticmethod
@@ -97,7 +98,7 @@ class _BN1dReLUFunction(Function):
         from . import _lib
         lib = _lib.load()
         x, y, gamma, saved = ctx.saved_tensors
-        n, c, count, relu, has_res, sync = ctx.geom
+        n, c, count, relu, has_res, sync, exact = ctx.geom
         dy = dy.contiguous().float()
         sums = torch.empty(2 * c, dtype=torch.float32, device=x.device)
         _lib.check(lib.isf_bn1d_backward_sums(_lib.ptr(dy), _lib.ptr(x), _lib.ptr(y), n, c, _lib.ptr(saved),
@@ -105,7 +106,7 @@ class _BN1dReLUFunction(Function):
         local = sums
         if sync:                      # dgamma / dbeta stay the LOCAL sums (DDP averages parameter gradients itself);
             local = sums.clone()      # dx needs the global ones
-            dist.all_reduce(sums, op=dist.ReduceOp.SUM)
+            all_reduce_sum_(sums, exact)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if has_res else None
         dgamma = torch.empty(c, dtype=torch.float32, device=x.device) if gamma is not None else None

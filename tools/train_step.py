@@ -26,10 +26,20 @@ point-cloud path; --loss detection goes through ISFusionDetector.forward_train. 
 convs receive no gradient (only the stride-16 map reaches Point-to-Grid), so --camera FREEZES those parameters
 (requires_grad False) rather than asking DistributedDataParallel for find_unused_parameters: no per-step graph search,
 and the optimizer skips them.  --deterministic runs every step under isfusion_amd.set_deterministic(True) (exact,
-order-independent accumulation in the four scattering kernels; any --loss / --camera / --optimizer / --gt-paste); on one
-rank the steps are then bit-identical run to run -- the mode makes no claim about RCCL's reduction order across ranks.
-Also runs on a single GPU without torchrun (world size 1)."""
+order-independent accumulation in the four scattering kernels; any --loss / --camera / --optimizer / --gt-paste): the steps
+are then bit-identical run to run.  With more than one rank the mode also covers the sums that cross ranks
+(isfusion_amd.collectives): the forward runs under ddp.no_sync() and exact_all_reduce_gradients sums the local gradients
+in 64-bit fixed point (an integer all-reduce), the naiveSyncBN statistics go through the exact all_reduce_sum_ -- losses,
+gradients and updated parameters then depend only on the SET of per-rank inputs and seeds, not on the backend, the
+collective's algorithm or the order of the ranks.  --data-order i,j,k deals the data differently: rank r takes the frames,
+scenes, images and seeds rank order[r] takes by default.  A deterministic run's JSON line carries `param_digest`, the sha256
+of rank 0's parameters and naiveSyncBN buffers after the last step (a plain BatchNorm's running statistics are one
+rank's own and stay out): equal for every --data-order and every --backend (`replicas_agree`: every rank's digest is rank
+0's).  A deterministic run also seeds torch's, numpy's and Python's generators -- one seed while the model is built, one per
+share of the data for the steps (attention dropout, region noise) -- so that it repeats from its command line.  The mode makes no claim about a different
+NUMBER of ranks.  Also runs on a single GPU without torchrun (world size 1)."""
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -65,6 +75,48 @@ def gt_paste_database(first_seed, scenes=4, points_per_object=24):
             db[names[label]].append(dict(name=names[label], path=pts, box3d_lidar=box, num_points_in_gt=points_per_object,
                                          box2d_camera=np.zeros(5, np.float32), difficulty=0))
     return db
+
+
+def parse_data_order(text, world):
+    """--data-order 'i,j,k' -> [i, j, k]: rank r takes what rank order[r] takes by default.  Empty: the identity.  Anything
+    but a permutation of range(world) is an error."""
+    if not text:
+        return list(range(world))
+    try:
+        order = [int(v) for v in text.split(",")]
+    except ValueError:
+        raise ValueError(f"--data-order {text!r}: expected comma-separated rank numbers") from None
+    if sorted(order) != list(range(world)):
+        raise ValueError(f"--data-order {text!r} is not a permutation of the {world} ranks")
+    return order
+
+
+def seed_everything(seed):
+    """torch's, numpy's and Python's global generators: initial weights that are not loaded from a seeded state dict, the
+    seeds of the attention dropout, the region noise"""
+    import random
+    import numpy as np
+    torch.manual_seed(seed)
+    np.random.seed(seed % 2 ** 32)
+    random.seed(seed)
+
+
+def param_digest(module):
+    """sha256 over the parameters and the cross-rank buffers of `module`, in state-dict order: every parameter, and the
+    buffers of the naiveSyncBN layers (statistics of ALL ranks' rows).  The running statistics of a plain BatchNorm are
+    one rank's own -- they follow the data that rank drew, by design -- and are left out."""
+    import hashlib
+    from isfusion_amd.norm import NaiveSyncBatchNorm1d, NaiveSyncBatchNorm2d
+    h = hashlib.sha256()
+    for name, p in module.named_parameters():
+        h.update(name.encode())
+        h.update(p.detach().cpu().numpy().tobytes())
+    for mname, mod in module.named_modules():
+        if isinstance(mod, (NaiveSyncBatchNorm1d, NaiveSyncBatchNorm2d)):
+            for name, b in mod.named_buffers(recurse=False):
+                h.update(f"{mname}.{name}".encode())
+                h.update(b.detach().cpu().numpy().tobytes())
+    return h.hexdigest()
 
 
 def main():
@@ -103,6 +155,9 @@ def main():
     ap.add_argument("--deterministic", action="store_true",
                     help="isfusion_amd.set_deterministic(True): the isf_*_det entries (fixed-point accumulation) in "
                          "DynamicScatter, Point-to-Grid backward and both MSDA backwards")
+    ap.add_argument("--data-order", default="",
+                    help="i,j,k: rank r takes the frames, scenes, images and seeds that rank order[r] takes by default "
+                         "(the identity); with --deterministic the step's result does not depend on it")
     a = ap.parse_args()
     if a.gt_paste and a.loss != "detection":
         ap.error("--gt-paste pastes ground truth: it needs --loss detection")
@@ -118,11 +173,17 @@ def main():
     from isfusion_amd.fusion_modules import seeded_state_dict
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = 0 if a.shared_device else int(os.environ.get("LOCAL_RANK", "0"))
+    try:
+        src = parse_data_order(a.data_order, world)[rank]           # whose share of the data this rank takes
+    except ValueError as e:
+        ap.error(str(e))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
     os.environ.setdefault("MASTER_PORT", "29540")
     dist.init_process_group(a.backend, rank=rank, world_size=world)  # "nccl" IS RCCL on ROCm
+    if a.deterministic:
+        seed_everything(4242)        # a deterministic run repeats from its command line: the same model on every rank ...
     if a.camera:
         from isfusion_amd.detector import ISFusionDetector
         # img_backbone / img_neck / detach of configs/isfusion/isfusion_0075voxel.py:17-45
@@ -175,6 +236,8 @@ def main():
     # after the backward pass (~300 copy launches per step); every parameter that requires a gradient gets one in the
     # step, so no unused-parameter search either
     ddp = torch.nn.parallel.DistributedDataParallel(Wrap(net), device_ids=[local], gradient_as_bucket_view=True)
+    if a.deterministic:
+        seed_everything(4300 + src)  # ... and the draws of the steps belong to the share of the data, not to the rank
     recipe = None
     if a.optimizer == "config":
         from isfusion_amd.optim import TrainingRecipe
@@ -182,17 +245,17 @@ def main():
         opt = recipe.optimizer
     else:
         opt = torch.optim.SGD([p for p in net.parameters() if p.requires_grad], lr=1e-4, momentum=0.9)
-    pts = [torch.from_numpy(synthetic.lidar_sweeps(9000 + 100 * rank + i, a.points)).to(dev) for i in range(a.batch)]
+    pts = [torch.from_numpy(synthetic.lidar_sweeps(9000 + 100 * src + i, a.points)).to(dev) for i in range(a.batch)]
     gt = None
     if detection:
-        scenes = [synthetic.scene_boxes(9000 + 100 * rank + i) for i in range(a.batch)]
+        scenes = [synthetic.scene_boxes(9000 + 100 * src + i) for i in range(a.batch)]
         gt = ([torch.from_numpy(b).to(dev) for b, _ in scenes], [torch.from_numpy(l).to(dev) for _, l in scenes])
     paste = None
     if a.gt_paste:
         import numpy as np
         from isfusion_amd.gt_paste import GTPasteSampler
         from isfusion_amd.input_pipeline import MultiSweepPointLoader
-        np.random.seed(1234 + rank)
+        np.random.seed(1234 + src)
         # the scenes hold ~38 boxes each, so the per-class ceilings sit above that: a dozen candidates per frame
         sampler = GTPasteSampler(db_infos=gt_paste_database(9900), rate=1.0, classes=["car", "truck"],
                                  sample_groups=dict(car=40, truck=20), sample_2d=False)
@@ -205,15 +268,21 @@ def main():
             return (loader(frames, paste=plans), ([torch.from_numpy(r["gt_bboxes_3d"]).to(dev) for r in results],
                                                   [torch.from_numpy(r["gt_labels_3d"]).to(dev) for r in results]),
                     sum(len(p.objects) for p in plans if p is not None))
-    inp = synthetic.fusion_inputs(7 + rank, a.batch)
+    inp = synthetic.fusion_inputs(7 + src, a.batch)
     if a.camera:
         h, w = inp["input_shape"]
-        img = torch.randn(a.batch, 6, 3, h, w, generator=torch.Generator().manual_seed(70 + rank)).to(dev)
+        img = torch.randn(a.batch, 6, 3, h, w, generator=torch.Generator().manual_seed(70 + src)).to(dev)
     else:
         img = tuple(torch.from_numpy(x).to(dev).to(torch.bfloat16 if a.bf16 else torch.float32) for x in inp["img_feats"])
     kw = dict(lidar2img=torch.from_numpy(inp["lidar2img"]), img_aug_matrix=torch.from_numpy(inp["img_aug_matrix"]),
               lidar_aug_matrix=torch.from_numpy(inp["lidar_aug_matrix"]))
     metas = [dict(input_shape=inp["input_shape"]) for _ in range(a.batch)]
+    # deterministic mode across ranks: DDP leaves the gradients local (no_sync) and the exact reduction sums them, the
+    # same bits under every backend and every order of the ranks (isfusion_amd.collectives)
+    exact = a.deterministic and world > 1
+    if exact:
+        from isfusion_amd.collectives import exact_all_reduce_gradients
+        reduced = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
     losses, norms, pasted, t0 = [], [], [], None
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 2)]   # per-step GPU time stamps (no extra sync)
     for step in range(a.steps + 1):
@@ -225,7 +294,8 @@ def main():
         if paste is not None:
             pts, gt, count = paste()
             pasted.append(count)
-        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=a.autocast):
+        with ddp.no_sync() if exact else contextlib.nullcontext(), \
+                torch.autocast("cuda", dtype=torch.bfloat16, enabled=a.autocast):
             if detection:
                 ld = ddp(pts, img, metas, kw, gt)
                 loss = sum(v.float() for k, v in ld.items() if k != "matched_ious")
@@ -233,7 +303,9 @@ def main():
                 out, hm = ddp(pts, img, metas, kw)
                 loss = (out[0].float() ** 2).mean() + hm.float().sigmoid().mean()
         opt.zero_grad(set_to_none=True)
-        loss.backward()                                              # bucketed RCCL all-reduce inside
+        loss.backward()                                              # bucketed RCCL all-reduce inside ...
+        if exact:
+            exact_all_reduce_gradients(reduced)                      # ... or local gradients (no_sync) and the exact sum
         if recipe is not None:
             norms.append(float(recipe.step(step)))                  # the device scalar is rewritten by the next step
         else:
@@ -244,11 +316,19 @@ def main():
     dist.barrier()
     dt = (time.perf_counter() - t0) / max(a.steps, 1)
     per_step = [round(marks[i].elapsed_time(marks[i + 1]), 1) for i in range(a.steps + 1)]   # [0] = the warm-up step
+    digest = {}
+    if a.deterministic:
+        digest["param_digest"] = param_digest(net)
+        if world > 1:                                                # the replicas hold the same bits after the last step
+            every = [None] * world
+            dist.all_gather_object(every, digest["param_digest"])
+            digest["replicas_agree"] = len(set(every)) == 1
     if rank == 0:
         print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss, "camera": a.camera, "deterministic": a.deterministic,
                           "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses],
                           "optimizer": a.optimizer, **({"grad_norm": [round(n, 6) for n in norms]} if recipe else {}),
-                          **({"gt_paste_objects": pasted} if paste is not None else {})}))
+                          **({"gt_paste_objects": pasted} if paste is not None else {}),
+                          **digest}))
     dist.destroy_process_group()
 
 
