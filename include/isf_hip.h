@@ -309,6 +309,12 @@ int isf_pack_filters_f16x3(const float* filters, int num_taps, int c_in, int c_o
                            isf_stream_t stream);
 /* ... from the per-tap TRANSPOSE: filters_t [num_taps, c_out, c_in] -- e.g. the forward filter when the packed one (c_in x c_out
  * = forward c_out x c_in) is the data gradient's, dX = dY W_k^T: no transposed copy of the weights per layer and step */
+/* ... the filters of a DATA GRADIENT with headroom: isf_pack_filters_f16x3_transposed whose inv_scale carries a further
+ * 2^-e, e = max(0, ceil(log2 gain) - 5), gain = max over the c_out columns of sum |w|: gradient rows scaled to max |g| < 2^10
+ * (isf_grad_to_split) then give split rows |dX| <= 2^15, inside f16's range whatever the filters' magnitude.  room (device
+ * float[2]) = {2^e, 2^-e}: multiply the result by room[0] (isf_split_to_f32_scaled2).  Same launches as the plain pack. */
+int isf_pack_filters_dx(const float* filters_t, int num_taps, int c_in, int c_out, void* packed16, float* room,
+                        isf_stream_t stream);
 int isf_pack_filters_f16x3_transposed(const float* filters_t, int num_taps, int c_in, int c_out, void* packed16,
                                       isf_stream_t stream);
 int isf_f32_to_split(const float* x, size_t num_elems, void* xs, isf_stream_t stream);
@@ -942,6 +948,9 @@ int isf_rulebook_pair_lists(const int32_t* nbr, int nbr_stride, int num_out, int
 int isf_grad_to_split(const float* grad, size_t num_elems, void* grad_split, float* scale_out, isf_stream_t stream);
 int isf_grad_rescale(const float* grad, size_t num_elems, float* out, float* scale_out, isf_stream_t stream);
 int isf_split_to_f32_scaled(const void* xs, size_t num_elems, const float* mul, float* x, isf_stream_t stream);
+/* ... * *mul * *mul2 (either may be NULL = 1): the gradient's scale and the dX filters' headroom (isf_pack_filters_dx) */
+int isf_split_to_f32_scaled2(const void* xs, size_t num_elems, const float* mul, const float* mul2, float* x,
+                             isf_stream_t stream);
 int isf_sparse_conv_backward_filter_f16x3(const void* features_split, int num_in, int c_in, const void* grad_out_split,
                                           int num_out, int c_out, const int32_t* indice_pairs, const int32_t* indice_num,
                                           int capacity, int num_taps, const float* grad_inv_scale, float* grad_filters,

@@ -214,6 +214,7 @@ SIGNATURES = {
     "isf_packed_filter16_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
     "isf_pack_filters_f16x3": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "isf_pack_filters_f16x3_transposed": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "isf_pack_filters_dx": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "isf_f32_to_split": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
     "isf_split_to_f32": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
     "isf_f32_to_half": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p]),
@@ -359,6 +360,7 @@ SIGNATURES = {
     "isf_grad_to_split": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p]),
     "isf_grad_rescale": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p]),
     "isf_split_to_f32_scaled": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p]),
+    "isf_split_to_f32_scaled2": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),
     "isf_sparse_conv_backward_filter_f16x3": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                                       c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "isf_msda_backward": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p] * 4),

@@ -474,7 +474,8 @@ int stage_tables_impl(const int32_t* nbr, int nbr_stride, int K, uint16_t* slots
 int sparse_conv_forward_staged_impl(const ConvCall& c /* c.nbr is not read */, const uint16_t* slots, const int32_t* ulist,
                                     const int32_t* ucount, int stage_rows);
 int pack_filters16_impl(Arena& a, const float* w, int K, int cin, int cout, void* packed16, hipStream_t st,
-                        bool transposed = false /* w = [K][cout][cin], the per-tap transpose of the packed filter */);
+                        bool transposed = false /* w = [K][cout][cin], the per-tap transpose of the packed filter */,
+                        float* room = nullptr /* transposed only: the dX filters' headroom, see pack_filters16_kernel */);
 int f32_to_split_impl(const float* x, size_t n_elems, void* xs, hipStream_t st);
 int split_to_f32_impl(const void* xs, size_t n_elems, float* x, hipStream_t st);
 int f32_to_half_impl(const float* x, size_t n_elems, void* xh, hipStream_t st);   // [N][C] f16 rows (f16 storage mode)

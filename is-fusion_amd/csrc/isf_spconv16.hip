@@ -735,21 +735,66 @@ __global__ void absmax_kernel(const float* __restrict__ w, size_t n, unsigned* _
   if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
 }
 
+// absmax_kernel for the dX filters: `wt` = [K][cout][cin] (the forward filter; the packed one is its per-tap transpose).
+// One workgroup per output column co of the dX convolution: out[0] = max |w| as absmax_kernel, out[1] = max over co of
+// sum_{k, ci} |w| -- the largest |dX| a gradient of magnitude 1 can produce (non-finite sums do not set it).
+__global__ __launch_bounds__(256) void dx_gain_kernel(const float* __restrict__ wt, int K, int cin, int cout,
+                                                      unsigned* __restrict__ out) {
+  const int co = blockIdx.x;
+  float m = 0.f, s = 0.f;
+  for (int i = threadIdx.x; i < K * cin; i += 256) {
+    const int k = i / cin, ci = i - k * cin;
+    const float a = fabsf(wt[((size_t)k * cout + co) * cin + ci]);
+    m = fmaxf(m, a);
+    s += a;
+  }
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    m = fmaxf(m, __shfl_xor(m, d, 64));
+    s += __shfl_xor(s, d, 64);
+  }
+  __shared__ float ws[4];
+  if ((threadIdx.x & 63) == 0) {
+    atomicMax(out, __float_as_uint(m));
+    ws[threadIdx.x >> 6] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float t = ws[0] + ws[1] + ws[2] + ws[3];
+    if (t <= 3.0e38f) atomicMax(out + 1, __float_as_uint(t));
+  }
+}
+
 // packed16[tap][chunk][ntile][hi|lo][lane][8 halves], lane = (col j = lane&15, k-group = lane>>4):
 //   element jj = W[tap][32*chunk + 8*(lane>>4) + jj][16*ntile + (lane&15)] * 2^sw
 // header (after the data): float inv_scale = 2^-sw
 // transposed: `w` is the per-tap TRANSPOSE of the filter that is packed -- [K][cout][cin], i.e. the forward filter when the
 // packed one is the data gradient's (dX = dY W_k^T): no transposed copy of the weights per layer and step
+// room (dX filters, isf_pack_filters_dx; absmax_bits[1] = dx_gain_kernel's gain): the gradient rows arrive scaled to
+// max |g| < 2^10 (isf_grad_to_split) and dX leaves as split rows, finite below 65504 only, so |dX| <= 2^10 * gain must stay
+// under 2^16: the header's inv_scale carries a further 2^-e, e = max(0, ceil(log2 gain) - 5) (2^10 * gain * 2^-e <= 2^15), and
+// room[0] = 2^e is what the way back to fp32 multiplies with.  Powers of two: the same bits, e = 0 for gains up to 32.
 __global__ void pack_filters16_kernel(const float* __restrict__ w, int K, int cin, int cout,
                                       const unsigned* __restrict__ absmax_bits, uint4* __restrict__ packed,
-                                      float* __restrict__ header, int transposed) {
+                                      float* __restrict__ header, int transposed, float* __restrict__ room) {
   const float amax = __uint_as_float(*absmax_bits);
   int e = 0;
   if (amax > 0.f) (void)frexpf(amax, &e);
   const int sw = amax > 0.f ? 13 - e : 0;  // max|w|*2^sw in [2^12, 2^13)
   const float s = ldexpf(1.f, sw);
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0) header[0] = ldexpf(1.f, -sw);
+  if (t == 0) {
+    int er = 0;
+    if (room) {
+      const float gain = __uint_as_float(absmax_bits[1]);
+      int eg = 0;
+      if (gain > 0.f) (void)frexpf(gain, &eg);   // gain < 2^eg
+      er = eg > 5 ? eg - 5 : 0;
+      room[0] = ldexpf(1.f, er);
+      room[1] = ldexpf(1.f, -er);
+    }
+    header[0] = ldexpf(1.f, -sw - er);
+  }
   const int nch = cin >> 5, ntiles = cout >> 4;
   const long long total = (long long)K * nch * ntiles * 64;
   if (t >= total) return;
@@ -1411,19 +1456,23 @@ int conv16_band_order_impl(const int32_t* coors4, int n_out, const Conv16LaunchI
   return ISF_OK;
 }
 
-int pack_filters16_impl(Arena& a, const float* w, int K, int cin, int cout, void* packed16, hipStream_t st, bool transposed) {
+int pack_filters16_impl(Arena& a, const float* w, int K, int cin, int cout, void* packed16, hipStream_t st, bool transposed,
+                        float* room) {
   unsigned* amax = nullptr;
   ISF_TRY(a.alloc_n(&amax, 64));
-  ISF_HIP_TRY(hipMemsetAsync(amax, 0, sizeof(unsigned), st));
+  ISF_HIP_TRY(hipMemsetAsync(amax, 0, 2 * sizeof(unsigned), st));
   const size_t n = (size_t)K * cin * cout;
   // at most 64 workgroups: every wave ends in an atomicMax on ONE word (~88 memory-side updates per microsecond), and
   // 1024 workgroups x 4 waves made this 19 us per call -- 42 calls per training step (profiles/r05_train_step_after.txt)
-  hipLaunchKernelGGL(absmax_kernel, dim3(ceil_div((long long)n, 4096) < 64 ? ceil_div((long long)n, 4096) : 64),
-                     dim3(256), 0, st, w, n, amax);
+  if (room)   // the dX filters: the same launch count, one workgroup per column (<= 256), the column sums beside the maximum
+    hipLaunchKernelGGL(dx_gain_kernel, dim3(cout), dim3(256), 0, st, w, K, cin, cout, amax);
+  else
+    hipLaunchKernelGGL(absmax_kernel, dim3(ceil_div((long long)n, 4096) < 64 ? ceil_div((long long)n, 4096) : 64),
+                       dim3(256), 0, st, w, n, amax);
   const long long total = (long long)K * (cin >> 5) * (cout >> 4) * 64;
   hipLaunchKernelGGL(pack_filters16_kernel, dim3(ceil_div(total, 256)), dim3(256), 0, st, w, K, cin, cout, amax,
                      reinterpret_cast<uint4*>(packed16),
-                     reinterpret_cast<float*>(reinterpret_cast<char*>(packed16) + n * 4), transposed ? 1 : 0);
+                     reinterpret_cast<float*>(reinterpret_cast<char*>(packed16) + n * 4), transposed ? 1 : 0, room);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }
@@ -1490,6 +1539,16 @@ int isf_pack_filters_f16x3_transposed(const float* filters_t, int num_taps, int 
   isf::Arena& a = isf::arena_for_stream(isf::as_stream(stream));
   ISF_TRY(a.reset());
   return isf::pack_filters16_impl(a, filters_t, num_taps, c_in, c_out, packed16, isf::as_stream(stream), true);
+}
+
+int isf_pack_filters_dx(const float* filters, int num_taps, int c_in, int c_out, void* packed16, float* room,
+                        isf_stream_t stream) {
+  ISF_REQUIRE(filters && packed16 && room && num_taps > 0, ISF_ERR_ARG, "pack_filters_dx: bad arguments");
+  ISF_REQUIRE(isf::sparse_conv_f16x3_supported(c_in, c_out), ISF_ERR_UNSUPPORTED,
+              "pack_filters_dx: (Cin,Cout)=(%d,%d) not built", c_in, c_out);
+  isf::Arena& a = isf::arena_for_stream(isf::as_stream(stream));
+  ISF_TRY(a.reset());
+  return isf::pack_filters16_impl(a, filters, num_taps, c_in, c_out, packed16, isf::as_stream(stream), true, room);
 }
 
 int isf_f32_to_split(const float* x, size_t num_elems, void* xs, isf_stream_t stream) {

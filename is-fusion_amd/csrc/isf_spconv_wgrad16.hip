@@ -147,11 +147,11 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const float* __restrict
 }
 
 __global__ void split_to_f32_scaled_kernel(const uint4* __restrict__ xs, size_t n8, const float* __restrict__ mul,
-                                           float* __restrict__ x) {
+                                           const float* __restrict__ mul2, float* __restrict__ x) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n8) return;
   const size_t o = (i >> 2) * 8 + (i & 3);
-  *reinterpret_cast<f32x8*>(x + i * 8) = join8(xs[o], xs[o + 4]) * (mul ? *mul : 1.f);
+  *reinterpret_cast<f32x8*>(x + i * 8) = join8(xs[o], xs[o + 4]) * ((mul ? *mul : 1.f) * (mul2 ? *mul2 : 1.f));
 }
 
 // ------------------------------------------------------------------------------------------------ dW
@@ -490,15 +490,20 @@ int isf_grad_rescale(const float* grad, size_t num_elems, float* out, float* sca
   return ISF_OK;
 }
 
-int isf_split_to_f32_scaled(const void* xs, size_t num_elems, const float* mul, float* x, isf_stream_t stream) {
+int isf_split_to_f32_scaled2(const void* xs, size_t num_elems, const float* mul, const float* mul2, float* x,
+                             isf_stream_t stream) {
   using namespace isf;
   ISF_REQUIRE(num_elems == 0 || (x && xs), ISF_ERR_ARG, "split_to_f32_scaled: null pointer");
   ISF_REQUIRE(num_elems % 32 == 0, ISF_ERR_ARG, "split_to_f32_scaled: element count must be a multiple of 32");
   if (num_elems == 0) return ISF_OK;
   hipLaunchKernelGGL(split_to_f32_scaled_kernel, dim3(ceil_div((long long)(num_elems / 8), 256)), dim3(256), 0,
-                     as_stream(stream), reinterpret_cast<const uint4*>(xs), num_elems / 8, mul, x);
+                     as_stream(stream), reinterpret_cast<const uint4*>(xs), num_elems / 8, mul, mul2, x);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
+}
+
+int isf_split_to_f32_scaled(const void* xs, size_t num_elems, const float* mul, float* x, isf_stream_t stream) {
+  return isf_split_to_f32_scaled2(xs, num_elems, mul, nullptr, x, stream);
 }
 
 int isf_sparse_conv_backward_filter_f16x3(const void* features_split, int num_in, int c_in, const void* grad_out_split,

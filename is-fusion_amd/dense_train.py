@@ -62,7 +62,7 @@ def _groups(weight, transpose):
     while off < cin:
         c = min(256, cin - off)
         wk = w5[:, :, off:off + c].contiguous().view(1, 3, 3, c, cout)
-        groups.append((off, c, sp.pack_filters_f16x3(wk), sp.pack_filters_f16x3(wk, transposed=True)))
+        groups.append((off, c, sp.pack_filters_f16x3(wk), *sp.pack_filters_dx(wk)))     # forward | dX filters, their headroom
         off += c
     s["groups", bool(transpose)] = groups
     return groups
@@ -81,7 +81,7 @@ class DenseConvFunction(torch.autograd.Function):
         rows = rows.detach()
         saved = []
         out = None
-        for off, c, pk, _ in groups:
+        for off, c, pk, _, _ in groups:
             xs = sp.to_split(rows if len(groups) == 1 else rows[:, off:off + c])
             y = sp.from_split(sp.sparse_conv_split(xs, pk, 9, c, cout, rb, ordered=False, mode=mode), (rb.num_out, cout))
             out = y if out is None else out.add_(y)
@@ -104,8 +104,8 @@ class DenseConvFunction(torch.autograd.Function):
         want_dx, want_dw = ctx.needs_input_grad[:2]
         # (WGRAD_FULL_TAPS: every tap list of a dense grid is full -- larger reduction chunks, a third of the partial-sum traffic)
         parts = [sp.split_backward(xs, gs, sc, rb, pkt, 9, c, cout, bool(mode & _lib.CONV_MODE_F16), want_dx, want_dw,
-                                   (1, 3, 3, c, cout), _lib.WGRAD_FULL_TAPS)
-                 for xs, (_, c, _, pkt) in zip(ctx.saved_tensors, groups)]
+                                   (1, 3, 3, c, cout), _lib.WGRAD_FULL_TAPS, dx_room=room)
+                 for xs, (_, c, _, pkt, room) in zip(ctx.saved_tensors, groups)]
         if want_dx:
             grad_rows = parts[0][0] if len(parts) == 1 else torch.cat([dx for dx, _ in parts], 1)
         if want_dw:

@@ -176,6 +176,22 @@ def pack_filters_f16x3(weight, transposed=False):
     return packed
 
 
+def pack_filters_dx(weight):
+    """[kD,kH,kW,Cin,Cout] fp32 -> (the packed per-tap TRANSPOSED filters, room float32 [2] = {2^e, 2^-e}) of the data
+    gradient's convolution (isf_pack_filters_dx): pack_filters_f16x3(weight, transposed=True) with headroom -- the gradient
+    rows arrive scaled to max |g| < 2^10 and dX leaves as split rows (finite below 65504), so filters whose column sums of
+    |w| exceed 32 would overflow them; the packed scale carries 2^-e and split_backward multiplies dX by room[0]."""
+    w = weight.detach().float().contiguous()
+    K = int(np.prod(w.shape[:-2]))
+    lib = _lib.load()
+    c_in, c_out = w.shape[-1], w.shape[-2]
+    packed = torch.empty(lib.isf_packed_filter16_bytes(K, c_in, c_out), dtype=torch.uint8, device=w.device)
+    room = torch.empty(2, dtype=torch.float32, device=w.device)
+    _lib.check(lib.isf_pack_filters_dx(_lib.ptr(w), K, c_in, c_out, _lib.ptr(packed), _lib.ptr(room), _lib.stream()),
+               "isf_pack_filters_dx")
+    return packed, room
+
+
 def to_split(x):
     """fp32 [N,C] -> split activation buffer (same bytes; opaque uint8 tensor)."""
     x = x.contiguous().float()
@@ -338,7 +354,7 @@ def rulebook_lines(rb, taps_per_line=3):
                                                      _lib.ptr(lines), _lib.ptr(mask), _lib.ptr(flag), _lib.stream()),
                    "isf_rulebook_to_lines")
         return lines, mask, flag
-    return rb.cached("lines", build)
+    return rb.cached(("lines", int(taps_per_line)), build)
 
 
 def lines_to_nbr(lines, mask, K, taps_per_line=3):
@@ -473,6 +489,8 @@ def sparse_conv_forward_cu(features, packed16, K, c_in, c_out, rb, scale=None, s
     11-15 timing knock-outs)."""
     _lib.require_cuda(features)
     xs, rs, ys, back = _row_format(features, residual, rb, c_out, 0)      # split rows: the kernel has no other mode
+    if rb.num_out == 0:      # no rows, no unit plan (isf_sparse_conv_cu_plan takes at least one row)
+        return back(ys, (0, c_out))
     plan, _buf = cu_plan(rb, variant)
     plan = _lib.ConvCuPlan(plan.group_masks, plan.units, plan.num_units, plan.max_units, plan.num_out, int(variant), plan.cap)
     _lib.check(_lib.load().isf_sparse_conv_forward_cu(
@@ -649,11 +667,11 @@ def grad_to_split(g):
     return gs, sc
 
 
-def from_split_scaled(xs, shape, mul):
-    """split rows -> fp32 * mul[0] (mul: device float tensor)"""
+def from_split_scaled(xs, shape, mul, mul2=None):
+    """split rows -> fp32 * mul[0] (* mul2[0]) (device float tensors)"""
     out = torch.empty(shape, dtype=torch.float32, device=xs.device)
-    _lib.check(_lib.load().isf_split_to_f32_scaled(_lib.ptr(xs), out.numel(), _lib.ptr(mul), _lib.ptr(out),
-                                                   _lib.stream()), "isf_split_to_f32_scaled")
+    _lib.check(_lib.load().isf_split_to_f32_scaled2(_lib.ptr(xs), out.numel(), _lib.ptr(mul), _lib.ptr(mul2), _lib.ptr(out),
+                                                    _lib.stream()), "isf_split_to_f32_scaled2")
     return out
 
 
@@ -712,24 +730,26 @@ drop_packed_pairs = derived.drop_all     # every parameter's packed filters, spa
 
 
 def _packed_pair(weight, w, K, c_in, c_out):
-    """(packed filters of the forward conv, packed per-tap TRANSPOSED filters of the dX conv) of a weight parameter,
-    packed once per parameter version: the forward pass packs both, the backward pass finds its half here instead of
-    transposing + packing again (5 launches per layer and step)."""
+    """(packed filters of the forward conv, packed per-tap TRANSPOSED filters of the dX conv, their headroom: pack_filters_dx)
+    of a weight parameter, packed once per parameter version: the forward pass packs both, the backward pass finds its half
+    here instead of transposing + packing again (5 launches per layer and step)."""
     s = derived.param_store(weight, PACKED_PAIR_CACHE)
     if "pair" not in s:
-        s["pair"] = (pack_filters_f16x3(w), pack_filters_f16x3(w, transposed=True))    # (no transposed copy: the pack kernel reads it)
+        s["pair"] = (pack_filters_f16x3(w), *pack_filters_dx(w))    # (no transposed copy: the pack kernel reads it)
     return s["pair"]
 
 
-def split_backward(xs, gs, sc, rb, packed_t, K, c_in, c_out, half, want_dx, want_dw, wshape, wgrad_flags=0):
+def split_backward(xs, gs, sc, rb, packed_t, K, c_in, c_out, half, want_dx, want_dw, wshape, wgrad_flags=0, dx_room=None):
     """(dX, dW) of a conv whose forward saved its split input rows `xs`.  gs, sc = grad_to_split(grad_out): one scaled
     split of the gradient serves dX (the forward kernel over the transposed rulebook with the per-tap transposed filters
     `packed_t`) and dW (isf_spconv_wgrad16.hip, [*wshape]); the scale is a device scalar, undone in either's last pass.
-    half: single-pass f16 arithmetic; wgrad_flags: further WGRAD_* bits (a dense grid's WGRAD_FULL_TAPS)."""
+    half: single-pass f16 arithmetic; wgrad_flags: further WGRAD_* bits (a dense grid's WGRAD_FULL_TAPS); dx_room: the room
+    of pack_filters_dx when `packed_t` is its pack (None: a plain transposed pack, dX finite while |dX| < 64 max |g|)."""
     grad_in = grad_w = None
     if want_dx:
         grad_in = from_split_scaled(sparse_conv_split(gs, packed_t, K, c_out, c_in, rb.transposed(), ordered=False,
-                                                      mode=_lib.CONV_MODE_F16 if half else 0), (rb.num_in, c_in), sc[1:])
+                                                      mode=_lib.CONV_MODE_F16 if half else 0), (rb.num_in, c_in), sc[1:],
+                                    dx_room)
     if want_dw:
         grad_w = sparse_conv_backward_filter_f16x3(xs, c_in, gs, c_out, rb, sc[1:], wshape,
                                                    mode=(_lib.WGRAD_F16 if half else 0) | wgrad_flags)
@@ -768,7 +788,7 @@ class SparseConvFunction(torch.autograd.Function):
                 "isf_sparse_conv_forward")
         ctx.split_saved = xs is not None
         ctx.half = bool(half) and xs is not None
-        ctx.packed_t = _packed_pair(weight, w, K, c_in, c_out)[1] if xs is not None else None   # dX's filters
+        ctx.packed_t, ctx.dx_room = _packed_pair(weight, w, K, c_in, c_out)[1:] if xs is not None else (None, None)   # dX's filters
         ctx.save_for_backward(xs if xs is not None else features, w)
         ctx.rb, ctx.wshape = rb, tuple(weight.shape)
         return out
@@ -782,10 +802,16 @@ class SparseConvFunction(torch.autograd.Function):
         g = grad_out.contiguous().float()
         lib = _lib.load()
         grad_in = grad_w = None
+        if rb.num_out == 0 or rb.num_in == 0:     # no pair at all (a stride that steps over every active input): zeros
+            if ctx.needs_input_grad[0]:
+                grad_in = torch.zeros((rb.num_in, c_in), dtype=torch.float32, device=g.device)
+            if ctx.needs_input_grad[1]:
+                grad_w = torch.zeros(ctx.wshape, dtype=torch.float32, device=g.device)
+            return grad_in, grad_w, None, None
         if ctx.split_saved:
             gs, sc = grad_to_split(g)
             return (*split_backward(features, gs, sc, rb, ctx.packed_t, K, c_in, c_out, ctx.half, ctx.needs_input_grad[0],
-                                    ctx.needs_input_grad[1], ctx.wshape), None, None)
+                                    ctx.needs_input_grad[1], ctx.wshape, dx_room=ctx.dx_room), None, None)
         if ctx.needs_input_grad[0]:
             rbt = rb.transposed()
             if f16x3_supported(c_out, c_in):
@@ -793,8 +819,8 @@ class SparseConvFunction(torch.autograd.Function):
                 # per-tap transposed filters.  Its operands travel as f16 hi + lo halves, so the gradient is brought
                 # into f16's normal range by a power of two first (exact; see _lib.pow2_rescale) and scaled back
                 gs, sc = _lib.pow2_rescale(g)
-                wt = w.view(K, c_in, c_out).transpose(1, 2).contiguous().view(*ctx.wshape[:-2], c_out, c_in)
-                grad_in = sparse_conv_forward_best(gs, pack_filters_f16x3(wt), K, c_out, c_in, rbt) / sc
+                packed_t, room = pack_filters_dx(w)     # (with headroom: split rows hold |dX| < 65504 only)
+                grad_in = sparse_conv_forward_best(gs, packed_t, K, c_out, c_in, rbt) * (room[0] / sc)
             else:   # fp32-MFMA kernel: no f16 halves, gradients of any magnitude are safe
                 grad_in = torch.empty((rb.num_in, c_in), dtype=torch.float32, device=g.device)
                 _lib.check(lib.isf_sparse_conv_backward_input(_lib.ptr(g), rb.num_out, c_out, _lib.ptr(w), K, c_in,
