@@ -378,7 +378,6 @@ static inline int conv_entry_check(const char* entry, const ConvCall& c, int num
   *run = true;
   return ISF_OK;
 }
-bool sparse_conv_f16x3_supported(int c_in, int c_out);
 int sparse_conv_forward_f16x3_impl(const ConvCall& c);
 // How a launch is cut into tiles (conv16_launch_info), and the per-part tile order that evens out the work of the tiles
 // sharing a CU (conv16_tile_order_impl; nullptr = slot j works on tile j).
@@ -412,7 +411,6 @@ int conv_group_masks_impl(const int32_t* nbr, int nbr_stride, int K, int n_out, 
                           hipStream_t st);
 // isf_spconv_dma.hip: the same convolution for the narrow layers (<= 64 channels in and out) with the gathered rows
 // brought in by LDS-DMA, one cache line per lane quad; bit-identical to sparse_conv_forward_f16x3_impl
-bool sparse_conv_dma_supported(int c_in, int c_out);
 int sparse_conv_forward_dma_impl(const ConvCall& c);   // c.lmask / c.nx: line-compressed table; mode kKernTrace: c.trace
 int conv_dma_launch_info(bool lines, int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info);   // conv16_launch_info's
 int conv16_tile_order_impl(const int32_t* nbr, int nbr_stride, int K, int n_out, const Conv16LaunchInfo& info,
@@ -448,9 +446,7 @@ int conv16_band_order_impl(const int32_t* coors4, int n_out, const Conv16LaunchI
                            hipStream_t st);
 // isf_spconv_deep.hip (round 6): the deep layers' 4-wave two-group launches with LDS-DMA gathers and one hand-scheduled
 // instruction stream per step; the tile kernel's plan / order / launch-info semantics; bit-identical to it
-bool sparse_conv_deep_supported(int c_in, int c_out);
-int sparse_conv_forward_deep_impl(const ConvCall& c);
-int conv_deep_launch_info(int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info);   // conv16_launch_info's
+int sparse_conv_deep_impl(const ConvCall& c, Conv16LaunchInfo* query);   // query: conv16_launch_info's (c: channels, rows, mode)
 // isf_spconv_cu.hip: the same convolution for the 256-column layers as one workgroup per compute unit over units of equal
 // matrix work (plan built once per rulebook); bit-identical to sparse_conv_forward_f16x3_impl
 struct ConvCuPlan {

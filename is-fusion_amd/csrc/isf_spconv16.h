@@ -1,5 +1,6 @@
-// isf_spconv16.h -- device helpers of the f16x3 sparse-conv kernel (isf_spconv16.hip): fragment types, LDS-DMA, the
-// split format, the XCD-aware tile mapping and the epilogue.
+// isf_spconv16.h -- what the f16x3 sparse-conv kernel (isf_spconv16.hip) and its siblings share: the mode bits and the
+// instantiation choice of a launch (host), fragment types, LDS-DMA, the split format, the XCD-aware tile mapping, the
+// plans and the epilogue.
 #pragma once
 #include "isf_common.h"
 
@@ -17,7 +18,7 @@ static constexpr int kConvModeNarrowTiles = 64;   // the 128-column layers of th
                                                   // instead of the 8-wave 256-row one (A/B; the encoder's ISF_ENC_DIAG_NARROW_TILES)
 static constexpr int kConvModeTileTable = 1024;   // `order` is a tile table (isf_sparse_conv_tile_table), not a tile order
 static constexpr int kConvModePartTable = 16384;  // `order` is a part table (conv16_part_table_impl): equal-work parts of a launch of several rounds
-// what launch16_rows ignores when it compares `mode` with one of the launch variants
+// what conv16_choose ignores when it compares `mode` with one of the launch variants
 static constexpr int kConvModeTileBits = ISF_CONV_MODE_UNIFORM_TILES | kConvModeTileTable | kConvModePartTable;
 
 // Modes the exported entry points accept: a BASE mode (one of the values below) | any of the entry point's option bits.
@@ -37,7 +38,7 @@ static constexpr int kConvOptsDma = ISF_CONV_MODE_UNIFORM_TILES;        // isf_s
 static constexpr int kConvOptsStaged = ISF_CONV_MODE_UNIFORM_TILES;     // isf_sparse_conv_forward_staged: base 0 | F16
 
 // The kernels' template parameter MODE is a THIRD number space (after the runtime `mode` and the encoder's `diagnostic`).
-// These bits mean what the runtime bit of the same value means: launch16_rows hands them over unchanged ...
+// These bits mean what the runtime bit of the same value means: conv_kern_bits hands them over unchanged ...
 static constexpr int kKernF16 = ISF_CONV_MODE_F16, kKernNoGather = ISF_CONV_MODE_NO_GATHER, kKernNoWeights = ISF_CONV_MODE_NO_WEIGHTS,
                      kKernNoLoop = ISF_CONV_MODE_NO_LOOP, kKernNoSharing = ISF_CONV_MODE_NO_SHARING, kKernF16Rows = ISF_CONV_MODE_F16_ROWS,
                      kKernStagger = ISF_CONV_MODE_STAGGER, kKernR4Issue = ISF_CONV_MODE_R4_ISSUE, kKernTwoAhead = ISF_CONV_MODE_TWO_AHEAD,
@@ -46,6 +47,111 @@ static constexpr int kKernF16 = ISF_CONV_MODE_F16, kKernNoGather = ISF_CONV_MODE
 // Every other runtime bit (tiles, workgroup shape, kernel choice) is resolved on the host and never reaches a kernel.
 static constexpr int kKernTrace = 512;         // per-workgroup trace (isf_sparse_conv_trace, isf_sparse_conv_dma_trace)
 static constexpr int kKernPhaseTrace = 2048;   // with kKernTrace: per-wave phase trace (isf_sparse_conv_phase_trace)
+// the kernels' MODE bits of a BASE mode: the mode itself (F16_STORAGE = kKernF16Rows | kKernF16); -1: not a base mode
+static constexpr int conv_kern_bits(int base) { return conv_mode_is_production(base) || conv_mode_is_knockout(base) ? base : -1; }
+
+// ------------------------------------------------------------------------------------------------------------------
+// THE INSTANTIATION CHOICE of the tile kernel: pure host arithmetic (tests/test_conv_choice.py walks it without a GPU).
+// The channel shapes each kernel of the family is built for:
+inline bool sparse_conv_f16x3_supported(int c_in, int c_out) {
+  return (c_in == 32 || c_in == 64 || c_in == 128 || c_in == 256) &&
+         (c_out == 32 || c_out == 64 || c_out == 128 || c_out == 256);
+}
+inline bool sparse_conv_dma_supported(int c_in, int c_out) { return (c_in == 32 || c_in == 64) && (c_out == 32 || c_out == 64); }
+inline bool sparse_conv_deep_supported(int c_in, int c_out) { return (c_in == 128 || c_in == 256) && (c_out == 128 || c_out == 256); }
+
+// Workgroup shape per layer, from the measured sweep (profiles/r02_call1_knockout_variants.txt, B=4 x 300 k points):
+// 8 waves x 32 rows (256-row tiles, two workgroups per CU) for the layers with exactly 128 output columns
+// (128 -> 128: 1.13 (4 waves) / 1.02 (16 waves) -> 0.94 ms per 4 launches; 64 -> 128: 0.142 -> 0.130 ms); everything
+// else on 4 waves x 32 rows: the narrow layers lose with wider workgroups (fewer independent workgroups to hide the
+// gather latency) and the 256-column layers of the small deep levels do not have enough tiles (8 waves: 1.41 -> 1.67 ms;
+// 12 waves = one 384-row workgroup per CU: 1.42 -> 1.55 ms, profiles/r02_call3_sharing.txt).
+static constexpr int kConv16NW = 4, kConv16RG = 2;   // the default shape: 4 waves x two 16-row groups (the deep kernel's only one)
+inline bool conv16_wide_shape(int c_out, int n_out) { return c_out == 128 && n_out >= 8 * 256; }   // -> 8 waves
+// SMALL LAUNCHES (round 5, profiles/r05_small_launch_ab.txt).  Below these row counts conv16_plan cuts a launch into HALF
+// tiles only (every compute unit still gets a workgroup): on the two-group kernel a half tile leaves half of each wave's
+// accumulators and of its prefetch registers idle.  The one-group instantiation (RG = 1: the same 16 rows per wave, the
+// same tiles, the same order of operations per output element -- bit-identical) runs them 16-19 % faster: 256 -> 256 at
+// 20 k rows 0.908 -> 0.764 ms per five launches, 128 -> 256 0.106 -> 0.088, 128 -> 128 at 30 k rows 0.434 -> 0.382 ms per four;
+// single-sweep line 454 -> 507 frames/s, two sweeps 706 -> 765.  Above the bound full tiles win by as much (40 k rows:
+// 1.22 -> 1.48 ms; 128 -> 128 at 119 k rows 0.835 -> 0.98 ms), so the bound is exactly where the plan stops being all-half:
+// rows <= 3 workgroups x 4 groups x 16 rows x CUs / 2 column blocks (24 576 on 256 CUs) for the 256-column layers,
+// rows <= 2 x 8 x 16 x CUs (65 536) for the 8-wave 128-column shape.
+inline int conv16_small_rows_256(int cus) { return 96 * cus; }
+inline int conv16_small_rows_wide(int cus) { return 256 * cus; }
+
+enum { kConv16Tile = 0, kConv16Deep = 1 };   // Conv16Choice::backend: spconv_f16x3_kernel | isf_spconv_deep.hip
+struct Conv16Choice {
+  int backend;
+  int nt, rg, nw;       // 16-column tiles per column block, 16-row groups per wave, waves: spconv_f16x3_kernel<c_in, nt, rg, nw, kern>
+  int kern;             // kKern* bits
+  bool uniform_tiles;   // the launch runs with ISF_CONV_MODE_UNIFORM_TILES whatever the caller's mode says
+  bool drop_order;      // ... and without the caller's tile order / table
+};
+// ISF_CONV_MODE_* bits that only pick a shape or a variant: peeled off `mode` one after the other, in this order.  A variant
+// takes the launch when what is left of the mode (tile bits aside) is EXACTLY its bit(s) and the layer is one it is built
+// for; otherwise its bit is ignored.  What remains at the end is a base mode.
+static constexpr int kConvModeOneBlock = ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W;
+static constexpr int kConvModeShapeBits = kConvModeNarrowTiles | ISF_CONV_MODE_DEEP | kConvIssueOpts | kConvModeOneBlock;
+// -> ISF_OK | ISF_ERR_UNSUPPORTED (channels) | ISF_ERR_ARG (the base mode left in mode & ~kConvModeShapeBits is none:
+// single-pass precision and the knock-outs do not combine).  cus: the device's compute units.
+inline int conv16_choose(int c_in, int c_out, int n_out, int mode, bool has_rowmap, int cus, Conv16Choice* out) {
+  if (!sparse_conv_f16x3_supported(c_in, c_out)) return ISF_ERR_UNSUPPORTED;
+  const bool deep = sparse_conv_deep_supported(c_in, c_out), nt8 = c_out >= 128;   // column blocks of 128, or the whole narrow layer
+  const bool wide = conv16_wide_shape(c_out, n_out), small256 = deep && c_out == 256 && n_out <= conv16_small_rows_256(cus);
+  *out = Conv16Choice{kConv16Tile, nt8 ? 8 : c_out / 16, kConv16RG, kConv16NW, 0, false, false};
+  int m = mode & ~(kConvModeNarrowTiles | ISF_CONV_MODE_DEEP);
+  const auto left = [&m](int bits) { return (m & ~kConvModeTileBits) == bits; };
+  const auto variant = [out](int nw, int kern) { out->nw = nw; out->kern = kern; return ISF_OK; };
+  // CHUNK_SPLIT (256-column layers; two workgroups per tile): the workgroup shape follows the small-launch rule
+  if (deep && c_out == 256 && left(ISF_CONV_MODE_CHUNK_SPLIT)) { out->rg = small256 ? 1 : 2; return variant(4, kKernChunkSplit); }
+  m &= ~ISF_CONV_MODE_CHUNK_SPLIT;
+  // ONE_BLOCK_4W / _8W (round 5 experiment, valid results, bit-identical): the 256-COLUMN layers as ONE column block -- a
+  // workgroup owns all 256 output columns of its rows, so a row is gathered ONCE per tap and chunk instead of once per
+  // column block.  The phase trace (profiles/r05_att_256.txt) shows the step bound by the vector-memory issue path (a
+  // gather in the MFMA operand layout costs 64 address cycles, 12 resident waves x (3 gathers + 4 weight DMA pieces) =
+  // the step time): per MFMA this halves the gather instructions.  _4W: 4 waves x 32 rows (two workgroups per CU:
+  // 64 KiB weight stage); _8W: 8 waves x 16 rows (one group per wave: no half tiles).  Tile-order tables belong to the
+  // two-block launch plan: ignored.
+  if (deep && c_out == 256 && !has_rowmap && (m & kConvModeOneBlock) && left(m & kConvModeOneBlock)) {
+    const bool w8 = (m & ISF_CONV_MODE_ONE_BLOCK_8W) != 0;
+    *out = Conv16Choice{kConv16Tile, 16, w8 ? 1 : 2, w8 ? 8 : 4, 0, w8, true};
+    return ISF_OK;
+  }
+  m &= ~kConvModeOneBlock;
+  // TWO_AHEAD: gathered rows two steps ahead (A2 loop; 4-wave shapes only)
+  if (deep && !wide && left(ISF_CONV_MODE_TWO_AHEAD)) return variant(4, kKernTwoAhead);
+  m &= ~ISF_CONV_MODE_TWO_AHEAD;
+  // R4_ISSUE: round 4's issue phase (index reads in the step, four separate DMA pieces): A/B
+  if (nt8 && left(ISF_CONV_MODE_R4_ISSUE)) return variant(wide ? 8 : 4, kKernR4Issue);
+  m &= ~ISF_CONV_MODE_R4_ISSUE;
+  // STAGGER: staggered issue phases (deep layers; valid results, bit-identical)
+  if (nt8 && left(ISF_CONV_MODE_STAGGER)) return variant(wide ? 8 : 4, kKernStagger);
+  m &= ~ISF_CONV_MODE_STAGGER;
+  // a base mode other than 0: f16 storage and no-sharing on the production workgroup shapes, single-pass f16 (opt-in) and
+  // the timing knock-outs on the 4-wave shape
+  if (const int base = m & ~kConvModeTileBits) {
+    if (conv_kern_bits(base) < 0) return ISF_ERR_ARG;
+    const bool production = base == ISF_CONV_MODE_F16_STORAGE || base == ISF_CONV_MODE_NO_SHARING;
+    return variant(production && wide ? 8 : 4, conv_kern_bits(base));
+  }
+  // mode 0.  kConvModeNarrowTiles (A/B): the wide layers on the 4-wave 128-row tile -- but not their small launches
+  const bool small_wide = wide && n_out <= conv16_small_rows_wide(cus);
+  if (small_wide || small256) out->rg = 1;   // small launches: one 16-row group per wave
+  if (small_wide || (wide && !(mode & kConvModeNarrowTiles))) return variant(8, 0);
+  // ISF_CONV_MODE_DEEP (opt-in, bit-identical, measured 8 % slower: profiles/r06_deep.txt): what is left on the default
+  // shape of the deep layers, on isf_spconv_deep.hip (LDS-DMA gathers + one instruction stream per step; it reads no row
+  // map and no part table)
+  const bool use_deep = deep && !small256 && (mode & ISF_CONV_MODE_DEEP) && !has_rowmap && !(m & kConvModePartTable);
+  if (use_deep) out->backend = kConv16Deep;
+  return ISF_OK;
+}
+// The trace instantiations (mode: kKernTrace, + kKernPhaseTrace for the per-wave phase records) exist on the production
+// workgroup shape of the two deep input widths: c_in 256, and 128 (which any other width is answered with).
+inline Conv16Choice conv16_choose_trace(int c_in, int c_out, int n_out, int mode) {
+  return Conv16Choice{kConv16Tile, 8, kConv16RG, c_in != 256 && conv16_wide_shape(c_out, n_out) ? 8 : kConv16NW,
+                      kKernTrace | (mode & kKernPhaseTrace), false, false};
+}
 
 // narrow layers (CIN <= 64, <= 64 output columns) run all their 32-channel chunks in one step: half / the same
 // number of barriers for twice the MFMAs per barrier

@@ -816,11 +816,6 @@ __global__ void pack_filters16_kernel(const float* __restrict__ w, int K, int ci
   packed[base + 64 + lane] = lo;
 }
 
-bool sparse_conv_f16x3_supported(int c_in, int c_out) {
-  return (c_in == 32 || c_in == 64 || c_in == 128 || c_in == 256) &&
-         (c_out == 32 || c_out == 64 || c_out == 128 || c_out == 256);
-}
-
 // One instantiation of the kernel: launches `c`, or with `query` reports how that launch would be cut (conv16_launch_info;
 // c then carries the channels, the row count and the mode alone).
 template <int CIN, int NT, int RG, int NW, int MODE = 0>
@@ -848,21 +843,7 @@ static int launch16(const ConvCall& c, Conv16LaunchInfo* query) {
   return ISF_OK;
 }
 
-// Workgroup shape per layer, from the measured sweep (profiles/r02_call1_knockout_variants.txt, B=4 x 300 k points):
-// 8 waves x 32 rows (256-row tiles, two workgroups per CU) for the layers with exactly 128 output columns
-// (128 -> 128: 1.13 (4 waves) / 1.02 (16 waves) -> 0.94 ms per 4 launches; 64 -> 128: 0.142 -> 0.130 ms); everything
-// else on 4 waves x 32 rows: the narrow layers lose with wider workgroups (fewer independent workgroups to hide the
-// gather latency) and the 256-column layers of the small deep levels do not have enough tiles (8 waves: 1.41 -> 1.67 ms;
-// 12 waves = one 384-row workgroup per CU: 1.42 -> 1.55 ms, profiles/r02_call3_sharing.txt).
-// SMALL LAUNCHES (round 5, profiles/r05_small_launch_ab.txt).  Below these row counts conv16_plan cuts a launch into HALF
-// tiles only (every compute unit still gets a workgroup): on the two-group kernel a half tile leaves half of each wave's
-// accumulators and of its prefetch registers idle.  The one-group instantiation (RG = 1: the same 16 rows per wave, the
-// same tiles, the same order of operations per output element -- bit-identical) runs them 16-19 % faster: 256 -> 256 at
-// 20 k rows 0.908 -> 0.764 ms per five launches, 128 -> 256 0.106 -> 0.088, 128 -> 128 at 30 k rows 0.434 -> 0.382 ms per four;
-// single-sweep line 454 -> 507 frames/s, two sweeps 706 -> 765.  Above the bound full tiles win by as much (40 k rows:
-// 1.22 -> 1.48 ms; 128 -> 128 at 119 k rows 0.835 -> 0.98 ms), so the bound is exactly where the plan stops being all-half:
-// rows <= 3 workgroups x 4 groups x 16 rows x CUs / 2 column blocks (24 576 on 256 CUs) for the 256-column layers,
-// rows <= 2 x 8 x 16 x CUs (65 536) for the 8-wave 128-column shape.
+// the compute units of the device: the one runtime input of conv16_choose (its small-launch bounds, isf_spconv16.h)
 static int conv16_device_cus() {
   static std::atomic<int> cus{0};
   int c = cus.load(std::memory_order_acquire);
@@ -875,114 +856,58 @@ static int conv16_device_cus() {
   return c;
 }
 
-// THE instantiation choice of the tile kernel: every launch and every launch-info query (`query`, see launch16) of a
-// (CIN, 16 * NT columns per block) shape comes through here.
-template <int CIN, int NT>
-static int launch16_rows(const ConvCall& c, Conv16LaunchInfo* query) {
-  int mode = c.mode;
-  const int cout = c.c_out, n_out = c.n_out;
-  // kConvModeNarrowTiles (A/B): the 128-column layers of the large levels on the 4-wave 128-row tile instead of the 8-wave 256-row one
-  const bool narrow_tiles = (mode & kConvModeNarrowTiles) != 0;
-  mode &= ~kConvModeNarrowTiles;
-  // ISF_CONV_MODE_DEEP (opt-in, bit-identical, measured 8 % slower: profiles/r06_deep.txt): the deep layers' 4-wave launches on
-  // isf_spconv_deep.hip (LDS-DMA gathers + one instruction stream per step)
-  const bool use_deep = (mode & ISF_CONV_MODE_DEEP) != 0;
-  mode &= ~ISF_CONV_MODE_DEEP;
-  // ISF_CONV_MODE_ONE_BLOCK_4W / _8W (round 5 experiment, valid results, bit-identical): the 256-COLUMN layers as ONE column block
-  // -- a workgroup owns all 256 output columns of its rows, so a row is gathered ONCE per tap and chunk instead of once per
-  // column block.  The phase trace (profiles/r05_att_256.txt) shows the step bound by the vector-memory issue path (a
-  // gather in the MFMA operand layout costs 64 address cycles, 12 resident waves x (3 gathers + 4 weight DMA pieces) =
-  // the step time): per MFMA this halves the gather instructions.  _4W: 4 waves x 32 rows (two workgroups per CU:
-  // 64 KiB weight stage); _8W: 8 waves x 16 rows.  Tile-order tables belong to the two-block launch plan: ignored.
-  // ISF_CONV_MODE_CHUNK_SPLIT: CHUNK SPLIT for the 256-column layers (see the kernel); the workgroup shape follows the small-launch
-  // rule below (the choice does not change the arithmetic); other shapes / modes ignore the bit
-  if constexpr (NT == 8 && CIN >= 128) {
-    if ((mode & ISF_CONV_MODE_CHUNK_SPLIT) && cout == 256 && (mode & ~(kConvModeTileBits | ISF_CONV_MODE_CHUNK_SPLIT)) == 0) {
-      if (n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4, kKernChunkSplit>(c, query);
-      return launch16<CIN, NT, 2, 4, kKernChunkSplit>(c, query);
-    }
-  }
-  mode &= ~ISF_CONV_MODE_CHUNK_SPLIT;
-  if constexpr (NT == 8 && CIN >= 128) {
-    constexpr int one_block = ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W;
-    if ((mode & one_block) && cout == 256 && (mode & ~(kConvModeTileBits | one_block)) == 0 && !c.rowmap) {
-      ConvCall one = c;
-      one.order = nullptr;
-      if (mode & ISF_CONV_MODE_ONE_BLOCK_8W) {   // (one group per wave: no half tiles)
-        one.mode |= ISF_CONV_MODE_UNIFORM_TILES;
-        return launch16<CIN, 16, 1, 8>(one, query);
-      }
-      return launch16<CIN, 16, 2, 4>(one, query);
-    }
-  }
-  mode &= ~(ISF_CONV_MODE_ONE_BLOCK_4W | ISF_CONV_MODE_ONE_BLOCK_8W);
-  if constexpr (NT == 8 && CIN >= 128) {   // ISF_CONV_MODE_TWO_AHEAD: gathered rows two steps ahead (A2 loop; 4-wave shapes)
-    if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_TWO_AHEAD && !(cout == 128 && n_out >= 8 * 256)) return launch16<CIN, NT, 2, 4, kKernTwoAhead>(c, query);
-  }
-  mode &= ~ISF_CONV_MODE_TWO_AHEAD;
-  if constexpr (NT == 8) {   // ISF_CONV_MODE_R4_ISSUE: round 4's issue phase (index reads in the step, four separate DMA pieces): A/B
-    if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_R4_ISSUE) {
-      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, kKernR4Issue>(c, query);
-      return launch16<CIN, NT, 2, 4, kKernR4Issue>(c, query);
-    }
-  }
-  mode &= ~ISF_CONV_MODE_R4_ISSUE;
-  if constexpr (NT == 8) {   // ISF_CONV_MODE_STAGGER: staggered issue phases (deep layers; valid results, bit-identical)
-    if ((mode & ~kConvModeTileBits) == ISF_CONV_MODE_STAGGER) {
-      if (cout == 128 && n_out >= 8 * 256) return launch16<CIN, NT, 2, 8, kKernStagger>(c, query);
-      return launch16<CIN, NT, 2, 4, kKernStagger>(c, query);
-    }
-  }
-  mode &= ~ISF_CONV_MODE_STAGGER;
-  switch (mode & ~kConvModeTileBits) {   // single-pass f16 (opt-in) and the timing diagnostics run on the 4-wave shape
-    case 0: break;
-    case ISF_CONV_MODE_F16: return launch16<CIN, NT, 2, 4, kKernF16>(c, query);
-    case ISF_CONV_MODE_NO_GATHER: return launch16<CIN, NT, 2, 4, kKernNoGather>(c, query);
-    case ISF_CONV_MODE_NO_WEIGHTS: return launch16<CIN, NT, 2, 4, kKernNoWeights>(c, query);
-    case ISF_CONV_MODE_NO_GATHER | ISF_CONV_MODE_NO_WEIGHTS: return launch16<CIN, NT, 2, 4, kKernNoGather | kKernNoWeights>(c, query);
-    case ISF_CONV_MODE_NO_LOOP: return launch16<CIN, NT, 2, 4, kKernNoLoop>(c, query);
-    case ISF_CONV_MODE_F16_STORAGE:   // f16 storage (+ single-pass f16 arithmetic), production workgroup shapes
-      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, kKernF16Rows | kKernF16>(c, query);
-      return launch16<CIN, NT, 2, 4, kKernF16Rows | kKernF16>(c, query);
-    case ISF_CONV_MODE_NO_SHARING:   // no neighbour sharing, production workgroup shapes
-      if (NT == 8 && cout == 128 && n_out >= 8 * 256) return launch16<CIN, (NT == 8 ? NT : 2), 2, 8, kKernNoSharing>(c, query);
-      return launch16<CIN, NT, 2, 4, kKernNoSharing>(c, query);
-    default:
-      ISF_REQUIRE(false, ISF_ERR_ARG, "sparse_conv16: mode %d (single-pass precision and the diagnostics {2,4,6,8} "
-                  "are not combinable)", mode);
-  }
-  if constexpr (NT == 8) {   // small launches: one 16-row group per wave (see conv16_device_cus above)
-    if (cout == 128 && n_out >= 8 * 256 && n_out <= 256 * conv16_device_cus()) return launch16<CIN, NT, 1, 8>(c, query);
-  }
-  if (NT == 8 && cout == 128 && n_out >= 8 * 256 && !narrow_tiles)
-    return launch16<CIN, (NT == 8 ? NT : 2), 2, 8>(c, query);
-  if constexpr (NT == 8 && CIN >= 128) {
-    if (cout == 256 && n_out <= 96 * conv16_device_cus()) return launch16<CIN, NT, 1, 4>(c, query);
-  }
-  if constexpr (NT == 8 && CIN >= 128) {
-    if (use_deep && !c.rowmap && (mode & ~kConvModeTileBits) == 0 && !(mode & kConvModePartTable) && sparse_conv_deep_supported(CIN, cout))
-      return query ? conv_deep_launch_info(CIN, cout, n_out, c.mode, query) : sparse_conv_forward_deep_impl(c);
-  }
-  return launch16<CIN, NT, 2, 4>(c, query);
-}
+// EVERY INSTANTIATION of the tile kernel that is built, once: X(first c_in, last c_in, NT, RG, NW, kernel MODE).
+#define ISF_CONV16_BASE_MODES(X, NT) /* the default shape runs every base mode */                                          \
+  X(32, 256, NT, 2, 4, 0) X(32, 256, NT, 2, 4, kKernF16) X(32, 256, NT, 2, 4, kKernF16Rows | kKernF16)                      \
+  X(32, 256, NT, 2, 4, kKernNoSharing) X(32, 256, NT, 2, 4, kKernNoGather) X(32, 256, NT, 2, 4, kKernNoWeights)            \
+  X(32, 256, NT, 2, 4, kKernNoGather | kKernNoWeights) X(32, 256, NT, 2, 4, kKernNoLoop)
+#define ISF_CONV16_INSTANCES(X)                                                                                            \
+  ISF_CONV16_BASE_MODES(X, 2) ISF_CONV16_BASE_MODES(X, 4) ISF_CONV16_BASE_MODES(X, 8)                                      \
+  /* 128 / 256 columns: the 8-wave shape and its small launches, the issue variants on both shapes */                      \
+  X(32, 256, 8, 2, 8, 0) X(32, 256, 8, 2, 8, kKernF16Rows | kKernF16) X(32, 256, 8, 2, 8, kKernNoSharing)                  \
+  X(32, 256, 8, 1, 8, 0)                                                                                                    \
+  X(32, 256, 8, 2, 4, kKernR4Issue) X(32, 256, 8, 2, 8, kKernR4Issue)                                                       \
+  X(32, 256, 8, 2, 4, kKernStagger) X(32, 256, 8, 2, 8, kKernStagger)                                                       \
+  /* the deep layers: small 256-column launches, rows two ahead, chunk split, one column block */                          \
+  X(128, 256, 8, 1, 4, 0) X(128, 256, 8, 2, 4, kKernTwoAhead)                                                               \
+  X(128, 256, 8, 2, 4, kKernChunkSplit) X(128, 256, 8, 1, 4, kKernChunkSplit)                                               \
+  X(128, 256, 16, 2, 4, 0) X(128, 256, 16, 1, 8, 0)                                                                         \
+  /* the traces (conv16_choose_trace) */                                                                                   \
+  X(128, 256, 8, 2, 4, kKernTrace) X(128, 256, 8, 2, 4, kKernTrace | kKernPhaseTrace)                                       \
+  X(128, 128, 8, 2, 8, kKernTrace) X(128, 128, 8, 2, 8, kKernTrace | kKernPhaseTrace)                                       \
+  /* built, but no choice names them: 8 waves on a 32-column block */                                                      \
+  X(32, 256, 2, 2, 8, 0) X(32, 256, 2, 2, 8, kKernF16Rows | kKernF16) X(32, 256, 2, 2, 8, kKernNoSharing)
 
 template <int CIN>
-static int dispatch16(const ConvCall& c, Conv16LaunchInfo* query) {
-  switch (c.c_out) {
-    case 32:  return launch16_rows<CIN, 2>(c, query);
-    case 64:  return launch16_rows<CIN, 4>(c, query);
-    case 128:
-    case 256: return launch16_rows<CIN, 8>(c, query);
-  }
-  return ISF_ERR_UNSUPPORTED;
+static int conv16_instance_of(const Conv16Choice& ch, const ConvCall& c, Conv16LaunchInfo* query) {
+#define ISF_CONV16_TRY(LO, HI, NT, RG, NW, KERN)                          \
+  if constexpr (CIN >= LO && CIN <= HI)                                   \
+    if (ch.nt == NT && ch.rg == RG && ch.nw == NW && ch.kern == (KERN)) return launch16<CIN, NT, RG, NW, (KERN)>(c, query);
+  ISF_CONV16_INSTANCES(ISF_CONV16_TRY)
+#undef ISF_CONV16_TRY
+  ISF_REQUIRE(false, ISF_ERR_UNSUPPORTED, "sparse_conv16: no kernel <%d, %d, %d, %d, %d>", CIN, ch.nt, ch.rg, ch.nw, ch.kern);
 }
 
-static int run16(const ConvCall& c, Conv16LaunchInfo* query) {
-  switch (c.c_in) {
-    case 32:  return dispatch16<32>(c, query);
-    case 64:  return dispatch16<64>(c, query);
-    case 128: return dispatch16<128>(c, query);
-    case 256: return dispatch16<256>(c, query);
+// EVERY launch and every launch-info query of the tile kernel: the choice (isf_spconv16.h: conv16_choose, or with `trace`
+// -- c.mode holds kKernTrace -- conv16_choose_trace), then its instantiation, which launches `c` or with `query` reports
+// how that launch would be cut.
+static int run16(const ConvCall& c, Conv16LaunchInfo* query, bool trace = false) {
+  Conv16Choice ch = conv16_choose_trace(c.c_in, c.c_out, c.n_out, c.mode);
+  if (!trace) {
+    const int r = conv16_choose(c.c_in, c.c_out, c.n_out, c.mode, c.rowmap != nullptr, conv16_device_cus(), &ch);
+    ISF_REQUIRE(r != ISF_ERR_ARG, ISF_ERR_ARG, "sparse_conv16: mode %d (single-pass precision and the diagnostics {2,4,6,8} "
+                "are not combinable)", c.mode & ~kConvModeShapeBits);
+    ISF_TRY(r);
+  }
+  if (ch.backend == kConv16Deep) return sparse_conv_deep_impl(c, query);
+  ConvCall one = c;
+  if (ch.uniform_tiles) one.mode |= ISF_CONV_MODE_UNIFORM_TILES;
+  if (ch.drop_order) one.order = nullptr;
+  switch (trace && c.c_in != 256 ? 128 : c.c_in) {   // (the traces are built for the two deep widths)
+    case 32:  return conv16_instance_of<32>(ch, one, query);
+    case 64:  return conv16_instance_of<64>(ch, one, query);
+    case 128: return conv16_instance_of<128>(ch, one, query);
+    case 256: return conv16_instance_of<256>(ch, one, query);
   }
   return ISF_ERR_UNSUPPORTED;
 }
@@ -993,20 +918,6 @@ int sparse_conv_forward_f16x3_impl(const ConvCall& c) {
   return run16(c, nullptr);
 }
 
-// The trace instantiations (c.mode = kKernTrace, + kKernPhaseTrace for the per-wave phase records): the production
-// workgroup shape of the two deep channel shapes.  As launch16_rows: launch, or with `query` the launch's shape.
-static int trace16(const ConvCall& c, Conv16LaunchInfo* query) {
-  const bool wide = c.c_out == 128 && c.n_out >= 8 * 256;
-  if (c.mode & kKernPhaseTrace) {
-    if (c.c_in == 256) return launch16<256, 8, 2, 4, kKernTrace | kKernPhaseTrace>(c, query);
-    if (wide) return launch16<128, 8, 2, 8, kKernTrace | kKernPhaseTrace>(c, query);
-    return launch16<128, 8, 2, 4, kKernTrace | kKernPhaseTrace>(c, query);
-  }
-  if (c.c_in == 256) return launch16<256, 8, 2, 4, kKernTrace>(c, query);
-  if (wide) return launch16<128, 8, 2, 8, kKernTrace>(c, query);
-  return launch16<128, 8, 2, 4, kKernTrace>(c, query);
-}
-
 int conv16_launch_info(ConvKernel kernel, int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info) {
   *info = Conv16LaunchInfo{0, 0, 0, 0, 0, 0, 0};
   if (n_out <= 0) return ISF_OK;
@@ -1015,10 +926,10 @@ int conv16_launch_info(ConvKernel kernel, int c_in, int c_out, int n_out, int mo
               c_in, c_out);
   ConvCall q;
   q.c_in = c_in; q.c_out = c_out; q.n_out = n_out; q.mode = mode;
-  return (mode & kKernTrace) ? trace16(q, info) : run16(q, info);
+  return run16(q, info, (mode & kKernTrace) != 0);
 }
 
-// per-workgroup trace of one launch: where the time of a launch goes -- tools/conv_trace.py.  c.mode: trace16's
+// per-workgroup trace of one launch: where the time of a launch goes -- tools/conv_trace.py.  c.mode: conv16_choose_trace's
 static int sparse_conv_trace_impl(const ConvCall& c, int trace_capacity_blocks, int* grid_blocks, size_t phase_capacity_bytes = 0,
                                   int* waves_per_block = nullptr) {
   const bool phase = (c.mode & kKernPhaseTrace) != 0;
@@ -1027,7 +938,7 @@ static int sparse_conv_trace_impl(const ConvCall& c, int trace_capacity_blocks, 
   ISF_REQUIRE(c.K >= 1 && c.K <= kMaxTaps && c.n_out > 0 && c.nbr_stride % 128 == 0 && c.nbr_stride >= c.n_out, ISF_ERR_ARG,
               "sparse_conv_trace: bad arguments");
   // the per-wave phase records sit behind the per-workgroup records: [grid][8] int64, then dwords
-  const int nw = (c.c_in == 256 || !(c.c_out == 128 && c.n_out >= 8 * 256)) ? 4 : 8;
+  const int nw = conv16_choose_trace(c.c_in, c.c_out, c.n_out, c.mode).nw;
   if (phase && waves_per_block) *waves_per_block = nw;
   Conv16LaunchInfo info;
   ISF_TRY(conv16_launch_info(kConvKernelTile, c.c_in, c.c_out, c.n_out, c.mode, &info));
@@ -1037,7 +948,7 @@ static int sparse_conv_trace_impl(const ConvCall& c, int trace_capacity_blocks, 
               "sparse_conv_trace: the launch has %d workgroups, the trace buffer holds %d", blocks, trace_capacity_blocks);
   ISF_REQUIRE(!phase || (size_t)blocks * (64 + (size_t)nw * (kPhaseHdr + kPhaseStep * kPhaseMaxSteps) * 4) <= phase_capacity_bytes,
               ISF_ERR_ARG, "sparse_conv_phase_trace: trace buffer too small");
-  ISF_TRY(trace16(c, nullptr));
+  ISF_TRY(run16(c, nullptr, true));
   *grid_blocks = blocks;
   return ISF_OK;
 }

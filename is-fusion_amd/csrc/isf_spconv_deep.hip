@@ -213,15 +213,13 @@ __global__ __launch_bounds__(64 * NW, 3) void spconv_deep_kernel(
                                  row_end, relu, half_tile ? RG / 2 : RG);
 }
 
-bool sparse_conv_deep_supported(int c_in, int c_out) {
-  return (c_in == 128 || c_in == 256) && (c_out == 128 || c_out == 256);
-}
-
-// the tile kernel's launch (launch16<CIN, 8, 2, 4>): same plan, same tile order tables, same launch info
+// the launch of the tile kernel's default shape, which conv16_choose hands over: same plan, same tile order tables, same
+// launch info
 template <int CIN>
 static int launch_deep(const ConvCall& c, Conv16LaunchInfo* query) {
-  constexpr int NW = 4;
+  constexpr int NW = kConv16NW;
   using S = ConvDeepSmem<NW>;
+  static_assert(S::NT == 8 && S::RG == kConv16RG, "the deep kernel stands in for spconv_f16x3_kernel<CIN, 8, kConv16RG, kConv16NW>");
   auto kern = spconv_deep_kernel<CIN, NW>;
   static ConvSlots slots;
   ISF_TRY(conv_kernel_slots(slots, reinterpret_cast<const void*>(kern), 64 * NW, S::bytes, S::bytes));
@@ -237,19 +235,11 @@ static int launch_deep(const ConvCall& c, Conv16LaunchInfo* query) {
   return ISF_OK;
 }
 
-static int run_deep(const ConvCall& c, Conv16LaunchInfo* query) {
+// c: a launch the tile kernel's dispatch hands over (checked there; no row map, no part table), or with `query` its query
+int sparse_conv_deep_impl(const ConvCall& c, Conv16LaunchInfo* query) {
   ISF_REQUIRE(sparse_conv_deep_supported(c.c_in, c.c_out), ISF_ERR_UNSUPPORTED, "sparse_conv_deep: (Cin,Cout)=(%d,%d) not built",
               c.c_in, c.c_out);
   return c.c_in == 128 ? launch_deep<128>(c, query) : launch_deep<256>(c, query);
-}
-
-// c: a launch the tile kernel's dispatch hands over (checked there; no row map, no part table)
-int sparse_conv_forward_deep_impl(const ConvCall& c) { return run_deep(c, nullptr); }
-
-int conv_deep_launch_info(int c_in, int c_out, int n_out, int mode, Conv16LaunchInfo* info) {
-  ConvCall q;
-  q.c_in = c_in; q.c_out = c_out; q.n_out = n_out; q.mode = mode;
-  return run_deep(q, info);
 }
 
 }  // namespace isf

@@ -374,10 +374,6 @@ __global__ __launch_bounds__(64 * NW) void spconv_dma_kernel(
   }
 }
 
-bool sparse_conv_dma_supported(int c_in, int c_out) {
-  return (c_in == 32 || c_in == 64) && (c_out == 32 || c_out == 64);
-}
-
 // 4 waves x 32 rows per workgroup.  Measured slower (profiles/r03_dma_gather.txt): 8 waves (one weight stage per 256 rows,
 // 3 workgroups per CU) 64 -> 64 0.740 -> 0.768 ms per step; 4 waves x 64 rows (RG = 4: twice the MFMAs per step and
 // barrier, 3 workgroups per CU) 0.770 -> 0.865 -- the resident workgroups are what hides the loads' round trip.
@@ -399,25 +395,20 @@ static int launch_dma(const ConvCall& c, Conv16LaunchInfo* query) {
   return ISF_OK;
 }
 
-// THE instantiation choice of the LDS-DMA kernel: every launch and every launch-info query comes through here.
 // lines: the line-compressed table's instantiations (a launch: c.lmask != nullptr)
+template <int CIN, int NT, int MODE>
+static int launch_dma_table(const ConvCall& c, bool lines, Conv16LaunchInfo* query) {
+  return lines ? launch_dma<CIN, NT, MODE, true>(c, query) : launch_dma<CIN, NT, MODE, false>(c, query);
+}
+// THE instantiation choice of the LDS-DMA kernel: every launch and every launch-info query comes through here.
 template <int CIN, int NT>
 static int dispatch_dma(const ConvCall& c, bool lines, Conv16LaunchInfo* query) {
-  const int mode = c.mode & ~kConvModePartTable;
-  if (lines) {
-    switch (mode & ~kConvOptsDma) {
-      case kKernTrace: return launch_dma<CIN, NT, kKernTrace, true>(c, query);   // isf_sparse_conv_dma_trace hands the kernel's bit over as a mode
-      case 0: return launch_dma<CIN, NT, 0, true>(c, query);
-      case ISF_CONV_MODE_F16: return launch_dma<CIN, NT, kKernF16, true>(c, query);
-      case ISF_CONV_MODE_F16_STORAGE: return launch_dma<CIN, NT, kKernF16Rows | kKernF16, true>(c, query);
-    }
-  } else {
-    switch (mode & ~kConvOptsDma) {
-      case kKernTrace: return launch_dma<CIN, NT, kKernTrace, false>(c, query);
-      case 0: return launch_dma<CIN, NT, 0, false>(c, query);
-      case ISF_CONV_MODE_F16: return launch_dma<CIN, NT, kKernF16, false>(c, query);
-      case ISF_CONV_MODE_F16_STORAGE: return launch_dma<CIN, NT, kKernF16Rows | kKernF16, false>(c, query);
-    }
+  const int mode = c.mode & ~kConvModePartTable, base = mode & ~kConvOptsDma;
+  switch (base == kKernTrace ? base : conv_kern_bits(base)) {   // isf_sparse_conv_dma_trace hands the kernel's bit over as a mode
+    case kKernTrace: return launch_dma_table<CIN, NT, kKernTrace>(c, lines, query);
+    case 0: return launch_dma_table<CIN, NT, 0>(c, lines, query);
+    case kKernF16: return launch_dma_table<CIN, NT, kKernF16>(c, lines, query);
+    case kKernF16Rows | kKernF16: return launch_dma_table<CIN, NT, kKernF16Rows | kKernF16>(c, lines, query);
   }
   ISF_REQUIRE(false, ISF_ERR_ARG, "sparse_conv_dma: mode %d (0, 1, 257, +32)", mode);
 }

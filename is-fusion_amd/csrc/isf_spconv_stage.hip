@@ -502,8 +502,8 @@ static int launch_staged(const ConvCall& c, const StagePlan& sp) {
 
 template <int CIN, int NT>
 static int launch_staged_rows(const ConvCall& c, const StagePlan& sp) {
-  const bool wide = NT == 8 && c.c_out == 128 && c.n_out >= 8 * 256;   // the 8-wave shape of launch16_rows
-  if ((c.mode & ~kConvOptsStaged) == ISF_CONV_MODE_F16) {
+  const bool wide = NT == 8 && conv16_wide_shape(c.c_out, c.n_out);   // the tile kernel's 8-wave rule
+  if (conv_kern_bits(c.mode & ~kConvOptsStaged) == kKernF16) {
     if (wide) return launch_staged<CIN, (NT == 8 ? NT : 2), 2, 8, kKernF16>(c, sp);
     return launch_staged<CIN, NT, 2, 4, kKernF16>(c, sp);
   }

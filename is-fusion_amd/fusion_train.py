@@ -18,9 +18,10 @@ The reference does the same composition with torch modules (sst_basic_block_v2.p
 
 Training-time stochastic ops of the reference: the residual / feed-forward Dropouts (p = 0.1) of
 DeformableTransformerDecoderLayer (dropout1..4, fusion_encoder.py:604-668) and Instane2SceneAtt (:478, :492) and the
-Point-to-Grid `random_noise` jitter (:992-995) are applied in training mode.  NOT applied: the dropout on the attention
-PROBABILITIES inside the two nn.MultiheadAttention modules (:614, :476 -> :458) -- the flash-style HIP attention core
-never materialises the probability matrix; reproducing it needs an in-kernel random stream (not built).
+Point-to-Grid `random_noise` jitter (:992-995) are applied in training mode.  So is the dropout on the attention
+PROBABILITIES inside the two nn.MultiheadAttention modules (:614, :476 -> :458): the flash-style HIP attention core never
+materialises the probability matrix and draws the mask in the kernel from a per-call seed (`_mha`; for up to 512 keys and
+16 channels per head, the shapes of the two modules -- other shapes run without it).
 
 No CPU fallback: tensors must live on a GPU."""
 import torch

@@ -89,7 +89,7 @@ def test_one_round_launches_are_dealt_evenly(plan_exe):
 
 @pytest.mark.parametrize("TM,ncb,k,bound", [(128, 2, 3, 96 * 256), (256, 1, 2, 256 * 256)])
 def test_small_launch_bounds_are_where_the_plan_stops_being_all_half(plan_exe, TM, ncb, k, bound):
-    """round 5 (isf_spconv16.hip: launch16_rows / conv16_device_cus): a launch of at most
+    """round 5 (isf_spconv16.h: conv16_small_rows_256 / conv16_small_rows_wide): a launch of at most
     96 x CUs rows (256-column layers: 128-row tiles, two column blocks, 3 workgroups per CU) or 256 x CUs rows (the 8-wave
     128-column shape: 256-row tiles, 2 per CU) is cut into HALF tiles only -- the launches the one-group instantiation
     takes over -- and the first row past the bound brings full tiles in.  The one-group launch itself (tiles of TM / 2 rows,
