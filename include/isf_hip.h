@@ -54,6 +54,12 @@ int isf_workspace_bytes(size_t* bytes_host); /* current arena size on the curren
  * (stream handle, base address, bytes) -- per workspace its blocks, then its two persistent byte maps; *num_triples = how
  * many exist.  tools/graph_fault.py maps a GPU memory-fault address onto them. */
 int isf_debug_workspace_blocks(unsigned long long* stream_base_bytes, int max_triples, int* num_triples);
+/* DIAGNOSTIC: the library's stable sort on its own (csrc/isf_sort.hip; tests/test_gpu_sort.py).  order [num] = the stable
+ * order of keys [num] by their low key_bits bits (1 .. 32) -- bits above them never decide.  after (or NULL): a permutation
+ * of 0 .. num-1 from an earlier call; the keys are then taken in that sequence, and order still holds original indices
+ * (minor key first, major key after it = lexicographic order).  keys_sorted (or NULL) [num] = keys[order[j]]. */
+int isf_debug_stable_sort(const uint32_t* keys, int num, int key_bits, const int32_t* after, int32_t* order,
+                          uint32_t* keys_sorted, isf_stream_t stream);
 
 /* A1  dynamic voxelization ------------------------------------------------------------------------
  * replaces voxel_layer.dynamic_voxelize(points, coors, voxel_size, coors_range, NDim=3)

@@ -5,29 +5,36 @@
 //     ingroup_inds_kernel.cu:17-31 (get_inner_win_inds of SST, ops/sst/sst_ops.py:197-211)
 //   * mmcv `_ext.ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step)`
 //     (models/middle_encoders/multi_scale_deformable_attn_function.py:118-124; kernel ms_deform_im2col_cuda.cuh:237-299)
-#include <hipcub/hipcub.hpp>
-
 #include "isf_common.h"
 #include "isf_fixed.h"
 
 namespace isf {
 
-__global__ void iota_kernel(int32_t* __restrict__ v, int n) {
+// the two sort keys of a group id: its low and its high 32 bits
+__global__ void ingroup_split_kernel(const int64_t* __restrict__ ids, int n, uint32_t* __restrict__ lo,
+                                     uint32_t* __restrict__ hi) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) v[i] = i;
+  if (i >= n) return;
+  const unsigned long long v = (unsigned long long)ids[i];
+  lo[i] = (uint32_t)v;
+  hi[i] = (uint32_t)(v >> 32);
 }
 
-// start[pos] = pos where a new group begins in the sorted key sequence, else 0 (an inclusive max-scan then carries the
-// start of every element's segment)
-__global__ void segment_starts_kernel(const int64_t* __restrict__ keys, int n, int32_t* __restrict__ start) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) start[i] = (i == 0 || keys[i] != keys[i - 1]) ? i : 0;
-}
-
-__global__ void ingroup_rank_kernel(const int32_t* __restrict__ seg_start, const int32_t* __restrict__ order, int n,
-                                    int64_t* __restrict__ out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[order[i]] = (int64_t)(i - seg_start[i]);
+// order: the elements stably sorted by their id taken as an unsigned 64-bit number.  Equal ids are adjacent and in input
+// order, so an element's rank in its group is its position minus the first position of its id: a lower-bound search.
+__global__ void ingroup_first_come_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ order, int n,
+                                          int64_t* __restrict__ out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int row = order[j];
+  const unsigned long long id = (unsigned long long)ids[row];
+  int lo = 0, hi = j;                          // the first position whose id is not below `id` lies in [0, j]
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if ((unsigned long long)ids[order[mid]] < id) lo = mid + 1;
+    else hi = mid;
+  }
+  out[row] = (int64_t)(j - lo);
 }
 
 // one thread per (b, q, head, channel): channels of a head are consecutive lanes, so the four bilinear taps of a
@@ -169,26 +176,20 @@ int isf_ingroup_indices(const int64_t* group_inds, int num, int64_t* out_inds, i
   hipStream_t st = as_stream(stream);
   Arena& a = arena_for_stream(as_stream(stream));
   ISF_TRY(a.reset());
-  int64_t* keys = nullptr;
-  int32_t *iota = nullptr, *order = nullptr, *start = nullptr, *seg = nullptr;
-  ISF_TRY(a.alloc_n(&keys, (size_t)num));
-  ISF_TRY(a.alloc_n(&iota, (size_t)num));
+  uint32_t *lo = nullptr, *hi = nullptr;
+  int32_t *by_lo = nullptr, *order = nullptr;
+  ISF_TRY(a.alloc_n(&lo, (size_t)num));
+  ISF_TRY(a.alloc_n(&hi, (size_t)num));
+  ISF_TRY(a.alloc_n(&by_lo, (size_t)num));
   ISF_TRY(a.alloc_n(&order, (size_t)num));
-  ISF_TRY(a.alloc_n(&start, (size_t)num));
-  ISF_TRY(a.alloc_n(&seg, (size_t)num));
   const dim3 grid(ceil_div(num, 256)), block(256);
-  hipLaunchKernelGGL(iota_kernel, grid, block, 0, st, iota, num);
-  size_t tb1 = 0, tb2 = 0;
-  ISF_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb1, group_inds, keys, iota, order, num, 0, 64, st));
-  ISF_HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, tb2, start, seg, hipcub::Max(), num, st));
-  void* temp = nullptr;
-  ISF_TRY(a.alloc(&temp, tb1 > tb2 ? tb1 : tb2));
-  // stable LSD radix sort: equal group ids keep their input order, so the position inside a segment is the
-  // first-come rank -- one of the numberings the reference's atomicAdd can produce, and always the same one
-  ISF_HIP_TRY(hipcub::DeviceRadixSort::SortPairs(temp, tb1, group_inds, keys, iota, order, num, 0, 64, st));
-  hipLaunchKernelGGL(segment_starts_kernel, grid, block, 0, st, keys, num, start);
-  ISF_HIP_TRY(hipcub::DeviceScan::InclusiveScan(temp, tb2, start, seg, hipcub::Max(), num, st));
-  hipLaunchKernelGGL(ingroup_rank_kernel, grid, block, 0, st, seg, order, num, out_inds);
+  hipLaunchKernelGGL(ingroup_split_kernel, grid, block, 0, st, group_inds, num, lo, hi);
+  // stable LSD radix sort, low word first and the high word after it: equal group ids keep their input order, so the
+  // position inside a segment is the first-come rank -- one of the numberings the reference's atomicAdd can produce, and
+  // always the same one.  (How different ids are ordered among themselves -- here as unsigned numbers -- does not matter.)
+  ISF_TRY(stable_sort_u32_impl(a, lo, num, 32, by_lo, st));
+  ISF_TRY(stable_sort_u32_impl(a, hi, num, 32, order, st, nullptr, by_lo));
+  hipLaunchKernelGGL(ingroup_first_come_kernel, grid, block, 0, st, group_inds, order, num, out_inds);
   ISF_LAUNCH_CHECK();
   return ISF_OK;
 }

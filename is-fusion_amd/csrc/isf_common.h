@@ -423,8 +423,11 @@ bool conv16_parts_apply(const Conv16LaunchInfo& info, bool several_rounds = fals
 int conv16_part_table_impl(const int32_t* nbr, const uint32_t* lmask, int nbr_stride, int K, int n_out, int c_in, int c_out,
                            const Conv16LaunchInfo& info, bool raster, int32_t* work, int32_t* table, hipStream_t st,
                            bool equal_rows = false /* the plan's own parts: the order alone (ISF_ENC_DIAG_UNIFORM_TILES) */);
-// isf_voxelize.hip: hand-written stable LSD radix sort (wave multi-split): idx_sorted = stable order of the keys' low bits
-int stable_sort_u32_impl(Arena& a, const uint32_t* keys, int n, int key_bits, int* idx_sorted, hipStream_t st);
+// isf_sort.hip: hand-written stable LSD radix sort (wave multi-split): idx_sorted = stable order of the keys' low key_bits
+// bits, and of nothing above them; keys_sorted: the caller's [n] buffer when it wants the sorted keys too; after: an
+// earlier order to continue (minor key first, major key after it = lexicographic order)
+int stable_sort_u32_impl(Arena& a, const uint32_t* keys, int n, int key_bits, int* idx_sorted, hipStream_t st,
+                         uint32_t* keys_sorted = nullptr, const int* after = nullptr);
 // ROW SORT of a deep SubM launch (round 6): the positions of a launch's part are dealt to its rows in the order of their
 // TAP MASKS, so that the rows of a tile (and of a 16-row group) want the same taps -- a tile walks popcount(OR of its rows'
 // masks) taps, a group multiplies through popcount(OR of its 16 masks): -15 % steps and -17 % MFMAs at level 3 on the

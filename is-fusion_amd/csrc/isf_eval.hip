@@ -209,15 +209,7 @@ __global__ __launch_bounds__(kEvThreads) void ev_match_kernel(
 }
 
 // ----------------------------------------------------------------------------- stage 2: order
-__global__ void ev_gather_cls_kernel(const int32_t* __restrict__ cls, const int* __restrict__ idx, int n,
-                                     uint32_t* __restrict__ out) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n) out[j] = (uint32_t)cls[idx[j]];
-}
-__global__ void ev_compose_kernel(const int* __restrict__ idx1, const int* __restrict__ idx2, int n, int32_t* __restrict__ out) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n) out[j] = idx1[idx2[j]];
-}
+// (no kernel of its own: two calls of the stable sort, isf_sort.hip -- isf_eval_order below)
 
 // ----------------------------------------------------------------------------- stage 3: curves
 // inclusive scan over the workgroup's kEvThreads values; *total = their sum.  ws: kEvWaves shared entries.
@@ -519,18 +511,11 @@ int isf_eval_order(const uint32_t* keys, const int32_t* cls, int rows, int num_c
   hipStream_t st = as_stream(stream);
   Arena& a = arena_for_stream(st);
   ISF_TRY(a.reset());
-  int *idx1 = nullptr, *idx2 = nullptr;
-  uint32_t* cls1 = nullptr;
-  ISF_TRY(a.alloc_n(&idx1, (size_t)rows));
-  ISF_TRY(a.alloc_n(&idx2, (size_t)rows));
-  ISF_TRY(a.alloc_n(&cls1, (size_t)rows));
-  // LSD: the score digits first, the class (5 bits: num_classes = "dropped row") last; both passes stable
-  ISF_TRY(stable_sort_u32_impl(a, keys, rows, 32, idx1, st));
-  hipLaunchKernelGGL(ev_gather_cls_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, st, cls, idx1, rows, cls1);
-  ISF_TRY(stable_sort_u32_impl(a, cls1, rows, 5, idx2, st));
-  hipLaunchKernelGGL(ev_compose_kernel, dim3(ceil_div(rows, 256)), dim3(256), 0, st, idx1, idx2, rows, order);
-  ISF_LAUNCH_CHECK();
-  return ISF_OK;
+  int* by_score = nullptr;
+  ISF_TRY(a.alloc_n(&by_score, (size_t)rows));
+  // LSD: the score digits first, the class (5 bits: num_classes = "dropped row") after them; both sorts stable
+  ISF_TRY(stable_sort_u32_impl(a, keys, rows, 32, by_score, st));
+  return stable_sort_u32_impl(a, reinterpret_cast<const uint32_t*>(cls), rows, 5, order, st, nullptr, by_score);
 }
 
 int isf_eval_curves(const int32_t* order, const uint8_t* tp_mask, const double* conf, const double* errs, const int32_t* counts,

@@ -100,7 +100,7 @@ __global__ void hv_pack_bytes_kernel(const unsigned char* __restrict__ seen, siz
 }
 
 // points of a cell = one segment of the point indices STABLY sorted by the cell's rank (radix sort over the rank's bits,
-// hv_stable_sort below): inside a segment the indices ascend, so a cell's T smallest point indices -- what the reference's
+// stable_sort_u32_impl, isf_sort.hip): inside a segment the indices ascend, so a cell's T smallest point indices -- what the reference's
 // sequential scan keeps (voxelization_cpu.cpp:54-69) -- are the first T of its segment.  Deterministic, no atomics.
 // History: v1 atomicMin bubble insertion (720 us per 300 k points in pillars), v2 count -> scan -> fill -> select with
 // one atomic per point per pass (90 + 16 + 90 + 55 us: the pillar grid's hot cells serialise the atomics).
@@ -115,156 +115,7 @@ __global__ void hv_keys_kernel(const float* __restrict__ points, int P, int C, V
     key = (uint32_t)occ_lookup(cbits, cprefix,
                                ((unsigned long long)(cz + hv_sample_of(hb, i) * g.gz) * g.gy + cy) * g.gx + cx);
   keys[i] = key;
-  if (idx) idx[i] = i;     // (the sort below takes the identity permutation implicitly)
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The stable sort itself (round 6; hand-written, replaces rocprim::radix_sort_pairs -- 8 launches, 270 us per two-sample
-// forward, one of them 214 us: a library tuned for arrays a thousand times larger).  LSD radix sort, `bits` (<= 10) key
-// bits per pass, WAVE MULTI-SPLIT ranking: a wave owns a tile of kRsTile consecutive elements and walks it in order, 64 at
-// a time; `bits` ballots tell every lane which lanes hold the same digit (mask &= my bit ? ballot : ~ballot), so its rank
-// among them is a popcount and the group's first lane keeps the wave's running count of the digit in LDS -- no atomics,
-// no sorting network, stable by construction (lanes, sub-tiles and tiles are all taken in index order).
-//   count pass   per (digit, tile) counts                -> hist [digits][tiles]   (digit-major: the order of the output)
-//   row scan     per digit: exclusive prefix over its tiles, and its total
-//   scatter pass out[first position of the digit + hist[digit][tile] + running count in the tile + rank in the sub-tile]
-constexpr int kRsTile = 1024;     // elements per wave (16 sub-tiles): 293 waves for 300 k points
-constexpr int kRsWaves = 4;       // waves (tiles) per workgroup
-
-template <bool SCATTER>
-__global__ __launch_bounds__(64 * kRsWaves) void hv_radix_pass_kernel(const uint32_t* __restrict__ keys_in,
-                                                                      const int* __restrict__ vals_in /* nullptr: identity */,
-                                                                      int n, int shift, int bits, int tiles,
-                                                                      uint32_t* __restrict__ hist,
-                                                                      const uint32_t* __restrict__ totals /* [digits] */,
-                                                                      uint32_t* __restrict__ keys_out, int* __restrict__ vals_out) {
-  __shared__ uint32_t cnt_s[kRsWaves][1024];
-  __shared__ uint32_t dbase_s[1024];                 // SCATTER: first output position of every digit
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int tile = blockIdx.x * kRsWaves + wave;
-  const int nd = 1 << bits;
-  if (SCATTER) {                                     // exclusive prefix of the digit totals (<= 1024 values: one wave)
-    if (wave == 0) {
-      uint32_t run = 0u;
-      for (int b0 = 0; b0 < nd; b0 += 64) {
-        const uint32_t v = totals[b0 + lane];
-        uint32_t x = v;
-#pragma unroll
-        for (int dlt = 1; dlt < 64; dlt <<= 1) {
-          const uint32_t o = __shfl_up(x, dlt, 64);
-          if (lane >= dlt) x += o;
-        }
-        dbase_s[b0 + lane] = run + x - v;
-        run += __shfl(x, 63, 64);
-      }
-    }
-    __syncthreads();
-  }
-  if (tile >= tiles) return;
-  volatile uint32_t* cnt = cnt_s[wave];
-  for (int d = lane; d < nd; d += 64) cnt[d] = 0u;
-  __builtin_amdgcn_wave_barrier();
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  // the tile's keys (and values) are requested up front: kRsTile / 64 independent loads in flight per lane instead of one
-  // exposed round trip per sub-tile (147 waves walking 32 dependent round trips each made a pass 50 us)
-  constexpr int NSUB = kRsTile / 64;
-  uint32_t kreg[NSUB];
-  int vreg[NSUB];
-#pragma unroll
-  for (int sub = 0; sub < NSUB; ++sub) {
-    const int i = tile * kRsTile + sub * 64 + lane;
-    kreg[sub] = i < n ? keys_in[i] : 0u;
-    vreg[sub] = (SCATTER && i < n) ? (vals_in ? vals_in[i] : i) : 0;
-  }
-#pragma unroll
-  for (int sub = 0; sub < NSUB; ++sub) {
-    const int i = tile * kRsTile + sub * 64 + lane;
-    const bool valid = i < n;
-    const uint32_t key = kreg[sub];
-    const uint32_t d = (key >> shift) & (uint32_t)(nd - 1);
-    unsigned long long m = __ballot(valid);
-    for (int b = 0; b < bits; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long bal = __ballot(bit);
-      m &= bit ? bal : ~bal;
-    }
-    const int rank = __popcll(m & lt), group = __popcll(m);
-    uint32_t base = 0u;
-    if (valid) base = cnt[d];                       // every lane of a digit group reads the count before ...
-    __builtin_amdgcn_wave_barrier();
-    if (valid && rank == 0) cnt[d] = base + (uint32_t)group;   // ... its first lane advances it (one address per group)
-    __builtin_amdgcn_wave_barrier();
-    if (SCATTER && valid) {
-      const uint32_t pos = dbase_s[d] + hist[(size_t)d * tiles + tile] + base + (uint32_t)rank;
-      keys_out[pos] = key;
-      vals_out[pos] = vreg[sub];
-    }
-  }
-  if (!SCATTER)
-    for (int d = lane; d < nd; d += 64) hist[(size_t)d * tiles + tile] = cnt[d];
-}
-
-// per digit (one wave each): exclusive prefix of its row of per-tile counts in place (coalesced, ceil(tiles / 64) rounds)
-// and the digit's total; the scatter pass turns the totals into the digits' first output positions itself.  (A single
-// workgroup scanning all digits x tiles entries with a chunk per thread was 100 us of dependent, uncoalesced loads.)
-__global__ __launch_bounds__(256) void hv_radix_rowscan_kernel(uint32_t* __restrict__ hist, int nd, int tiles,
-                                                               uint32_t* __restrict__ totals) {
-  const int lane = threadIdx.x & 63, d = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (d >= nd) return;
-  uint32_t* row = hist + (size_t)d * tiles;
-  uint32_t run = 0u;
-  for (int b0 = 0; b0 < tiles; b0 += 64) {
-    const int t = b0 + lane;
-    const uint32_t v = t < tiles ? row[t] : 0u;
-    uint32_t x = v;
-#pragma unroll
-    for (int dlt = 1; dlt < 64; dlt <<= 1) {
-      const uint32_t o = __shfl_up(x, dlt, 64);
-      if (lane >= dlt) x += o;
-    }
-    if (t < tiles) row[t] = run + x - v;
-    run += __shfl(x, 63, 64);
-  }
-  if (lane == 0) totals[d] = run;
-}
-
-// (keys, 0 .. n - 1) stably sorted by the low `key_bits` bits of the keys -> (keys_sorted, idx_sorted); keys_tmp / idx_tmp:
-// scratch of n entries each, hist: (1 << 10) * tiles entries.  The sorted data always ends in keys_sorted / idx_sorted.
-static int hv_stable_sort(const uint32_t* keys, uint32_t* keys_tmp, uint32_t* keys_sorted, int* idx_tmp, int* idx_sorted,
-                          uint32_t* hist /* 1024 * (tiles + 1) */, int n, int key_bits, hipStream_t st) {
-  const int passes = (key_bits + 9) / 10, bits = (key_bits + passes - 1) / passes;
-  const int tiles = ceil_div(n, kRsTile), blocks = ceil_div(tiles, kRsWaves);
-  const uint32_t* kin = keys;
-  const int* vin = nullptr;
-  for (int p = 0; p < passes; ++p) {
-    // ping-pong so that the LAST pass writes the caller's output buffers
-    const bool to_out = ((passes - 1 - p) & 1) == 0;
-    uint32_t* kout = to_out ? keys_sorted : keys_tmp;
-    int* vout = to_out ? idx_sorted : idx_tmp;
-    uint32_t* totals = hist + (size_t)1024 * tiles;
-    hipLaunchKernelGGL(hv_radix_pass_kernel<false>, dim3(blocks), dim3(64 * kRsWaves), 0, st, kin, vin, n, p * bits, bits, tiles,
-                       hist, totals, kout, vout);
-    hipLaunchKernelGGL(hv_radix_rowscan_kernel, dim3(ceil_div(1 << bits, 4)), dim3(256), 0, st, hist, 1 << bits, tiles, totals);
-    hipLaunchKernelGGL(hv_radix_pass_kernel<true>, dim3(blocks), dim3(64 * kRsWaves), 0, st, kin, vin, n, p * bits, bits, tiles,
-                       hist, totals, kout, vout);
-    kin = kout;
-    vin = vout;
-  }
-  ISF_LAUNCH_CHECK();
-  return ISF_OK;
-}
-
-// the same sort for other callers (the row sort of the deep conv launches, isf_spconv16.hip): idx_sorted [n] = the stable
-// order of the low `key_bits` bits of keys [n]; scratch from the arena
-int stable_sort_u32_impl(Arena& a, const uint32_t* keys, int n, int key_bits, int* idx_sorted, hipStream_t st) {
-  ISF_REQUIRE(keys && idx_sorted && n > 0 && key_bits >= 1 && key_bits <= 32, ISF_ERR_ARG, "stable_sort: bad arguments");
-  uint32_t *keys_tmp = nullptr, *keys_sorted = nullptr, *hist = nullptr;
-  int* idx_tmp = nullptr;
-  ISF_TRY(a.alloc_n(&keys_tmp, (size_t)n));
-  ISF_TRY(a.alloc_n(&keys_sorted, (size_t)n));
-  ISF_TRY(a.alloc_n(&idx_tmp, (size_t)n));
-  ISF_TRY(a.alloc_n(&hist, (size_t)1024 * (ceil_div(n, kRsTile) + 1)));
-  return hv_stable_sort(keys, keys_tmp, keys_sorted, idx_tmp, idx_sorted, hist, n, key_bits, st);
+  if (idx) idx[i] = i;     // (the sort takes the identity permutation implicitly)
 }
 
 // first sorted position of every cell
@@ -450,13 +301,7 @@ int hard_voxelize_impl(Arena& a, const float* points, int P, int C, const float 
     hipLaunchKernelGGL(hv_keys_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, points, P, C, g, hb, cocc.bits,
                        cocc.prefix, none, keys, (int*)nullptr);
     ISF_LAUNCH_CHECK();
-    uint32_t* keys_tmp = nullptr;
-    int* idx_tmp = nullptr;
-    uint32_t* hist = nullptr;
-    ISF_TRY(a.alloc_n(&keys_tmp, (size_t)P));
-    ISF_TRY(a.alloc_n(&idx_tmp, (size_t)P));
-    ISF_TRY(a.alloc_n(&hist, (size_t)1024 * (ceil_div(P, kRsTile) + 1)));
-    ISF_TRY(hv_stable_sort(keys, keys_tmp, keys_sorted, idx_tmp, idx_sorted, hist, P, key_bits, st));
+    ISF_TRY(stable_sort_u32_impl(a, keys, P, key_bits, idx_sorted, st, keys_sorted));
     hipLaunchKernelGGL(hv_segment_heads_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, keys_sorted, P, none, start);
     hipLaunchKernelGGL(hv_segment_slots_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, keys_sorted, idx_sorted, P,
                        start, none, max_points, slots);

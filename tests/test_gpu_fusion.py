@@ -478,6 +478,31 @@ def test_ingroup_indices_first_come_rank(dev, n, groups, seed):
     assert ops.ingroup_indices(torch.zeros((0,), dtype=torch.long, device=dev)).numel() == 0
 
 
+@pytest.mark.parametrize("case", ["high word only", "negative ids", "one group"])
+def test_ingroup_indices_takes_all_64_bits_of_an_id(dev, case):
+    """the ids are sorted as two 32-bit words: ids that differ only above bit 32 are different groups, negative ids are
+    groups like any other, and one group of more than a sort tile numbers its elements 0 .. n - 1"""
+    from isfusion_amd import fusion_ops as ops
+    rng = np.random.default_rng(11)
+    if case == "high word only":
+        n = 3000
+        g = rng.integers(0, 7, n).astype(np.int64) + (1 << 40) * (np.arange(n, dtype=np.int64) % 3)
+    elif case == "negative ids":
+        n = 3000
+        g = rng.integers(-9, 9, n).astype(np.int64)
+        g[::5] -= 1 << 35
+    else:
+        n = 1025
+        g = np.full(n, 123456789012, np.int64)
+    out = ops.ingroup_indices(torch.from_numpy(g).to(dev)).cpu().numpy()
+    want = np.zeros(n, np.int64)
+    seen = {}
+    for i, v in enumerate(g.tolist()):
+        want[i] = seen.get(v, 0)
+        seen[v] = want[i] + 1
+    assert np.array_equal(out, want)
+
+
 def test_sst_modules_forward_like_the_reference(dev):
     """SSTInputLayerV2.forward(voxel_feats, voxel_coors, batch_size) -> SSTv2.forward(voxel_info) -> [BEV map]
     (sst_input_layer_v2.py:63, sst_v2.py:65; the call sequence of fusion_encoder.py:1179-1181) on the dense token grid,

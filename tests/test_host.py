@@ -34,6 +34,14 @@ def test_library_exports_every_declared_symbol():
     assert list(o) == [21, 720, 720]
 
 
+def test_library_sources_include_no_sort_or_scan_library():
+    csrc = os.path.join(ROOT, "is-fusion_amd", "csrc")
+    names = [f for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
+    assert len(names) >= 30
+    for f in names:
+        assert not re.search(r"#\s*include\s*[<\"][^>\"]*(hipcub|rocprim)", open(os.path.join(csrc, f)).read()), f
+
+
 def test_ops_refuse_cpu_tensors():
     import isfusion_amd as m
     from isfusion_amd._lib import IsfError
