@@ -1415,6 +1415,62 @@ int isf_rows_weight_grad(const float* g, const float* x, int ldx, int x_hw, int 
                          const float* inv_scale, float* workspace, int num_chunks, float* dw, int ldw,
                          isf_stream_t stream);
 
+/* Backward of the Swin-T backbone (isf_swin_train.hip) -------------------------------------------------------
+ * What autograd runs under SwinTransformer.forward in training mode.  The matrix products are isf_swin_gemm on the
+ * transposed packed weight (dX = dY . W) and isf_rows_weight_grad (dW = dY^T . X); the entries below are the rest.
+ * Every reduction over rows, windows or images is two passes -- per-workgroup partial sums over a fixed range, then a
+ * sum of the partials in index order -- so results are bit-identical run to run, without float atomics.  Gradient rows
+ * arrive pre-scaled by a power of two (isf_grad_rescale); inv_scale (device scalar, NULL = 1) multiplies every
+ * parameter gradient an entry writes.
+ * isf_swin_operand_rows writes out the operand rows the A loader generates, out [num_rows, k]: ROWS / MERGE (with the
+ *   LayerNorm prologue when a->ln_stats is set: the normalised rows X^ of dW = dY^T . X^ for WindowMSA.qkv, swin.py:88,
+ *   FFN's first Linear, and PatchMerging.reduction in the loader's q*C + c order, utils/transformer.py:371-384), or
+ *   PATCH with k = 16 c (im2col of PatchEmbed.projection, utils/transformer.py:250-252).
+ * isf_swin_layernorm_backward differentiates nn.LayerNorm (SwinBlock.norm1 / norm2, swin.py:356-368; PatchEmbed.norm,
+ *   utils/transformer.py:255-256; PatchMerging.norm, :383; the out_indices norms, swin.py:756-762) over the loader's
+ *   rows x (ROWS or MERGE; a->ln_stats = the forward's (mean, rstd) rows, a->ln_gamma):
+ *     dx = rstd (dy gamma - mean_k(dy gamma) - x^ mean_k(dy gamma x^)) + residual_grad,  dgamma = sum_r dy x^,
+ *     dbeta = sum_r dy,  with dy read as rows [num_rows, k] or, dy_hw > 0, as an NCHW map [num_rows / dy_hw, k, dy_hw]
+ *     (the layout swin.py:759-761 hands the out_indices maps out in) and multiplied by *dy_scale (NULL = 1).
+ *   ROWS: dx rows [num_rows, k], residual_grad rows or NULL.  MERGE: dx token rows [n*h*w, c] -- the adjoint of
+ *   nn.Unfold(2, 2) with corner padding (utils/transformer.py:368-371): every token lies in one merged row, the
+ *   gradient of padded cells is dropped; no residual_grad.  k <= 1536.  workspace: fp32 [num_parts, 2, k],
+ *   num_parts = isf_swin_layernorm_backward_parts(num_rows).
+ * isf_swin_column_sums: out[c] = *inv_scale * (sum_r g[r, c] + extra[c]) (extra NULL = 0): the bias gradients of
+ *   nn.Linear (swin.py:88 and :115, mmcv FFN) and PatchEmbed.projection.  workspace fp32 [num_parts, channels], num_parts =
+ *   isf_swin_column_sums_parts(num_rows).
+ * isf_swin_gelu_backward differentiates nn.GELU of mmcv FFN (erf form, activation 2 of isf_swin_gemm), in place:
+ *   hidden holds the pre-activation z and receives gelu(z), grad holds dL/dgelu and receives dL/dz.
+ * isf_swin_scale_rows: out[r, :] = g[r, :] * row_scale[r / rows_per_sample] -- the DropPath factor (swin.py:251, mmcv
+ *   FFN) on a branch's incoming gradient; a factor 0 gives exact zeros.
+ * isf_swin_window_attention_backward differentiates isf_swin_window_attention (ShiftWindowMSA + WindowMSA after the
+ *   qkv Linear, swin.py:79-117 and :178-253) with the forward's geometry: dout [batch*height*width, channels] is the
+ *   gradient of the attention output rows; the probabilities are recomputed from qkv.  Writes dqkv [batch*height*
+ *   width, 3 channels] (every element), drel_bias [heads, 49, 49] (gradient of the gathered bias, in dout's scale),
+ *   dtable [table_rows, heads] = *inv_scale * the sum of drel_bias over rel_index (int64 [49, 49], swin.py:96-100;
+ *   dtable NULL = skip) and dqkv_bias_pad [3 channels]: padded cells produce no output but take part as keys and
+ *   values with k / v = the qkv bias (the zero padding follows norm1, swin.py:187 after :360), so their dK / dV are gradient
+ *   of the qkv bias and of nothing else; in dout's scale, [0, channels) is 0.  workspace: fp32 [num_groups * heads *
+ *   (49 * 49 + 64)], num_groups = isf_swin_window_attention_backward_groups(...).  window 7, head dim 32. */
+int isf_swin_operand_rows(const isf_swin_a* a, int num_rows, int k, float* out, isf_stream_t stream);
+int isf_swin_layernorm_backward_parts(int num_rows);
+int isf_swin_layernorm_backward(const isf_swin_a* a, int num_rows, int k, const float* dy, int dy_hw,
+                                const float* dy_scale, const float* residual_grad, float* dx, const float* inv_scale,
+                                float* workspace, int num_parts, float* dgamma, float* dbeta, isf_stream_t stream);
+int isf_swin_column_sums_parts(int num_rows);
+int isf_swin_column_sums(const float* g, int num_rows, int channels, const float* extra, const float* inv_scale,
+                         float* workspace, int num_parts, float* out, isf_stream_t stream);
+int isf_swin_gelu_backward(float* hidden, float* grad, size_t num_elems, isf_stream_t stream);
+int isf_swin_scale_rows(const float* g, int num_rows, int channels, const float* row_scale, int rows_per_sample, float* out,
+                        isf_stream_t stream);
+int isf_swin_window_attention_backward_groups(int batch, int height, int width, int heads);
+int isf_swin_window_attention_backward(const float* qkv, const float* qkv_bias, const float* rel_bias,
+                                       const int64_t* rel_index, const float* dout, int batch, int height, int width,
+                                       int channels, int heads, int window, int shift, float scale,
+                                       const float* inv_scale, float* workspace, int num_groups, float* dqkv,
+                                       float* drel_bias, float* dtable, int table_rows, float* dqkv_bias_pad,
+                                       isf_stream_t stream);
+
 /* Fused AdamW with global-norm gradient clipping (isf_optim.hip) ---------------------------------------------
  * isf_optim_grad_sumsq + isf_optim_adamw replace, together, mmcv OptimizerHook.clip_grads (mmcv/runner/hooks/
  *   optimizer.py: torch.nn.utils.clip_grad_norm_ over every gradient, max_norm, norm_type 2) followed by the step of

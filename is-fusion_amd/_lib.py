@@ -408,6 +408,18 @@ SIGNATURES = {
     "isf_rows_weight_grad_chunks": (c_int, [c_int, c_int, c_int]),
     "isf_rows_weight_grad": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
                                      c_void_p, c_int, c_void_p]),
+    "isf_swin_operand_rows": (c_int, [ctypes.POINTER(SwinA), c_int, c_int, c_void_p, c_void_p]),
+    "isf_swin_layernorm_backward_parts": (c_int, [c_int]),
+    "isf_swin_layernorm_backward": (c_int, [ctypes.POINTER(SwinA), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "isf_swin_column_sums_parts": (c_int, [c_int]),
+    "isf_swin_column_sums": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "isf_swin_gelu_backward": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "isf_swin_scale_rows": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "isf_swin_window_attention_backward_groups": (c_int, [c_int, c_int, c_int, c_int]),
+    "isf_swin_window_attention_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                   c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p, c_void_p, c_int,
+                                                   c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "isf_swin_row_stats": (c_int, [ctypes.POINTER(SwinA), c_int, c_int, ctypes.c_float, c_void_p, c_void_p]),
     "isf_swin_layernorm": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, ctypes.c_float, c_void_p, c_int,
                                    c_void_p]),

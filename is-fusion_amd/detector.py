@@ -430,8 +430,10 @@ class ISFusionDetector(ISFusionPtsPath):
     """The whole model of isfusion.py: the camera branch (img_backbone = SwinTransformer, img_neck =
     GeneralizedLSSFPN, swin.py / generalized_lss.py) in front of ISFusionPtsPath.  Images in, boxes out (eval mode) or
     losses out (forward_train); the ISFusionPtsPath methods keep their signatures (they take camera features).
-    Training needs detach=True, as the shipped config sets it: the backbone runs its training-mode forward (stochastic
-    depth) without a backward, the neck trains."""
+    Training with detach=True, as the shipped config sets it: the backbone runs its training-mode forward (stochastic
+    depth) without a backward, the neck trains.  Training with detach=False (the reference class's default,
+    isfusion.py:40) fine-tunes the backbone too; its backward is opt-in through `camera_backward = True`, and without
+    it detach=False raises."""
 
     def __init__(self, img_backbone=None, img_neck=None, detach=False, **pts_kwargs):
         super().__init__(**pts_kwargs)
@@ -440,6 +442,9 @@ class ISFusionDetector(ISFusionPtsPath):
         self.img_backbone = _build_camera(img_backbone, SwinTransformer)
         self.img_neck = _build_camera(img_neck, GeneralizedLSSFPN)
         self.detach = detach
+
+    camera_backward = False     # a plain attribute: not a parameter, buffer or constructor argument.  True: training
+                                # with detach=False runs the camera backbone's backward (swin.py, isf_swin_train.hip)
 
     @property
     def with_img_backbone(self):
@@ -478,8 +483,12 @@ class ISFusionDetector(ISFusionPtsPath):
         B, N, C, H, W = img.size()
         if self.training:
             if not self.detach:
-                raise NotImplementedError("ISFusionDetector: training with detach=False needs the Swin backbone's "
-                                          "backward, which is not built (the shipped config has detach=True)")
+                if not self.camera_backward:
+                    raise NotImplementedError("ISFusionDetector: training with detach=False needs the Swin backbone's "
+                                              "backward, which is opt-in: set camera_backward = True (the shipped "
+                                              "config has detach=True)")
+                img_feats = self.img_backbone.forward_train(img.reshape(B * N, C, H, W).float(), backward=True)
+                return self.img_neck.forward_train(img_feats, input_grads=True) if self.with_img_neck else img_feats
             img_feats = self.img_backbone.forward_train(img.reshape(B * N, C, H, W).float())
             return self.img_neck.forward_train(img_feats) if self.with_img_neck else img_feats
         img_feats = self.img_backbone(img.reshape(B * N, C, H, W).float())

@@ -64,8 +64,9 @@ def rows_weight_grad(g, x, inv_scale=None, out=None):
 
 class LateralFunction(torch.autograd.Function):
     """rows [B*H*W, N] = conv1x1(cat([fine, interpolate(coarse, fine's size, bilinear, align_corners=True)], 1)) without
-    a bias, for NCHW maps fine [B, C1, H, W] (no gradient: a backbone output) and coarse [B, C2, H2, W2], weight
-    [N, C1 + C2, 1, 1]."""
+    a bias, for NCHW maps fine [B, C1, H, W] and coarse [B, C2, H2, W2], weight [N, C1 + C2, 1, 1].  fine gets a
+    gradient (G W[:, :C1], NCHW) only when it requires one: forward_train(input_grads=True) on a backbone with a
+    backward."""
 
     @staticmethod
     @_amp_fwd
@@ -86,13 +87,18 @@ class LateralFunction(torch.autograd.Function):
         fine, coarse, w = ctx.saved_tensors
         B, C1, H, W = fine.shape
         _, C2, H2, W2 = coarse.shape
-        need_coarse, need_w = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if not (need_coarse or need_w):
+        need_fine, need_coarse, need_w = ctx.needs_input_grad
+        if not (need_fine or need_coarse or need_w):
             return None, None, None
         # gradients are tiny: a power-of-two scale keeps the GEMMs' f16 halves in range (exact; up^T is linear)
         gs, sc = _lib.grad_rescale(grad_rows)
         g2 = upsample_rows_adjoint(gs, B, H, W, H2, W2)
-        grad_coarse = grad_w = None
+        grad_fine = grad_coarse = grad_w = None
+        if need_fine:
+            # dfine = G W[:, :C1], stored as NCHW by the GEMM's epilogue
+            pl = PackedLinear(w[:, :C1].contiguous(), transposed=True)
+            grad_fine = gemm(_a(_lib.SWIN_A_ROWS, gs, ldx=gs.shape[1]), gs.shape[0], gs.shape[1], pl,
+                             scale=sc[1:].expand(C1).contiguous(), out_nchw=(B, H, W))
         if need_w:
             grad_w = torch.empty((w.shape[0], C1 + C2), dtype=torch.float32, device=w.device)
             rows_weight_grad(gs, fine, sc[1:], out=grad_w[:, :C1])
@@ -104,7 +110,7 @@ class LateralFunction(torch.autograd.Function):
             rows = gemm(_a(_lib.SWIN_A_ROWS, g2, ldx=g2.shape[1]), g2.shape[0], g2.shape[1], pl,
                         scale=sc[1:].expand(C2).contiguous())
             grad_coarse = rows.view(B, H2, W2, C2).permute(0, 3, 1, 2)          # NCHW view of rows, as the forward hands out
-        return None, grad_coarse, grad_w
+        return grad_fine, grad_coarse, grad_w
 
 
 class ConvModule(nn.Module):
@@ -202,19 +208,23 @@ class GeneralizedLSSFPN(nn.Module):
             lat[i] = p["fpn"][i](SplitMap.from_nchw(y)).to_nchw()
         return tuple(lat[:len(lat) - 1])
 
-    def forward_train(self, inputs):
+    def forward_train(self, inputs, input_grads=False):
         """Training-mode forward with a backward towards every parameter: batch-statistics BatchNorm (running mean /
         variance and num_batches_tracked move as nn.BatchNorm2d's do), all levels computed as in forward().  inputs: the
-        backbone's NCHW maps, without a gradient (the backbone has no backward).  Returns NCHW views of token rows."""
+        backbone's NCHW maps.  input_grads=False: they come without a gradient (the backbone's default forward_train has
+        no backward) and one that requires grad is refused.  input_grads=True: inputs that require grad receive one
+        (SwinTransformer.forward_train(..., backward=True)); the parameters' gradients are the same either way.
+        Returns NCHW views of token rows."""
         from . import spconv as sp
         from .dense_train import DenseConvFunction, from_rows, supported
         from .norm import bn1d_relu
         assert len(inputs) == len(self.in_channels)
         _lib.require_cuda(*inputs)
         assert self.training, "call .train() first (forward() is the eval-mode forward)"
-        if any(x.requires_grad for x in inputs):
-            raise NotImplementedError("GeneralizedLSSFPN.forward_train: inputs that require grad (the camera backbone "
-                                      "has no backward; the shipped config detaches its outputs)")
+        if not input_grads and any(x.requires_grad for x in inputs):
+            raise NotImplementedError("GeneralizedLSSFPN.forward_train: inputs that require grad need input_grads=True "
+                                      "(off by default: the camera backbone's backward is opt-in, and the shipped "
+                                      "config detaches its outputs)")
         if self.no_norm_on_lateral:
             raise NotImplementedError("GeneralizedLSSFPN.forward_train: no_norm_on_lateral (biased lateral convs)")
         for m in self.fpn_convs:

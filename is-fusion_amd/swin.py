@@ -1,7 +1,10 @@
 """Camera backbone: the reference's SwinTransformer (mmdet3d/models/backbones/swin.py, with PatchEmbed / PatchMerging of
 models/utils/transformer.py) on the HIP kernels of isf_swin.hip.  ``forward`` is the eval-mode forward;
-``forward_train`` is the training-mode forward (stochastic depth) without a backward: the shipped config detaches the
-backbone's outputs (``detach=True``, isfusion.py:76-77), so training needs no gradient through it.
+``forward_train`` is the training-mode forward (stochastic depth).  By default it has no backward: the shipped config
+detaches the backbone's outputs (``detach=True``, isfusion.py:76-77), so training needs no gradient through it.
+``forward_train(..., backward=True)`` runs the same launches and hangs ONE autograd node on the maps whose backward is
+built from the kernels of isf_swin_train.hip (window-attention, LayerNorm and GELU backward, fixed-order column sums) and
+from the forward's own GEMM on transposed packed weights (dX) and isf_rows_weight_grad (dW); DESIGN.md section 4.0c.
 
 Same sub-module names, parameters and buffers as the reference, so an IS-Fusion checkpoint's ``img_backbone.*`` loads
 with ``strict=True`` (187 entries for configs/isfusion/isfusion_0075voxel.py, mmcv FFN naming ``ffn.layers.0.0`` /
@@ -133,6 +136,104 @@ def window_attention(qkv, qkv_bias, rel_bias, B, H, W, C, heads, window, shift, 
     return out
 
 
+# ------------------------------------------------------------------------------------------- backward (isf_swin_train.hip)
+def operand_rows(a, rows, k):
+    """isf_swin_operand_rows: the loader's operand rows written out, [rows, k] (after its LayerNorm prologue, if any)"""
+    s, keep = a
+    out = torch.empty((rows, k), dtype=torch.float32, device=keep[0].device)
+    _lib.check(_lib.load().isf_swin_operand_rows(ctypes.byref(s), rows, k, _lib.ptr(out), _lib.stream()),
+               "isf_swin_operand_rows")
+    return out
+
+
+def layernorm_backward(a, rows, k, dy, *, dy_hw=0, dy_scale=None, residual=None, dx_shape=None, inv_scale=None):
+    """isf_swin_layernorm_backward over the loader's rows (ROWS or MERGE with stats and gamma) -> (dx, dgamma, dbeta).
+    dy: rows [rows, k], or an NCHW map [B, k, H, W] with dy_hw = H * W; dy_scale / inv_scale: device scalars (factor on
+    dy / on dgamma and dbeta) or None; residual: rows added to dx (ROWS); dx_shape: the token rows a MERGE loader
+    gathers from (default [rows, k])."""
+    s, keep = a
+    _lib.require_cuda(dy)
+    assert dy.dtype == torch.float32 and dy.is_contiguous() and dy.numel() == rows * k
+    assert residual is None or (residual.dtype == torch.float32 and residual.is_contiguous()
+                                and tuple(residual.shape) == (rows, k))
+    dev = dy.device
+    dx = torch.empty(dx_shape or (rows, k), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    parts = lib.isf_swin_layernorm_backward_parts(rows)
+    ws = torch.empty((parts, 2, k), dtype=torch.float32, device=dev)
+    dg, db = torch.empty(k, dtype=torch.float32, device=dev), torch.empty(k, dtype=torch.float32, device=dev)
+    _lib.check(lib.isf_swin_layernorm_backward(ctypes.byref(s), rows, k, _lib.ptr(dy), dy_hw, _lib.ptr(dy_scale),
+                                               _lib.ptr(residual), _lib.ptr(dx), _lib.ptr(inv_scale), _lib.ptr(ws), parts,
+                                               _lib.ptr(dg), _lib.ptr(db), _lib.stream()), "isf_swin_layernorm_backward")
+    return dx, dg, db
+
+
+def column_sums(g, extra=None, inv_scale=None):
+    """isf_swin_column_sums: inv_scale * (g.sum(0) + extra) in a fixed order"""
+    _lib.require_cuda(g)
+    assert g.dtype == torch.float32 and g.is_contiguous() and g.dim() == 2
+    M, N = g.shape
+    lib = _lib.load()
+    parts = lib.isf_swin_column_sums_parts(M)
+    ws = torch.empty((parts, N), dtype=torch.float32, device=g.device)
+    out = torch.empty(N, dtype=torch.float32, device=g.device)
+    _lib.check(lib.isf_swin_column_sums(_lib.ptr(g), M, N, _lib.ptr(extra), _lib.ptr(inv_scale), _lib.ptr(ws), parts,
+                                        _lib.ptr(out), _lib.stream()), "isf_swin_column_sums")
+    return out
+
+
+def gelu_backward(hidden, grad):
+    """isf_swin_gelu_backward, in place: hidden (pre-activation) -> gelu(hidden), grad -> grad * gelu'(hidden)"""
+    assert hidden.dtype == grad.dtype == torch.float32 and hidden.is_contiguous() and grad.is_contiguous()
+    assert hidden.shape == grad.shape
+    _lib.check(_lib.load().isf_swin_gelu_backward(_lib.ptr(hidden), _lib.ptr(grad), hidden.numel(), _lib.stream()),
+               "isf_swin_gelu_backward")
+
+
+def scale_rows(g, row_scale):
+    """isf_swin_scale_rows: g [M, N] * row_scale[sample of the row] (DropPath on a gradient); None passes g through"""
+    if row_scale is None:
+        return g
+    M, N = g.shape
+    assert g.dtype == torch.float32 and g.is_contiguous() and M % row_scale.numel() == 0
+    out = torch.empty_like(g)
+    _lib.check(_lib.load().isf_swin_scale_rows(_lib.ptr(g), M, N, _lib.ptr(row_scale), M // row_scale.numel(),
+                                               _lib.ptr(out), _lib.stream()), "isf_swin_scale_rows")
+    return out
+
+
+def window_attention_backward(qkv, qkv_bias, rel_bias, dout, B, H, W, C, heads, window, shift, scale, rel_index=None,
+                              table_rows=0, inv_scale=None):
+    """isf_swin_window_attention_backward: gradient rows dout [B*H*W, C] of window_attention's output ->
+    (dqkv [B*H*W, 3C], drel_bias [heads, 49, 49], dtable [table_rows, heads] * inv_scale or None (without rel_index),
+    the padded cells' share of the qkv-bias gradient [3C])"""
+    _lib.require_cuda(qkv, dout)
+    M = B * H * W
+    assert qkv.dtype == torch.float32 and qkv.is_contiguous() and tuple(qkv.shape) == (M, 3 * C)
+    assert dout.dtype == torch.float32 and dout.is_contiguous() and tuple(dout.shape) == (M, C)
+    dev = qkv.device
+    lib = _lib.load()
+    groups = lib.isf_swin_window_attention_backward_groups(B, H, W, heads)
+    n = window * window
+    ws = torch.empty(groups * heads * (n * n + 64), dtype=torch.float32, device=dev)
+    dqkv = torch.empty_like(qkv)
+    drel = torch.empty((heads, n, n), dtype=torch.float32, device=dev)
+    dtable = torch.empty((table_rows, heads), dtype=torch.float32, device=dev) if rel_index is not None else None
+    pad = torch.empty(3 * C, dtype=torch.float32, device=dev)
+    if rel_index is not None:
+        assert rel_index.dtype == torch.int64 and rel_index.is_contiguous() and rel_index.numel() == n * n
+    _lib.check(lib.isf_swin_window_attention_backward(
+        _lib.ptr(qkv), _lib.ptr(qkv_bias), _lib.ptr(rel_bias), _lib.ptr(rel_index), _lib.ptr(dout), B, H, W, C, heads,
+        window, shift, float(scale), _lib.ptr(inv_scale), _lib.ptr(ws), groups, _lib.ptr(dqkv), _lib.ptr(drel),
+        _lib.ptr(dtable), table_rows, _lib.ptr(pad), _lib.stream()), "isf_swin_window_attention_backward")
+    return dqkv, drel, dtable, pad
+
+
+def _rows_weight_grad(g, x, inv_scale):
+    from .generalized_lss import rows_weight_grad       # (generalized_lss imports this module)
+    return rows_weight_grad(g, x, inv_scale)
+
+
 def _ln_only(norm_cfg):
     if (norm_cfg or {}).get("type", "LN") != "LN":
         raise NotImplementedError(f"SwinTransformer: norm {norm_cfg} (only LN is built)")
@@ -228,12 +329,20 @@ class SwinBlock(nn.Module):
                     proj=linear(m.proj.weight), proj_b=m.proj.bias.detach(), rel=m.relative_bias(),
                     fc1=linear(l1.weight), fc1_b=l1.bias.detach(), fc2=linear(l2.weight), fc2_b=l2.bias.detach())
 
-    def run(self, p, x, B, H, W, keep=(None, None)):
+    def pack_backward(self):
+        """the transposed packed weights of dX = dY . W, one per Linear"""
+        m = self.attn.w_msa
+        l1, l2 = self.ffn.layers[0][0], self.ffn.layers[1]
+        return dict(qkv=PackedLinear(m.qkv.weight, transposed=True), proj=PackedLinear(m.proj.weight, transposed=True),
+                    fc1=PackedLinear(l1.weight, transposed=True), fc2=PackedLinear(l2.weight, transposed=True))
+
+    def run(self, p, x, B, H, W, keep=(None, None), tape=None):
         """x: token rows [B*H*W, C] -> the block's output rows; x and the result are the fp32 residual rows.  With the
         f16 pack (pack(PackedLinearF16)) qkv, the attention output and the FFN hidden are f16 rows.  keep: per-image
         DropPath factors [B] (keep / keep_prob) of the attention and the FFN branch, or None: the branch output is
         multiplied by them after window reverse / un-shift and before the identity is added (swin.py:251, mmcv FFN);
-        gemm refuses them with the f16 pack."""
+        gemm refuses them with the f16 pack.  tape: a list that receives what run_backward needs (the same launches
+        either way)."""
         M, C = x.shape
         m = self.attn.w_msa
         h16 = isinstance(p["qkv"], PackedLinearF16)
@@ -242,13 +351,64 @@ class SwinBlock(nn.Module):
         qkv = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln1), M, C, p["qkv"], shift=p["qkv_b"], out_f16=h16)
         att = window_attention(qkv, p["qkv_b"], p["rel"], B, H, W, C, m.num_heads, self.attn.window_size,
                                self.attn.shift_size, m.scale)
+        rec = None if tape is None else dict(x=x, st1=st, qkv=qkv, att=att, keep=keep)
         x = gemm(_a(_lib.SWIN_A_ROWS, att, ldx=C), M, C, p["proj"], shift=p["proj_b"], residual=x, row_scale=keep[0])
         ln2 = (self.norm2.weight.detach(), self.norm2.bias.detach())
         st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm2.eps)
         F = self.ffn.feedforward_channels
         h = gemm(_a(_lib.SWIN_A_ROWS, x, ldx=C, stats=st, ln=ln2), M, C, p["fc1"], shift=p["fc1_b"], act=ACT_GELU,
                  out_f16=h16)
+        if tape is not None:
+            rec.update(y=x, st2=st)
+            tape.append(rec)
         return gemm(_a(_lib.SWIN_A_ROWS, h, ldx=F), M, F, p["fc2"], shift=p["fc2_b"], residual=x, row_scale=keep[1])
+
+    def run_backward(self, p, pb, rec, g, B, H, W, inv, grads):
+        """g: gradient rows [B*H*W, C] of the block's output, pre-scaled (1 / inv[0] is the scale) -> the gradient rows
+        of its input in the same scale; the twelve parameter gradients (times inv) go into grads[parameter].
+        rec: what run() left on the tape -- the block's input x, the rows y between its branches, both LayerNorms'
+        (mean, rstd) rows, the qkv rows and the attention output.  The FFN's hidden rows are not kept: the first Linear
+        runs again (without GELU) and isf_swin_gelu_backward turns them into gelu(.) and the gradient into dL/dz."""
+        M, C = g.shape
+        m = self.attn.w_msa
+        l1, l2 = self.ffn.layers[0][0], self.ffn.layers[1]
+        F = self.ffn.feedforward_channels
+        rows = lambda t: _a(_lib.SWIN_A_ROWS, t, ldx=t.shape[1])
+        # FFN branch: out = y + keep1 * (gelu(LN2(y) W1^T + b1) W2^T + b2)
+        y, x = rec["y"], rec["x"]
+        ln2 = (self.norm2.weight.detach(), self.norm2.bias.detach())
+        a2 = _a(_lib.SWIN_A_ROWS, y, ldx=C, stats=rec["st2"], ln=ln2)
+        df = scale_rows(g, rec["keep"][1])
+        h = gemm(a2, M, C, p["fc1"], shift=p["fc1_b"])
+        dh = gemm(rows(df), M, C, pb["fc2"])
+        gelu_backward(h, dh)
+        grads[l2.weight] = _rows_weight_grad(df, h, inv)
+        grads[l2.bias] = column_sums(df, inv_scale=inv)
+        del h
+        grads[l1.weight] = _rows_weight_grad(dh, operand_rows(a2, M, C), inv)
+        grads[l1.bias] = column_sums(dh, inv_scale=inv)
+        dn = gemm(rows(dh), M, F, pb["fc1"])
+        del dh
+        dy, grads[self.norm2.weight], grads[self.norm2.bias] = layernorm_backward(a2, M, C, dn, residual=g,
+                                                                                  inv_scale=inv)
+        # attention branch: y = x + keep0 * (attention(LN1(x) Wqkv^T + bqkv) Wp^T + bp)
+        dp = scale_rows(dy, rec["keep"][0])
+        grads[m.proj.weight] = _rows_weight_grad(dp, rec["att"], inv)
+        grads[m.proj.bias] = column_sums(dp, inv_scale=inv)
+        datt = gemm(rows(dp), M, C, pb["proj"])
+        table = m.relative_position_bias_table
+        dqkv, _, grads[table], pad = window_attention_backward(
+            rec["qkv"], p["qkv_b"], p["rel"], datt, B, H, W, C, m.num_heads, self.attn.window_size, self.attn.shift_size,
+            m.scale, rel_index=m.relative_position_index, table_rows=table.shape[0], inv_scale=inv)
+        ln1 = (self.norm1.weight.detach(), self.norm1.bias.detach())
+        a1 = _a(_lib.SWIN_A_ROWS, x, ldx=C, stats=rec["st1"], ln=ln1)
+        grads[m.qkv.weight] = _rows_weight_grad(dqkv, operand_rows(a1, M, C), inv)
+        if m.qkv.bias is not None:
+            grads[m.qkv.bias] = column_sums(dqkv, extra=pad, inv_scale=inv)
+        dn = gemm(rows(dqkv), M, 3 * C, pb["qkv"])
+        dx, grads[self.norm1.weight], grads[self.norm1.bias] = layernorm_backward(a1, M, C, dn, residual=dy,
+                                                                                  inv_scale=inv)
+        return dx
 
 
 class PatchEmbed(nn.Module):
@@ -273,14 +433,31 @@ class PatchEmbed(nn.Module):
         wp = torch.cat([w, w.new_zeros(w.shape[0], k - w.shape[1])], 1)
         return dict(w=linear(wp), b=self.projection.bias.detach().float().contiguous(), k=k)
 
-    def run(self, p, img):
+    def run(self, p, img, tape=None):
         N, C, H, W = img.shape
         Ho, Wo = (H + 3) // 4, (W + 3) // 4
         M = N * Ho * Wo
         x = gemm(_a(_lib.SWIN_A_PATCH, img, n=N, c=C, h=H, w=W), M, p["k"], p["w"], shift=p["b"])
+        if tape is not None:
+            tape.append(dict(img=img, raw=x))
         if self.norm is not None:
             x = layernorm(x, self.norm)
         return x, (Ho, Wo)
+
+    def run_backward(self, rec, g, cum, grads):
+        """g: gradient rows of run()'s output times cum[0] -> the projection's (and the norm's) gradients; the image
+        gets none.  dW = dY^T . patches on the im2col rows (isf_swin_operand_rows, PATCH)."""
+        img, raw = rec["img"], rec["raw"]
+        N, C, H, W = img.shape
+        M, E = raw.shape
+        inv = cum[1:]
+        if self.norm is not None:
+            st = row_stats(_a(_lib.SWIN_A_ROWS, raw, ldx=E), M, E, self.norm.eps)
+            a = _a(_lib.SWIN_A_ROWS, raw, ldx=E, stats=st, ln=(self.norm.weight.detach(), self.norm.bias.detach()))
+            g, grads[self.norm.weight], grads[self.norm.bias] = layernorm_backward(a, M, E, g, inv_scale=inv)
+        patches = operand_rows(_a(_lib.SWIN_A_PATCH, img, n=N, c=C, h=H, w=W), M, 16 * C)
+        grads[self.projection.weight] = _rows_weight_grad(g, patches, inv).view(self.projection.weight.shape)
+        grads[self.projection.bias] = column_sums(g, inv_scale=inv)
 
 
 class PatchMerging(nn.Module):
@@ -311,7 +488,7 @@ class PatchMerging(nn.Module):
             p["b"] = self.norm.bias.detach().float().view(C, 4).t().contiguous().view(-1)
         return p
 
-    def run(self, p, x, B, H, W):
+    def run(self, p, x, B, H, W, tape=None):
         C = self.in_channels
         Ho, Wo = (H + 1) // 2, (W + 1) // 2
         M = B * Ho * Wo
@@ -320,8 +497,36 @@ class PatchMerging(nn.Module):
             st = row_stats(_a(_lib.SWIN_A_MERGE, x, **geo), M, 4 * C, self.norm.eps)
             a = _a(_lib.SWIN_A_MERGE, x, stats=st, ln=(p["g"], p["b"]), **geo)
         else:
+            st = None
             a = _a(_lib.SWIN_A_MERGE, x, **geo)
+        if tape is not None:
+            tape.append(dict(x=x, st=st))
         return gemm(a,M, 4 * C, p["w"]), (Ho, Wo)
+
+    def pack_backward(self, p):
+        """the transposed packed reduction weight, in the loader's column order"""
+        C = self.in_channels
+        w = self.reduction.weight.detach().float()
+        return PackedLinear(w.view(-1, C, 4).permute(0, 2, 1).reshape(w.shape[0], 4 * C).contiguous(), transposed=True)
+
+    def run_backward(self, p, pb, rec, g, B, H, W, inv, grads):
+        """g: gradient rows [B*Ho*Wo, 2C] of run()'s output (pre-scaled; inv as in SwinBlock.run_backward) -> the
+        gradient of the token rows [B*H*W, C].  The LayerNorm backward writes dx on the token rows: that is the adjoint
+        of the 2 x 2 gather, and the gradient of corner padding is dropped.  Gradients are computed in the loader's
+        q*C + c column order and handed out in nn.Unfold's c*4 + q."""
+        if self.norm is None:
+            raise NotImplementedError("PatchMerging: backward without the LayerNorm (norm_cfg=None) is not built")
+        x = rec["x"]
+        C = self.in_channels
+        M, N = g.shape
+        a = _a(_lib.SWIN_A_MERGE, x, stats=rec["st"], ln=(p["g"], p["b"]), n=B, c=C, h=H, w=W)
+        dw = _rows_weight_grad(g, operand_rows(a, M, 4 * C), inv)
+        grads[self.reduction.weight] = dw.view(N, 4, C).permute(0, 2, 1).reshape(N, 4 * C)
+        dn = gemm(_a(_lib.SWIN_A_ROWS, g, ldx=N), M, N, pb)
+        dx, dg, db = layernorm_backward(a, M, 4 * C, dn, dx_shape=tuple(x.shape), inv_scale=inv)
+        grads[self.norm.weight] = dg.view(4, C).t().reshape(-1)
+        grads[self.norm.bias] = db.view(4, C).t().reshape(-1)
+        return dx
 
 
 class SwinBlockSequence(nn.Module):
@@ -419,13 +624,23 @@ class SwinTransformer(nn.Module):
         FFN; a block whose rate is 0 draws nothing (mmcv DropPath returns its input)"""
         return [r for r in self.drop_path_rates if r > 0.0 for _ in range(2)]
 
-    @torch.no_grad()
-    def forward_train(self, x, drop_keep=None):
+    def forward_train(self, x, drop_keep=None, backward=False):
         """Training-mode forward: forward()'s kernels with stochastic depth (mmcv DropPath: per image keep =
-        floor(keep_prob + U[0, 1)), branch output * keep / keep_prob).  No backward: the maps come back without a
-        gradient (the shipped config detaches them).  drop_keep: [len(drop_layers()), N] of 0 / 1, one row per drawing
-        layer in drop_layers() order; None draws every mask with ONE torch.rand call on the device (mmcv's random
-        stream is not reproduced draw for draw)."""
+        floor(keep_prob + U[0, 1)), branch output * keep / keep_prob).  backward=False: no backward, the maps come back
+        without a gradient (the shipped config detaches them).  backward=True: the same launches, and the maps carry ONE
+        autograd node (_SwinBackward) whose backward runs the kernels of isf_swin_train.hip and hands fp32 gradients to
+        the backbone's parameters; the image gets none.  drop_keep: [len(drop_layers()), N] of 0 / 1, one row per
+        drawing layer in drop_layers() order; None draws every mask with ONE torch.rand call on the device (mmcv's
+        random stream is not reproduced draw for draw)."""
+        with torch.no_grad():
+            x, scales = self._train_inputs(x, drop_keep)
+            if not backward:
+                return self._run(x, scales)
+        params = [q for q in self.parameters() if q.requires_grad]
+        return list(_SwinBackward.apply(self, x.detach(), scales, *params))
+
+    def _train_inputs(self, x, drop_keep):
+        """forward_train's checks -> (x, the DropPath factors [len(drop_layers()), N] or None)"""
         assert self.training, "call .train() first (forward() is the eval-mode forward)"
         if self.precision != "f32":
             raise NotImplementedError(f"SwinTransformer.forward_train: precision {self.precision!r} is an inference "
@@ -436,7 +651,7 @@ class SwinTransformer(nn.Module):
         _lib.require_cuda(x)
         rates = self.drop_layers()
         if not rates:
-            return self._run(x, None)
+            return x, None
         N = x.shape[0]
         keep_prob = 1.0 - torch.tensor(rates, dtype=torch.float32, device=x.device)[:, None]
         if drop_keep is None:
@@ -445,28 +660,108 @@ class SwinTransformer(nn.Module):
             _lib.require_cuda(drop_keep)
             if tuple(drop_keep.shape) != (len(rates), N):
                 raise ValueError(f"drop_keep {tuple(drop_keep.shape)}: need {(len(rates), N)}")
-        return self._run(x, (drop_keep.to(torch.float32) / keep_prob).contiguous())
+        return x, (drop_keep.to(torch.float32) / keep_prob).contiguous()
 
-    def _run(self, x, scales):
-        """scales: [len(drop_layers()), N] DropPath factors (keep / keep_prob) or None"""
+    def _run(self, x, scales, tape=None):
+        """scales: [len(drop_layers()), N] DropPath factors (keep / keep_prob) or None.  tape: a dict that receives what
+        _run_backward needs (the launches are the same with and without it)."""
         _lib.require_cuda(x)
         assert x.dim() == 4, x.shape
         x = x.float().contiguous()
         N = x.shape[0]
         assert scales is None or self.precision == "f32"      # DropPath is not built for the f16 inference mode
         p = self._packed(x.device)
-        t, (H, W) = self.patch_embed.run(p["patch"], x)
+        if tape is not None:
+            tape.update(n=N, patch=[], stages=[])
+        t, (H, W) = self.patch_embed.run(p["patch"], x, None if tape is None else tape["patch"])
         outs = []
         row = 0
         for i, stage in enumerate(self.stages):
+            blocks, merge = (None, None) if tape is None else ([], [])
             for blk, bp in zip(stage.blocks, p["blocks"][i]):
                 keep = (None, None)
                 if scales is not None and blk.attn.drop_path_rate > 0.0:
                     keep = (scales[row], scales[row + 1])
                     row += 2
-                t = blk.run(bp, t, N, H, W, keep)
+                t = blk.run(bp, t, N, H, W, keep, blocks)
+            if tape is not None:
+                tape["stages"].append(dict(blocks=blocks, merge=merge, out=t, hw=(H, W)))
             if i in self.out_indices:
                 outs.append(layernorm(t, getattr(self, f"norm{i}"), out_nchw=(N, H, W)))
             if stage.downsample is not None:
-                t, (H, W) = stage.downsample.run(p["merge"][i], t, N, H, W)
+                t, (H, W) = stage.downsample.run(p["merge"][i], t, N, H, W, merge)
         return outs
+
+    def _packed_backward(self, dev):
+        """the transposed packed weights of the backward's dX = dY . W products, in the same derived-weight store as the
+        forward's: a parameter update drops both"""
+        c = _cache(self, dev)
+        if "f32_backward" not in c:
+            p = self._packed(dev)
+            with torch.no_grad():
+                c["f32_backward"] = dict(
+                    blocks=[[blk.pack_backward() for blk in st.blocks] for st in self.stages],
+                    merge=[st.downsample.pack_backward(p["merge"][i]) if st.downsample is not None else None
+                           for i, st in enumerate(self.stages)])
+        return c["f32_backward"]
+
+    @torch.no_grad()
+    def _run_backward(self, tape, gouts):
+        """gouts: the gradient (or None) of each map _run returned, NCHW -> {parameter: fp32 gradient} for the
+        parameters a gradient reaches.  The stream gradient g is carried pre-scaled by a power of two, renewed at every
+        block's entry (_lib.grad_rescale: the f16 hi / lo products want operands near 2^10, gradients are 1e-5 and
+        below); cum = [scale, 1 / scale] of g against the true gradient."""
+        dev = tape["stages"][0]["out"].device
+        p, pb = self._packed(dev), self._packed_backward(dev)
+        N = tape["n"]
+        gmaps = dict(zip([i for i in range(len(self.stages)) if i in self.out_indices], gouts))
+        grads = {}
+        cum = torch.ones(2, dtype=torch.float32, device=dev)
+        g = None
+        for i in reversed(range(len(self.stages))):
+            stage, rec = self.stages[i], tape["stages"][i]
+            H, W = rec["hw"]
+            t = rec["out"]
+            M, C = t.shape
+            if g is not None:          # from the stage above, through this stage's PatchMerging
+                g = stage.downsample.run_backward(p["merge"][i], pb["merge"][i], rec["merge"][0], g, N, H, W, cum[1:], grads)
+            go = gmaps.get(i)
+            if go is not None:
+                norm = getattr(self, f"norm{i}")
+                _lib.require_cuda(go)
+                st = row_stats(_a(_lib.SWIN_A_ROWS, t, ldx=C), M, C, norm.eps)
+                a = _a(_lib.SWIN_A_ROWS, t, ldx=C, stats=st, ln=(norm.weight.detach(), norm.bias.detach()))
+                g, grads[norm.weight], grads[norm.bias] = layernorm_backward(
+                    a, M, C, go.float().contiguous(), dy_hw=H * W, dy_scale=cum[:1], residual=g, inv_scale=cum[1:])
+            if g is None:
+                continue
+            for blk, bp, bpb, brec in reversed(list(zip(stage.blocks, p["blocks"][i], pb["blocks"][i], rec["blocks"]))):
+                g, sc = _lib.grad_rescale(g)
+                cum = cum * sc
+                g = blk.run_backward(bp, bpb, brec, g, N, H, W, cum[1:], grads)
+        if g is not None:
+            self.patch_embed.run_backward(tape["patch"][0], g, cum, grads)
+        return grads
+
+
+class _SwinBackward(torch.autograd.Function):
+    """SwinTransformer._run with a backward: one node for the whole backbone (the training step is paced by the host).
+    Inputs: the module, the image batch (no gradient), the DropPath factors, and the parameters (so that autograd routes
+    their gradients); outputs: the out_indices maps."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, mod, x, scales, *params):
+        tape = {}
+        outs = mod._run(x, scales, tape)
+        ctx.mod, ctx.tape, ctx.params = mod, tape, params
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gouts):
+        grads = ctx.mod._run_backward(ctx.tape, gouts)
+        ctx.tape = None
+        return (None, None, None) + tuple(grads.get(q) for q in ctx.params)

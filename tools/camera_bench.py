@@ -6,7 +6,7 @@
   * ISFusionDetector.simple_test (images -> boxes) against ISFusionPtsPath.simple_test on precomputed camera features
 
     python tools/camera_bench.py [--steps 10] [--warmup 3] [--points 300000]
-    python tools/camera_bench.py --train [--steps 10] [--warmup 3] [--runs 3]
+    python tools/camera_bench.py --train [--backward] [--steps 10] [--warmup 3] [--runs 3]
     python tools/camera_bench.py --precision both [--steps 10] [--warmup 3] [--runs 3]
 
 --precision f32 (default) is the run above.  f16 / both: the backbone's precision modes (SwinTransformer.set_precision)
@@ -18,6 +18,8 @@ restatement at the bench size.
 + GeneralizedLSSFPN.forward_train + the neck's backward from a gradient on the stride-16 output (what Point-to-Grid
 sends back), against the float32 stock-torch composition of tests/camera_train_common.py (same masks, autograd) on the
 same GPU, each measured --runs times; plus the single kernels of the lateral step's backward at the shipped level-1 size.
+--train --backward: the step with the backbone's backward as well (ISFusionDetector.camera_backward), against stock-torch
+autograd over backbone and neck, --runs times each, and the peak memory each step adds.
 
 Prints one JSON line per measurement (ms per call, mean over --steps)."""
 import argparse
@@ -80,6 +82,8 @@ def train_bench(a, dev):
         outs = CT.neck_forward_train(nd, feats)
         outs[1].backward(up)
 
+    if a.backward:
+        return train_backward_bench(a, bb, nk, flat, keep, up, sd, nd)
     for run in range(a.runs):
         ms = timed(hip_step, a.steps, a.warmup)
         print(json.dumps(dict(what="camera_train_step", impl="hip", images=B * 6, hw=[H, W], run=run, ms=round(ms, 3))))
@@ -116,6 +120,61 @@ def train_bench(a, dev):
                      ("rows_weight_grad coarse [R 4752, N 256, K 768]", lambda: gl.rows_weight_grad(g2, coarse, sc[1:])),
                      ("torch fp32 g^T x fine (rows)", lambda: g.t().matmul(fine.permute(0, 2, 3, 1).reshape(-1, 384)))):
         print(json.dumps(dict(what=what, ms=round(timed(fn, a.steps * 5, a.warmup), 4))))
+
+
+def train_backward_bench(a, bb, nk, flat, keep, up, sd, nd):
+    """--train --backward: backbone forward with DropPath + neck forward + both backwards from a gradient on the stride-16
+    map, next to float32 stock-torch autograd over the same modules and masks; and the peak memory either step adds to
+    what is resident before it"""
+    import camera_train_common as CT
+    n, (H, W) = flat.shape[0], flat.shape[-2:]
+
+    def clear(params):
+        for p in params:
+            p.grad = None
+
+    def hip_step():
+        clear(list(bb.parameters()) + list(nk.parameters()))
+        outs = nk.forward_train(bb.forward_train(flat, drop_keep=keep, backward=True), input_grads=True)
+        outs[1].backward(up)
+
+    bd = CT.leaf_params(sd, torch.float32, flat.device)
+
+    def torch_step():
+        clear(list(bd.values()) + list(nd.values()))
+        outs = CT.neck_forward_train(nd, CT.swin_forward_train(bd, flat, keep))
+        outs[1].backward(up)
+
+    if a.profile_backward:
+        for _ in range(a.warmup + a.steps):
+            hip_step()
+        torch.cuda.synchronize()
+        return
+    for run in range(a.runs):
+        for impl, fn in (("hip", hip_step), ("torch_fp32", torch_step)):
+            ms = timed(fn, a.steps, a.warmup)
+            print(json.dumps(dict(what="camera_train_step_backward", impl=impl, images=n, hw=[H, W], run=run,
+                                  ms=round(ms, 3))))
+    for impl, fn in (("hip", hip_step), ("torch_fp32", torch_step)):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        print(json.dumps(dict(what="camera_train_step_backward_peak_memory", impl=impl,
+                              mib_over_resident=round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1))))
+
+    def hip_forward_only():
+        outs = nk.forward_train(bb.forward_train(flat, drop_keep=keep))
+        outs[1].backward(up)
+
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    hip_forward_only()
+    torch.cuda.synchronize()
+    print(json.dumps(dict(what="camera_train_step_peak_memory", impl="hip", note="backward off",
+                          mib_over_resident=round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1))))
 
 
 def build_detector(dev):
@@ -171,6 +230,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--points", type=int, default=300000)
     ap.add_argument("--train", action="store_true", help="time one camera training step (forward_train + neck backward)")
+    ap.add_argument("--backward", action="store_true",
+                    help="with --train: the step with the backbone's backward (forward_train(backward=True), the neck "
+                         "with input_grads=True) next to stock-torch autograd over backbone and neck")
+    ap.add_argument("--profile-backward", action="store_true",
+                    help="with --train --backward: run the HIP step --warmup + --steps times and exit (the process to "
+                         "put under a kernel trace)")
     ap.add_argument("--runs", type=int, default=3, help="--train / --precision f16|both: repetitions of the measurement")
     ap.add_argument("--precision", choices=("f32", "f16", "both"), default="f32",
                     help="f16 / both: time the backbone's precision modes in one process (default: the f32 run)")

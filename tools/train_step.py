@@ -2,7 +2,8 @@
 all-reduce over xGMI on the GRADIENTS only -- the forward has no collective):
 
     python tools/train_step.py --gpus N [--batch 2] [--points 60000] [--steps 3] [--bf16] [--autocast]
-                               [--optimizer sgd|config] [--max-iters M] [--gt-paste] [--camera] [--deterministic]
+                               [--optimizer sgd|config] [--max-iters M] [--gt-paste] [--camera [--camera-backward]]
+                               [--deterministic]
 
 starts N ranks by itself (isfusion_amd.launch.self_launch: a re-exec under torch.distributed.run on 127.0.0.1; fewer
 than N visible GPUs is an error) -- the reference's tools/run-nus.sh:11-13; under a launcher it runs as the rank it is:
@@ -25,7 +26,9 @@ training-mode forward (stochastic depth, no backward: detach=True), the LSS-FPN 
 point-cloud path; --loss detection goes through ISFusionDetector.forward_train.  The backbone and the neck's level-0
 convs receive no gradient (only the stride-16 map reaches Point-to-Grid), so --camera FREEZES those parameters
 (requires_grad False) rather than asking DistributedDataParallel for find_unused_parameters: no per-step graph search,
-and the optimizer skips them.  --deterministic runs every step under isfusion_amd.set_deterministic(True) (exact,
+and the optimizer skips them.  --camera-backward (with --camera) builds the detector with detach=False and
+camera_backward = True instead: the backbone's backward runs (swin.py, isf_swin_train.hip) and only the norm of its
+first output map and the neck's level-0 convs stay frozen.  --deterministic runs every step under isfusion_amd.set_deterministic(True) (exact,
 order-independent accumulation in the four scattering kernels; any --loss / --camera / --optimizer / --gt-paste): the steps
 are then bit-identical run to run.  With more than one rank the mode also covers the sums that cross ranks
 (isfusion_amd.collectives): the forward runs under ddp.no_sync() and exact_all_reduce_gradients sums the local gradients
@@ -152,6 +155,9 @@ def main():
                     help="train ISFusionDetector from images (Swin forward_train + LSS-FPN forward_train / backward) instead "
                          "of precomputed camera features; the parameters that get no gradient -- img_backbone.* and the "
                          "neck's level-0 convs -- are frozen (requires_grad False), not left to find_unused_parameters")
+    ap.add_argument("--camera-backward", action="store_true",
+                    help="with --camera: detach=False and ISFusionDetector.camera_backward = True -- the Swin backbone's "
+                         "backward runs too (the reference class's default; the shipped optimizer's lr_mult 0.1 group)")
     ap.add_argument("--deterministic", action="store_true",
                     help="isfusion_amd.set_deterministic(True): the isf_*_det entries (fixed-point accumulation) in "
                          "DynamicScatter, Point-to-Grid backward and both MSDA backwards")
@@ -159,6 +165,8 @@ def main():
                     help="i,j,k: rank r takes the frames, scenes, images and seeds that rank order[r] takes by default "
                          "(the identity); with --deterministic the step's result does not depend on it")
     a = ap.parse_args()
+    if a.camera_backward and not a.camera:
+        ap.error("--camera-backward switches the camera branch's backward on: it needs --camera")
     if a.gt_paste and a.loss != "detection":
         ap.error("--gt-paste pastes ground truth: it needs --loss detection")
     import isfusion_amd
@@ -193,14 +201,18 @@ def main():
                               drop_path_rate=0.2, patch_norm=True, out_indices=[1, 2, 3], with_cp=False,
                               convert_weights=False),
             img_neck=dict(type="GeneralizedLSSFPN", in_channels=[192, 384, 768], out_channels=256, start_level=0,
-                          num_outs=3), detach=True).train()
+                          num_outs=3), detach=not a.camera_backward).train()
+        net.camera_backward = a.camera_backward
         g = torch.Generator().manual_seed(4100)
         with torch.no_grad():                                        # O(1) activations through the 12 blocks
             for name, p in list(net.img_backbone.named_parameters()) + list(net.img_neck.named_parameters()):
                 if p.dim() > 1 and not name.endswith("relative_position_bias_table"):
                     p.copy_(torch.randn(p.shape, generator=g) * (p[0].numel() ** -0.5))
+        # --camera-backward: the backbone trains too; only the norm of its first output map stays without a gradient
+        no_grad = ("img_backbone.norm1." if a.camera_backward else "img_backbone.", "img_neck.lateral_convs.0.",
+                   "img_neck.fpn_convs.0.")
         for name, p in net.named_parameters():
-            if name.startswith(("img_backbone.", "img_neck.lateral_convs.0.", "img_neck.fpn_convs.0.")):
+            if name.startswith(no_grad):
                 p.requires_grad_(False)                              # no gradient reaches them (module docstring)
     else:
         net = ISFusionPtsPath().train()
@@ -324,7 +336,7 @@ def main():
             dist.all_gather_object(every, digest["param_digest"])
             digest["replicas_agree"] = len(set(every)) == 1
     if rank == 0:
-        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss, "camera": a.camera, "deterministic": a.deterministic,
+        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss, "camera": a.camera, "camera_backward": a.camera_backward, "deterministic": a.deterministic,
                           "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses],
                           "optimizer": a.optimizer, **({"grad_norm": [round(n, 6) for n in norms]} if recipe else {}),
                           **({"gt_paste_objects": pasted} if paste is not None else {}),
