@@ -1471,6 +1471,48 @@ int isf_swin_window_attention_backward(const float* qkv, const float* qkv_bias, 
                                        float* drel_bias, float* dtable, int table_rows, float* dqkv_bias_pad,
                                        isf_stream_t stream);
 
+/* Mixed-precision training of the Swin-T backbone (isf_swin.hip, isf_swin_train_f16.hip) ----------------------
+ * SwinTransformer.set_precision("mixed"): what the reference trains under torch.autocast(float16) -- half products with
+ * fp32 accumulation; fp32 master weights, residual stream, statistics, softmax and parameter gradients; the forward keeps
+ * the f16 qkv rows and the f16 attention output.  The forward is the f16 inference mode's plus the entry below; dX = dY . W
+ * is isf_swin_gemm_f16 on isf_pack_linear_f16 of the transposed weight; the other backward entries above stay fp32.
+ * Gradient rows arrive pre-scaled by a power of two with their largest entry in [2^9, 2^10) (isf_grad_rescale).
+ * isf_swin_gemm_f16_rowscale replaces the half nn.Linear followed by DropPath and the identity (WindowMSA.proj with
+ *   swin.py:251, the second Linear of mmcv FFN with its DropPath): isf_swin_gemm_f16 with isf_swin_gemm_rowscale's factor,
+ *     y = act((A . W^T) * scale + shift) * row_scale[r / rows_per_sample] + residual.
+ *   Built for the ROWS loader on f16 A rows (a_is_f16 != 0) without the LayerNorm prologue and fp32 y (y_is_f16 == 0,
+ *   y_hw == 0); any other form and a NULL row_scale are refused before a launch.  A factor 1 changes nothing by a bit, a
+ *   factor 0 leaves the residual row exactly.
+ * isf_rows_weight_grad_f16 replaces autograd's weight gradient of a half nn.Linear (swin.py:88 and :115, mmcv FFN,
+ *   PatchMerging.reduction, PatchEmbed.projection as im2col rows): isf_rows_weight_grad with ONE matrix instruction per
+ *   product.  g fp32 rows [num_rows, out_features] and x rows [num_rows, ldx] -- fp32, or _Float16 when x_is_f16 != 0 (ldx
+ *   in elements of the row type) -- are rounded to f16 in the kernel (nearest even, saturating at +-65504); products are
+ *   exact in fp32, accumulation is fp32.  Row-major x only.  workspace, num_chunks, inv_scale, dw / ldw and the
+ *   run-to-run bit identity as isf_rows_weight_grad.
+ * isf_swin_window_attention_backward_f16 differentiates isf_swin_window_attention_f16 (ShiftWindowMSA + WindowMSA after
+ *   the half qkv Linear, swin.py:79-117 and :178-253) on the matrix cores: qkv is _Float16 rows [batch*height*width,
+ *   3 channels] as the forward stored them (a padded cell's q / k / v = the f16-rounded qkv_bias), every other argument,
+ *   output, scale and the workspace (isf_swin_window_attention_backward_groups) as isf_swin_window_attention_backward.
+ *   Scores, softmax, dP - rowsum(P dP), every accumulation and the bias gradient (summed from the unrounded dS) are
+ *   fp32; only P, dS and dO are rounded to f16, as operands of the next product.  dO is read as dout * 2^-6 and every
+ *   output multiplied by 2^6 (exact): for |dout| < 2^10 and |v| <= 32 (value third of qkv and of qkv_bias) neither dO
+ *   nor dS reaches f16's range (|dS 2^-6| < 2^15), and beyond it the operand stores saturate at +-65504 instead of
+ *   producing inf.  Entries with |dS 2^-6| < 2^-14 fall into f16's subnormals (absolute error <= 2^-19 in dout's
+ *   scale).  Bit-identical run to run. */
+int isf_swin_gemm_f16_rowscale(const isf_swin_a* a, int a_is_f16, int num_rows, int k, const void* packed_weight_f16,
+                               int out_features, const float* scale, const float* shift, int activation,
+                               const float* residual, const float* row_scale, int rows_per_sample, void* y, int y_is_f16,
+                               int ldy, int y_hw, isf_stream_t stream);
+int isf_rows_weight_grad_f16(const float* g, const void* x, int x_is_f16, int ldx, int num_rows, int out_features, int k,
+                             const float* inv_scale, float* workspace, int num_chunks, float* dw, int ldw,
+                             isf_stream_t stream);
+int isf_swin_window_attention_backward_f16(const void* qkv, const float* qkv_bias, const float* rel_bias,
+                                           const int64_t* rel_index, const float* dout, int batch, int height, int width,
+                                           int channels, int heads, int window, int shift, float scale,
+                                           const float* inv_scale, float* workspace, int num_groups, float* dqkv,
+                                           float* drel_bias, float* dtable, int table_rows, float* dqkv_bias_pad,
+                                           isf_stream_t stream);
+
 /* Fused AdamW with global-norm gradient clipping (isf_optim.hip) ---------------------------------------------
  * isf_optim_grad_sumsq + isf_optim_adamw replace, together, mmcv OptimizerHook.clip_grads (mmcv/runner/hooks/
  *   optimizer.py: torch.nn.utils.clip_grad_norm_ over every gradient, max_norm, norm_type 2) followed by the step of

@@ -431,6 +431,14 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "isf_swin_window_attention_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                               c_int, ctypes.c_float, c_void_p, c_void_p]),
+    "isf_swin_gemm_f16_rowscale": (c_int, [ctypes.POINTER(SwinA), c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "isf_rows_weight_grad_f16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_int, c_void_p]),
+    "isf_swin_window_attention_backward_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                                       c_int, c_int, c_int, c_int, c_int, ctypes.c_float, c_void_p,
+                                                       c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                                       c_void_p]),
     "isf_optim_grad_sumsq": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "isf_optim_adamw": (c_int, [c_void_p, c_void_p, c_int, ctypes.POINTER(AdamWHp), c_int, c_void_p, c_void_p,
                                 ctypes.c_float, c_void_p, c_int, c_void_p]),

@@ -479,6 +479,14 @@ int f32_to_split_impl(const float* x, size_t n_elems, void* xs, hipStream_t st);
 int split_to_f32_impl(const void* xs, size_t n_elems, float* x, hipStream_t st);
 int f32_to_half_impl(const float* x, size_t n_elems, void* xh, hipStream_t st);   // [N][C] f16 rows (f16 storage mode)
 int half_to_f32_impl(const void* xh, size_t n_elems, float* x, hipStream_t st);
+// isf_swin_train.hip: what the backbone's backward shares with its mixed-precision entries (isf_swin_train_f16.hip) --
+// the row chunking of dW = dY^T . X and the (image, window) ranges of the attention backward, and their second passes
+int wgrad_rows_per_chunk(int R, int N, int K);
+int rows_wgrad_reduce(const float* ws, int chunks, int N, int K, const float* inv_scale, float* dw, int ldw, hipStream_t st);
+int attn_bwd_items_per_group(int batch, int height, int width, int heads);
+int swin_attn_bwd_finish(const float* part_bias, const float* part_pad, int groups, int heads, int C, float* drel,
+                         float* pad, const int64_t* rel_index, const float* inv_scale, float* dtable, int table_rows,
+                         hipStream_t st);
 // isf_encoder.hip
 // fmt: 0 = fp32 rows, 1 = split rows, 2 = f16 rows
 int sparse_to_dense_bev_impl(Arena& a, const void* feats, int fmt, const int32_t* indices, int n, int C,

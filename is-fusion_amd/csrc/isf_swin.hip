@@ -23,7 +23,7 @@
 //                        (isf_pack_linear_f16); accumulation and the epilogue stay fp32; the output rows are fp32 (into
 //                        the residual stream) or f16 (qkv, the FFN hidden).  Every store to an f16 tensor saturates at
 //                        +-65504 instead of producing inf.  Window attention of this mode: isf_swin_f16.hip.
-//                        All three GEMM entries (swin.gemm in Python) end in swin_gemm_launch; swin_gemm_forms is the one
+//                        All four GEMM entries (swin.gemm, swin.gemm_f16_rowscale) end in swin_gemm_launch; swin_gemm_forms is the one
 //                        statement of which (loader, LayerNorm, row scale, precision, f16 output) forms are built.
 //   isf_swin_row_stats   mean / rstd of the loader's rows (one wave per row, two passes in fp32)
 //   isf_swin_layernorm   LayerNorm of token rows, stored as rows or NCHW (patch_norm, the out_indices norms)
@@ -475,7 +475,8 @@ static int swin_check_a(const isf_swin_a* a, int M, int K, bool gemm) {
 // The swin_gemm_kernel instantiations that are built, one row each: swin_gemm_launch looks the call's form up here, and a
 // form without a row is ISF_ERR_UNSUPPORTED.  Default mode (X3): ROWS plain / LayerNorm / row scale, MERGE plain /
 // LayerNorm, PATCH, UPCAT.  f16 inference mode: ROWS {fp32 rows plain, fp32 rows LayerNorm, f16 rows} x {fp32, f16 out},
-// MERGE plain / LayerNorm, PATCH -- the forms SwinTransformer's forward is made of (no DropPath, no UPCAT).
+// MERGE plain / LayerNorm, PATCH -- the forms SwinTransformer's forward is made of (no DropPath, no UPCAT).  Mixed-precision
+// training (isf_swin_gemm_f16_rowscale): ROWS f16 rows with the row scale -> fp32, the proj / fc2 epilogue with DropPath.
 // The kernels stand in the code object in row order.
 using SwinGemmKernel = void (*)(isf_swin_a, int, int, const uint4*, const float*, int, SwinEpi, float*);
 struct SwinGemmForm { int mode; bool ln, rs; int prec; bool y16; SwinGemmKernel kernel; };
@@ -498,6 +499,7 @@ static const SwinGemmForm swin_gemm_forms[] = {
     swin_gemm_form<ISF_SWIN_A_MERGE, false>(),
     swin_gemm_form<ISF_SWIN_A_PATCH, false>(),
     swin_gemm_form<ISF_SWIN_A_UPCAT, false>(),
+    swin_gemm_form<ISF_SWIN_A_ROWS, false, true, SWIN_PREC_F16_ROWS, false>(),
 };
 
 }  // namespace isf
@@ -561,6 +563,16 @@ int isf_swin_gemm_f16(const isf_swin_a* a, int a_is_f16, int num_rows, int k, co
                       void* y, int y_is_f16, int ldy, int y_hw, isf_stream_t stream) {
   return swin_gemm_launch(a, num_rows, k, packed_weight_f16, out_features, scale, shift, activation, residual, nullptr, 0,
                           reinterpret_cast<float*>(y), ldy, y_hw, stream,
+                          a_is_f16 ? isf::SWIN_PREC_F16_ROWS : isf::SWIN_PREC_F16, y_is_f16 != 0);
+}
+
+int isf_swin_gemm_f16_rowscale(const isf_swin_a* a, int a_is_f16, int num_rows, int k, const void* packed_weight_f16,
+                               int out_features, const float* scale, const float* shift, int activation,
+                               const float* residual, const float* row_scale, int rows_per_sample, void* y, int y_is_f16,
+                               int ldy, int y_hw, isf_stream_t stream) {
+  ISF_REQUIRE(row_scale, ISF_ERR_ARG, "swin_gemm_f16_rowscale: null row_scale");
+  return swin_gemm_launch(a, num_rows, k, packed_weight_f16, out_features, scale, shift, activation, residual, row_scale,
+                          rows_per_sample, reinterpret_cast<float*>(y), ldy, y_hw, stream,
                           a_is_f16 ? isf::SWIN_PREC_F16_ROWS : isf::SWIN_PREC_F16, y_is_f16 != 0);
 }
 

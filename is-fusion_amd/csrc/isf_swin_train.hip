@@ -40,7 +40,7 @@ __device__ __forceinline__ void wg_split8(const wf8 v, wh8& hi, wh8& lo) {
   lo = __builtin_convertvector(r, wh8);
 }
 
-static int wgrad_rows_per_chunk(int R, int N, int K) {
+int wgrad_rows_per_chunk(int R, int N, int K) {
   const int tiles = ceil_div(N, WG_TN) * ceil_div(K, WG_TK);
   const int steps = ceil_div(R, WG_STEP);
   int chunks = ceil_div(WG_TARGET, tiles);
@@ -442,7 +442,7 @@ __global__ __launch_bounds__(256) void swin_scale_rows_kernel(const float* __res
 constexpr int AB_WS = 7, AB_T = 49, AB_HD = 32;
 constexpr int AB_TARGET = 1024;   // workgroups (groups x heads) a launch aims at
 
-static int attn_bwd_items_per_group(int batch, int height, int width, int heads) {
+int attn_bwd_items_per_group(int batch, int height, int width, int heads) {
   const int total = ceil_div(height, AB_WS) * ceil_div(width, AB_WS) * batch;
   int groups = AB_TARGET / heads;
   if (groups < 1) groups = 1;
@@ -666,6 +666,29 @@ static int rows_chunk(int M, int min_rows, int max_chunks) {
   return ceil_div(M, chunks);
 }
 
+// the second passes, shared with the mixed-precision entries of isf_swin_train_f16.hip (same workspace layouts)
+int rows_wgrad_reduce(const float* ws, int chunks, int N, int K, const float* inv_scale, float* dw, int ldw,
+                      hipStream_t st) {
+  hipLaunchKernelGGL(rows_wgrad_reduce_kernel, dim3(ceil_div((long long)N * K, 256)), dim3(256), 0, st, ws, chunks, N, K,
+                     inv_scale, dw, ldw);
+  ISF_LAUNCH_CHECK();
+  return ISF_OK;
+}
+
+int swin_attn_bwd_finish(const float* part_bias, const float* part_pad, int groups, int heads, int C, float* drel,
+                         float* pad, const int64_t* rel_index, const float* inv_scale, float* dtable, int table_rows,
+                         hipStream_t st) {
+  hipLaunchKernelGGL(swin_attn_bwd_reduce_kernel, dim3(ceil_div(heads * AB_T * AB_T + 3 * C, 256)), dim3(256), 0, st,
+                     part_bias, part_pad, groups, heads, C, drel, pad);
+  ISF_LAUNCH_CHECK();
+  if (dtable) {
+    hipLaunchKernelGGL(swin_attn_table_grad_kernel, dim3(table_rows, heads), dim3(256), 0, st, drel,
+                       reinterpret_cast<const long long*>(rel_index), heads, inv_scale, dtable);
+    ISF_LAUNCH_CHECK();
+  }
+  return ISF_OK;
+}
+
 }  // namespace isf
 
 extern "C" {
@@ -698,10 +721,7 @@ int isf_rows_weight_grad(const float* g, const float* x, int ldx, int x_hw, int 
     hipLaunchKernelGGL(rows_wgrad_kernel<false>, grid, block, 0, st, g, x, ldx, 0, num_rows, out_features, k, rpc,
                        workspace);
   ISF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rows_wgrad_reduce_kernel, dim3(ceil_div((long long)out_features * k, 256)), block, 0, st, workspace,
-                     num_chunks, out_features, k, inv_scale, dw, ldw);
-  ISF_LAUNCH_CHECK();
-  return ISF_OK;
+  return rows_wgrad_reduce(workspace, num_chunks, out_features, k, inv_scale, dw, ldw, st);
 }
 
 int isf_upsample_rows_adjoint(const float* g, int batch, int height, int width, int channels, int height2, int width2,
@@ -897,15 +917,8 @@ int isf_swin_window_attention_backward(const float* qkv, const float* qkv_bias, 
   hipLaunchKernelGGL(swin_window_attn_bwd_kernel, dim3(num_groups, heads), dim3(64), 0, st, qkv, qkv_bias, rel_bias, dout,
                      batch, height, width, channels, heads, shift, scale, ipg, dqkv, part_bias, part_pad);
   ISF_LAUNCH_CHECK();
-  hipLaunchKernelGGL(swin_attn_bwd_reduce_kernel, dim3(ceil_div(heads * AB_T * AB_T + 3 * channels, 256)), dim3(256), 0, st,
-                     part_bias, part_pad, num_groups, heads, channels, drel_bias, dqkv_bias_pad);
-  ISF_LAUNCH_CHECK();
-  if (dtable) {
-    hipLaunchKernelGGL(swin_attn_table_grad_kernel, dim3(table_rows, heads), dim3(256), 0, st, drel_bias,
-                       reinterpret_cast<const long long*>(rel_index), heads, inv_scale, dtable);
-    ISF_LAUNCH_CHECK();
-  }
-  return ISF_OK;
+  return swin_attn_bwd_finish(part_bias, part_pad, num_groups, heads, channels, drel_bias, dqkv_bias_pad, rel_index,
+                              inv_scale, dtable, table_rows, st);
 }
 
 }  // extern "C"

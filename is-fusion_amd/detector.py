@@ -456,8 +456,9 @@ class ISFusionDetector(ISFusionPtsPath):
 
     @property
     def camera_precision(self):
-        """"f32" (default) or "f16": the precision mode of the camera backbone (SwinTransformer.set_precision); the neck
-        takes the backbone's fp32 maps in either mode"""
+        """"f32" (default), "f16" (inference only) or "mixed" (mixed-precision training; the f16 forward in eval()): the
+        precision mode of the camera backbone (SwinTransformer.set_precision).  The neck takes the backbone's fp32 maps
+        in every mode; camera_backward and detach mean the same in "mixed" as in "f32"."""
         return self.img_backbone.precision
 
     @camera_precision.setter

@@ -25,6 +25,13 @@ out_indices maps are the same fp32 NCHW tensors.  Both modes run the one schedul
 ``window_attention``: the precision is carried by the packed weight (PackedLinear / PackedLinearF16) and by the dtype of
 the qkv rows, nothing else.  Each mode's packed weights live under its name in the same per-module cache.
 ``precision`` is a plain attribute: no parameter, no buffer, no constructor argument.
+
+``set_precision("mixed")`` is mixed-precision training: in eval() it is the f16 mode bit for bit (the same packed
+weights), in train() ``forward_train`` runs the f16 block with the DropPath factor in the proj / fc2 epilogue
+(isf_swin_gemm_f16_rowscale) and keeps, per block, the fp32 rows x and y, both LayerNorms' statistics and the f16 qkv
+rows and attention output.  The backward is the f32 mode's schedule with single-pass products: dX on the f16 pack of the
+transposed weight, dW by isf_rows_weight_grad_f16, the window attention by isf_swin_window_attention_backward_f16
+(isf_swin_train_f16.hip); gradient rows, LayerNorm / GELU backward, column sums and every parameter gradient stay fp32.
 """
 import ctypes
 
@@ -99,6 +106,29 @@ def gemm(a, rows, k, pl, *, scale=None, shift=None, act=ACT_NONE, residual=None,
     else:
         _lib.check(lib.isf_swin_gemm(ctypes.byref(s), *ops, _lib.ptr(y), *lay), "isf_swin_gemm")
     return y
+
+
+def gemm_f16_rowscale(a, rows, k, pl, row_scale, *, shift=None, residual=None):
+    """isf_swin_gemm_f16_rowscale: (A W^T + shift) * row_scale[sample of the row] + residual -> fp32 rows [rows, N], for
+    f16 A rows and a PackedLinearF16 (the proj / fc2 epilogue of mixed-precision training, DropPath)"""
+    s, keep = a
+    x, N = keep[0], pl.out_features
+    assert isinstance(pl, PackedLinearF16) and x.dtype == torch.float16
+    assert row_scale.dtype == torch.float32 and row_scale.is_contiguous() and rows % row_scale.numel() == 0
+    assert residual is None or (residual.dtype == torch.float32 and residual.is_contiguous()
+                                and tuple(residual.shape) == (rows, N))
+    y = torch.empty((rows, N), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().isf_swin_gemm_f16_rowscale(
+        ctypes.byref(s), 1, rows, k, _lib.ptr(pl.packed), N, None, _lib.ptr(shift), ACT_NONE, _lib.ptr(residual),
+        _lib.ptr(row_scale), rows // row_scale.numel(), _lib.ptr(y), 0, N, 0, _lib.stream()), "isf_swin_gemm_f16_rowscale")
+    return y
+
+
+def _branch_out(a, rows, k, pl, shift, residual, row_scale):
+    """the Linear that closes a block's branch: + bias, DropPath factor (or None), + identity"""
+    if row_scale is not None and isinstance(pl, PackedLinearF16):
+        return gemm_f16_rowscale(a, rows, k, pl, row_scale, shift=shift, residual=residual)
+    return gemm(a, rows, k, pl, shift=shift, residual=residual, row_scale=row_scale)
 
 
 def row_stats(a, rows, k, eps):
@@ -206,32 +236,61 @@ def window_attention_backward(qkv, qkv_bias, rel_bias, dout, B, H, W, C, heads, 
                               table_rows=0, inv_scale=None):
     """isf_swin_window_attention_backward: gradient rows dout [B*H*W, C] of window_attention's output ->
     (dqkv [B*H*W, 3C], drel_bias [heads, 49, 49], dtable [table_rows, heads] * inv_scale or None (without rel_index),
-    the padded cells' share of the qkv-bias gradient [3C])"""
+    the padded cells' share of the qkv-bias gradient [3C]), all fp32.  f16 qkv rows (the f16 forward's) go to
+    isf_swin_window_attention_backward_f16."""
     _lib.require_cuda(qkv, dout)
     M = B * H * W
-    assert qkv.dtype == torch.float32 and qkv.is_contiguous() and tuple(qkv.shape) == (M, 3 * C)
+    entry = {torch.float32: "isf_swin_window_attention_backward",
+             torch.float16: "isf_swin_window_attention_backward_f16"}[qkv.dtype]
+    assert qkv.is_contiguous() and tuple(qkv.shape) == (M, 3 * C)
     assert dout.dtype == torch.float32 and dout.is_contiguous() and tuple(dout.shape) == (M, C)
     dev = qkv.device
     lib = _lib.load()
     groups = lib.isf_swin_window_attention_backward_groups(B, H, W, heads)
     n = window * window
     ws = torch.empty(groups * heads * (n * n + 64), dtype=torch.float32, device=dev)
-    dqkv = torch.empty_like(qkv)
+    dqkv = torch.empty((M, 3 * C), dtype=torch.float32, device=dev)
     drel = torch.empty((heads, n, n), dtype=torch.float32, device=dev)
     dtable = torch.empty((table_rows, heads), dtype=torch.float32, device=dev) if rel_index is not None else None
     pad = torch.empty(3 * C, dtype=torch.float32, device=dev)
     if rel_index is not None:
         assert rel_index.dtype == torch.int64 and rel_index.is_contiguous() and rel_index.numel() == n * n
-    _lib.check(lib.isf_swin_window_attention_backward(
+    _lib.check(getattr(lib, entry)(
         _lib.ptr(qkv), _lib.ptr(qkv_bias), _lib.ptr(rel_bias), _lib.ptr(rel_index), _lib.ptr(dout), B, H, W, C, heads,
         window, shift, float(scale), _lib.ptr(inv_scale), _lib.ptr(ws), groups, _lib.ptr(dqkv), _lib.ptr(drel),
-        _lib.ptr(dtable), table_rows, _lib.ptr(pad), _lib.stream()), "isf_swin_window_attention_backward")
+        _lib.ptr(dtable), table_rows, _lib.ptr(pad), _lib.stream()), entry)
     return dqkv, drel, dtable, pad
 
 
-def _rows_weight_grad(g, x, inv_scale):
+def _rows_weight_grad(g, x, inv_scale, f16=False):
+    if f16:
+        return rows_weight_grad_f16(g, x, inv_scale)
     from .generalized_lss import rows_weight_grad       # (generalized_lss imports this module)
     return rows_weight_grad(g, x, inv_scale)
+
+
+def rows_weight_grad_f16(g, x, inv_scale=None):
+    """isf_rows_weight_grad_f16: dW [N, K] = inv_scale * g^T x with single-pass products, for fp32 gradient rows g [R, N]
+    and token rows x [R, K], fp32 or f16 (both rounded to f16 in the kernel; fp32 accumulation)"""
+    _lib.require_cuda(g, x)
+    assert g.dtype == torch.float32 and x.dtype in (torch.float32, torch.float16) and g.is_contiguous()
+    assert x.is_contiguous() and x.dim() == 2 and x.shape[0] == g.shape[0]
+    (R, N), K = g.shape, x.shape[1]
+    lib = _lib.load()
+    chunks = lib.isf_rows_weight_grad_chunks(R, N, K)
+    ws = torch.empty((chunks, N, K), dtype=torch.float32, device=g.device)
+    out = torch.empty((N, K), dtype=torch.float32, device=g.device)
+    _lib.check(lib.isf_rows_weight_grad_f16(_lib.ptr(g), _lib.ptr(x), int(x.dtype == torch.float16), K, R, N, K,
+                                            _lib.ptr(inv_scale), _lib.ptr(ws), chunks, _lib.ptr(out), K, _lib.stream()),
+               "isf_rows_weight_grad_f16")
+    return out
+
+
+def _pack_transposed(weight, linear):
+    """W [out, in] packed for dX = dY . W: PackedLinear packs the transpose itself, PackedLinearF16 takes W^T"""
+    if linear is PackedLinearF16:
+        return PackedLinearF16(weight.detach().float().t().contiguous())
+    return linear(weight, transposed=True)
 
 
 def _ln_only(norm_cfg):
@@ -329,20 +388,20 @@ class SwinBlock(nn.Module):
                     proj=linear(m.proj.weight), proj_b=m.proj.bias.detach(), rel=m.relative_bias(),
                     fc1=linear(l1.weight), fc1_b=l1.bias.detach(), fc2=linear(l2.weight), fc2_b=l2.bias.detach())
 
-    def pack_backward(self):
-        """the transposed packed weights of dX = dY . W, one per Linear"""
+    def pack_backward(self, linear=PackedLinear):
+        """the transposed packed weights of dX = dY . W, one per Linear; linear as in pack()"""
         m = self.attn.w_msa
         l1, l2 = self.ffn.layers[0][0], self.ffn.layers[1]
-        return dict(qkv=PackedLinear(m.qkv.weight, transposed=True), proj=PackedLinear(m.proj.weight, transposed=True),
-                    fc1=PackedLinear(l1.weight, transposed=True), fc2=PackedLinear(l2.weight, transposed=True))
+        return {name: _pack_transposed(w, linear)
+                for name, w in (("qkv", m.qkv.weight), ("proj", m.proj.weight), ("fc1", l1.weight), ("fc2", l2.weight))}
 
     def run(self, p, x, B, H, W, keep=(None, None), tape=None):
         """x: token rows [B*H*W, C] -> the block's output rows; x and the result are the fp32 residual rows.  With the
         f16 pack (pack(PackedLinearF16)) qkv, the attention output and the FFN hidden are f16 rows.  keep: per-image
         DropPath factors [B] (keep / keep_prob) of the attention and the FFN branch, or None: the branch output is
         multiplied by them after window reverse / un-shift and before the identity is added (swin.py:251, mmcv FFN);
-        gemm refuses them with the f16 pack.  tape: a list that receives what run_backward needs (the same launches
-        either way)."""
+        with the f16 pack they go through gemm_f16_rowscale (mixed-precision training).  tape: a list that receives what
+        run_backward needs (the same launches either way)."""
         M, C = x.shape
         m = self.attn.w_msa
         h16 = isinstance(p["qkv"], PackedLinearF16)
@@ -352,7 +411,7 @@ class SwinBlock(nn.Module):
         att = window_attention(qkv, p["qkv_b"], p["rel"], B, H, W, C, m.num_heads, self.attn.window_size,
                                self.attn.shift_size, m.scale)
         rec = None if tape is None else dict(x=x, st1=st, qkv=qkv, att=att, keep=keep)
-        x = gemm(_a(_lib.SWIN_A_ROWS, att, ldx=C), M, C, p["proj"], shift=p["proj_b"], residual=x, row_scale=keep[0])
+        x = _branch_out(_a(_lib.SWIN_A_ROWS, att, ldx=C), M, C, p["proj"], p["proj_b"], x, keep[0])
         ln2 = (self.norm2.weight.detach(), self.norm2.bias.detach())
         st = row_stats(_a(_lib.SWIN_A_ROWS, x, ldx=C), M, C, self.norm2.eps)
         F = self.ffn.feedforward_channels
@@ -361,15 +420,18 @@ class SwinBlock(nn.Module):
         if tape is not None:
             rec.update(y=x, st2=st)
             tape.append(rec)
-        return gemm(_a(_lib.SWIN_A_ROWS, h, ldx=F), M, F, p["fc2"], shift=p["fc2_b"], residual=x, row_scale=keep[1])
+        return _branch_out(_a(_lib.SWIN_A_ROWS, h, ldx=F), M, F, p["fc2"], p["fc2_b"], x, keep[1])
 
     def run_backward(self, p, pb, rec, g, B, H, W, inv, grads):
         """g: gradient rows [B*H*W, C] of the block's output, pre-scaled (1 / inv[0] is the scale) -> the gradient rows
         of its input in the same scale; the twelve parameter gradients (times inv) go into grads[parameter].
         rec: what run() left on the tape -- the block's input x, the rows y between its branches, both LayerNorms'
         (mean, rstd) rows, the qkv rows and the attention output.  The FFN's hidden rows are not kept: the first Linear
-        runs again (without GELU) and isf_swin_gelu_backward turns them into gelu(.) and the gradient into dL/dz."""
+        runs again (without GELU) and isf_swin_gelu_backward turns them into gelu(.) and the gradient into dL/dz.
+        With the f16 packs (mixed precision) every product is single-pass and rec's qkv / attention rows are f16; the
+        gradient rows, the recomputed hidden and everything that is not a product stay fp32."""
         M, C = g.shape
+        h16 = isinstance(p["qkv"], PackedLinearF16)
         m = self.attn.w_msa
         l1, l2 = self.ffn.layers[0][0], self.ffn.layers[1]
         F = self.ffn.feedforward_channels
@@ -382,10 +444,10 @@ class SwinBlock(nn.Module):
         h = gemm(a2, M, C, p["fc1"], shift=p["fc1_b"])
         dh = gemm(rows(df), M, C, pb["fc2"])
         gelu_backward(h, dh)
-        grads[l2.weight] = _rows_weight_grad(df, h, inv)
+        grads[l2.weight] = _rows_weight_grad(df, h, inv, h16)
         grads[l2.bias] = column_sums(df, inv_scale=inv)
         del h
-        grads[l1.weight] = _rows_weight_grad(dh, operand_rows(a2, M, C), inv)
+        grads[l1.weight] = _rows_weight_grad(dh, operand_rows(a2, M, C), inv, h16)
         grads[l1.bias] = column_sums(dh, inv_scale=inv)
         dn = gemm(rows(dh), M, F, pb["fc1"])
         del dh
@@ -393,7 +455,7 @@ class SwinBlock(nn.Module):
                                                                                   inv_scale=inv)
         # attention branch: y = x + keep0 * (attention(LN1(x) Wqkv^T + bqkv) Wp^T + bp)
         dp = scale_rows(dy, rec["keep"][0])
-        grads[m.proj.weight] = _rows_weight_grad(dp, rec["att"], inv)
+        grads[m.proj.weight] = _rows_weight_grad(dp, rec["att"], inv, h16)
         grads[m.proj.bias] = column_sums(dp, inv_scale=inv)
         datt = gemm(rows(dp), M, C, pb["proj"])
         table = m.relative_position_bias_table
@@ -402,7 +464,7 @@ class SwinBlock(nn.Module):
             m.scale, rel_index=m.relative_position_index, table_rows=table.shape[0], inv_scale=inv)
         ln1 = (self.norm1.weight.detach(), self.norm1.bias.detach())
         a1 = _a(_lib.SWIN_A_ROWS, x, ldx=C, stats=rec["st1"], ln=ln1)
-        grads[m.qkv.weight] = _rows_weight_grad(dqkv, operand_rows(a1, M, C), inv)
+        grads[m.qkv.weight] = _rows_weight_grad(dqkv, operand_rows(a1, M, C), inv, h16)
         if m.qkv.bias is not None:
             grads[m.qkv.bias] = column_sums(dqkv, extra=pad, inv_scale=inv)
         dn = gemm(rows(dqkv), M, 3 * C, pb["qkv"])
@@ -444,9 +506,9 @@ class PatchEmbed(nn.Module):
             x = layernorm(x, self.norm)
         return x, (Ho, Wo)
 
-    def run_backward(self, rec, g, cum, grads):
+    def run_backward(self, rec, g, cum, grads, f16=False):
         """g: gradient rows of run()'s output times cum[0] -> the projection's (and the norm's) gradients; the image
-        gets none.  dW = dY^T . patches on the im2col rows (isf_swin_operand_rows, PATCH)."""
+        gets none.  dW = dY^T . patches on the im2col rows (isf_swin_operand_rows, PATCH); f16: single-pass products."""
         img, raw = rec["img"], rec["raw"]
         N, C, H, W = img.shape
         M, E = raw.shape
@@ -456,7 +518,7 @@ class PatchEmbed(nn.Module):
             a = _a(_lib.SWIN_A_ROWS, raw, ldx=E, stats=st, ln=(self.norm.weight.detach(), self.norm.bias.detach()))
             g, grads[self.norm.weight], grads[self.norm.bias] = layernorm_backward(a, M, E, g, inv_scale=inv)
         patches = operand_rows(_a(_lib.SWIN_A_PATCH, img, n=N, c=C, h=H, w=W), M, 16 * C)
-        grads[self.projection.weight] = _rows_weight_grad(g, patches, inv).view(self.projection.weight.shape)
+        grads[self.projection.weight] = _rows_weight_grad(g, patches, inv, f16).view(self.projection.weight.shape)
         grads[self.projection.bias] = column_sums(g, inv_scale=inv)
 
 
@@ -503,11 +565,11 @@ class PatchMerging(nn.Module):
             tape.append(dict(x=x, st=st))
         return gemm(a,M, 4 * C, p["w"]), (Ho, Wo)
 
-    def pack_backward(self, p):
-        """the transposed packed reduction weight, in the loader's column order"""
+    def pack_backward(self, p, linear=PackedLinear):
+        """the transposed packed reduction weight, in the loader's column order; linear as in pack()"""
         C = self.in_channels
         w = self.reduction.weight.detach().float()
-        return PackedLinear(w.view(-1, C, 4).permute(0, 2, 1).reshape(w.shape[0], 4 * C).contiguous(), transposed=True)
+        return _pack_transposed(w.view(-1, C, 4).permute(0, 2, 1).reshape(w.shape[0], 4 * C).contiguous(), linear)
 
     def run_backward(self, p, pb, rec, g, B, H, W, inv, grads):
         """g: gradient rows [B*Ho*Wo, 2C] of run()'s output (pre-scaled; inv as in SwinBlock.run_backward) -> the
@@ -520,7 +582,7 @@ class PatchMerging(nn.Module):
         C = self.in_channels
         M, N = g.shape
         a = _a(_lib.SWIN_A_MERGE, x, stats=rec["st"], ln=(p["g"], p["b"]), n=B, c=C, h=H, w=W)
-        dw = _rows_weight_grad(g, operand_rows(a, M, 4 * C), inv)
+        dw = _rows_weight_grad(g, operand_rows(a, M, 4 * C), inv, isinstance(pb, PackedLinearF16))
         grads[self.reduction.weight] = dw.view(N, 4, C).permute(0, 2, 1).reshape(N, 4 * C)
         dn = gemm(_a(_lib.SWIN_A_ROWS, g, ldx=N), M, N, pb)
         dx, dg, db = layernorm_backward(a, M, 4 * C, dn, dx_shape=tuple(x.shape), inv_scale=inv)
@@ -589,12 +651,14 @@ class SwinTransformer(nn.Module):
         for i in out_indices:
             self.add_module(f"norm{i}", nn.LayerNorm(self.num_features[i]))
 
-    PRECISIONS = ("f32", "f16")
+    PRECISIONS = ("f32", "f16", "mixed")
     precision = "f32"       # a plain attribute (set_precision): not a parameter, buffer or constructor argument
 
     def set_precision(self, mode):
         """"f32": the default f16x3 kernels (fp32-class accuracy).  "f16": the f16 inference mode -- single-pass
-        products, f16 branch intermediates, fp32 residual stream; eval-mode forward only."""
+        products, f16 branch intermediates, fp32 residual stream; eval-mode forward only.  "mixed": mixed-precision
+        training -- the f16 mode's forward in eval(), and in train() forward_train with f16 products, f16 saved qkv /
+        attention rows, fp32 residual stream, statistics, softmax and parameter gradients."""
         if mode not in self.PRECISIONS:
             raise ValueError(f"SwinTransformer.set_precision: {mode!r} (one of {self.PRECISIONS})")
         self.precision = mode
@@ -604,14 +668,17 @@ class SwinTransformer(nn.Module):
         """the packed weights of the current mode; both modes' copies share the module's one derived-weight store, so a
         parameter change drops both and each is derived again on its next use"""
         c = _cache(self, dev)
-        if self.precision not in c:
-            linear = {"f32": PackedLinear, "f16": PackedLinearF16}[self.precision]
+        key = self._PACKS[self.precision]      # "mixed" runs on the f16 mode's packed weights
+        if key not in c:
+            linear = {"f32": PackedLinear, "f16": PackedLinearF16}[key]
             with torch.no_grad():
-                c[self.precision] = dict(
+                c[key] = dict(
                     patch=self.patch_embed.pack(linear),
                     blocks=[[blk.pack(linear) for blk in st.blocks] for st in self.stages],
                     merge=[st.downsample.pack(linear) if st.downsample is not None else None for st in self.stages])
-        return c[self.precision]
+        return c[key]
+
+    _PACKS = {"f32": "f32", "f16": "f16", "mixed": "f16"}
 
     @torch.no_grad()
     def forward(self, x):
@@ -642,9 +709,9 @@ class SwinTransformer(nn.Module):
     def _train_inputs(self, x, drop_keep):
         """forward_train's checks -> (x, the DropPath factors [len(drop_layers()), N] or None)"""
         assert self.training, "call .train() first (forward() is the eval-mode forward)"
-        if self.precision != "f32":
+        if self.precision == "f16":
             raise NotImplementedError(f"SwinTransformer.forward_train: precision {self.precision!r} is an inference "
-                                      'mode (train with set_precision("f32"))')
+                                      'mode (train with set_precision("f32") or set_precision("mixed"))')
         if self.drop_rate != 0.0 or self.attn_drop_rate != 0.0:
             raise NotImplementedError(f"SwinTransformer.forward_train: drop_rate {self.drop_rate} / attn_drop_rate "
                                       f"{self.attn_drop_rate} (only DropPath is built)")
@@ -669,10 +736,10 @@ class SwinTransformer(nn.Module):
         assert x.dim() == 4, x.shape
         x = x.float().contiguous()
         N = x.shape[0]
-        assert scales is None or self.precision == "f32"      # DropPath is not built for the f16 inference mode
+        assert scales is None or self.precision in ("f32", "mixed")      # the f16 mode is inference only
         p = self._packed(x.device)
         if tape is not None:
-            tape.update(n=N, patch=[], stages=[])
+            tape.update(n=N, patch=[], stages=[], precision=self.precision)
         t, (H, W) = self.patch_embed.run(p["patch"], x, None if tape is None else tape["patch"])
         outs = []
         row = 0
@@ -696,14 +763,16 @@ class SwinTransformer(nn.Module):
         """the transposed packed weights of the backward's dX = dY . W products, in the same derived-weight store as the
         forward's: a parameter update drops both"""
         c = _cache(self, dev)
-        if "f32_backward" not in c:
+        key = self._PACKS[self.precision] + "_backward"
+        if key not in c:
             p = self._packed(dev)
+            linear = PackedLinearF16 if key == "f16_backward" else PackedLinear
             with torch.no_grad():
-                c["f32_backward"] = dict(
-                    blocks=[[blk.pack_backward() for blk in st.blocks] for st in self.stages],
-                    merge=[st.downsample.pack_backward(p["merge"][i]) if st.downsample is not None else None
+                c[key] = dict(
+                    blocks=[[blk.pack_backward(linear) for blk in st.blocks] for st in self.stages],
+                    merge=[st.downsample.pack_backward(p["merge"][i], linear) if st.downsample is not None else None
                            for i, st in enumerate(self.stages)])
-        return c["f32_backward"]
+        return c[key]
 
     @torch.no_grad()
     def _run_backward(self, tape, gouts):
@@ -712,6 +781,9 @@ class SwinTransformer(nn.Module):
         block's entry (_lib.grad_rescale: the f16 hi / lo products want operands near 2^10, gradients are 1e-5 and
         below); cum = [scale, 1 / scale] of g against the true gradient."""
         dev = tape["stages"][0]["out"].device
+        if tape["precision"] != self.precision:
+            raise RuntimeError(f"SwinTransformer: the forward ran in precision {tape['precision']!r}, the backward is "
+                               f"asked for in {self.precision!r} (set_precision between forward_train and backward)")
         p, pb = self._packed(dev), self._packed_backward(dev)
         N = tape["n"]
         gmaps = dict(zip([i for i in range(len(self.stages)) if i in self.out_indices], gouts))
@@ -740,7 +812,7 @@ class SwinTransformer(nn.Module):
                 cum = cum * sc
                 g = blk.run_backward(bp, bpb, brec, g, N, H, W, cum[1:], grads)
         if g is not None:
-            self.patch_embed.run_backward(tape["patch"][0], g, cum, grads)
+            self.patch_embed.run_backward(tape["patch"][0], g, cum, grads, f16=self.precision == "mixed")
         return grads
 
 

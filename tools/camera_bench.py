@@ -8,6 +8,7 @@
     python tools/camera_bench.py [--steps 10] [--warmup 3] [--points 300000]
     python tools/camera_bench.py --train [--backward] [--steps 10] [--warmup 3] [--runs 3]
     python tools/camera_bench.py --precision both [--steps 10] [--warmup 3] [--runs 3]
+    python tools/camera_bench.py --train [--backward] --precision mixed [--steps 5] [--warmup 2] [--runs 3]
 
 --precision f32 (default) is the run above.  f16 / both: the backbone's precision modes (SwinTransformer.set_precision)
 in ONE process on the same weights and images -- per run and mode the backbone, extract_img_feat and
@@ -20,6 +21,9 @@ sends back), against the float32 stock-torch composition of tests/camera_train_c
 same GPU, each measured --runs times; plus the single kernels of the lateral step's backward at the shipped level-1 size.
 --train --backward: the step with the backbone's backward as well (ISFusionDetector.camera_backward), against stock-torch
 autograd over backbone and neck, --runs times each, and the peak memory each step adds.
+--train [--backward] --precision mixed: the HIP step in the f32 mode and in the mixed-precision training mode
+(SwinTransformer.set_precision("mixed")), one after the other in ONE process on the same weights, images and masks; the
+rows carry a "precision" field.
 
 Prints one JSON line per measurement (ms per call, mean over --steps)."""
 import argparse
@@ -85,8 +89,12 @@ def train_bench(a, dev):
     if a.backward:
         return train_backward_bench(a, bb, nk, flat, keep, up, sd, nd)
     for run in range(a.runs):
-        ms = timed(hip_step, a.steps, a.warmup)
-        print(json.dumps(dict(what="camera_train_step", impl="hip", images=B * 6, hw=[H, W], run=run, ms=round(ms, 3))))
+        for mode in train_modes(a):
+            bb.set_precision(mode)
+            ms = timed(hip_step, a.steps, a.warmup)
+            print(json.dumps(dict(what="camera_train_step", impl="hip", precision=mode, images=B * 6, hw=[H, W], run=run,
+                                  ms=round(ms, 3))))
+        bb.set_precision("f32")
         ms = timed(torch_step, a.steps, a.warmup)
         print(json.dumps(dict(what="camera_train_step", impl="torch_fp32", images=B * 6, hw=[H, W], run=run,
                               ms=round(ms, 3))))
@@ -122,6 +130,11 @@ def train_bench(a, dev):
         print(json.dumps(dict(what=what, ms=round(timed(fn, a.steps * 5, a.warmup), 4))))
 
 
+def train_modes(a):
+    """--train: the backbone's precision modes to time, in one process"""
+    return ("f32", "mixed") if a.precision == "mixed" else ("f32",)
+
+
 def train_backward_bench(a, bb, nk, flat, keep, up, sd, nd):
     """--train --backward: backbone forward with DropPath + neck forward + both backwards from a gradient on the stride-16
     map, next to float32 stock-torch autograd over the same modules and masks; and the peak memory either step adds to
@@ -146,23 +159,29 @@ def train_backward_bench(a, bb, nk, flat, keep, up, sd, nd):
         outs[1].backward(up)
 
     if a.profile_backward:
+        bb.set_precision(a.precision)
         for _ in range(a.warmup + a.steps):
             hip_step()
         torch.cuda.synchronize()
         return
+    cases = [("hip", mode, hip_step) for mode in train_modes(a)] + [("torch_fp32", "f32", torch_step)]
     for run in range(a.runs):
-        for impl, fn in (("hip", hip_step), ("torch_fp32", torch_step)):
+        for impl, mode, fn in cases:
+            bb.set_precision(mode)
             ms = timed(fn, a.steps, a.warmup)
-            print(json.dumps(dict(what="camera_train_step_backward", impl=impl, images=n, hw=[H, W], run=run,
-                                  ms=round(ms, 3))))
-    for impl, fn in (("hip", hip_step), ("torch_fp32", torch_step)):
+            print(json.dumps(dict(what="camera_train_step_backward", impl=impl, precision=mode, images=n, hw=[H, W],
+                                  run=run, ms=round(ms, 3))))
+    for impl, mode, fn in cases:
+        bb.set_precision(mode)
+        fn()                                  # this mode's packed weights and gradients are resident before the measurement
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         base = torch.cuda.memory_allocated()
         fn()
         torch.cuda.synchronize()
-        print(json.dumps(dict(what="camera_train_step_backward_peak_memory", impl=impl,
+        print(json.dumps(dict(what="camera_train_step_backward_peak_memory", impl=impl, precision=mode,
                               mib_over_resident=round((torch.cuda.max_memory_allocated() - base) / 2 ** 20, 1))))
+    bb.set_precision("f32")
 
     def hip_forward_only():
         outs = nk.forward_train(bb.forward_train(flat, drop_keep=keep))
@@ -237,15 +256,20 @@ def main():
                     help="with --train --backward: run the HIP step --warmup + --steps times and exit (the process to "
                          "put under a kernel trace)")
     ap.add_argument("--runs", type=int, default=3, help="--train / --precision f16|both: repetitions of the measurement")
-    ap.add_argument("--precision", choices=("f32", "f16", "both"), default="f32",
-                    help="f16 / both: time the backbone's precision modes in one process (default: the f32 run)")
+    ap.add_argument("--precision", choices=("f32", "f16", "both", "mixed"), default="f32",
+                    help="f16 / both: time the backbone's precision modes in one process (default: the f32 run); mixed "
+                         "(with --train): the training step in the f32 and the mixed-precision mode in one process")
     ap.add_argument("--profile-forward", action="store_true",
                     help="run the backbone forward of --precision (f32 or f16) --steps times and exit: the process to "
                          "put under a kernel trace (profiles/camera_f16_kernels.txt)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     if a.train:
+        if a.precision in ("f16", "both"):
+            ap.error("--train times the training modes: --precision f32 or mixed")
         return train_bench(a, dev)
+    if a.precision == "mixed":
+        ap.error("--precision mixed is a training mode (its eval forward is f16's): use it with --train")
     if a.profile_forward:
         if a.precision == "both":
             ap.error("--profile-forward traces one mode: --precision f32 or f16")

@@ -2,7 +2,7 @@
 all-reduce over xGMI on the GRADIENTS only -- the forward has no collective):
 
     python tools/train_step.py --gpus N [--batch 2] [--points 60000] [--steps 3] [--bf16] [--autocast]
-                               [--optimizer sgd|config] [--max-iters M] [--gt-paste] [--camera [--camera-backward]]
+                               [--optimizer sgd|config] [--max-iters M] [--gt-paste] [--camera [--camera-backward] [--camera-precision f32|mixed]]
                                [--deterministic]
 
 starts N ranks by itself (isfusion_amd.launch.self_launch: a re-exec under torch.distributed.run on 127.0.0.1; fewer
@@ -28,7 +28,8 @@ convs receive no gradient (only the stride-16 map reaches Point-to-Grid), so --c
 (requires_grad False) rather than asking DistributedDataParallel for find_unused_parameters: no per-step graph search,
 and the optimizer skips them.  --camera-backward (with --camera) builds the detector with detach=False and
 camera_backward = True instead: the backbone's backward runs (swin.py, isf_swin_train.hip) and only the norm of its
-first output map and the neck's level-0 convs stay frozen.  --deterministic runs every step under isfusion_amd.set_deterministic(True) (exact,
+first output map and the neck's level-0 convs stay frozen.  --camera-precision mixed (with --camera) runs the backbone in its
+mixed-precision training mode (ISFusionDetector.camera_precision).  --deterministic runs every step under isfusion_amd.set_deterministic(True) (exact,
 order-independent accumulation in the four scattering kernels; any --loss / --camera / --optimizer / --gt-paste): the steps
 are then bit-identical run to run.  With more than one rank the mode also covers the sums that cross ranks
 (isfusion_amd.collectives): the forward runs under ddp.no_sync() and exact_all_reduce_gradients sums the local gradients
@@ -158,6 +159,9 @@ def main():
     ap.add_argument("--camera-backward", action="store_true",
                     help="with --camera: detach=False and ISFusionDetector.camera_backward = True -- the Swin backbone's "
                          "backward runs too (the reference class's default; the shipped optimizer's lr_mult 0.1 group)")
+    ap.add_argument("--camera-precision", default="f32", choices=["f32", "mixed"],
+                    help="with --camera: ISFusionDetector.camera_precision -- mixed: the Swin backbone's mixed-precision "
+                         "training mode (f16 products, fp32 master weights and gradients)")
     ap.add_argument("--deterministic", action="store_true",
                     help="isfusion_amd.set_deterministic(True): the isf_*_det entries (fixed-point accumulation) in "
                          "DynamicScatter, Point-to-Grid backward and both MSDA backwards")
@@ -167,6 +171,8 @@ def main():
     a = ap.parse_args()
     if a.camera_backward and not a.camera:
         ap.error("--camera-backward switches the camera branch's backward on: it needs --camera")
+    if a.camera_precision != "f32" and not a.camera:
+        ap.error("--camera-precision sets the camera backbone's mode: it needs --camera")
     if a.gt_paste and a.loss != "detection":
         ap.error("--gt-paste pastes ground truth: it needs --loss detection")
     import isfusion_amd
@@ -203,6 +209,7 @@ def main():
             img_neck=dict(type="GeneralizedLSSFPN", in_channels=[192, 384, 768], out_channels=256, start_level=0,
                           num_outs=3), detach=not a.camera_backward).train()
         net.camera_backward = a.camera_backward
+        net.camera_precision = a.camera_precision
         g = torch.Generator().manual_seed(4100)
         with torch.no_grad():                                        # O(1) activations through the 12 blocks
             for name, p in list(net.img_backbone.named_parameters()) + list(net.img_neck.named_parameters()):
@@ -336,7 +343,7 @@ def main():
             dist.all_gather_object(every, digest["param_digest"])
             digest["replicas_agree"] = len(set(every)) == 1
     if rank == 0:
-        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss, "camera": a.camera, "camera_backward": a.camera_backward, "deterministic": a.deterministic,
+        print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss, "camera": a.camera, "camera_backward": a.camera_backward, "camera_precision": a.camera_precision, "deterministic": a.deterministic,
                           "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses],
                           "optimizer": a.optimizer, **({"grad_norm": [round(n, 6) for n in norms]} if recipe else {}),
                           **({"gt_paste_objects": pasted} if paste is not None else {}),
