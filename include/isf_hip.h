@@ -771,6 +771,23 @@ int isf_attention_forward_dropout(const float* q, int ldq, const float* k, const
  *   out = query_scene + softmax(query_scene . query_ins^T, dim=-1) . query_ins */
 int isf_channel_attention_forward(const float* query_scene, const float* query_ins, int num_maps, int size,
                                   float* out, isf_stream_t stream);
+/* ... and its gradient (training): replaces what autograd runs behind fusion_encoder.py:495-500 -- the backward of the
+ * two torch.matmul calls and of the softmax between them, with the [B, C, size, size] probabilities saved by the forward.
+ * Nothing is saved here: per map, with A = query_scene[m], Bm = query_ins[m], G = grad_out[m] (size x size, row-major)
+ *   P  = softmax(A Bm^T, dim = -1)                  (recomputed, fp32 MFMA, row maximum subtracted)
+ *   gP = G Bm^T
+ *   gS = P o (gP - rowsum(gP o P))
+ *   gA = G + gS Bm                                   -> grad_query_scene[m]
+ *   gB = P^T G + gS^T A                              -> grad_query_ins[m]
+ * Domain: the forward's (size % 4 == 0, size <= 192; anything else is ISF_ERR_UNSUPPORTED, checked before any HIP call).
+ * Either output may be NULL: the work only it needs is skipped and the other output has the bits of the full call (both
+ * NULL: nothing is launched).  Deterministic (no atomics, fixed summation order); map m's result does not depend on
+ * num_maps or on the other maps.  Scratch: P and gS of up to 256 maps at a time (2 * 256 * size^2 floats at most, 66 MB
+ * at size 180) from the stream's workspace -- more maps are processed in groups of 256 in order, fewer per group if the
+ * device cannot provide that much; grad_query_ins = NULL needs none.  Asynchronous. */
+int isf_channel_attention_backward(const float* query_scene, const float* query_ins, const float* grad_out,
+                                   int num_maps, int size, float* grad_query_scene /* may be NULL */,
+                                   float* grad_query_ins /* may be NULL */, isf_stream_t stream);
 
 /* A8  Point-to-Grid sampling ------------------------------------------------------------------------------
  * replaces ISFusionEncoder.img_fv_to_bev + img_point_sampling (fusion_encoder.py:965-1070).

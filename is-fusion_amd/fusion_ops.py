@@ -782,6 +782,22 @@ def channel_attention(query_scene, query_ins):
     return out
 
 
+def channel_attention_backward(query_scene, query_ins, grad_out, need_scene=True, need_ins=True):
+    """Gradients of `channel_attention` towards its two inputs for the output gradient grad_out, all [B, C, H, H]
+    (isf_channel_attention_backward: the probabilities are recomputed, nothing is saved by the forward).  An input that
+    needs no gradient gets None, and the kernel work only it needs is skipped."""
+    _lib.require_cuda(query_scene, query_ins, grad_out)
+    qs, qi, go = query_scene.float().contiguous(), query_ins.float().contiguous(), grad_out.float().contiguous()
+    B, C, H, W = qs.shape
+    assert H == W and qi.shape == qs.shape and go.shape == qs.shape
+    g_scene = torch.empty_like(qs) if need_scene else None
+    g_ins = torch.empty_like(qs) if need_ins else None
+    _lib.check(_lib.load().isf_channel_attention_backward(_lib.ptr(qs), _lib.ptr(qi), _lib.ptr(go), B * C, H,
+                                                          _lib.ptr(g_scene), _lib.ptr(g_ins), _lib.stream()),
+               "isf_channel_attention_backward")
+    return g_scene, g_ins
+
+
 def instance_to_scene(mod, query, x_ins, scene_feats, bev_size):
     """Instane2SceneAtt.forward (fusion_encoder.py:480-502), eval mode: query [B, E, H, W] = conv_ins(bev),
     x_ins [B, E, Q] (or token-major [B*Q, E], as ins_context_att(mined=...) returns it), scene_feats [B, E, H, W] (the

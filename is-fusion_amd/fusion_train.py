@@ -7,7 +7,7 @@ the HIP kernel and whose BACKWARD is
   * fused linear            dX on the same f16x3 MFMA GEMM (transposed weight), dW = dY^T X and db as plain library
                             GEMMs / reductions (rocBLAS through torch.matmul: the rules' "plain library GEMM");
   * window / small-key attention, MSDA      the hand-written backward kernels (isf_attention_bwd.hip, isf_fusion.hip);
-  * per-channel map attention               forward isf_channel_attention_forward, backward batched GEMMs;
+  * per-channel map attention               isf_channel_attention_forward / isf_channel_attention_backward;
   * Point-to-Grid                           isf_p2g_backward (scatter with fp32 atomics);
 
 bias / position-table / GELU / residual / LayerNorm epilogues, the 3x3 convolutions + BatchNorm (stock, as the north_star
@@ -142,10 +142,26 @@ def linear_w(x, weight, bias=None):
     return LinearFunction.apply(x, weight, bias)
 
 
+def channel_attention_backward_reference(qs, qi, g):
+    """Gradients of out = qs + softmax(qs qi^T) qi towards qs and qi for the output gradient g ([..., H, H] each), as a
+    torch composition in the inputs' dtype and on their device: the probabilities are recomputed, then four batched GEMMs.
+    It is what ChannelAttentionFunction.backward ran before isf_channel_attention_backward existed and the yardstick that
+    kernel is tested against (float64 on the CPU: exact to rounding; float32 on the GPU: the library-GEMM error)."""
+    H, W = qs.shape[-2:]
+    a, b, go = qs.reshape(-1, H, W), qi.reshape(-1, H, W), g.reshape(-1, H, W)
+    p = torch.softmax(torch.bmm(a, b.transpose(1, 2)), -1)          # [BC, H, H]
+    gp = torch.bmm(go, b.transpose(1, 2))                            # d loss / d P
+    gs = p * (gp - (gp * p).sum(-1, keepdim=True))                   # through the softmax
+    ga = go + torch.bmm(gs, b)                                       # query_scene: identity + scores
+    gb = torch.bmm(p.transpose(1, 2), go) + torch.bmm(gs.transpose(1, 2), a)
+    return ga.view(qs.shape), gb.view(qs.shape)
+
+
 class ChannelAttentionFunction(torch.autograd.Function):
     """out = query_scene + softmax(query_scene query_ins^T) query_ins per (batch, channel) map
-    (fusion_encoder.py:495-500).  Forward = isf_channel_attention_forward; backward recomputes the probabilities and
-    runs four batched GEMMs."""
+    (fusion_encoder.py:495-500).  Forward = isf_channel_attention_forward; backward = isf_channel_attention_backward
+    (probabilities recomputed on the matrix cores, only the gradients an input needs; faster and smaller than the torch
+    composition above: tools/channel_attention_bench.py)."""
 
     @staticmethod
     @_amp_fwd
@@ -158,14 +174,7 @@ class ChannelAttentionFunction(torch.autograd.Function):
     @_amp_bwd
     def backward(ctx, g):
         qs, qi = ctx.saved_tensors
-        B, C, H, W = qs.shape
-        a, b, go = qs.view(B * C, H, W), qi.view(B * C, H, W), g.contiguous().float().view(B * C, H, W)
-        p = torch.softmax(torch.bmm(a, b.transpose(1, 2)), -1)          # [BC, H, H]
-        gp = torch.bmm(go, b.transpose(1, 2))                            # d loss / d P
-        gs = p * (gp - (gp * p).sum(-1, keepdim=True))                   # through the softmax
-        ga = go + torch.bmm(gs, b)                                       # query_scene: identity + scores
-        gb = torch.bmm(p.transpose(1, 2), go) + torch.bmm(gs.transpose(1, 2), a)
-        return ga.view(B, C, H, W), gb.view(B, C, H, W)
+        return ops.channel_attention_backward(qs, qi, g, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
 
 
 class P2GFunction(torch.autograd.Function):
