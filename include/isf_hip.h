@@ -761,7 +761,10 @@ int isf_attention_forward(const float* q, int ldq, const float* k, const float* 
  * dropout_p and the kept ones scaled by 1 / (1 - dropout_p); the row normalisation keeps every term.  The keep / drop
  * decision of (sample * heads + head, query, key) is a counter-based hash of `seed` (MurmurHash3's finaliser over the
  * packed indices; isf_attention_backward_dropout recomputes it from the same seed), so no mask is stored.  dropout_p = 0
- * is isf_attention_forward.  head_dim 16, num_keys <= 512. */
+ * is isf_attention_forward.  With dropout_p > 0: head_dim 16, any number of keys (more than 512: the 512-key splits and
+ * the merge of isf_attention_forward, each split hashing its global key indices), and the hash's index fields bound the
+ * sizes: num_queries < 2^24, num_keys < 2^24, batch_size * num_heads < 2^16.  Outside this domain both entries return
+ * ISF_ERR_UNSUPPORTED, naming the value, before anything else is looked at. */
 int isf_attention_forward_dropout(const float* q, int ldq, const float* k, const float* v, int ldkv, int batch_size,
                                   int num_queries, int num_keys, int embed_dims, int num_heads, float dropout_p,
                                   unsigned long long seed, float* out, int ldo, isf_stream_t stream);
@@ -1190,7 +1193,9 @@ int isf_attention_backward(const float* q, int ldq, const float* k, const float*
                            const float* grad_out, int ldo, int batch_size, int num_queries, int num_keys,
                            int embed_dims, int num_heads, float* grad_q, int ldgq, float* grad_k, float* grad_v,
                            int ldgkv, isf_stream_t stream);
-/* ... of isf_attention_forward_dropout (same dropout_p and seed; `out` = that call's result) */
+/* ... of isf_attention_forward_dropout (same dropout_p, seed and domain; `out` = that call's result).  With dropout_p > 0,
+ * more than 512 keys and at most 256 queries (the head's 200 x 32400 cross-attention) dQ is computed by 512-key splits
+ * and an ordered merge instead of a wave per query: the same gradients, still no atomics and nothing of size Lq x Lk. */
 int isf_attention_backward_dropout(const float* q, int ldq, const float* k, const float* v, int ldkv, const float* out,
                                    const float* grad_out, int ldo, int batch_size, int num_queries, int num_keys,
                                    int embed_dims, int num_heads, float dropout_p, unsigned long long seed, float* grad_q,

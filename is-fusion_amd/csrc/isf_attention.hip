@@ -9,6 +9,7 @@
 //  (the per-channel map attention of A14 lives in isf_channel_attn.hip)
 // head_dim 16 (every use on the IS-Fusion path) runs attention_mfma16_kernel on the matrix cores, the window attention of
 // both levels window_attention_mfma_kernel; the fp32 VALU kernels serve head_dim 32 of the generic entry point.
+#include "isf_attention_plan.h"
 #include "isf_common.h"
 
 namespace isf {
@@ -430,8 +431,15 @@ static int attention_forward_impl(const float* q, int ldq, const float* k, const
                                   int num_queries, int num_keys, int embed_dims, int num_heads, float* out, int ldo,
                                   isf::AttnDrop drop, isf_stream_t stream) {
   using namespace isf;
-  ISF_REQUIRE(drop.thresh == 0 || (num_heads > 0 && embed_dims == 16 * num_heads && num_keys <= 512), ISF_ERR_UNSUPPORTED,
-              "attention: probability dropout is built for head_dim 16 and <= 512 keys (the training path's two shapes)");
+  if (drop.thresh) {   // the dropout kernels' domain, checked before anything else is looked at
+    ISF_REQUIRE(num_heads > 0 && embed_dims == 16 * num_heads, ISF_ERR_UNSUPPORTED,
+                "attention: probability dropout is built for head_dim 16 (got %d: %d dims, %d heads)",
+                num_heads > 0 ? embed_dims / num_heads : 0, embed_dims, num_heads);
+    long long value = 0, limit = 0;
+    const char* what = attention_dropout_out_of_range(batch_size, num_queries, num_keys, num_heads, &value, &limit);
+    ISF_REQUIRE(what == nullptr, ISF_ERR_UNSUPPORTED,
+                "attention: probability dropout hashes %s into a field of %lld values (got %lld)", what ? what : "", limit, value);
+  }
   ISF_REQUIRE(batch_size >= 0 && num_queries >= 0 && num_keys > 0, ISF_ERR_ARG, "attention: bad sizes");
   if (batch_size == 0 || num_queries == 0) return ISF_OK;
   ISF_REQUIRE(q && k && v && out, ISF_ERR_ARG, "attention: null pointer");
@@ -443,7 +451,8 @@ static int attention_forward_impl(const float* q, int ldq, const float* k, const
     hipStream_t st = as_stream(stream);
     // <= 512 keys: one resident set; more (the head's 32400): 512-key splits + merge (256-key splits measured the
     // same: 157 us against 159 us per call incl. the merge, tools/attention_time.py)
-    const int kps = num_keys > 512 ? 512 : num_keys, nsplit = ceil_div(num_keys, kps);
+    const AttnForwardPlan plan = attention_forward_plan(batch_size, num_queries, num_keys, num_heads, hd);
+    const int kps = plan.keys_per_split, nsplit = plan.splits;
     const float scale = 0.25f;   // 1 / sqrt(16)
     const dim3 grid(ceil_div(num_queries, 256), num_heads, batch_size * nsplit), block(256);
     const size_t lds = (size_t)round_up(kps, 16) * kAttnLs * 2 * sizeof(float);
@@ -462,7 +471,7 @@ static int attention_forward_impl(const float* q, int ldq, const float* k, const
       Arena& a = arena_for_stream(st);
       ISF_TRY(a.reset());
       float* part = nullptr;
-      ISF_TRY(a.alloc_n(&part, (size_t)batch_size * num_heads * nsplit * num_queries * (hd + 2)));
+      ISF_TRY(a.alloc_n(&part, plan.workspace_floats));
       hipLaunchKernelGGL((attention_mfma16_kernel<true>), grid, block, lds, st, q, ldq, k, v, ldkv, num_queries, num_keys,
                          kps, nsplit, scale, out, ldo, part, drop);
       const long long total = (long long)batch_size * num_heads * num_queries * hd;
@@ -474,11 +483,12 @@ static int attention_forward_impl(const float* q, int ldq, const float* k, const
   }
   if (num_keys > 512) {   // keys split into <= 512-key chunks + merge
     hipStream_t st = as_stream(stream);
-    const int kps = 512, nsplit = ceil_div(num_keys, kps);
+    const AttnForwardPlan plan = attention_forward_plan(batch_size, num_queries, num_keys, num_heads, hd);
+    const int kps = plan.keys_per_split, nsplit = plan.splits;
     Arena& a = arena_for_stream(as_stream(stream));
     ISF_TRY(a.reset());
     float* part = nullptr;
-    ISF_TRY(a.alloc_n(&part, (size_t)batch_size * num_heads * nsplit * num_queries * (hd + 2)));
+    ISF_TRY(a.alloc_n(&part, plan.workspace_floats));
     static bool split_attr_set = false;
     if (!split_attr_set) {
       ISF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&split_key_attention_kernel<16>),

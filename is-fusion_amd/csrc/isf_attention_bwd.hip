@@ -11,9 +11,12 @@
 //   cols    wave per (b, head, key j),   lanes over queries: dV_j = sum_i p_ij dO_i,
 //                                                            dK_j = scale * sum_i p_ij (dO_i.v_j - D_i) q_i
 //   window  the 36-token windows of the dense grid: one wave per (window, head) does both roles out of LDS.
+// Many queries put a LANE on a row / column (rows_lanes, cols_lanes); few queries under many keys with probability
+// dropout cut the KEYS (rows_keysplit + merge).  Which of them a call runs: attention_backward_plan, isf_attention_plan.h.
 // fp32 VALU like the forward cores (head dim 16: these are dot products of 16 floats).
 #include <algorithm>
 
+#include "isf_attention_plan.h"
 #include "isf_common.h"
 
 namespace isf {
@@ -179,7 +182,7 @@ __global__ __launch_bounds__(256) void attention_bwd_cols_kernel(
 //   cols_lanes   lane = key j (k_j, v_j, dK_j, dV_j in registers), a tile of queries (q_i, dO_i, L_i, D_i) staged in LDS and
 //                broadcast; query chunks -> partial buffers -> the ordered reduce above.
 // Same sums as the wave kernels in a different (fixed) order: deterministic, equal to fp32 rounding.
-constexpr int kAttTile = 128;   // keys (rows_lanes) / queries (cols_lanes) per LDS tile
+// (kAttTile, the keys (rows_lanes) / queries (cols_lanes) per LDS tile: isf_attention_plan.h)
 
 template <int HD>
 __global__ __launch_bounds__(256) void attention_bwd_rows_lanes_kernel(
@@ -338,6 +341,108 @@ __global__ __launch_bounds__(256) void attention_bwd_cols_lanes_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------- many keys, few queries, dropout
+// The head's 200 x 32400 cross-attention in training mode (transfusion_head_v2.py:49, :490): a wave per query
+// (attention_bwd_rows_kernel) would walk 32400 keys twice with per-lane row fetches and a hash per pair on 3 200 waves.
+// Here the KEYS are cut into splits of kAttnKeysPerSplit, grid (split, head, sample), lane = query (Lq <= 256: one
+// workgroup holds them all), the split's keys / values staged in LDS tiles and read as broadcasts as in rows_lanes.  One
+// pass, flash style: with the running maximum m of the split's scores a lane keeps
+//     sum = sum_j exp(s_ij - m),   acc = sum_j exp(s_ij - m) (mask_ij dO_i . v_j / (1 - p) - D_i) k_j
+// and writes (m, sum, acc) to part [B][heads][splits][Lq][HD + 2] (the forward's partial layout).  The merge kernel adds
+// the splits IN ORDER:  L_i = M + log(sum_s sum_s e^(m_s - M)),  dQ_i = scale * sum_s e^(m_s - L_i) acc_s -- fixed order,
+// no atomics, nothing of size Lq x Lk stored.  stat (L, D) then feeds attention_bwd_cols_lanes_kernel (one query chunk,
+// writing grad_k / grad_v directly).
+template <int HD>
+__global__ __launch_bounds__(256) void attention_bwd_rows_keysplit_kernel(
+    const float* __restrict__ q, int ldq, const float* __restrict__ k, const float* __restrict__ v, int ldkv,
+    const float* __restrict__ out, const float* __restrict__ gout, int ldo, int Lq, int Lk, int kps, float scale,
+    float* __restrict__ part, float* __restrict__ stat, AttnDrop drop) {
+  __shared__ __attribute__((aligned(16))) float ks[kAttTile][HD];
+  __shared__ __attribute__((aligned(16))) float vs[kAttTile][HD];
+  const int i = threadIdx.x;                                   // Lq <= 256 = blockDim.x
+  const int sp = blockIdx.x, nsplit = gridDim.x, head = blockIdx.y, b = blockIdx.z, heads = gridDim.y;
+  const bool live = i < Lq;
+  const int ic = live ? i : Lq - 1;
+  float qi[HD], go[HD], oi[HD];
+  load_row<HD>(q + ((size_t)b * Lq + ic) * ldq + head * HD, qi);
+  load_row<HD>(gout + ((size_t)b * Lq + ic) * ldo + head * HD, go);
+  load_row<HD>(out + ((size_t)b * Lq + ic) * ldo + head * HD, oi);
+#pragma unroll
+  for (int c = 0; c < HD; ++c) qi[c] *= scale;                 // s_ij = (scale q_i) . k_j
+  const float D = dot_row<HD>(go, oi);
+  const float* kb = k + (size_t)b * Lk * ldkv + head * HD;
+  const float* vb = v + (size_t)b * Lk * ldkv + head * HD;
+  const int k_begin = sp * kps, k_end = min(Lk, k_begin + kps);
+  float m = -INFINITY, sum = 0.f, acc[HD];
+#pragma unroll
+  for (int c = 0; c < HD; ++c) acc[c] = 0.f;
+  for (int j0 = k_begin; j0 < k_end; j0 += kAttTile) {
+    __syncthreads();
+    for (int e = threadIdx.x; e < kAttTile * (HD / 4); e += 256) {
+      const int r = e / (HD / 4), c4 = (e % (HD / 4)) * 4;
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f), bb = a;
+      if (j0 + r < k_end) {
+        a = *reinterpret_cast<const float4*>(kb + (size_t)(j0 + r) * ldkv + c4);
+        bb = *reinterpret_cast<const float4*>(vb + (size_t)(j0 + r) * ldkv + c4);
+      }
+      *reinterpret_cast<float4*>(&ks[r][c4]) = a;
+      *reinterpret_cast<float4*>(&vs[r][c4]) = bb;
+    }
+    __syncthreads();
+    const int nj = min(kAttTile, k_end - j0);
+    for (int j = 0; j < nj; ++j) {
+      float sdot = 0.f, dp = 0.f;
+#pragma unroll
+      for (int c = 0; c < HD; ++c) {
+        sdot = fmaf(qi[c], ks[j][c], sdot);
+        dp = fmaf(go[c], vs[j][c], dp);
+      }
+      if (drop.thresh)
+        dp = attn_keep(drop.seed, (unsigned)(b * heads + head), (unsigned)i, (unsigned)(j0 + j), drop.thresh) ? dp * drop.inv_keep : 0.f;
+      const float nm = fmaxf(m, sdot);
+      const float corr = __expf(m - nm);                       // first key: exp(-inf) = 0
+      const float e = __expf(sdot - nm);
+      sum = fmaf(sum, corr, e);
+      const float ds = e * (dp - D);
+#pragma unroll
+      for (int c = 0; c < HD; ++c) acc[c] = fmaf(ds, ks[j][c], acc[c] * corr);
+      m = nm;
+    }
+  }
+  if (live) {
+    float* pp = part + ((((size_t)b * heads + head) * nsplit + sp) * Lq + i) * (HD + kAttnPartFloats);
+    pp[0] = m;
+    pp[1] = sum;
+#pragma unroll
+    for (int c = 0; c < HD; ++c) pp[kAttnPartFloats + c] = acc[c];
+    if (sp == 0) stat[(((size_t)b * heads + head) * Lq + i) * 2 + 1] = D;
+  }
+}
+
+// one thread per (sample, head, query, column): the splits' partial rows in split order -> grad_q, and L_i into stat
+template <int HD>
+__global__ void attention_bwd_keysplit_merge_kernel(const float* __restrict__ part, int B, int heads, int nsplit, int Lq,
+                                                    float scale, float* __restrict__ gq, int ldgq, float* __restrict__ stat) {
+  const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (long long)B * heads * Lq * HD) return;
+  const int c = (int)(t % HD);
+  const int i = (int)((t / HD) % Lq);
+  const int head = (int)((t / ((long long)HD * Lq)) % heads);
+  const int b = (int)(t / ((long long)HD * Lq * heads));
+  const float* pb = part + (((size_t)b * heads + head) * nsplit * Lq + i) * (HD + kAttnPartFloats);
+  const size_t sstride = (size_t)Lq * (HD + kAttnPartFloats);
+  float M = -INFINITY;
+  for (int s = 0; s < nsplit; ++s) M = fmaxf(M, pb[s * sstride]);
+  float num = 0.f, den = 0.f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float w = __expf(pb[s * sstride] - M);
+    den = fmaf(pb[s * sstride + 1], w, den);
+    num = fmaf(pb[s * sstride + kAttnPartFloats + c], w, num);
+  }
+  gq[((size_t)b * Lq + i) * ldgq + head * HD + c] = scale * num / den;
+  if (c == 0) stat[(((size_t)b * heads + head) * Lq + i) * 2] = M + __logf(den);
+}
+
 // gk / gv [rows][ld] (first `cols` columns) = sum over chunks, in order, of the partial buffers
 __global__ void attention_bwd_cols_reduce_kernel(const float* __restrict__ pk, const float* __restrict__ pv, int chunks,
                                                  size_t rows, int cols, int ld, float* __restrict__ gk,
@@ -477,6 +582,16 @@ static int attention_backward_impl(const float* q, int ldq, const float* k, cons
                                    int embed_dims, int num_heads, float* grad_q, int ldgq, float* grad_k, float* grad_v,
                                    int ldgkv, isf::AttnDrop drop, isf_stream_t stream) {
   using namespace isf;
+  if (drop.thresh) {   // the dropout kernels' domain, checked before anything else is looked at (as the forward does)
+    ISF_REQUIRE(num_heads > 0 && embed_dims == 16 * num_heads, ISF_ERR_UNSUPPORTED,
+                "attention_backward: probability dropout is built for head_dim 16 (got %d: %d dims, %d heads)",
+                num_heads > 0 ? embed_dims / num_heads : 0, embed_dims, num_heads);
+    long long value = 0, limit = 0;
+    const char* what = attention_dropout_out_of_range(batch_size, num_queries, num_keys, num_heads, &value, &limit);
+    ISF_REQUIRE(what == nullptr, ISF_ERR_UNSUPPORTED,
+                "attention_backward: probability dropout hashes %s into a field of %lld values (got %lld)", what ? what : "",
+                limit, value);
+  }
   ISF_REQUIRE(batch_size >= 0 && num_queries >= 0 && num_keys > 0 && num_heads > 0, ISF_ERR_ARG,
               "attention_backward: bad sizes");
   if (batch_size == 0) return ISF_OK;
@@ -497,23 +612,33 @@ static int attention_backward_impl(const float* q, int ldq, const float* k, cons
   }
   Arena& a = arena_for_stream(as_stream(stream));
   ISF_TRY(a.reset());
+  const AttnBackwardPlan plan = attention_backward_plan(batch_size, num_queries, num_keys, num_heads, drop.thresh != 0, ldgkv);
   float* stat = nullptr;
   ISF_TRY(a.alloc_n(&stat, (size_t)batch_size * num_heads * num_queries * 2));
   const float scale = 1.f / sqrtf(16.f);
-  const bool many = num_queries >= 2048;   // lanes own queries / keys (see attention_bwd_rows_lanes_kernel)
-  if (many)
+  const int chunks = plan.chunks;
+  const size_t rows = (size_t)batch_size * num_keys;
+  if (plan.route == kAttnBwdKeySplit) {   // few queries under many keys, with dropout: dQ by key splits + ordered merge
+    const int nsplit = plan.key_splits;
+    float* part = nullptr;
+    ISF_TRY(a.alloc_n(&part, (size_t)batch_size * num_heads * nsplit * num_queries * (16 + kAttnPartFloats)));
+    hipLaunchKernelGGL((attention_bwd_rows_keysplit_kernel<16>), dim3(nsplit, num_heads, batch_size), dim3(256), 0, st, q, ldq,
+                       k, v, ldkv, out, grad_out, ldo, num_queries, num_keys, kAttnKeysPerSplit, scale, part, stat, drop);
+    const long long total = (long long)batch_size * num_heads * num_queries * 16;
+    hipLaunchKernelGGL((attention_bwd_keysplit_merge_kernel<16>), dim3(ceil_div(total, 256)), dim3(256), 0, st, part,
+                       batch_size, num_heads, nsplit, num_queries, scale, grad_q, ldgq, stat);
+    // one query chunk: the "partial" buffers are grad_k / grad_v themselves
+    hipLaunchKernelGGL((attention_bwd_cols_lanes_kernel<16>), dim3(ceil_div(num_keys, 256), num_heads, batch_size), dim3(256), 0,
+                       st, q, ldq, k, v, ldkv, grad_out, ldo, num_queries, num_keys, scale, stat, grad_k, grad_v, ldgkv, 1,
+                       batch_size, drop);
+    ISF_LAUNCH_CHECK();
+    return ISF_OK;
+  }
+  if (plan.route == kAttnBwdLanes) {
     hipLaunchKernelGGL((attention_bwd_rows_lanes_kernel<16>), dim3(ceil_div(num_queries, 256), num_heads, batch_size), dim3(256),
                        0, st, q, ldq, k, v, ldkv, out, grad_out, ldo, num_queries, num_keys, scale, grad_q, ldgq, stat, drop);
-  else
-    hipLaunchKernelGGL((attention_bwd_rows_kernel<16>), dim3(ceil_div(num_queries, 4), num_heads, batch_size), dim3(256),
-                       0, st, q, ldq, k, v, ldkv, out, grad_out, ldo, num_queries, num_keys, scale, grad_q, ldgq, stat, drop);
-  ISF_LAUNCH_CHECK();
-  if (many) {
-    // enough (key block, chunk, head, sample) workgroups to fill the chip: ~2000 of them, at least 2 query tiles each
+    ISF_LAUNCH_CHECK();
     const int kblocks = ceil_div(num_keys, 256);
-    int chunks = std::max(1, 2048 / std::max(1, kblocks * num_heads * batch_size));
-    chunks = std::max(1, std::min(chunks, num_queries / (2 * kAttTile)));
-    const size_t rows = (size_t)batch_size * num_keys;
     float *pk = nullptr, *pv = nullptr;
     ISF_TRY(a.alloc_n(&pk, (size_t)chunks * rows * ldgkv));
     ISF_TRY(a.alloc_n(&pv, (size_t)chunks * rows * ldgkv));
@@ -524,13 +649,14 @@ static int attention_backward_impl(const float* q, int ldq, const float* k, cons
     ISF_LAUNCH_CHECK();
     return ISF_OK;
   }
-  const int chunks = std::max(1, std::min(64, num_queries / 1024));
+  hipLaunchKernelGGL((attention_bwd_rows_kernel<16>), dim3(ceil_div(num_queries, 4), num_heads, batch_size), dim3(256),
+                     0, st, q, ldq, k, v, ldkv, out, grad_out, ldo, num_queries, num_keys, scale, grad_q, ldgq, stat, drop);
+  ISF_LAUNCH_CHECK();
   if (chunks == 1) {
     hipLaunchKernelGGL((attention_bwd_cols_kernel<16>), dim3(ceil_div(num_keys, 4), num_heads, batch_size), dim3(256), 0,
                        st, q, ldq, k, v, ldkv, grad_out, ldo, num_queries, num_keys, scale, stat, grad_k, grad_v, ldgkv, 1,
                        batch_size, drop);
   } else {
-    const size_t rows = (size_t)batch_size * num_keys;
     float *pk = nullptr, *pv = nullptr;
     ISF_TRY(a.alloc_n(&pk, (size_t)chunks * rows * ldgkv));
     ISF_TRY(a.alloc_n(&pv, (size_t)chunks * rows * ldgkv));

@@ -549,7 +549,9 @@ class MSDAFunction(torch.autograd.Function):
 class AttentionFunction(torch.autograd.Function):
     """softmax(q k^T / sqrt(hd)) v of nn.MultiheadAttention (fusion_encoder.py:371-470) with a gradient: forward =
     isf_attention_forward, backward = isf_attention_backward (validated on an MI355X: tests/test_gpu_train.py, tests/test_gpu_widened.py).
-    q [B*Lq, E], k / v [B*Lk, E] row-major."""
+    q [B*Lq, E], k / v [B*Lk, E] row-major.  dropout_p > 0: the probability dropout of training mode on the _dropout entries
+    -- 16 channels per head, any number of keys (tests/test_gpu_attention_dropout_keys.py), Lq and Lk below 2^24 and
+    B * nhead below 2^16 (the mask hash's index fields); anything else raises IsfError."""
 
     @staticmethod
     @_amp_fwd

@@ -20,8 +20,8 @@ Training-time stochastic ops of the reference: the residual / feed-forward Dropo
 DeformableTransformerDecoderLayer (dropout1..4, fusion_encoder.py:604-668) and Instane2SceneAtt (:478, :492) and the
 Point-to-Grid `random_noise` jitter (:992-995) are applied in training mode.  So is the dropout on the attention
 PROBABILITIES inside the two nn.MultiheadAttention modules (:614, :476 -> :458): the flash-style HIP attention core never
-materialises the probability matrix and draws the mask in the kernel from a per-call seed (`_mha`; for up to 512 keys and
-16 channels per head, the shapes of the two modules -- other shapes run without it).
+materialises the probability matrix and draws the mask in the kernel from a per-call seed (`_mha`; any number of keys, 16
+channels per head -- the shape of the two modules and of the head's decoder layer; another head width raises).
 
 No CPU fallback: tensors must live on a GPU."""
 import torch
@@ -278,13 +278,14 @@ def sstv2_forward(sst, bev, win, temperature=1000.0):
 def _mha(q_in, k_in, v_in, attn, B, Lq, Lk, nhead, dropout_p=0.0):
     """nn.MultiheadAttention arithmetic on row-major [B*L, E] tokens with the HIP attention core.  dropout_p > 0 (training):
     the module's dropout on the attention probabilities (fusion_encoder.py:458), one fresh seed per call from torch's CPU
-    generator (torch.manual_seed makes a run repeatable)."""
+    generator (torch.manual_seed makes a run repeatable).  Any number of keys; a shape the dropout kernels do not take
+    (channels per head other than 16) raises IsfError rather than running without the op."""
     E = q_in.size(1)
     w, b = attn.in_proj_weight, attn.in_proj_bias
     q = linear_w(q_in, w[:E], b[:E])
     k = linear_w(k_in, w[E:2 * E], b[E:2 * E])
     v = linear_w(v_in, w[2 * E:], b[2 * E:])
-    if dropout_p > 0.0 and Lk <= 512 and E == 16 * nhead:
+    if dropout_p > 0.0:
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         att = ops.AttentionFunction.apply(q, k, v, B, Lq, Lk, E, nhead, float(dropout_p), seed)
     else:

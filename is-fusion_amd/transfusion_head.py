@@ -84,6 +84,9 @@ class TransformerDecoderLayer(nn.Module):
 
 class TransFusionHeadV2(nn.Module):
     _warned_cross_dropout = False
+    cross_attention_dropout = False   # a plain attribute: not a parameter, buffer or constructor argument.  True: in training
+                                      # mode with dropout > 0, forward_train applies the decoder layer's dropout to the
+                                      # probabilities of the proposals x BEV-cells cross-attention (see forward_train)
 
     def __init__(self, num_proposals=200, auxiliary=True, in_channels=512, hidden_channel=128, num_classes=10,
                  num_decoder_layers=1, num_heads=8, nms_kernel_size=3, ffn_channel=256, common_heads=None,
@@ -327,9 +330,13 @@ class TransFusionHeadV2(nn.Module):
         of the proposal features, the decoder layer's attention through fusion_train._mha (HIP linear + attention
         kernels), FFN / layer norms, the prediction heads as HIP linears + bn1d_relu.  Dropout p = self.dropout where the
         reference applies it (dropout1..3 and the FFN dropout; the attention-probability dropout of the 200 x 200
-        self-attention on the dropout kernels).  The 200 x 32400 cross-attention has no probability dropout (the kernels
-        take Lk <= 512): a warning says so once.  feats: [B, in_channels, X, Y] or a one-element list -> ([dict],) as
-        forward returns it."""
+        self-attention on the dropout kernels).  The 200 x 32400 cross-attention gets its probability dropout
+        (MultiheadAttention(dropout=0.1), transfusion_head_v2.py:49, :490) when `cross_attention_dropout` is True: the same
+        hash-seeded kernels, the backward by key splits (isf_attention_bwd.hip).  The switch is off by default, and then a
+        warning says once that the op is missing: tests/test_gpu_head_train.py records a 30-step loss curve with dropout
+        on, and the extra mask moves that curve and, through its seed, every later random draw of the step -- turning it
+        on by default is a change of its own with a re-recorded curve.  feats: [B, in_channels, X, Y] or a one-element
+        list -> ([dict],) as forward returns it."""
         from . import dense_train, fusion_train
         x = feats[0] if isinstance(feats, (list, tuple)) else feats
         _lib_require_cuda(x)
@@ -354,10 +361,11 @@ class TransFusionHeadV2(nn.Module):
         query_pos = bev_pos[0][cell]                                                       # [B, P, 2]
         drop = torch.nn.functional.dropout
         ln = torch.nn.functional.layer_norm
-        if p > 0.0 and tr and not TransFusionHeadV2._warned_cross_dropout:
+        cross_p = p if tr and self.cross_attention_dropout else 0.0
+        if p > 0.0 and tr and not self.cross_attention_dropout and not TransFusionHeadV2._warned_cross_dropout:
             TransFusionHeadV2._warned_cross_dropout = True
             warnings.warn("TransFusionHeadV2.forward_train: no dropout on the attention probabilities of the 200 x 32400 "
-                          "cross-attention (the dropout kernels take at most 512 keys); the output dropout is applied")
+                          "cross-attention (set cross_attention_dropout = True to apply it); the output dropout is applied")
         ret_dicts = []
         for i, l in enumerate(self.decoder):
             qpe = ops._pos_embed(l.self_posembed, query_pos).reshape(B * P, E)
@@ -366,7 +374,7 @@ class TransFusionHeadV2(nn.Module):
             sa = fusion_train._mha(xq, xq, xq, l.self_attn, B, P, P, l.nhead, p if tr else 0.0)
             query = ln(query + drop(sa, p, tr), (E,), l.norm1.weight, l.norm1.bias, l.norm1.eps)
             kv = (rows.view(B, HW, E) + kpe[None]).reshape(B * HW, E)                      # key = value = feat + pos
-            ca = fusion_train._mha(query + qpe, kv, kv, l.multihead_attn, B, P, HW, l.nhead)
+            ca = fusion_train._mha(query + qpe, kv, kv, l.multihead_attn, B, P, HW, l.nhead, cross_p)
             query = ln(query + drop(ca, p, tr), (E,), l.norm2.weight, l.norm2.bias, l.norm2.eps)
             h = drop(torch.relu(fusion_train.linear(query, l.linear1)), p, tr)
             query = ln(query + drop(fusion_train.linear(h, l.linear2), p, tr), (E,), l.norm3.weight, l.norm3.bias,

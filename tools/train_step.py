@@ -162,6 +162,9 @@ def main():
     ap.add_argument("--camera-precision", default="f32", choices=["f32", "mixed"],
                     help="with --camera: ISFusionDetector.camera_precision -- mixed: the Swin backbone's mixed-precision "
                          "training mode (f16 products, fp32 master weights and gradients)")
+    ap.add_argument("--head-cross-dropout", action="store_true",
+                    help="with --loss detection: TransFusionHeadV2.cross_attention_dropout = True -- the decoder layer's "
+                         "dropout (p = 0.1) on the probabilities of the head's 200 x 32400 cross-attention too")
     ap.add_argument("--deterministic", action="store_true",
                     help="isfusion_amd.set_deterministic(True): the isf_*_det entries (fixed-point accumulation) in "
                          "DynamicScatter, Point-to-Grid backward and both MSDA backwards")
@@ -173,6 +176,8 @@ def main():
         ap.error("--camera-backward switches the camera branch's backward on: it needs --camera")
     if a.camera_precision != "f32" and not a.camera:
         ap.error("--camera-precision sets the camera backbone's mode: it needs --camera")
+    if a.head_cross_dropout and a.loss != "detection":
+        ap.error("--head-cross-dropout trains the detection head: it needs --loss detection")
     if a.gt_paste and a.loss != "detection":
         ap.error("--gt-paste pastes ground truth: it needs --loss detection")
     import isfusion_amd
@@ -231,6 +236,7 @@ def main():
         from isfusion_amd import head_loss
         if net.pts_bbox_head.train_cfg is None:
             net.pts_bbox_head.train_cfg = dict(head_loss.SHIPPED_TRAIN_CFG)
+        net.pts_bbox_head.cross_attention_dropout = a.head_cross_dropout
     else:
         for p in net.pts_bbox_head.parameters():
             p.requires_grad_(False)                                  # the stand-in loss does not reach the head
@@ -344,7 +350,7 @@ def main():
             digest["replicas_agree"] = len(set(every)) == 1
     if rank == 0:
         print(json.dumps({"world_size": world, "n_gpus": world, "parallelism": f"dp{world}", "rccl": launch.rccl_version(), "backend": a.backend, "shared_device": a.shared_device, "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY"), "batch_per_gpu": a.batch, "points": a.points, "bf16_camera_features": a.bf16, "autocast_bf16": a.autocast, "loss": a.loss, "camera": a.camera, "camera_backward": a.camera_backward, "camera_precision": a.camera_precision, "deterministic": a.deterministic,
-                          "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses],
+                          "head_cross_dropout": a.head_cross_dropout, "ms_per_train_step": round(dt * 1e3, 2), "ms_each_step_gpu_clock": per_step, "losses": [round(v, 5) for v in losses],
                           "optimizer": a.optimizer, **({"grad_norm": [round(n, 6) for n in norms]} if recipe else {}),
                           **({"gt_paste_objects": pasted} if paste is not None else {}),
                           **digest}))
