@@ -1019,6 +1019,29 @@ int isf_bn1d_backward_apply(const float* grad_y, const float* x, const float* y_
                             const float* mean_invstd, const float* gamma, const float* sums, float count, float* grad_x,
                             float* grad_residual, float* grad_gamma, float* grad_beta, isf_stream_t stream);
 
+/* thin-K linear layer, forward and backward: the first layer of PositionEmbeddingLearned in training mode
+ * (fusion_encoder.py:173-189: Conv1d(2 -> E, k = 1) on [B, 2, N] = a linear layer on B * N rows of 2 coordinates).
+ * in_features = 2 is far below what isf_linear_forward tiles (K % 32 == 0); padding the coordinates to 32 columns and
+ * splitting them into f16 halves would move 16 x the bytes and round positions of up to 180.  Plain fp32 FMA on the
+ * vector ALU instead, every sum in one fixed order:
+ *   isf_thin_linear_forward: y [M, N] = x [M, K] w^T + b, w [N, K] (nn.Linear layout), b [N] or NULL; per element
+ *     b + x_0 w_0 + ... + x_{K-1} w_{K-1}, left to right, one fused multiply-add per term.
+ *   isf_thin_linear_parts(M): row chunks the backward reduces over (ceil(M / 128), a function of M alone; 0 for M <= 0);
+ *     the caller hands isf_thin_linear_backward a workspace of parts * (K + 1) * N floats.
+ *   isf_thin_linear_backward: grad_w [N, K] = grad_y^T x, grad_b [N] = column sums of grad_y (NULL: not computed),
+ *     grad_x [M, K] = grad_y w (NULL: not computed; the positions this layer embeds need none).  grad_w / grad_b: one
+ *     workgroup per chunk sums its rows in ascending order, a second launch adds the chunks in ascending order -- no
+ *     atomics, bit-identical run to run; the longest addition chain is 128 + parts terms.  grad_w NULL: only grad_x.
+ *     grad_x: per row, every lane's four columns in ascending order, then a fixed xor tree over the 64 lanes.
+ * Domain: 1 <= K <= 8, N % 16 == 0, 16 <= N <= 256; anything else is ISF_ERR_UNSUPPORTED before any launch.  All
+ * asynchronous. */
+int isf_thin_linear_forward(const float* x, const float* w, const float* b, float* y, int num_rows, int out_features,
+                            int in_features, isf_stream_t stream);
+int isf_thin_linear_parts(int num_rows);
+int isf_thin_linear_backward(const float* grad_y, const float* x, const float* w, float* parts, float* grad_w,
+                             float* grad_b, float* grad_x, int num_rows, int out_features, int in_features,
+                             isf_stream_t stream);
+
 /* 8f #3  input pre-pass: multi-sweep assembly + augmentation + range filter ---------------------------------
  * replaces, per batch, the dataloader-side numpy / torch code of LoadPointsFromMultiSweeps.__call__
  * (datasets/pipelines/loading.py:860-903), the point side of GlobalRotScaleTransV2 and RandomFlip3DV2

@@ -357,6 +357,10 @@ SIGNATURES = {
     "isf_bn1d_backward_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "isf_bn1d_backward_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                         ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "isf_thin_linear_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "isf_thin_linear_parts": (c_int, [c_int]),
+    "isf_thin_linear_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_int, c_int, c_void_p]),
     "isf_pair_list_capacity": (c_int, [c_int, c_int]),
     "isf_rulebook_pair_lists": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "isf_grad_to_split": (c_int, [c_void_p, ctypes.c_size_t, c_void_p, c_void_p, c_void_p]),

@@ -178,7 +178,14 @@ class ISFusionEncoder(nn.Module):
                 # tokens instead (transpose=True), as the inference path does
                 t = stack(self.heatmap_head_2, stack(self.heatmap_head_1, stack(self.conv_heatmap, bev_feats, True), True),
                           True)
-                ins_hm = self.heatmap_head_3(t.permute(0, 1, 3, 2))       # 64 -> 10 classes: stock conv
+                # 64 -> 10 classes: the same kernels on 32 zero-padded columns (dense_train.py).  ins_hm keeps the
+                # reference's orientation -- the map OF THE TRANSPOSED input, which instance_topk and the heat-map loss
+                # read -- so stack()'s permute back is undone, in the one packed copy of the 10-channel map that both
+                # readers would otherwise make
+                if tr.STOCK_CONVS or self.dense_conv != "hip":
+                    ins_hm = self.heatmap_head_3(t.permute(0, 1, 3, 2))
+                else:
+                    ins_hm = dt.conv_stack(self.heatmap_head_3, t, True, narrow=True).permute(0, 1, 3, 2).contiguous()
                 x_scene_t = stack(self.conv_scene, bev_feats, True)
                 q = stack(self.conv_ins, bev_feats)
                 with torch.no_grad():

@@ -345,10 +345,40 @@ def seeded_state_dict(module, seed):
     return sd
 
 
+class _LevelsToMap(torch.autograd.Function):
+    """SECONDFPN's channel concatenation and final permute(0, 1, 3, 2) of the up-sampled levels, given as rows
+    [B*H*W*s*s, Cout] in (b, h, w, dy, dx) order: out[b, c0 + co, w*s + dx, h*s + dy] = rows[b, h, w, dy, dx, co] -- one
+    copy per level, forward (forward_tokens' index map) and backward."""
+
+    @staticmethod
+    def forward(ctx, geom, *ys):
+        B, H, W, s, _ = geom[0]
+        out = ys[0].new_empty((B, sum(g[4] for g in geom), W * s, H * s))
+        c0 = 0
+        for (B, H, W, s, cout), y in zip(geom, ys):
+            assert (W * s, H * s) == tuple(out.shape[2:]), "SECONDFPN levels of different up-sampled sizes"
+            out[:, c0:c0 + cout].view(B, cout, W, s, H, s).copy_(y.view(B, H, W, s, s, cout).permute(0, 5, 2, 4, 1, 3))
+            c0 += cout
+        ctx.geom = geom
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        grads = []
+        c0 = 0
+        for B, H, W, s, cout in ctx.geom:
+            gl = g[:, c0:c0 + cout].reshape(B, cout, W, s, H, s).permute(0, 4, 2, 5, 3, 1)      # [B, H, W, dy, dx, Cout]
+            grads.append(gl.reshape(B * H * W * s * s, cout))
+            c0 += cout
+        return (None, *grads)
+
+
 class SECONDFPN(nn.Module):
     """necks/second_fpn.py:10-93 as the IS-Fusion config builds it (use_conv_for_no_stride=True): per level a
     Conv2d(k = 1/stride) or ConvTranspose2d(k = stride) without bias + BN(eps 1e-3) + ReLU, concatenated, and the
-    final `permute(0, 1, 3, 2)`.  Training: stock PyTorch-ROCm ops (a 1x1 conv and a 2x2 transposed conv per frame)."""
+    final `permute(0, 1, 3, 2)`.  Training (dense_conv = "hip"): the same GEMMs over BEV tokens as inference, with batch
+    statistics and gradients -- fusion_train.linear_w and norm.bn1d_relu (forward_train); dense_conv = "stock" or
+    fusion_train.STOCK_CONVS: the torch modules (MIOpen)."""
 
     def __init__(self, in_channels=(128, 256), out_channels=(256, 256), upsample_strides=(1, 2),
                  norm_cfg=dict(type="BN", eps=1e-3, momentum=0.01), upsample_cfg=dict(type="deconv", bias=False),
@@ -448,11 +478,61 @@ class SECONDFPN(nn.Module):
         assert all((m.H, m.W) == (maps[0].H, maps[0].W) for m in maps)
         return maps
 
+    def _train_weights(self, i):
+        """level i's weight as the GEMMs of training mode read it: one [Cout, Cin] matrix per sub-cell (dy, dx) of the
+        k = s transposed conv (sub-cell dy*s + dx = rows (dy*s + dx)*Cout ... of _folded's layout, no BN fold), one for the
+        1x1 conv -- differentiable views of the parameter, so autograd returns the gradient in the parameter's layout"""
+        up = self.deblocks[i][0]
+        w = up.weight
+        if isinstance(up, nn.ConvTranspose2d):
+            s = up.stride[0]
+            assert up.kernel_size == (s, s) and up.stride == (s, s) and up.bias is None
+            wt = w.permute(2, 3, 1, 0).reshape(s * s, w.shape[1], w.shape[0])      # [dy*s + dx, Cout, Cin]
+            return [wt[j] for j in range(s * s)], s
+        assert up.kernel_size == (1, 1) and up.stride == (1, 1) and up.bias is None
+        return [w[:, :, 0, 0]], 1
+
+    def forward_train_tokens(self, x, linear, bn_relu):
+        """forward_tokens' sibling for TRAINING mode (batch statistics, gradients), the GEMM and the BatchNorm injected:
+        linear(x [B, Cin, H, W], weight [Cout, Cin]) -> [B*H*W, Cout] rows ((b, y, x) order), bn_relu(bn, rows) ->
+        relu(BatchNorm over the rows).  Per level: one GEMM per sub-cell (the fused linear kernel's dX contracts over
+        at most 256 output columns), their outputs side by side = [M, s*s*Cout] with sub-cell-major columns = [M*s*s, Cout]
+        rows, over which BatchNorm2d of the up-sampled map is BatchNorm1d; then one copy per level into the concatenated,
+        permuted output (forward_tokens' index map), with its own backward."""
+        ys, geom = [], []
+        for i in range(len(self.deblocks)):
+            ws, s = self._train_weights(i)
+            B, _, H, W = x[i].shape
+            cols = [linear(x[i], w) for w in ws]
+            cout = cols[0].shape[1]
+            y = cols[0] if len(cols) == 1 else torch.stack(cols, 1).view(B * H * W * s * s, cout)
+            ys.append(bn_relu(self.deblocks[i][1], y))
+            geom.append((B, H, W, s, cout))
+        return [_LevelsToMap.apply(tuple(geom), *ys)]
+
+    def forward_train(self, x):
+        """training mode on the HIP kernels: fusion_train.linear_w on the token rows (dense_train.to_rows: a view when the
+        level is the NCHW view of token-major rows, as SECONDV2's training path hands it over), norm.bn1d_relu (running
+        statistics, num_batches_tracked, cross-rank sync as the modules')"""
+        from . import dense_train as dt
+        from .fusion_train import linear_w
+        from .norm import bn1d_relu
+        with torch.autocast("cuda", enabled=False):
+            return self.forward_train_tokens(x, lambda t, w: linear_w(dt.to_rows(t), w),
+                                             lambda bn, rows: bn1d_relu(bn, rows, relu=True))
+
+    def _train_on_kernels(self, x):
+        from . import dense_train as dt, fusion_train as tr, spconv as sp
+        return (self.dense_conv == "hip" and not tr.STOCK_CONVS and dt.ENABLED and sp.TRAINING_KERNELS and
+                torch.is_grad_enabled() and all(t.is_cuda for t in x))
+
     def forward(self, x, **kwargs):
         assert len(x) == len(self.in_channels)
         if self.dense_conv == "hip" and not self.training:
             with torch.no_grad():
                 return self.forward_tokens(x, *self._linear_relu())
+        if self.training and self._train_on_kernels(x):
+            return self.forward_train(x)
         ups = [d(x[i]) for i, d in enumerate(self.deblocks)]
         out = torch.cat(ups, dim=1) if len(ups) > 1 else ups[0]
         return [out.permute(0, 1, 3, 2).contiguous()]

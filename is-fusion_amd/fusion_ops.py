@@ -651,9 +651,16 @@ def _pos_embed(mod, xy):
     """PositionEmbeddingLearned (fusion_encoder.py:173-189): Conv1d(k=1) / BN1d / ReLU / Conv1d(k=1) on [B, N, 2] ->
     [B, N, E].  In eval mode the two kernel-size-1 convolutions are what they are -- two small GEMMs with the BN folded
     (library GEMMs: K = 2 and K = E are far below the MFMA tile of the fused linear kernel) -- instead of four MIOpen
-    launches with layout transposes; training mode runs the stock modules (batch statistics)."""
+    launches with layout transposes.  Training mode (batch statistics over the B * N rows, with gradients): the thin-K
+    kernel pair for the first layer, the fused BatchNorm + ReLU kernels, the fused linear kernel for the second
+    (fusion_train.pos_embed_train); fusion_train.STOCK_CONVS, or anything that is not fp32-class rows on a GPU with
+    gradients enabled, runs the stock modules."""
     seq = mod.position_embedding_head
     if seq.training:
+        from . import fusion_train as tr
+        from . import spconv as sp
+        if not tr.STOCK_CONVS and sp.TRAINING_KERNELS and xy.is_cuda and torch.is_grad_enabled():
+            return tr.pos_embed_train(seq, xy)
         return seq(xy.transpose(1, 2).contiguous()).transpose(1, 2).contiguous()
     from .norm import fold_bn
     c1, bn, _, c2 = seq

@@ -9,9 +9,13 @@ the HIP kernel and whose BACKWARD is
   * window / small-key attention, MSDA      the hand-written backward kernels (isf_attention_bwd.hip, isf_fusion.hip);
   * per-channel map attention               isf_channel_attention_forward / isf_channel_attention_backward;
   * Point-to-Grid                           isf_p2g_backward (scatter with fp32 atomics);
+  * thin-K linear (position MLPs, K = 2)    isf_thin_linear_forward / _backward (fp32 FMA, fixed summation order);
 
-bias / position-table / GELU / residual / LayerNorm epilogues, the 3x3 convolutions + BatchNorm (stock, as the north_star
-prescribes) and the top-k instance mining (indices: no gradient, as in the reference) are stock differentiable torch ops.
+bias / position-table / GELU / residual / LayerNorm epilogues and the top-k instance mining (indices: no gradient, as in
+the reference) are stock differentiable torch ops.  No nn.Conv* module runs in a training step: the 3x3 convolutions +
+BatchNorm are dense_train.py's (the 10-class heat-map convs on zero-padded columns), the neck's 1x1 conv and deconvolution
+are LinearFunction GEMMs (SECONDFPN.forward_train), the position embeddings' Conv1d(k = 1) pairs are pos_embed_train below;
+STOCK_CONVS = True puts the stock modules (MIOpen) back at those four sites.
 The reference does the same composition with torch modules (sst_basic_block_v2.py:77-126, fusion_encoder.py:480-502,
 :560-600, :795-830).  Mixed precision: bf16 / fp16 inputs are accepted and promoted -- the kernels compute fp32-class
 (>= the reference's autocast arithmetic); gradients come back in the input dtype.
@@ -140,6 +144,78 @@ def linear(x, lin, **kw):
 
 def linear_w(x, weight, bias=None):
     return LinearFunction.apply(x, weight, bias)
+
+
+class ThinLinearFunction(torch.autograd.Function):
+    """y = x W^T (+ b) for a THIN input: x [M, K] with 1 <= K <= 8, weight [N, K], N a multiple of 16 up to 256 -- the first
+    layer of a PositionEmbeddingLearned (K = 2 coordinates).  isf_thin_linear_forward / _backward (isf_thin.hip): plain
+    fp32 FMA in a fixed order, forward and backward bit-identical run to run; dX only when x requires a gradient."""
+
+    @staticmethod
+    @_amp_fwd
+    def forward(ctx, x, weight, bias):
+        _lib.require_cuda(x, weight)
+        xd, wd = x.detach().float().contiguous(), weight.detach().float().contiguous()
+        bd = bias.detach().float().contiguous() if bias is not None else None
+        M, K = xd.shape
+        N = wd.shape[0]
+        y = torch.empty((M, N), dtype=torch.float32, device=xd.device)
+        if M > 0:
+            _lib.check(_lib.load().isf_thin_linear_forward(_lib.ptr(xd), _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(y), M, N, K,
+                                                           _lib.stream()), "isf_thin_linear_forward")
+        ctx.save_for_backward(xd, wd)
+        ctx.has_bias = bias is not None
+        ctx.in_dtype = x.dtype
+        return y
+
+    @staticmethod
+    @_amp_bwd
+    def backward(ctx, gy):
+        xd, wd = ctx.saved_tensors
+        g = gy.contiguous().float()
+        M, K = xd.shape
+        N = wd.shape[0]
+        want_x, want_w = ctx.needs_input_grad[:2]
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        want_w = want_w or want_b                   # the column sums come out of the weight gradient's passes
+        if M == 0:
+            return (torch.zeros_like(xd).to(ctx.in_dtype) if want_x else None, torch.zeros_like(wd) if want_w else None,
+                    g.new_zeros(N) if want_b else None)
+        lib = _lib.load()
+        gx = torch.empty_like(xd) if want_x else None
+        gw = torch.empty_like(wd) if want_w else None
+        gb = torch.empty(N, dtype=torch.float32, device=g.device) if want_b else None
+        parts = torch.empty(lib.isf_thin_linear_parts(M) * (K + 1) * N, dtype=torch.float32, device=g.device) if want_w \
+            else None
+        if want_x or want_w:
+            _lib.check(lib.isf_thin_linear_backward(_lib.ptr(g), _lib.ptr(xd), _lib.ptr(wd), _lib.ptr(parts), _lib.ptr(gw),
+                                                    _lib.ptr(gb), _lib.ptr(gx), M, N, K, _lib.stream()),
+                       "isf_thin_linear_backward")
+        return (gx.to(ctx.in_dtype) if want_x else None), (gw if ctx.needs_input_grad[1] else None), gb
+
+
+def thin_linear(x, weight, bias=None):
+    return ThinLinearFunction.apply(x, weight, bias)
+
+
+# True: the stock nn.Conv* modules (MIOpen) at the four training-path sites that ran on them before the kernels below
+# covered them -- ISFusionEncoder.heatmap_head_3, the head's 10-class heat-map conv, SECONDFPN and every
+# PositionEmbeddingLearned -- for A/B runs and as a cross-check (the style of dense_train.ENABLED)
+STOCK_CONVS = False
+
+
+def pos_embed_train(seq, xy, thin=thin_linear, dense=linear_w, bn_relu=None):
+    """PositionEmbeddingLearned.position_embedding_head (fusion_encoder.py:173-189: Conv1d(2 -> E, k = 1) / BatchNorm1d /
+    ReLU / Conv1d(E -> E, k = 1)) in TRAINING mode on [B, N, 2] positions -> [B, N, E]: kernel-size-1 convolutions are
+    linear layers over the B * N rows, BatchNorm1d on [B, C, N] takes its statistics over those rows -- the thin-K kernel
+    pair, norm.bn1d_relu, the fused linear kernel.  (thin / dense / bn_relu: the three pieces, injectable.)"""
+    from .norm import bn1d_relu
+    c1, bn, _, c2 = seq
+    rows = xy.reshape(-1, xy.shape[-1])
+    h = thin(rows, c1.weight[:, :, 0], c1.bias)
+    h = (bn_relu or bn1d_relu)(bn, h, relu=True)
+    out = dense(h, c2.weight[:, :, 0], c2.bias)
+    return out.view(*xy.shape[:-1], -1)
 
 
 def channel_attention_backward_reference(qs, qi, g):

@@ -345,7 +345,9 @@ class TransFusionHeadV2(nn.Module):
         E = self.shared_conv.out_channels
         p, tr = self.dropout, self.training
         feat = dense_train.conv_stack(self.shared_conv, x)                                # NCHW view of [B*HW, E] rows
-        dense_heatmap = dense_train.conv_stack(self.heatmap_head[1], dense_train.conv_stack(self.heatmap_head[0], feat))
+        # (128 -> 10 classes: the kernels on 32 zero-padded columns, the bias added behind them)
+        dense_heatmap = dense_train.conv_stack(self.heatmap_head[1], dense_train.conv_stack(self.heatmap_head[0], feat),
+                                               narrow=not fusion_train.STOCK_CONVS)
         dense_heatmap = dense_heatmap.float().contiguous()
         pool1 = (8, 9) if self.test_cfg["dataset"] == "nuScenes" else (1, 2)
         top, raw, masked = ops.instance_topk(dense_heatmap.detach(), P, self.nms_kernel_size, pool1, return_masked=True)
